@@ -3,11 +3,15 @@
 
 Metric (BASELINE.json): candidate-camera coverage-gain evals/sec (100k pts, 200 cams); NBV step p50 latency.
 
-    python bench.py --gpus 1 --steps K --warmup W
+    python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
-What one run reports, with no extra flags, at any N:
+A plain run measures (A) alone and prints its line.  `--dump-outputs DIR` writes what the last timed step of (A) returned, as
+DIR/gains.npy (float32 [1, C], the gains of rank 0's cameras) and DIR/record.npy (float32 [1, 2]: the decision, max gain and arg-max
+camera); the inputs are seeded, so two builds given the same arguments can be compared output for output.
+
+What a `--full` run reports, at any N:
   (A)  `value` — the contract line: scorer throughput, WEAK scaling.  A "step" = one pass of the scorer
        (SconeVis.compute_coverage_gain semantics) over one synthetic cloud of 100 000 points x 200 candidate cameras per GPU,
        inputs resident in HBM, followed by the arg-max decision record (N > 1: the all-gather of every rank's record).
@@ -20,7 +24,7 @@ What one run reports, with no extra flags, at any N:
        (strong scaling of one decision) and the occupancies / records travel over RCCL.
   `ranks_seen` — how many distinct ranks an RCCL all-gather of the rank ids returned (proof the collective path ran at N).
 
-Rank 0 prints ONE JSON line (contract in the task statement) with extra objects:
+Rank 0 prints ONE JSON line (contract in the task statement); under --full with extra objects:
   roofline              dominant kernel of (A), sh_gain_kernel, timed ALONE with HIP events (K launches of the first stage only):
                         algorithmic flop per launch / its mean duration vs the fp32 vector peak; the step-level figure
                         (gain + reduce + decision record per step) sits beside it as `step_*`
@@ -781,6 +785,9 @@ def main():
     ap.add_argument("--legs-deadline", type=int, default=None, help="seconds the extra legs (NBV step, scene batch, MACARONS decision, CPU baselines) "
                                                                     "may take together before every rank leaves and rank 0 prints the contract line without them "
                                                                     "(default: 240 on one GPU -- they take ~25 s -- and 120 on several)")
+    ap.add_argument("--full", action="store_true", help="besides the headline (A): the strong-scaling leg, the kernel-alone roofline, the "
+                                                        "in-run PMC traffic pass, the NBV / scene-batch / MACARONS legs and the CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the outputs of the last timed step of (A) as DIR/<name>.npy")
     args = ap.parse_args()
 
     if args.watchdog > 0:
@@ -834,6 +841,7 @@ def main():
         score_best = lambda p_, h_, c_: ops.sh_coverage_gain_best(p_, h_, c_, True, args.waves_per_simd)
 
     scorer_streams = []
+    last_gains = [None]                                    # the gains of the latest step (what --dump-outputs writes)
 
     def scorer_run(pts, harm, cams, cam_offset, steps, warmup):
         # --streams S (default 2): consecutive steps are independent batches and are issued round-robin on S streams, each step whole
@@ -851,6 +859,7 @@ def main():
         def step():
             def one():
                 gains, record = score_best(pts, harm, cams)    # record [B,2] = (max gain, arg-max camera): the decision (torch.max semantics)
+                last_gains[0] = gains
                 if pipe is not None:                           # records of 16 decisions per all-gather, on a side stream
                     return pipe.submit(gains, cam_offset)      # (the record kernel on the step's own stream; the exchange waits for all of them)
                 return record
@@ -870,7 +879,31 @@ def main():
 
     # ---- (A) weak scaling: every rank its own shard of C cameras out of world*C -------------------------------------------
     pts, harm, cams = make_inputs(N, C, 1234, dev, cam_offset=rank * C, n_cam_total=world * C)
-    wall, dev_ms, _ = scorer_run(pts, harm, cams, rank * C, args.steps, args.warmup)
+    wall, dev_ms, decision = scorer_run(pts, harm, cams, rank * C, args.steps, args.warmup)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last_gains[0], decision)
+
+    def headline():
+        """The contract line: the fields of (A), all that a plain run prints."""
+        return {
+            "metric": "candidate-camera coverage-gain evals/sec (100k pts, 200 cams)",
+            "value": world * C * args.steps / wall, "unit": "evals/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": wall * 1e3 / args.steps, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+            "dtype": "f32", "data": "synthetic",
+            "config": {"workload": f"scorer: B=1 cloud x N={N} points x C={C} cameras per GPU "
+                                   f"(BASELINE headline 100k pts / 200 cams), inputs resident in HBM",
+                       "points": N, "cams_per_gpu": C, "parallelism": f"camera-shard x{world}", "entry": scorer_entry,
+                       "streams": args.streams, "untimed_clock_ramp_steps": 1000,
+                       "timing_note": "1000 untimed clock-ramp steps precede the --warmup steps (a warm-clock number by construction: the "
+                                      "driver's --warmup 5 alone ends before the shader clock has left idle); steps are independent batches "
+                                      f"issued round-robin on {args.streams} stream(s): roofline.ms_per_step_one_stream (--full) is the "
+                                      "one-stream step"},
+            "ranks_seen": ranks_seen,
+        }
+
+    if not args.full:
+        leave(dist, rank, lambda: print(json.dumps(headline()), flush=True))
+        return
 
     # ---- (A') strong scaling, BASELINE config 4: strong_cams cameras in total, block-partitioned ---------------------------
     Cs = args.strong_cams
@@ -952,8 +985,6 @@ def main():
         leg_seconds[name] = round(time.perf_counter() - t_leg, 2)
 
     if rank == 0:
-        ms_per_step = wall * 1e3 / args.steps
-        evals_per_s = world * C * args.steps / wall
         step_ms = dev_ms / args.steps              # device time of one whole step (gain + reduce + decision record)
         alg_flop = N * C * FLOP_PER_PAIR
         exe_flop = N * C * FLOP_PER_PAIR_EXECUTED
@@ -996,22 +1027,7 @@ def main():
                                                   "static property of the code at this size) x 2 issue cycles / (1024 SIMDs x kernel cycles at "
                                                   "2.4 GHz): how busy the vector pipe is, as opposed to `frac`")
             roof["valu_insts_per_launch"] = valu
-        res = {
-            "metric": "candidate-camera coverage-gain evals/sec (100k pts, 200 cams)",
-            "value": evals_per_s, "unit": "evals/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "f32", "data": "synthetic",
-            "config": {"workload": f"scorer: B=1 cloud x N={N} points x C={C} cameras per GPU "
-                                   f"(BASELINE headline 100k pts / 200 cams), inputs resident in HBM",
-                       "points": N, "cams_per_gpu": C, "parallelism": f"camera-shard x{world}", "entry": scorer_entry,
-                       "streams": args.streams, "untimed_clock_ramp_steps": 1000,
-                       "timing_note": "1000 untimed clock-ramp steps precede the --warmup steps (a warm-clock number by construction: the "
-                                      "driver's --warmup 5 alone ends before the shader clock has left idle); steps are independent batches "
-                                      f"issued round-robin on {args.streams} stream(s): roofline.ms_per_step_one_stream is the one-stream step"},
-            "ranks_seen": ranks_seen,
-            "roofline": roof,
-            "scorer_strong": strong,
-        }
+        res = dict(headline(), roofline=roof, scorer_strong=strong)
     else:
         res = None
 
@@ -1068,6 +1084,20 @@ def main():
             run_leg("cpu_baseline_nbv", lambda: cpu_baseline_nbv(C))
     legs_done.set()
     timer.cancel()
+    leave(dist, rank, emit)
+
+
+def dump_outputs(path, gains, decision):
+    """--dump-outputs: the last timed step's gains [B, C] and decision record [B, 2] = (max gain, arg-max camera), float32."""
+    if isinstance(decision, tuple):                        # N > 1: the exchanged decision (max gains, global camera indices)
+        decision = torch.stack([decision[0].float(), decision[1].float()], -1)
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "gains.npy"), gains.float().cpu().numpy())
+    np.save(os.path.join(path, "record.npy"), decision.float().cpu().numpy())
+
+
+def leave(dist, rank, emit):
+    """End of a run: rank 0 prints its JSON line (emit) as the LAST line of stdout."""
     if dist is not None:
         dist.destroy_process_group()       # RCCL prints its version banner to stdout on the way out: keep the JSON the LAST line
     sys.stdout.flush()

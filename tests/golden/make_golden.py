@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Generate the committed golden vectors by running the REAL reference (this container only).
 
-    python tests/golden/make_golden.py [group ...]      # groups: scorer sh knn view sampler blocks vis occ e2e
+    python tests/golden/make_golden.py [group ...]      # groups: scorer sh knn view sampler blocks vis occ e2e losses ...
 
 The reference Python lives read-only at /root/reference and never travels; what is committed is
 data only (inputs + the reference's outputs, as small .npz files) together with this script.
@@ -1532,7 +1532,26 @@ def gen_trajectory():
     save("macarons_trajectory", **out)
 
 
-GROUPS = {"masked": gen_masked, "trajectory": gen_trajectory, "decision": gen_decision, "occ_field": gen_occ_field, "formats": gen_formats, "e2e_grid": gen_e2e_grid, "fov": gen_fov, "distance": gen_distance, "wrapper": gen_macarons_wrapper, "single_camera": gen_single_camera, "cell": gen_cell, "unproject": gen_unproject, "viewspace": gen_viewspace, "filter": gen_filter, "macarons": gen_macarons, "e2e": gen_e2e, "view": gen_view, "scorer": gen_scorer, "sh": gen_sh, "knn": gen_knn, "blocks": gen_blocks, "vis": gen_vis, "occ": gen_occ}
+def gen_losses():
+    """The three training losses of SconeVis.py (KLDivCE, L1_loss, Uncentered_L1_loss) on the inputs of
+    tests/test_patch_reference.py::test_losses_equal_the_reference: value and input gradient, float64 and float32."""
+    V = ref["SconeVis"]
+    g = torch.Generator().manual_seed(0)
+    out = {}
+    for si, shape in enumerate(((4, 52, 1), (1, 20, 1), (3, 7, 2))):
+        x = torch.rand(shape, generator=g, dtype=torch.float64) + 0.05
+        y = torch.rand(shape, generator=g, dtype=torch.float64) + 0.05
+        out[f"x{si}"], out[f"y{si}"] = x.numpy(), y.numpy()
+        for n in ("KLDivCE", "L1_loss", "Uncentered_L1_loss"):
+            for dt in (torch.float64, torch.float32):
+                xa = x.detach().clone().to(dt).requires_grad_(True)
+                a = getattr(V, n)()(xa, y.to(dt))
+                a.backward()
+                tag = f"{n}_{si}_{str(dt).split('.')[-1]}"
+                out[tag + "_loss"], out[tag + "_grad"] = a.detach().numpy(), xa.grad.numpy()
+    save("reference_losses", **out)
+
+GROUPS = {"losses": gen_losses, "masked": gen_masked, "trajectory": gen_trajectory, "decision": gen_decision, "occ_field": gen_occ_field, "formats": gen_formats, "e2e_grid": gen_e2e_grid, "fov": gen_fov, "distance": gen_distance, "wrapper": gen_macarons_wrapper, "single_camera": gen_single_camera, "cell": gen_cell, "unproject": gen_unproject, "viewspace": gen_viewspace, "filter": gen_filter, "macarons": gen_macarons, "e2e": gen_e2e, "view": gen_view, "scorer": gen_scorer, "sh": gen_sh, "knn": gen_knn, "blocks": gen_blocks, "vis": gen_vis, "occ": gen_occ}
 
 if __name__ == "__main__":
     todo = sys.argv[1:] or list(GROUPS)

@@ -1,5 +1,5 @@
 """Dev: GPU idle time inside one NBV step from a rocprofv3 kernel trace (csv): the holes in the union of the kernel intervals.
-    cd /tmp && rocprofv3 --kernel-trace --output-format csv -d out -o t -- python bench.py --steps 5 --warmup 2 --no-cpu-baseline --nbv-iters 20
+    rocprofv3 --kernel-trace --output-format csv -d out -o t -- python bench.py --steps 5 --warmup 2 --full --no-cpu-baseline --nbv-iters 20
     python tools/trace_gaps.py out/t_kernel_trace.csv"""
 import csv, sys
 rows = sorted(((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), r["Kernel_Name"]) for r in csv.DictReader(open(sys.argv[1]))))
