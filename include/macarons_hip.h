@@ -54,6 +54,22 @@ int mcr_sh_coverage_gain_best(const float* pts, int pts_dim, const float* harmon
 int mcr_sh_visibilities(const float* pts, int pts_dim, const float* harmonics, const float* cams, float* vis,
                         int64_t B, int64_t N, int64_t C, int use_sigmoid, void* stream);
 
+/* ---- K9 backward: gradients of the scorer ---------------------------------------------------------
+ * The backward of out = act(z),  z[b,c,n] = sum_k Y_k(dir(cams[b,c] - pts[b,n,:3])) * harmonics[b,n,k]  (the function of
+ * mcr_sh_coverage_gain / mcr_sh_visibilities).  grad is the upstream gradient: gains [B,C] (grad_per_pair = 0; the per-pair weight is
+ * grad[b,c] / N) or per-pair [B,C,N] (grad_per_pair != 0).  With s = act'(z) * weight (sigmoid: sigma (1 - sigma); relu: 1 where z > 0,
+ * 0 elsewhere, as torch's threshold_backward) and u = grad_d z, the gradient of z along the ray d = cams[b,c] - pts[b,n,:3]:
+ *   d_harm [B,N,64]      = sum_c s * Y(dir)
+ *   d_pts  [B,N,pts_dim] = -sum_c s * u   (channels >= 3 are 0)
+ *   d_cams [B,C,3]       = sum_n s * u
+ * An output pointer may be NULL: that gradient is neither computed nor written (d_harm alone skips the direction derivatives).
+ * workspace: mcr_sh_scorer_backward_workspace_bytes(B, N, C) bytes of device scratch.  Deterministic (fixed-order partial sums,
+ * no float atomics): two calls on the same inputs give bit-identical gradients. */
+size_t mcr_sh_scorer_backward_workspace_bytes(int64_t B, int64_t N, int64_t C);
+int mcr_sh_scorer_backward(const float* pts, int pts_dim, const float* harmonics, const float* cams, const float* grad, int grad_per_pair,
+                           int use_sigmoid, float* d_harm, float* d_pts, float* d_cams, int64_t B, int64_t N, int64_t C, void* workspace,
+                           size_t workspace_bytes, void* stream);
+
 /* ---- K1: k nearest surface points per query ---------------------------------------------------------
  * Replaces get_knn_points (macarons/utility/utils.py:1497-1509: torch.cdist + topk(largest=False) +
  * pytorch3d.ops.knn_gather) and, with subtract_query != 0, the offset step of SconeOcc.forward

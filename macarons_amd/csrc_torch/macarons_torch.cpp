@@ -9,6 +9,7 @@
 // torch on ROCm keeps the device type "cuda": the guard / stream accessors are the Masquerading-As-CUDA flavours of c10::hip
 #include <ATen/hip/impl/HIPGuardImplMasqueradingAsCUDA.h>
 #include <ATen/hip/impl/HIPStreamMasqueradingAsCUDA.h>
+#include <torch/csrc/autograd/custom_function.h>
 #include <torch/library.h>
 #include <hip/hip_runtime.h>
 #include <immintrin.h>
@@ -96,6 +97,62 @@ at::Tensor sh_visibilities(const at::Tensor& pts_, const at::Tensor& harm_, cons
     ok(mcr_sh_visibilities(pts.data_ptr<float>(), (int)P, harm.data_ptr<float>(), cams.data_ptr<float>(), vis.data_ptr<float>(), B, N, C,
                            use_sigmoid ? 1 : 0, stream_of(pts)), "mcr_sh_visibilities");
     return vis;
+}
+
+// Gradients of the two scorer operators (mcr_sh_scorer_backward) with respect to (harmonics, pts, cams); an undefined tensor for each one
+// not asked for.  grad: [B,C] (gains) or [B,C,N] (per_pair).
+std::tuple<at::Tensor, at::Tensor, at::Tensor> sh_scorer_backward(const at::Tensor& pts_, const at::Tensor& harm_, const at::Tensor& cams_,
+                                                                  const at::Tensor& grad_, bool per_pair, bool use_sigmoid, bool need_h,
+                                                                  bool need_p, bool need_c) {
+    const at::Tensor pts = f32(pts_, "pts"), harm = f32(harm_, "harmonics"), cams = f32(cams_, "cams"), grad = f32(grad_, "grad");
+    const int64_t B = pts.size(0), N = pts.size(1), P = pts.size(2), C = cams.size(1);
+    TORCH_CHECK(per_pair ? (grad.dim() == 3 && grad.size(0) == B && grad.size(1) == C && grad.size(2) == N)
+                         : (grad.dim() == 2 && grad.size(0) == B && grad.size(1) == C), "sh_scorer_backward: grad shape mismatch");
+    c10::hip::HIPGuardMasqueradingAsCUDA guard(pts.device());
+    at::Tensor dh = need_h ? at::empty({B, N, 64}, pts.options()) : at::Tensor();
+    at::Tensor dp = need_p ? at::empty({B, N, P}, pts.options()) : at::Tensor();
+    at::Tensor dc = need_c ? at::empty({B, C, 3}, pts.options()) : at::Tensor();
+    at::Tensor ws = scratch(pts, mcr_sh_scorer_backward_workspace_bytes(B, N, C));
+    auto ptr = [](at::Tensor& t) { return t.defined() ? t.data_ptr<float>() : nullptr; };
+    ok(mcr_sh_scorer_backward(pts.data_ptr<float>(), (int)P, harm.data_ptr<float>(), cams.data_ptr<float>(), grad.data_ptr<float>(),
+                              per_pair ? 1 : 0, use_sigmoid ? 1 : 0, ptr(dh), ptr(dp), ptr(dc), B, N, C, ws.data_ptr(), (size_t)ws.numel(),
+                              stream_of(pts)), "mcr_sh_scorer_backward");
+    return std::make_tuple(dh, dp, dc);
+}
+
+// The Autograd kernels of sh_coverage_gain and sh_visibilities: the forward redispatches below autograd (to the CUDA kernel above; CPU
+// tensors still find no kernel), the backward is mcr_sh_scorer_backward for the inputs that need a gradient.  The backward builds no graph:
+// the operators are differentiable once.
+template <bool PER_PAIR>
+struct ScorerFunction : public torch::autograd::Function<ScorerFunction<PER_PAIR>> {
+    static at::Tensor forward(torch::autograd::AutogradContext* ctx, const at::Tensor& pts, const at::Tensor& harm, const at::Tensor& cams,
+                              bool use_sigmoid) {
+        ctx->save_for_backward({pts, harm, cams});
+        ctx->saved_data["use_sigmoid"] = use_sigmoid;
+        at::AutoDispatchBelowADInplaceOrView below;
+        static auto op = c10::Dispatcher::singleton()
+                             .findSchemaOrThrow(PER_PAIR ? "macarons::sh_visibilities" : "macarons::sh_coverage_gain", "")
+                             .typed<at::Tensor(const at::Tensor&, const at::Tensor&, const at::Tensor&, bool)>();
+        return op.call(pts, harm, cams, use_sigmoid);
+    }
+    static torch::autograd::variable_list backward(torch::autograd::AutogradContext* ctx, torch::autograd::variable_list grad_out) {
+        TORCH_CHECK(!at::GradMode::is_enabled(), "macarons::", PER_PAIR ? "sh_visibilities" : "sh_coverage_gain",
+                    " is differentiable once: its backward builds no graph (create_graph is not supported)");
+        const auto saved = ctx->get_saved_variables();
+        const bool need_p = ctx->needs_input_grad(0), need_h = ctx->needs_input_grad(1), need_c = ctx->needs_input_grad(2);
+        if (!grad_out[0].defined() || !(need_h || need_p || need_c)) return {at::Tensor(), at::Tensor(), at::Tensor(), at::Tensor()};
+        auto [dh, dp, dc] = sh_scorer_backward(saved[0], saved[1], saved[2], grad_out[0], PER_PAIR, ctx->saved_data["use_sigmoid"].toBool(),
+                                               need_h, need_p, need_c);
+        return {dp, dh, dc, at::Tensor()};
+    }
+};
+
+at::Tensor sh_coverage_gain_autograd(const at::Tensor& pts, const at::Tensor& harm, const at::Tensor& cams, bool use_sigmoid) {
+    return ScorerFunction<false>::apply(pts, harm, cams, use_sigmoid);
+}
+
+at::Tensor sh_visibilities_autograd(const at::Tensor& pts, const at::Tensor& harm, const at::Tensor& cams, bool use_sigmoid) {
+    return ScorerFunction<true>::apply(pts, harm, cams, use_sigmoid);
 }
 
 // get_knn_points + the offset step (utils.py:1497-1509, SconeOcc.py:297-298) -> (offsets [B,Q,k,3], dists [B,Q,k], idx int64)
@@ -659,4 +716,11 @@ TORCH_LIBRARY_IMPL(macarons, CUDA, m) {
     m.impl("sample_proxy", &sample_proxy);
     m.impl("scone_vis_forward", &scone_vis_forward);
     m.impl("scone_occ_forward", &scone_occ_forward);
+}
+
+// sh_coverage_gain and sh_visibilities only: sh_coverage_gain_best (the benchmark's timed entry) and the network operators have no
+// Autograd kernel (the networks keep their composite backward, macarons_amd/autograd.py).
+TORCH_LIBRARY_IMPL(macarons, Autograd, m) {
+    m.impl("sh_coverage_gain", &sh_coverage_gain_autograd);
+    m.impl("sh_visibilities", &sh_visibilities_autograd);
 }

@@ -174,11 +174,8 @@ class SconeVis(RangeGuard, nn.Module):
         d = self._degenerate(pts, X_cam, reduced=False)
         if d is not None:
             return d
-        sig = self.use_sigmoid
-        hip = lambda p, h, c: self._scorer_ops().sh_visibilities(p, h, c, sig)
-        if A.needs_grad(None, pts, harmonics, X_cam):
-            return A.with_torch_backward(hip, lambda p, h, c: A.visibilities(p, h, c, sig), (pts, harmonics, X_cam))
-        return hip(pts, harmonics, X_cam)
+        # differentiable: the operator's Autograd kernel runs the HIP backward (mcr_sh_scorer_backward)
+        return self._scorer_ops().sh_visibilities(pts, harmonics, X_cam, self.use_sigmoid)
 
     def compute_coverage_gain(self, pts, harmonics, X_cam):
         """-> [n_clouds, n_camera_candidates]   (SconeVis.py:210-252)."""
@@ -186,11 +183,7 @@ class SconeVis(RangeGuard, nn.Module):
         d = self._degenerate(pts, X_cam, reduced=True)
         if d is not None:
             return d
-        sig = self.use_sigmoid
-        hip = lambda p, h, c: self._scorer_ops().sh_coverage_gain(p, h, c, sig)
-        if A.needs_grad(None, pts, harmonics, X_cam):
-            return A.with_torch_backward(hip, lambda p, h, c: A.coverage_gain(p, h, c, sig), (pts, harmonics, X_cam))
-        return hip(pts, harmonics, X_cam)
+        return self._scorer_ops().sh_coverage_gain(pts, harmonics, X_cam, self.use_sigmoid)
 
     def compute_coverage_gain_multiple(self, pts, harmonics, X_cam, n_cam):
         """Every ordered n_cam-tuple of cameras: mean over points of the max over the tuple (SconeVis.py:254-303)."""

@@ -136,6 +136,29 @@ def sh_visibilities(pts, harmonics, cams, use_sigmoid=True):
     return vis
 
 
+def sh_scorer_backward(pts, harmonics, cams, grad, per_pair, use_sigmoid=True, need=(True, True, True)):
+    """Gradients of sh_coverage_gain (per_pair False: grad [B,C]) or sh_visibilities (per_pair True: grad [B,C,N]) with respect to
+    (harmonics, pts, cams), as (d_harm [B,N,64], d_pts [B,N,P], d_cams [B,C,3]); `need` selects which are computed (None for the
+    others).  mcr_sh_scorer_backward: deterministic, HIP kernels only."""
+    pts, harmonics, cams, B, N, P, C = _scorer_args(pts, harmonics, cams)
+    grad = _req(grad, "grad")                       # .contiguous(): x.sum().backward() hands in an expanded, zero-stride tensor
+    want = (B, C, N) if per_pair else (B, C)
+    if tuple(grad.shape) != want:
+        raise ValueError(f"grad must be {list(want)}, got {tuple(grad.shape)}")
+    need_h, need_p, need_c = (bool(x) for x in need)
+    d_harm = torch.empty((B, N, 64), dtype=torch.float32, device=pts.device) if need_h else None
+    d_pts = torch.empty((B, N, P), dtype=torch.float32, device=pts.device) if need_p else None
+    d_cams = torch.empty((B, C, 3), dtype=torch.float32, device=pts.device) if need_c else None
+    L = lib()
+    ws = _workspace(pts.device, max(int(L.mcr_sh_scorer_backward_workspace_bytes(c_i64(B), c_i64(N), c_i64(C))), 4))
+    ptr = lambda t: _p(t) if t is not None else c_vp(None)
+    with torch.cuda.device(pts.device):
+        check(L.mcr_sh_scorer_backward(_p(pts), c_int(P), _p(harmonics), _p(cams), _p(grad), c_int(int(bool(per_pair))),
+                                       c_int(int(bool(use_sigmoid))), ptr(d_harm), ptr(d_pts), ptr(d_cams), c_i64(B), c_i64(N), c_i64(C),
+                                       _p(ws), c_size(ws.numel()), _stream()), "mcr_sh_scorer_backward")
+    return d_harm, d_pts, d_cams
+
+
 # ---- K1 kNN ----------------------------------------------------------------------------------------
 def knn_points(X, pc, k, subtract_query=False):
     """(pts [B,Q,k,3], dists [B,Q,k], idx [B,Q,k] int64); replaces utils.get_knn_points (utils.py:1497-1509);
