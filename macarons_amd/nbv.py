@@ -68,8 +68,10 @@ def _guarded(impl, scone_occ, range_guard, group, draws, device, scone_vis=None)
         scone_vis.range_guard = scone_occ.range_guard
     try:
         # the flag exists on every rank before the step (not only on ranks that run a guarded forward: a rank with an empty query
-        # shard runs none), so that whether the all-reduce below is entered depends on rank-invariant state only
-        scone_occ.clear_range_flag(device if guard else None)
+        # shard runs none), so that whether the all-reduce below is entered depends on rank-invariant state only; and whenever the
+        # step reports it (range_guard=False too), so that SconeVis writes into it rather than into a flag of its own
+        flagged = scone_occ.range_guard != "off" and ops.current_variant() in (6, 7)
+        scone_occ.clear_range_flag(device if flagged else None)
         if vis_prev is not None:
             scone_vis._range_flag = scone_occ.range_flag()
         kw = draws() if (guard and not capturing) else {}

@@ -172,14 +172,6 @@ class SconeOcc(RangeGuard, nn.Module):
         self._range_pending = []            # (pinned host int32 [1], event) of forwards whose flag has not been looked at yet
         self._full_range = False            # True once an overflow was seen: variant 5 from then on
 
-    def _effective_guard(self):
-        """range_guard, except under stream capture: a read-back ("sync") or a host copy ("async") cannot be part of a graph, so a
-        captured forward leaves the flag in range_flag() ("defer") for whoever replays the graph to look at."""
-        g = self.range_guard
-        if g in ("sync", "async") and torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
-            return "defer"
-        return g
-
     def freeze_weight_caches(self, on=True):
         """Inference mode: fingerprint the parameters once, now, and trust them unchanged until freeze_weight_caches(False) or
         invalidate_weight_caches() (an optimizer step or load_state_dict in between would go unnoticed: opt-in)."""
@@ -440,7 +432,7 @@ class SconeOcc(RangeGuard, nn.Module):
             perms = self.draw_perms(full_seq_len)
         dev = pc.device
         L = _lib.lib()
-        if self.range_guard == "async" and (self._range_pending or self._full_range):
+        if self._effective_guard() == "async" and (self._range_pending or self._full_range):
             self.check_range()
         if self._full_range and ops.current_variant() in (6, 7):        # an earlier forward overflowed the fp16 split: full range from now on
             with ops.variant(5):

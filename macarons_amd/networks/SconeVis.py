@@ -123,25 +123,27 @@ class SconeVis(RangeGuard, nn.Module):
         # a stand-alone forward never returns non-finite harmonics; "defer": left in range_flag() (nbv_step and macarons_nbv_decision
         # share SconeOcc's flag and read it once per decision); "async" (opt-in): looked at without a stall by a later forward /
         # check_range(); "off": nothing.
-        if self.range_guard == "async" and (self._range_pending or self._full_range):
+        if self._effective_guard() == "async" and (self._range_pending or self._full_range):
             self.check_range()
         if self._full_range and ops.current_variant() in (6, 7):
             with ops.variant(5):
                 return self.forward(pts, mask, view_harmonics, lengths)
-        guarded = ops.current_variant() in (6, 7) and seq_len >= 512 and self.range_guard != "off" and not torch.cuda.is_current_stream_capturing()
+        # (under stream capture "sync" / "async" act as "defer": the flag kernel stays in the graph, the read-back does not)
+        guard = self._effective_guard()
+        guarded = ops.current_variant() in (6, 7) and seq_len >= 512 and guard != "off"
 
         def hip(p, vh):
             res_ = ops.scone_vis_forward(p, vh, self._table_cache.get(self, self.weight_table_with_planes), lengths)
             if guarded:
                 if self._range_flag is None or self._range_flag.device != p.device:
                     self._range_flag = torch.zeros(1, dtype=torch.int32, device=p.device)
-                elif self.range_guard in ("sync", "async"):
+                elif guard in ("sync", "async"):
                     self._range_flag.zero_()
                 ops.nonfinite_flag_(res_, self._range_flag)
-                if self.range_guard == "sync" and int(self._range_flag):
+                if guard == "sync" and int(self._range_flag):
                     with ops.variant(5):
                         res_ = ops.scone_vis_forward(p, vh, self._table_cache.get(self, self.weight_table_with_planes), lengths)
-                elif self.range_guard == "async":
+                elif guard == "async":
                     self._post_range_check(self._range_flag)
             return res_
         if A.needs_grad(self, pts, view_harmonics):     # trainers (pretrain_scone_vis.py:224): HIP forward, composite-torch backward

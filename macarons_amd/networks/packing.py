@@ -369,6 +369,14 @@ class RangeGuard:
         guarded forward)."""
         return self._range_flag
 
+    def _effective_guard(self):
+        """range_guard, except under stream capture: a read-back ("sync") or a host copy ("async") cannot be part of a graph, so a
+        captured forward leaves the flag in range_flag() ("defer") for whoever replays the graph to look at."""
+        g = self.range_guard
+        if g in ("sync", "async") and torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
+            return "defer"
+        return g
+
     def _post_range_check(self, flag):
         """"async" guard: queue a copy of the flag to pinned host memory behind the forward's kernels (no stall)."""
         host = torch.empty(1, dtype=torch.int32).pin_memory() if not self._range_pool else self._range_pool.pop()

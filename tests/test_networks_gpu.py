@@ -857,4 +857,4 @@ def test_stand_alone_forwards_can_be_captured_under_the_default_guard(dev):
         graph.replay()
         torch.cuda.synchronize()
     assert torch.equal(y_g, y_e) and torch.equal(h_g, h_e)
-    assert int(occ.range_flag()) == 0
+    assert int(occ.range_flag()) == 0 and int(vis.range_flag()) == 0
