@@ -140,6 +140,35 @@ int mcr_attention_planes(const float* qkv, int64_t ldq, float* out, int64_t ldo,
 int mcr_colmax_broadcast(const float* X, int64_t ldx, float* Y, int64_t ldy, int64_t S, int64_t L, int E, void* stream);
 int mcr_pool_max_avg(const float* X, int64_t ldx, float* Y, int64_t ldy, int64_t S, int64_t L, int E, void* stream);
 
+/* ---- backward building blocks (scone_vis_bwd.hip): fp32, deterministic (no float atomics; fixed-order sums) ----------------------
+ * mcr_attention_backward: gradient of mcr_attention's output (with lens as mcr_attention_planes: keys of sequence s = its first
+ *   min(L, max(1, lens[s])) rows; lens may be NULL) with respect to the packed rows: d_qkv [S*L, ld_dqkv] <- [dq | dk | dv] given
+ *   d_out [S*L, ld_dout].  Per-head widths 16 (q, k) and 64 (v) only.  The forward is recomputed (O and the log-sum-exp of every
+ *   (row, head)); P is rebuilt tile by tile and never stored.  Keys no query attends to get a zero gradient.  Leading dimensions
+ *   multiples of 4, operands 16-byte aligned.  workspace: mcr_attention_backward_workspace_bytes(S, L, n_heads, v_dim).
+ * mcr_linear_backward: for Y = act(X W^T + b), act = exact-erf GELU (gelu != 0; Z = the pre-activation X W^T + b, [M, N] with
+ *   leading dimension ldz) or identity (Z unused): dX[M, K] = dZ W (added to dX when accumulate_dx, else written), dW[N, K] = dZ^T X,
+ *   db[N] = sum over rows of dZ, dZ = dY * act'(Z).  dX, dW, db may each be NULL.  workspace: mcr_linear_backward_workspace_bytes.
+ * mcr_layernorm_backward: for Y = LayerNorm(X) (eps 1e-5): dX (+)= the input gradient, d_gamma, d_beta [E] (each may be NULL).
+ *   E in {64, 128, 256, 512}.  workspace: mcr_layernorm_backward_workspace_bytes(M, E).
+ * mcr_colmax_backward: for mcr_colmax_broadcast (lens as above, may be NULL: the max over the first lens[s] rows): for every
+ *   (sequence, column c < E) dX[row*, c] += sum over ALL L rows of d_bcast[row, c], row* = the lowest valid row holding the max
+ *   (torch.max(dim)'s choice on ties). */
+size_t mcr_attention_backward_workspace_bytes(int64_t S, int64_t L, int n_heads, int v_dim);
+int mcr_attention_backward(const float* qkv, int64_t ldq, const float* d_out, int64_t ld_dout, float* d_qkv, int64_t ld_dqkv, int64_t S,
+                           int64_t L, int n_heads, int qk_dim, int v_dim, const int* lens, void* workspace, size_t workspace_bytes,
+                           void* stream);
+size_t mcr_linear_backward_workspace_bytes(int64_t M, int N, int K);
+int mcr_linear_backward(const float* X, int64_t ldx, const float* W, const float* Z, int64_t ldz, const float* dY, int64_t ldy, int64_t M,
+                        int N, int K, int gelu, float* dX, int64_t ld_dx, int accumulate_dx, float* dW, float* db, void* workspace,
+                        size_t workspace_bytes, void* stream);
+size_t mcr_layernorm_backward_workspace_bytes(int64_t M, int E);
+int mcr_layernorm_backward(const float* X, int64_t ldx, const float* gamma, const float* dY, int64_t ldy, int64_t M, int E, float* dX,
+                           int64_t ld_dx, int accumulate_dx, float* d_gamma, float* d_beta, void* workspace, size_t workspace_bytes,
+                           void* stream);
+int mcr_colmax_backward(const float* X, int64_t ldx, const float* d_bcast, int64_t ldg, float* dX, int64_t ld_dx, int64_t S, int64_t L,
+                        int E, const int* lens, void* stream);
+
 /* ---- network forwards -----------------------------------------------------------------------------------
  * Weight tables are arrays of device pointers to contiguous fp32 tensors in nn.Module layout ([out,in] weights):
  *   ENCODER (12): norm1.weight, norm1.bias, qkv.weight, qkv.bias, out.weight, out.bias, norm2.weight, norm2.bias,
@@ -187,6 +216,19 @@ size_t mcr_scone_vis_workspace_bytes(int64_t B, int64_t N);
 int mcr_scone_vis_forward(const float* pts, const float* view_harmonics, float* out, int64_t B, int64_t N,
                           const float* const* weights, int n_weights, const int* lengths, void* workspace,
                           size_t workspace_bytes, void* stream);
+/* mcr_scone_vis_backward: gradient of mcr_scone_vis_forward (same arguments) given d_out [B,N,64], computed on the fp32 network
+ *   whatever the call's variant (on variants 6 and 7 it is the gradient of the fp32 network at the same inputs; the fp16 planes
+ *   path is never used, so no range guard applies).  The forward is recomputed: the residual stream at the four encoder boundaries
+ *   and the embedding / head pre-activations are kept, each encoder's interior is rebuilt just before its backward.
+ *   weights: the SCONE_VIS table (48 entries; a PLANES / END PLANES tail is accepted and ignored).
+ *   d_weights (may be NULL: no parameter gradients): 48 DEVICE pointers in the table's order and shapes (the packed qkv weight
+ *   [384,256] and bias [384] one entry each); written, not accumulated.  d_pts [B,N,4] and d_view_harmonics [B,N,64] may be NULL.
+ *   lengths: as the forward; padded rows keep their outputs and their upstream gradient flows like any other row's.
+ *   workspace: mcr_scone_vis_backward_workspace_bytes(B, N) bytes.  Deterministic (no float atomics), no host synchronisation. */
+size_t mcr_scone_vis_backward_workspace_bytes(int64_t B, int64_t N);
+int mcr_scone_vis_backward(const float* pts, const float* view_harmonics, const float* d_out, int64_t B, int64_t N,
+                           const float* const* weights, int n_weights, const int* lengths, float* const* d_weights, float* d_pts,
+                           float* d_view_harmonics, void* workspace, size_t workspace_bytes, void* stream);
 size_t mcr_scone_occ_workspace_bytes(int64_t B, int64_t Q, int64_t Lg);
 int mcr_scone_occ_forward(const float* pc_global, int64_t Lg, const float* const* pc_scale, const int64_t* M_scale,
                           const float* x, const float* view_harmonics, float* out, int64_t B, int64_t Q,

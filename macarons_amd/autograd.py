@@ -1,17 +1,20 @@
 """Gradients for the trainers (`loss.backward()` through SconeVis.forward / compute_coverage_gain at
 macarons/trainers/pretrain_scone_vis.py:224, through SconeOcc.forward at pretrain_scone_occ.py, train_macarons.py:1159-1162).
 
-The forward passes stay on the hand-written HIP kernels.  Each entry point is wrapped in a torch.autograd.Function whose
-backward RECOMPUTES the same mathematics with plain torch ops on the same device (composite functions below, written against
-the modules' own parameters) under autograd and back-propagates through that: no HIP backward kernels, no activations kept
-between forward and backward.  The composites are ordinary differentiable torch code, so they are also what the parity tests
-differentiate numerically (tests/test_autograd.py: fp64 finite differences on CPU; on the GPU the composite forward must
-reproduce the HIP forward to 1e-4, which makes its gradient the gradient of the kernels' function).
+The forward passes stay on the hand-written HIP kernels.  SconeVis.forward's backward is HIP too (SconeVisFunction below:
+mcr_scone_vis_backward, scone_vis_bwd.hip), as is the scorer's (the Autograd kernels of torch.ops.macarons.sh_coverage_gain /
+sh_visibilities).  SconeOcc's entry point is still wrapped in a torch.autograd.Function whose backward RECOMPUTES the same
+mathematics with plain torch ops on the same device (composite functions below, written against the modules' own parameters) under
+autograd and back-propagates through that; env MCR_SCONE_VIS_BWD=composite puts SconeVis back on that path (A/B).  The composites
+are ordinary differentiable torch code, so they are also what the parity tests differentiate numerically (tests/test_autograd.py:
+fp64 finite differences on CPU; on the GPU the composite forward must reproduce the HIP forward to 1e-4, which makes its gradient
+the gradient of the kernels' function) and the second reference of the HIP backward's tests.
 
 The k-nearest-neighbour indices of SconeOcc are taken from the HIP forward (the selection is piecewise constant: no gradient
 flows through it, exactly as with torch.topk indices in the reference, utils.py:1505-1509).
 """
 import math
+import os
 
 import torch
 import torch.nn.functional as F
@@ -180,3 +183,42 @@ def with_torch_backward(hip_fn, torch_fn, inputs, module=None):
     """Run hip_fn(*inputs); if a gradient is needed, make the result differentiable through torch_fn(*inputs)."""
     params = tuple(module.parameters()) if module is not None else ()
     return _HipForwardTorchBackward.apply(hip_fn, torch_fn, len(inputs), *inputs, *params)
+
+
+# ---- SconeVis: HIP forward + HIP backward ----------------------------------------------------------------------------------------
+def scone_vis_backward_mode():
+    """'hip' (default) or 'composite' (env MCR_SCONE_VIS_BWD=composite: the recomputing torch backward above, for A/B comparisons)."""
+    return "composite" if os.environ.get("MCR_SCONE_VIS_BWD", "").lower() == "composite" else "hip"
+
+
+class SconeVisFunction(torch.autograd.Function):
+    """apply(hip_fn, table_fn, slots, lengths, pts, view_harmonics, *params): forward = hip_fn(pts, view_harmonics) without a graph;
+    backward = ops.scone_vis_backward (mcr_scone_vis_backward: the gradient of the fp32 network, HIP kernels only) on the weight
+    table table_fn() returns.  slots[j] = (table index, row slice or None) of params[j] -- the packed qkv entries hand rows 0:64,
+    64:128 and 128:384 to w_q, w_k and w_v.  Differentiable once."""
+
+    @staticmethod
+    def forward(ctx, hip_fn, table_fn, slots, lengths, pts, view_harmonics, *params):
+        ctx.table_fn, ctx.slots, ctx.lengths = table_fn, slots, lengths
+        ctx.save_for_backward(pts, view_harmonics)
+        with torch.no_grad():
+            return hip_fn(pts, view_harmonics)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        if torch.is_grad_enabled():
+            raise RuntimeError("SconeVis.forward is differentiable once: its HIP backward builds no graph (create_graph is not supported)")
+        from . import ops
+        pts, vh = ctx.saved_tensors
+        need_p, need_v = ctx.needs_input_grad[4], ctx.needs_input_grad[5]
+        need_w = any(ctx.needs_input_grad[6:])
+        d_w, d_pts, d_vh = ops.scone_vis_backward(pts, vh, grad_out, ctx.table_fn(), ctx.lengths, need=(need_w, need_p, need_v))
+        grads = []
+        for j, (idx, rows) in enumerate(ctx.slots):
+            if not ctx.needs_input_grad[6 + j]:
+                grads.append(None)
+                continue
+            g = d_w[idx] if rows is None else d_w[idx][rows[0]:rows[1]]
+            grads.append(g)
+        return (None, None, None, None, d_pts.to(pts.dtype) if d_pts is not None else None,
+                d_vh.to(vh.dtype) if d_vh is not None else None, *grads)

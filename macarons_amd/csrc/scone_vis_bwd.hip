@@ -1,0 +1,1013 @@
+// SconeVis backward for gfx950 (MI355X): gradients of SconeVis.forward (macarons/networks/SconeVis.py:121-162, default architecture)
+// with respect to its 48 weight-table tensors, pts and view_harmonics, for the trainers' loss.backward() (pretrain_scone_vis.py:224,
+// train_macarons.py:1159-1162).
+//
+// mcr_scone_vis_backward recomputes the forward of the fp32 network, keeping the residual stream at the four encoder boundaries and
+// the pre-activations of the embedding and the head, then runs the backward in reverse order.  Each encoder's interior (LN1 output,
+// qkv, attention output O and its log-sum-exp, post-attention residual, LN2 output, FF pre-activation and GELU) is rebuilt from its
+// boundary just before that encoder's backward, in one region the three encoders share: one extra forward in all, one encoder's
+// interior in memory.
+//
+// Building blocks (each behind its own C entry point, include/macarons_hip.h):
+//   attention   flash-style: a stash-writing forward (O and LSE per (row, head)), then a query-major pass for dQ (and
+//               delta = rowsum(dO * O)) and a key-major pass for dK, dV.  P = exp(S - LSE) is recomputed tile by tile; nothing
+//               N x N is ever stored.  One lane owns one query (or key) row of one head; the 4 waves of a block share the row
+//               block and split the other side's rows, their partial results meet in LDS in a fixed order.
+//   linear      dZ = dY * GELU'(Z) (exact erf: Phi(z) + z phi(z)); dX = dZ W (written or added) on the forward's exact-fp32 MFMA GEMM
+//               through a transposed weight copy; dW | db = dZ^T [X | 1] as a VALU split-K GEMM whose slabs are summed in a fixed order.
+//   layernorm   per row mu, sigma recomputed (eps 1e-5); dx added into (or written to) the residual gradient; d_gamma | d_beta as
+//               per-block column partials summed in a fixed order.
+//   column max  the arg-max valid row of each column (ties: the lowest row, as torch.max(dim)) receives the column's gradient
+//               summed over all rows.
+// Numerics: fp32 throughout -- VALU FMA in the attention and weight-gradient kernels, the forward's exact-fp32 GEMM kernels
+// (launch_linear routed to the fp32 MFMA kernel) in the recompute and the dX products.  The fp16 planes path is never taken, whatever the caller's variant: the result is the gradient of
+// the fp32 network at the given inputs (on variants 6 and 7 too).  No float atomics: two calls give identical bits.
+#include "nn_kernels.h"
+#include <algorithm>
+#include <cmath>
+
+namespace mcr {
+
+namespace {
+
+typedef float f2 __attribute__((ext_vector_type(2)));
+
+constexpr int VB_E = 256, VB_F = 126, VB_NW = 48, VB_H = 4;
+constexpr int AB_DQK = 16, AB_DV = 64;                 // per-head q / k and v widths of the attention kernels
+constexpr int AB_TILE = 32;                            // keys (queries) staged per wave and step
+constexpr float AB_SCALE = 0.25f;                      // 1 / sqrt(16)
+
+__device__ __forceinline__ float gelu_f(float z) { return 0.5f * z * (1.0f + erff(z * 0.70710678118654752f)); }
+__device__ __forceinline__ float gelu_d(float z) {
+    return 0.5f * (1.0f + erff(z * 0.70710678118654752f)) + z * 0.39894228040143268f * __expf(-0.5f * z * z);
+}
+
+// ---- elementwise ------------------------------------------------------------------------------------------------------------------
+// mode 0: Y = gelu(Z);  mode 1: Y *= gelu'(Z)
+__global__ __launch_bounds__(256) void vb_gelu_kernel(const float* __restrict__ Z, long long ldz, float* Y, long long ldy, long long M,
+                                                      int C, int mode) {
+    const long long n = M * C;
+    for (long long e = blockIdx.x * 256ll + threadIdx.x; e < n; e += (long long)gridDim.x * 256) {
+        const long long m = e / C;
+        const int c = (int)(e - m * C);
+        const float z = Z[m * ldz + c];
+        float* y = Y + m * ldy + c;
+        *y = mode == 0 ? gelu_f(z) : *y * gelu_d(z);
+    }
+}
+
+void launch_gelu(hipStream_t s, const float* Z, int64_t ldz, float* Y, int64_t ldy, int64_t M, int C, int mode) {
+    const long long n = M * C;
+    if (n <= 0) return;
+    hipLaunchKernelGGL(vb_gelu_kernel, dim3((unsigned)std::min<long long>(cdiv(n, 256), 8192)), dim3(256), 0, s, Z, (long long)ldz, Y,
+                       (long long)ldy, (long long)M, C, mode);
+}
+
+// ---- weight-gradient GEMM: C[i*ldc + j] = sum_p A[i + p*ap] * B'(p, j),  B'(p, j) = B[p*bp + j] for j < nb, 1 for j == nb ------------
+// 64 x 64 tiles, 256 threads of 4 x 4 outputs, depth-16 LDS steps.  blockIdx.z: the K slab [z * p_chunk, (z + 1) * p_chunk) whose sum
+// goes to C + z * split_stride (split-K; the slabs are added in order by vb_reduce_kernel).  The ones column (nb < Nj) turns
+// dW = dZ^T X into [dW | db] in one product.
+__global__ __launch_bounds__(256) void vb_gemm_kernel(const float* __restrict__ A, long long ap, const float* __restrict__ B, long long bp,
+                                                      int nb, float* C, long long ldc, long long split_stride, int Mi, int Nj, long long P,
+                                                      long long p_chunk) {
+    __shared__ alignas(16) float As[16][68];                      // (read as float4 below)
+    __shared__ alignas(16) float Bs[16][68];
+    const int t = threadIdx.x, tx = t & 15, ty = t >> 4;
+    const int i0 = blockIdx.x * 64, j0 = blockIdx.y * 64;
+    const long long pb = (long long)blockIdx.z * p_chunk, pe = std::min(P, pb + p_chunk);
+    C += (long long)blockIdx.z * split_stride;
+    f2 acc[4][2];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) acc[r][0] = acc[r][1] = f2{0.f, 0.f};
+    for (long long p0 = pb; p0 < pe; p0 += 16) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int e = t + 256 * r;
+            const int pp = e >> 6, ii = e & 63;
+            const long long p = p0 + pp;
+            const int i = i0 + ii;
+            As[pp][ii] = (p < pe && i < Mi) ? A[i + p * ap] : 0.f;
+            const int jj = e & 63, qp = e >> 6;
+            const long long q = p0 + qp;
+            const int j = j0 + jj;
+            Bs[qp][jj] = (q < pe && j < Nj) ? (j < nb ? B[q * bp + j] : 1.f) : 0.f;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int k = 0; k < 16; ++k) {
+            const float4 a = *reinterpret_cast<const float4*>(&As[k][ty * 4]);
+            const float4 b = *reinterpret_cast<const float4*>(&Bs[k][tx * 4]);
+            const f2 b01{b.x, b.y}, b23{b.z, b.w};
+            const float av[4] = {a.x, a.y, a.z, a.w};
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const f2 ar{av[r], av[r]};
+                acc[r][0] = __builtin_elementwise_fma(ar, b01, acc[r][0]);
+                acc[r][1] = __builtin_elementwise_fma(ar, b23, acc[r][1]);
+            }
+        }
+        __syncthreads();
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const int i = i0 + ty * 4 + r;
+        if (i >= Mi) continue;
+        const float v[4] = {acc[r][0].x, acc[r][0].y, acc[r][1].x, acc[r][1].y};
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            const int j = j0 + tx * 4 + c;
+            if (j < Nj) C[(long long)i * ldc + j] = v[c];
+        }
+    }
+}
+
+// out[n*ldo + k] = sum_z part[z*stride + n*ldp + k] for k < kw, out_b[n] = the same at k == kw (when ldp > kw).  One block = 16
+// outputs x 16 slab lanes; lane l adds slabs l, l + 16, ... and the 16 lane sums meet in a fixed tree: a fixed order throughout.
+__global__ __launch_bounds__(256) void vb_reduce_kernel(const float* __restrict__ part, long long stride, int n_part, long long n_out,
+                                                        int ldp, int kw, float* out, long long ldo, float* out_b) {
+    __shared__ float red[16][17];
+    const int o = threadIdx.x & 15, l = threadIdx.x >> 4;
+    const long long e = blockIdx.x * 16ll + o;
+    float acc = 0.f;
+    if (e < n_out)
+        for (int z = l; z < n_part; z += 16) acc += part[z * stride + e];
+    red[l][o] = acc;
+    __syncthreads();
+    for (int w = 8; w > 0; w >>= 1) {
+        if (l < w) red[l][o] += red[l + w][o];
+        __syncthreads();
+    }
+    if (l == 0 && e < n_out) {
+        const long long n = e / ldp;
+        const int k = (int)(e - n * ldp);
+        if (k < kw) {
+            if (out) out[n * ldo + k] = red[0][o];
+        } else if (out_b) {
+            out_b[n] = red[0][o];
+        }
+    }
+}
+
+void launch_reduce(hipStream_t s, const float* part, long long stride, int n_part, long long n_out, int ldp, int kw, float* out, long long ldo,
+                   float* out_b) {
+    hipLaunchKernelGGL(vb_reduce_kernel, dim3((unsigned)cdiv(n_out, 16)), dim3(256), 0, s, part, stride, n_part, n_out, ldp, kw, out, ldo,
+                       out_b);
+}
+
+// K slabs of the weight-gradient products: a function of the row count alone (determinism), at most 64 slabs
+inline long long vb_slab_rows(int64_t M) { return std::max<long long>(256, cdiv(cdiv(M, 64), 16) * 16); }
+inline long long vb_slabs(int64_t M) { return cdiv(M, vb_slab_rows(M)); }
+inline size_t vb_gradw_floats(int64_t M, int N, int K) { return (size_t)vb_slabs(M) * N * (K + 1); }
+
+// Wt[k*N + n] = W[n*ldw + k]   (n < N, k < K)
+__global__ __launch_bounds__(256) void vb_transpose_kernel(const float* __restrict__ W, long long ldw, float* __restrict__ Wt, int N, int K) {
+    const long long e = blockIdx.x * 256ll + threadIdx.x;
+    if (e >= (long long)N * K) return;
+    const int k = (int)(e / N), n = (int)(e - (long long)k * N);
+    Wt[e] = W[n * ldw + k];
+}
+
+// dX[M, K] (= or +=) dZ[M, N] W[N, K]: the forward's exact-fp32 MFMA GEMM (launch_linear, routed on one row: never the split-precision
+// kernels) on a transposed copy of W in wt (N * K floats); accumulate = the GEMM's residual operand, in place
+void gemm_dx(hipStream_t s, const float* dZ, int64_t ldz, const float* W, int64_t ldw, float* dX, int64_t ldx, int64_t M, int N, int K,
+             bool accumulate, float* wt) {
+    hipLaunchKernelGGL(vb_transpose_kernel, dim3((unsigned)cdiv((int64_t)N * K, 256)), dim3(256), 0, s, W, (long long)ldw, wt, N, K);
+    launch_linear(s, dZ, ldz, wt, nullptr, accumulate ? dX : nullptr, ldx, dX, ldx, M, K, N, ACT_NONE, nullptr, 0, N, 1);
+}
+
+// dW[N, K] = dZ^T X, db[N] = sum_rows dZ (either may be NULL); part: vb_gradw_floats(M, N, K) floats
+void gemm_dw(hipStream_t s, const float* dZ, int64_t ldz, const float* X, int64_t ldx, int64_t M, int N, int K, float* dW, float* db,
+             float* part) {
+    if (!dW && !db) return;
+    const long long rows = vb_slab_rows(M), slabs = vb_slabs(M);
+    const long long stride = (long long)N * (K + 1);
+    dim3 grid((unsigned)cdiv(N, 64), (unsigned)cdiv(K + 1, 64), (unsigned)slabs);
+    hipLaunchKernelGGL(vb_gemm_kernel, grid, dim3(256), 0, s, dZ, (long long)ldz, X, (long long)ldx, K, part, (long long)(K + 1), stride, N,
+                       K + 1, (long long)M, rows);
+    launch_reduce(s, part, stride, (int)slabs, stride, K + 1, K, dW, K, db);
+}
+
+// ---- LayerNorm backward: one wave per row, 4 waves per block of `rows` rows ------------------------------------------------------------
+// dX (= or +=) rstd (g - mean(g) - xhat mean(g xhat)), g = dY gamma;  part[blk][c][0 | 1] = sum over the block's rows of dY xhat | dY
+template <int CPL>
+__global__ __launch_bounds__(256) void vb_ln_bwd_kernel(const float* __restrict__ X, long long ldx, const float* __restrict__ gamma,
+                                                        const float* __restrict__ dY, long long ldy, float* dX, long long ldd, int accumulate,
+                                                        float* part, long long M, int rows) {
+    constexpr int E = CPL * 64;
+    __shared__ float red[3][2][E];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const long long r0 = (long long)blockIdx.x * rows, r1 = std::min<long long>(M, r0 + rows);
+    const float inv_e = 1.0f / (float)E;
+    float gam[CPL], pg[CPL], pb[CPL];
+#pragma unroll
+    for (int j = 0; j < CPL; ++j) { gam[j] = gamma[lane + 64 * j]; pg[j] = 0.f; pb[j] = 0.f; }
+    for (long long r = r0 + w; r < r1; r += 4) {
+        float x[CPL], dy[CPL];
+        float sx = 0.f;
+#pragma unroll
+        for (int j = 0; j < CPL; ++j) { x[j] = X[r * ldx + lane + 64 * j]; dy[j] = dY[r * ldy + lane + 64 * j]; sx += x[j]; }
+        const float mean = wave_sum_all(sx) * inv_e;
+        float sv = 0.f;
+#pragma unroll
+        for (int j = 0; j < CPL; ++j) { const float d = x[j] - mean; sv = fmaf(d, d, sv); }
+        const float rstd = 1.0f / sqrtf(wave_sum_all(sv) * inv_e + 1e-5f);
+        float s1 = 0.f, s2 = 0.f, xh[CPL], g[CPL];
+#pragma unroll
+        for (int j = 0; j < CPL; ++j) {
+            xh[j] = (x[j] - mean) * rstd;
+            g[j] = dy[j] * gam[j];
+            s1 += g[j];
+            s2 = fmaf(g[j], xh[j], s2);
+            pg[j] = fmaf(dy[j], xh[j], pg[j]);
+            pb[j] += dy[j];
+        }
+        s1 = wave_sum_all(s1) * inv_e;
+        s2 = wave_sum_all(s2) * inv_e;
+#pragma unroll
+        for (int j = 0; j < CPL; ++j) {
+            const float dx = rstd * (g[j] - s1 - xh[j] * s2);
+            float* o = dX + r * ldd + lane + 64 * j;
+            *o = accumulate ? *o + dx : dx;
+        }
+    }
+    if (w > 0)
+#pragma unroll
+        for (int j = 0; j < CPL; ++j) { red[w - 1][0][lane + 64 * j] = pg[j]; red[w - 1][1][lane + 64 * j] = pb[j]; }
+    __syncthreads();
+    if (w == 0) {
+        float* pp = part + (long long)blockIdx.x * E * 2;
+#pragma unroll
+        for (int j = 0; j < CPL; ++j) {
+            const int c = lane + 64 * j;
+            pp[2 * c] = ((pg[j] + red[0][0][c]) + red[1][0][c]) + red[2][0][c];
+            pp[2 * c + 1] = ((pb[j] + red[0][1][c]) + red[1][1][c]) + red[2][1][c];
+        }
+    }
+}
+
+inline int vb_ln_rows(int64_t M) { return (int)std::max<long long>(16, cdiv(cdiv(M, 256), 4) * 4); }
+inline size_t vb_ln_part_floats(int64_t M, int E) { return (size_t)cdiv(M, vb_ln_rows(M)) * E * 2; }
+
+void launch_ln_bwd(hipStream_t s, const float* X, int64_t ldx, const float* gamma, const float* dY, int64_t ldy, float* dX, int64_t ldd,
+                   bool accumulate, float* d_gamma, float* d_beta, float* part, int64_t M, int E) {
+    const int rows = vb_ln_rows(M);
+    const long long blocks = cdiv(M, rows);
+#define MCR_LNB(C) hipLaunchKernelGGL(vb_ln_bwd_kernel<C>, dim3((unsigned)blocks), dim3(256), 0, s, X, (long long)ldx, gamma, dY, (long long)ldy, \
+                                      dX, (long long)ldd, (int)accumulate, part, (long long)M, rows)
+    switch (E) {
+        case 64: MCR_LNB(1); break;
+        case 128: MCR_LNB(2); break;
+        case 256: MCR_LNB(4); break;
+        default: MCR_LNB(8); break;
+    }
+#undef MCR_LNB
+    if (d_gamma || d_beta) launch_reduce(s, part, (long long)E * 2, (int)blocks, (long long)E * 2, 2, 1, d_gamma, 1, d_beta);
+}
+
+// ---- column-max backward ---------------------------------------------------------------------------------------------------------
+// dX[(s*L + r*)*ldd + c] += sum_r dG[(s*L + r)*ldg + c], r* = the lowest valid row holding the column's max.  Block: 64 columns x 16
+// row slices of one sequence; the slices meet in LDS in a fixed order.
+__global__ __launch_bounds__(1024) void vb_colmax_bwd_kernel(const float* __restrict__ X, long long ldx, const float* __restrict__ dG,
+                                                             long long ldg, float* dX, long long ldd, int L, int E,
+                                                             const int* __restrict__ lens) {
+    __shared__ float s_sum[16][64], s_max[16][64];
+    __shared__ int s_arg[16][64];
+    const int lane = threadIdx.x & 63, sl = threadIdx.x >> 6;
+    const int c = blockIdx.x * 64 + lane;
+    const long long s = blockIdx.y;
+    const int n_valid = lens ? std::min(L, std::max(1, lens[s])) : L;
+    float sum = 0.f, best = -INFINITY;
+    int arg = -1;
+    if (c < E) {
+        const float* g = dG + s * L * ldg + c;
+#pragma unroll 8
+        for (int r = sl; r < L; r += 16) sum += g[(long long)r * ldg];
+        const float* x = X + s * L * ldx + c;
+        for (int r = sl; r < n_valid; r += 16) {
+            const float v = x[(long long)r * ldx];
+            if (arg < 0 || v > best) { best = v; arg = r; }
+        }
+    }
+    s_sum[sl][lane] = sum; s_max[sl][lane] = best; s_arg[sl][lane] = arg;
+    __syncthreads();
+    if (sl == 0 && c < E) {
+        for (int k = 1; k < 16; ++k) {
+            sum += s_sum[k][lane];
+            const int a = s_arg[k][lane];
+            const float v = s_max[k][lane];
+            if (a >= 0 && (v > best || (v == best && a < arg))) { best = v; arg = a; }
+        }
+        float* o = dX + (s * L + arg) * ldd + c;
+        *o += sum;
+    }
+}
+
+void launch_colmax_bwd(hipStream_t s, const float* X, int64_t ldx, const float* dG, int64_t ldg, float* dX, int64_t ldd, int64_t S, int L,
+                       int E, const int* lens) {
+    hipLaunchKernelGGL(vb_colmax_bwd_kernel, dim3((unsigned)cdiv(E, 64), (unsigned)S), dim3(1024), 0, s, X, (long long)ldx, dG, (long long)ldg,
+                       dX, (long long)ldd, L, E, lens);
+}
+
+// ---- attention -----------------------------------------------------------------------------------------------------------------------
+// Packed rows qkv[m*ldq + ...] = [q (H*16) | k (H*16) | v (H*64)], head h owning q / k channels h*16.. and v channels h*64..;
+// S sequences of L rows; keys of sequence s: its first kmax = min(L, max(1, lens[s])) rows.  Grid (row blocks of 64, H, S), 4 waves.
+__device__ __forceinline__ int ab_kmax(const int* lens, long long s, int L) { return lens ? min(L, max(1, lens[s])) : L; }
+
+__device__ __forceinline__ void ab_load16(const float* p, f2 (&d)[8], float scale) {
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        const float4 v = *reinterpret_cast<const float4*>(p + 4 * c);
+        d[2 * c] = f2{v.x * scale, v.y * scale};
+        d[2 * c + 1] = f2{v.z * scale, v.w * scale};
+    }
+}
+
+__device__ __forceinline__ float ab_dot16(const f2 (&a)[8], const float* b) {
+    f2 acc{0.f, 0.f};
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        const float4 v = *reinterpret_cast<const float4*>(b + 4 * c);
+        acc = __builtin_elementwise_fma(a[2 * c], f2{v.x, v.y}, acc);
+        acc = __builtin_elementwise_fma(a[2 * c + 1], f2{v.z, v.w}, acc);
+    }
+    return acc.x + acc.y;
+}
+
+__device__ __forceinline__ float ab_dot64(const f2 (&a)[32], const float* b) {
+    f2 acc0{0.f, 0.f}, acc1{0.f, 0.f};
+#pragma unroll
+    for (int c = 0; c < 16; c += 2) {
+        const float4 v = *reinterpret_cast<const float4*>(b + 4 * c);
+        const float4 u = *reinterpret_cast<const float4*>(b + 4 * c + 4);
+        acc0 = __builtin_elementwise_fma(a[2 * c], f2{v.x, v.y}, acc0);
+        acc1 = __builtin_elementwise_fma(a[2 * c + 1], f2{v.z, v.w}, acc1);
+        acc0 = __builtin_elementwise_fma(a[2 * c + 2], f2{u.x, u.y}, acc0);
+        acc1 = __builtin_elementwise_fma(a[2 * c + 3], f2{u.z, u.w}, acc1);
+    }
+    const f2 t = acc0 + acc1;
+    return t.x + t.y;
+}
+
+template <int N2>
+__device__ __forceinline__ void ab_axpy(f2 (&y)[N2], float a, const float* x) {
+    const f2 aa{a, a};
+#pragma unroll
+    for (int c = 0; c < N2 / 2; ++c) {
+        const float4 v = *reinterpret_cast<const float4*>(x + 4 * c);
+        y[2 * c] = __builtin_elementwise_fma(aa, f2{v.x, v.y}, y[2 * c]);
+        y[2 * c + 1] = __builtin_elementwise_fma(aa, f2{v.z, v.w}, y[2 * c + 1]);
+    }
+}
+
+// stage rows [r0, r0 + AB_TILE) (rows >= rmax as zeros) of n4 float4 per row from src (row stride ld floats) into dst [AB_TILE][4*n4]
+template <int N4>
+__device__ __forceinline__ void ab_stage(float* dst, const float* src, long long ld, int r0, int rmax, int lane, float scale) {
+#pragma unroll
+    for (int e = lane; e < AB_TILE * N4; e += 64) {
+        const int rr = e / N4, c4 = e - rr * N4;
+        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (r0 + rr < rmax) {
+            v = *reinterpret_cast<const float4*>(src + (long long)(r0 + rr) * ld + 4 * c4);
+            v.x *= scale; v.y *= scale; v.z *= scale; v.w *= scale;
+        }
+        *reinterpret_cast<float4*>(dst + rr * 4 * N4 + 4 * c4) = v;
+    }
+}
+
+// Small problems (fewer than 512 blocks of 64 rows: one or two 2048-token clouds) split the other side's rows over 2 or 4 blocks, so that
+// every SIMD gets a wave; the parts are merged in part order by ab_fwd_merge_kernel / ab_sum_parts_kernel (a function of the shape
+// alone: determinism).  Part sp of nsplit takes row tiles [t_lo, t_hi) of the n rows' ceil(n / AB_TILE) tiles.
+inline int ab_nsplit(int64_t S, int L, int H) {
+    const int64_t blocks = S * H * cdiv(L, 64);
+    return blocks >= 512 ? 1 : blocks >= 256 ? 2 : 4;
+}
+inline size_t ab_part_floats(int64_t S, int L, int H) {
+    const int ns = ab_nsplit(S, L, H);
+    return ns > 1 ? (size_t)ns * S * L * H * (AB_DQK + AB_DV) : 0;   // (>= the forward's H * 66 and the dq parts' H * 16 per row)
+}
+__device__ __forceinline__ void ab_part_tiles(int n, int nsplit, int sp, int& t_lo, int& t_hi) {
+    const int tiles = (n + AB_TILE - 1) / AB_TILE, per = (tiles + nsplit - 1) / nsplit;
+    t_lo = min(tiles, sp * per);
+    t_hi = min(tiles, t_lo + per);
+}
+
+// O = (sum_p e^{m_p - m} o_p) / l, LSE = m + log l, l = sum_p e^{m_p - m} l_p over the key parts, in part order; one thread per (row, head)
+__global__ __launch_bounds__(256) void ab_fwd_merge_kernel(const float* __restrict__ part, int nsplit, long long TH, int H, float* __restrict__ O,
+                                                           long long ldo, float* __restrict__ lse) {
+    const long long e = blockIdx.x * 256ll + threadIdx.x;
+    if (e >= TH) return;
+    const long long row = e / H;
+    const int h = (int)(e - row * H);
+    float m = -INFINITY, l = 0.f, o[AB_DV];
+#pragma unroll
+    for (int c = 0; c < AB_DV; ++c) o[c] = 0.f;
+    for (int p = 0; p < nsplit; ++p) {
+        const float* pp = part + (p * TH + e) * (AB_DV + 2);
+        const float m2 = pp[0];
+        if (m2 == -INFINITY) continue;
+        const float mn = fmaxf(m, m2), a1 = __expf(m - mn), a2 = __expf(m2 - mn);
+        l = l * a1 + pp[1] * a2;
+#pragma unroll
+        for (int c = 0; c < AB_DV; ++c) o[c] = o[c] * a1 + pp[2 + c] * a2;
+        m = mn;
+    }
+    const float inv = 1.0f / l;
+    float* op = O + row * ldo + h * AB_DV;
+#pragma unroll
+    for (int c = 0; c < AB_DV; ++c) op[c] = o[c] * inv;
+    lse[e] = m + logf(l);
+}
+
+// out[r*ldo + c] = scale * sum_p part[(p*rows + r)*C + c], parts in order
+__global__ __launch_bounds__(256) void ab_sum_parts_kernel(const float* __restrict__ part, int nsplit, long long rows, int C, float scale,
+                                                           float* __restrict__ out, long long ldo) {
+    const long long e = blockIdx.x * 256ll + threadIdx.x;
+    if (e >= rows * C) return;
+    const long long r = e / C;
+    const int c = (int)(e - r * C);
+    float acc = 0.f;
+    for (int p = 0; p < nsplit; ++p) acc += part[p * rows * C + e];
+    out[r * ldo + c] = acc * scale;
+}
+
+constexpr int AB_KV_TILE = AB_TILE * (AB_DQK + AB_DV);            // floats of one wave's K | V tile
+constexpr int AB_FWD_LDS = 3 * 64 * (AB_DV + 2);                   // the combine buffer (> 4 staging tiles)
+static_assert(AB_FWD_LDS >= 4 * AB_KV_TILE, "LDS plan");
+
+// O = softmax(q k^T / 4) v and LSE = m + log(l) per (row, head).  Each wave runs the key tiles w, w + 4, ... with an online soft-max.
+__global__ __launch_bounds__(256) void ab_fwd_kernel(const float* __restrict__ qkv, long long ldq, float* __restrict__ O, long long ldo,
+                                                     float* __restrict__ lse, int L, int H, const int* __restrict__ lens,
+                                                     float* __restrict__ part, int nsplit) {
+    __shared__ float4 smem4[AB_FWD_LDS / 4];
+    float* smem = reinterpret_cast<float*>(smem4);
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, h = blockIdx.y;
+    const long long s = blockIdx.z / nsplit;
+    const int sp = blockIdx.z - (int)s * nsplit;
+    const int qi = blockIdx.x * 64 + lane;
+    const int kmax = ab_kmax(lens, s, L);
+    const int QK = H * AB_DQK;
+    const float* base = qkv + s * L * ldq;
+    f2 q[8];
+    if (qi < L) ab_load16(base + (long long)qi * ldq + h * AB_DQK, q, AB_SCALE);
+    else
+#pragma unroll
+        for (int c = 0; c < 8; ++c) q[c] = f2{0.f, 0.f};
+    f2 o[32];
+#pragma unroll
+    for (int c = 0; c < 32; ++c) o[c] = f2{0.f, 0.f};
+    float m = -INFINITY, l = 0.f;
+    float* kt = smem + w * AB_KV_TILE;
+    float* vt = kt + AB_TILE * AB_DQK;
+    int t_lo, n_tiles;
+    ab_part_tiles(kmax, nsplit, sp, t_lo, n_tiles);
+    for (int t0 = t_lo; t0 < n_tiles; t0 += 4) {
+        const int t = t0 + w;
+        if (t < n_tiles) {
+            ab_stage<AB_DQK / 4>(kt, base + QK + h * AB_DQK, ldq, t * AB_TILE, kmax, lane, 1.f);
+            ab_stage<AB_DV / 4>(vt, base + 2 * QK + h * AB_DV, ldq, t * AB_TILE, kmax, lane, 1.f);
+        }
+        __syncthreads();
+        if (t < n_tiles) {
+            const int nk = min(AB_TILE, kmax - t * AB_TILE);
+            float sc[AB_TILE];
+            float mt = m;
+#pragma unroll
+            for (int j = 0; j < AB_TILE; ++j) {
+                sc[j] = j < nk ? ab_dot16(q, kt + j * AB_DQK) : -INFINITY;
+                mt = fmaxf(mt, sc[j]);
+            }
+            const float alpha = __expf(m - mt);
+            l *= alpha;
+            const f2 aa{alpha, alpha};
+#pragma unroll
+            for (int c = 0; c < 32; ++c) o[c] *= aa;
+#pragma unroll
+            for (int j = 0; j < AB_TILE; ++j) {
+                const float p = __expf(sc[j] - mt);
+                l += p;
+                ab_axpy(o, p, vt + j * AB_DV);
+            }
+            m = mt;
+        }
+        __syncthreads();
+    }
+    constexpr int F = AB_DV + 2;
+    if (w > 0) {
+        float* cb = smem + (w - 1) * F * 64;
+        cb[lane] = m;
+        cb[64 + lane] = l;
+#pragma unroll
+        for (int c = 0; c < 32; ++c) { cb[(2 + 2 * c) * 64 + lane] = o[c].x; cb[(3 + 2 * c) * 64 + lane] = o[c].y; }
+    }
+    __syncthreads();
+    if (w == 0 && qi < L) {
+        for (int k = 0; k < 3; ++k) {
+            const float* cb = smem + k * F * 64;
+            const float m2 = cb[lane];
+            if (m2 == -INFINITY) continue;
+            const float l2 = cb[64 + lane];
+            const float mn = fmaxf(m, m2), a1 = __expf(m - mn), a2 = __expf(m2 - mn);
+            l = l * a1 + l2 * a2;
+#pragma unroll
+            for (int c = 0; c < 32; ++c) o[c] = o[c] * f2{a1, a1} + f2{cb[(2 + 2 * c) * 64 + lane], cb[(3 + 2 * c) * 64 + lane]} * f2{a2, a2};
+            m = mn;
+        }
+        if (nsplit > 1) {                                              // this key part's (max, sum, unnormalised O): ab_fwd_merge_kernel
+            const long long T = (long long)(gridDim.z / nsplit) * L;
+            float* pp = part + ((sp * T + s * L + qi) * H + h) * (AB_DV + 2);
+            pp[0] = m;
+            pp[1] = l;
+#pragma unroll
+            for (int c = 0; c < 32; ++c) { pp[2 + 2 * c] = o[c].x; pp[3 + 2 * c] = o[c].y; }
+            return;
+        }
+        const float inv = 1.0f / l;
+        float* op = O + (s * L + qi) * ldo + h * AB_DV;
+#pragma unroll
+        for (int c = 0; c < 16; ++c)
+            *reinterpret_cast<float4*>(op + 4 * c) = make_float4(o[2 * c].x * inv, o[2 * c].y * inv, o[2 * c + 1].x * inv, o[2 * c + 1].y * inv);
+        lse[(s * L + qi) * H + h] = m + logf(l);
+    }
+}
+
+// dQ pass (query-major): delta = rowsum(dO * O); for every key: p = exp(s - LSE), dp = dO . v, ds = p (dp - delta), dq += ds k / 4.
+__global__ __launch_bounds__(256) void ab_dq_kernel(const float* __restrict__ qkv, long long ldq, const float* __restrict__ O, long long ldo,
+                                                    const float* __restrict__ dO, long long lddo, const float* __restrict__ lse,
+                                                    float* __restrict__ delta, float* __restrict__ dqkv, long long lddq, int L, int H,
+                                                    const int* __restrict__ lens, float* __restrict__ part, int nsplit) {
+    __shared__ float4 smem4[4 * AB_KV_TILE / 4];
+    float* smem = reinterpret_cast<float*>(smem4);
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, h = blockIdx.y;
+    const long long s = blockIdx.z / nsplit;
+    const int sp = blockIdx.z - (int)s * nsplit;
+    const int qi = blockIdx.x * 64 + lane;
+    const int kmax = ab_kmax(lens, s, L);
+    const int QK = H * AB_DQK;
+    const float* base = qkv + s * L * ldq;
+    f2 q[8], g[32];
+    float lq = 0.f, dl = 0.f;
+    if (qi < L) {
+        const long long row = s * L + qi;
+        ab_load16(base + (long long)qi * ldq + h * AB_DQK, q, AB_SCALE);
+        const float* gp = dO + row * lddo + h * AB_DV;
+        const float* op = O + row * ldo + h * AB_DV;
+        f2 d2{0.f, 0.f};
+#pragma unroll
+        for (int c = 0; c < 16; ++c) {
+            const float4 a = *reinterpret_cast<const float4*>(gp + 4 * c);
+            const float4 b = *reinterpret_cast<const float4*>(op + 4 * c);
+            g[2 * c] = f2{a.x, a.y};
+            g[2 * c + 1] = f2{a.z, a.w};
+            d2 = __builtin_elementwise_fma(g[2 * c], f2{b.x, b.y}, d2);
+            d2 = __builtin_elementwise_fma(g[2 * c + 1], f2{b.z, b.w}, d2);
+        }
+        dl = d2.x + d2.y;
+        lq = lse[row * H + h];
+    } else {
+#pragma unroll
+        for (int c = 0; c < 8; ++c) q[c] = f2{0.f, 0.f};
+#pragma unroll
+        for (int c = 0; c < 32; ++c) g[c] = f2{0.f, 0.f};
+    }
+    f2 dq[8];
+#pragma unroll
+    for (int c = 0; c < 8; ++c) dq[c] = f2{0.f, 0.f};
+    float* kt = smem + w * AB_KV_TILE;
+    float* vt = kt + AB_TILE * AB_DQK;
+    int t_lo, n_tiles;
+    ab_part_tiles(kmax, nsplit, sp, t_lo, n_tiles);
+    for (int t0 = t_lo; t0 < n_tiles; t0 += 4) {
+        const int t = t0 + w;
+        if (t < n_tiles) {
+            ab_stage<AB_DQK / 4>(kt, base + QK + h * AB_DQK, ldq, t * AB_TILE, kmax, lane, 1.f);
+            ab_stage<AB_DV / 4>(vt, base + 2 * QK + h * AB_DV, ldq, t * AB_TILE, kmax, lane, 1.f);
+        }
+        __syncthreads();
+        if (t < n_tiles) {
+            const int nk = min(AB_TILE, kmax - t * AB_TILE);
+            for (int j = 0; j < nk; ++j) {
+                const float p = __expf(ab_dot16(q, kt + j * AB_DQK) - lq);
+                const float ds = p * (ab_dot64(g, vt + j * AB_DV) - dl);
+                ab_axpy(dq, ds, kt + j * AB_DQK);
+            }
+        }
+        __syncthreads();
+    }
+    if (w > 0) {
+        float* cb = smem + (w - 1) * AB_DQK * 64;
+#pragma unroll
+        for (int c = 0; c < 8; ++c) { cb[(2 * c) * 64 + lane] = dq[c].x; cb[(2 * c + 1) * 64 + lane] = dq[c].y; }
+    }
+    __syncthreads();
+    if (w == 0 && qi < L) {
+        for (int k = 0; k < 3; ++k) {
+            const float* cb = smem + k * AB_DQK * 64;
+#pragma unroll
+            for (int c = 0; c < 8; ++c) dq[c] += f2{cb[(2 * c) * 64 + lane], cb[(2 * c + 1) * 64 + lane]};
+        }
+        const long long row = s * L + qi;
+        const float sc = nsplit > 1 ? 1.f : AB_SCALE;                  // (parts: scaled once summed, ab_sum_parts_kernel)
+        float* dp = nsplit > 1 ? part + (sp * (long long)(gridDim.z / nsplit) * L + row) * QK + h * AB_DQK : dqkv + row * lddq + h * AB_DQK;
+#pragma unroll
+        for (int c = 0; c < 4; ++c)
+            *reinterpret_cast<float4*>(dp + 4 * c) = make_float4(dq[2 * c].x * sc, dq[2 * c].y * sc, dq[2 * c + 1].x * sc, dq[2 * c + 1].y * sc);
+        if (sp == 0) delta[row * H + h] = dl;
+    }
+}
+
+constexpr int AB_Q_TILE = AB_TILE * (AB_DQK + AB_DV + 2);          // floats of one wave's q | dO | LSE | delta tile
+constexpr int AB_KV_LDS = 3 * 64 * (AB_DQK + AB_DV);               // the combine buffer (> 4 staging tiles)
+static_assert(AB_KV_LDS >= 4 * AB_Q_TILE, "LDS plan");
+
+// dK / dV pass (key-major): every query row of the sequence (padded ones included) against this lane's key.
+__global__ __launch_bounds__(256) void ab_dkdv_kernel(const float* __restrict__ qkv, long long ldq, const float* __restrict__ dO, long long lddo,
+                                                      const float* __restrict__ lse, const float* __restrict__ delta, float* __restrict__ dqkv,
+                                                      long long lddq, int L, int H, const int* __restrict__ lens, float* __restrict__ part,
+                                                      int nsplit) {
+    __shared__ float4 smem4[AB_KV_LDS / 4];
+    float* smem = reinterpret_cast<float*>(smem4);
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, h = blockIdx.y;
+    const long long s = blockIdx.z / nsplit;
+    const int sp = blockIdx.z - (int)s * nsplit;
+    const int kj = blockIdx.x * 64 + lane;
+    const int kmax = ab_kmax(lens, s, L);
+    const int QK = H * AB_DQK;
+    const float* base = qkv + s * L * ldq;
+    const bool live_block = blockIdx.x * 64 < kmax;               // (uniform) a block of keys beyond every cloud's keys: zeros
+    f2 k[8], v[32], dk[8], dv[32];
+#pragma unroll
+    for (int c = 0; c < 8; ++c) dk[c] = f2{0.f, 0.f};
+#pragma unroll
+    for (int c = 0; c < 32; ++c) dv[c] = f2{0.f, 0.f};
+    if (kj < kmax) {
+        ab_load16(base + (long long)kj * ldq + QK + h * AB_DQK, k, 1.f);
+        const float* vp = base + (long long)kj * ldq + 2 * QK + h * AB_DV;
+#pragma unroll
+        for (int c = 0; c < 16; ++c) {
+            const float4 a = *reinterpret_cast<const float4*>(vp + 4 * c);
+            v[2 * c] = f2{a.x, a.y};
+            v[2 * c + 1] = f2{a.z, a.w};
+        }
+    } else {
+#pragma unroll
+        for (int c = 0; c < 8; ++c) k[c] = f2{0.f, 0.f};
+#pragma unroll
+        for (int c = 0; c < 32; ++c) v[c] = f2{0.f, 0.f};
+    }
+    float* qt = smem + w * AB_Q_TILE;
+    float* gt = qt + AB_TILE * AB_DQK;
+    float* lt = gt + AB_TILE * AB_DV;
+    float* dt = lt + AB_TILE;
+    int t_lo, n_tiles;
+    ab_part_tiles(live_block ? L : 0, nsplit, sp, t_lo, n_tiles);
+    for (int t0 = t_lo; t0 < n_tiles; t0 += 4) {
+        const int t = t0 + w;
+        if (t < n_tiles) {
+            ab_stage<AB_DQK / 4>(qt, base + h * AB_DQK, ldq, t * AB_TILE, L, lane, AB_SCALE);
+            ab_stage<AB_DV / 4>(gt, dO + s * L * lddo + h * AB_DV, lddo, t * AB_TILE, L, lane, 1.f);
+            if (lane < AB_TILE) {
+                const int r = t * AB_TILE + lane;
+                lt[lane] = r < L ? lse[(s * L + r) * H + h] : 0.f;
+                dt[lane] = r < L ? delta[(s * L + r) * H + h] : 0.f;
+            }
+        }
+        __syncthreads();
+        if (t < n_tiles) {
+            const int nq = min(AB_TILE, L - t * AB_TILE);
+            for (int i = 0; i < nq; ++i) {
+                const float p = __expf(ab_dot16(k, qt + i * AB_DQK) - lt[i]);
+                ab_axpy(dv, p, gt + i * AB_DV);
+                const float ds = p * (ab_dot64(v, gt + i * AB_DV) - dt[i]);
+                ab_axpy(dk, ds, qt + i * AB_DQK);
+            }
+        }
+        __syncthreads();
+    }
+    constexpr int F = AB_DQK + AB_DV;
+    if (w > 0) {
+        float* cb = smem + (w - 1) * F * 64;
+#pragma unroll
+        for (int c = 0; c < 8; ++c) { cb[(2 * c) * 64 + lane] = dk[c].x; cb[(2 * c + 1) * 64 + lane] = dk[c].y; }
+#pragma unroll
+        for (int c = 0; c < 32; ++c) { cb[(16 + 2 * c) * 64 + lane] = dv[c].x; cb[(17 + 2 * c) * 64 + lane] = dv[c].y; }
+    }
+    __syncthreads();
+    if (w == 0 && kj < L) {
+        if (live_block)
+            for (int kk = 0; kk < 3; ++kk) {
+                const float* cb = smem + kk * F * 64;
+#pragma unroll
+                for (int c = 0; c < 8; ++c) dk[c] += f2{cb[(2 * c) * 64 + lane], cb[(2 * c + 1) * 64 + lane]};
+#pragma unroll
+                for (int c = 0; c < 32; ++c) dv[c] += f2{cb[(16 + 2 * c) * 64 + lane], cb[(17 + 2 * c) * 64 + lane]};
+            }
+        if (kj >= kmax) {                                             // a key nobody attends to
+#pragma unroll
+            for (int c = 0; c < 8; ++c) dk[c] = f2{0.f, 0.f};
+#pragma unroll
+            for (int c = 0; c < 32; ++c) dv[c] = f2{0.f, 0.f};
+        }
+        // parts: rows [dk (QK) | dv (H * 64)] laid out as d_qkv from column QK on, summed by ab_sum_parts_kernel
+        const int W2 = QK + H * AB_DV;
+        float* dkp = nsplit > 1 ? part + (sp * (long long)(gridDim.z / nsplit) * L + s * L + kj) * W2 : dqkv + (s * L + kj) * lddq + QK;
+#pragma unroll
+        for (int c = 0; c < 4; ++c)
+            *reinterpret_cast<float4*>(dkp + h * AB_DQK + 4 * c) = make_float4(dk[2 * c].x, dk[2 * c].y, dk[2 * c + 1].x, dk[2 * c + 1].y);
+#pragma unroll
+        for (int c = 0; c < 16; ++c)
+            *reinterpret_cast<float4*>(dkp + QK + h * AB_DV + 4 * c) = make_float4(dv[2 * c].x, dv[2 * c].y, dv[2 * c + 1].x, dv[2 * c + 1].y);
+    }
+}
+
+// part: ab_part_floats(S, L, H) floats of scratch (none needed when the problem is not split)
+void launch_attn_fwd(hipStream_t s, const float* qkv, int64_t ldq, float* O, int64_t ldo, float* lse, int64_t S, int L, int H, const int* lens,
+                     float* part) {
+    const int ns = ab_nsplit(S, L, H);
+    hipLaunchKernelGGL(ab_fwd_kernel, dim3((unsigned)cdiv(L, 64), (unsigned)H, (unsigned)(S * ns)), dim3(256), 0, s, qkv, (long long)ldq, O,
+                       (long long)ldo, lse, L, H, lens, part, ns);
+    if (ns > 1) {
+        const long long TH = S * L * H;
+        hipLaunchKernelGGL(ab_fwd_merge_kernel, dim3((unsigned)cdiv(TH, 256)), dim3(256), 0, s, part, ns, TH, H, O, (long long)ldo, lse);
+    }
+}
+
+void launch_attn_bwd(hipStream_t s, const float* qkv, int64_t ldq, const float* O, int64_t ldo, const float* lse, const float* dO,
+                     int64_t lddo, float* delta, float* dqkv, int64_t lddq, int64_t S, int L, int H, const int* lens, float* part) {
+    const int ns = ab_nsplit(S, L, H);
+    const long long T = S * L;
+    const int QK = H * AB_DQK, W2 = QK + H * AB_DV;
+    const dim3 grid((unsigned)cdiv(L, 64), (unsigned)H, (unsigned)(S * ns));
+    hipLaunchKernelGGL(ab_dq_kernel, grid, dim3(256), 0, s, qkv, (long long)ldq, O, (long long)ldo, dO, (long long)lddo, lse, delta, dqkv,
+                       (long long)lddq, L, H, lens, part, ns);
+    if (ns > 1)
+        hipLaunchKernelGGL(ab_sum_parts_kernel, dim3((unsigned)cdiv(T * QK, 256)), dim3(256), 0, s, part, ns, T, QK, AB_SCALE, dqkv, (long long)lddq);
+    hipLaunchKernelGGL(ab_dkdv_kernel, grid, dim3(256), 0, s, qkv, (long long)ldq, dO, (long long)lddo, lse, delta, dqkv, (long long)lddq, L,
+                       H, lens, part, ns);
+    if (ns > 1)
+        hipLaunchKernelGGL(ab_sum_parts_kernel, dim3((unsigned)cdiv(T * W2, 256)), dim3(256), 0, s, part, ns, T, W2, 1.f, dqkv + QK,
+                           (long long)lddq);
+}
+
+// ---- the network -------------------------------------------------------------------------------------------------------------------
+struct VbLin { const float* w; const float* b; };
+struct VbEnc { const float *n1g, *n1b; VbLin qkv, out; const float *n2g, *n2b; VbLin ff1, ff2; };
+struct VbNet { VbLin l1, l2; VbEnc enc[3]; const float *ng, *nb; VbLin fc1, fc2, fc3; };
+
+VbNet vb_read(const float* const* p) {
+    VbNet n;
+    n.l1 = {p[0], p[1]};
+    n.l2 = {p[2], p[3]};
+    for (int e = 0; e < 3; ++e) {
+        const float* const* q = p + 4 + 12 * e;
+        n.enc[e] = {q[0], q[1], {q[2], q[3]}, {q[4], q[5]}, q[6], q[7], {q[8], q[9]}, {q[10], q[11]}};
+    }
+    n.ng = p[40]; n.nb = p[41];
+    n.fc1 = {p[42], p[43]}; n.fc2 = {p[44], p[45]}; n.fc3 = {p[46], p[47]};
+    return n;
+}
+
+inline size_t vb_al(size_t n_floats) { return (n_floats * sizeof(float) + 255) & ~(size_t)255; }
+
+struct VbArena {
+    char* base; size_t off = 0;
+    float* f(size_t n) { float* p = reinterpret_cast<float*>(base + off); off += vb_al(n); return p; }
+};
+
+// the encoder's interior, rebuilt from its input x: what its backward reads
+struct VbInterior { float *h1, *qkv, *O, *lse, *xm, *h2, *z, *g, *part; };   // part: the attention's split scratch
+constexpr int VB_W3 = 2 * 64 + VB_E;                             // packed q | k | v width
+
+size_t vb_part_floats(int64_t T) {
+    return std::max({vb_gradw_floats(T, 2 * VB_E, VB_E), vb_gradw_floats(T, VB_E, 2 * VB_E), vb_gradw_floats(T, VB_W3, VB_E),
+                     vb_ln_part_floats(T, VB_E)});
+}
+
+// the fp32 GEMMs of the forward (launch_linear routed on one row: never the split-precision kernels)
+void vb_linear(hipStream_t s, const float* X, int64_t ldx, const VbLin& w, const float* R, int64_t ldr, float* Y, int64_t ldy, int64_t T,
+               int N, int K, int act) {
+    launch_linear(s, X, ldx, w.w, w.b, R, ldr, Y, ldy, T, N, K, act, nullptr, 0, 0, 1);
+}
+
+// x_out = Encoder(x) (x_out NULL: the interior for the backward, LSE included).  The boundary pass (x_out given) needs no LSE: it takes
+// the forward's exact-fp32 MFMA attention (launch_attention, fp32 P V)
+void vb_encoder_fwd(hipStream_t s, const VbEnc& w, const float* x, float* x_out, const VbInterior& I, int64_t B, int N, const int* lens) {
+    const int64_t T = B * N;
+    launch_layernorm(s, x, VB_E, w.n1g, w.n1b, I.h1, VB_E, T, VB_E);
+    vb_linear(s, I.h1, VB_E, w.qkv, nullptr, 0, I.qkv, VB_W3, T, VB_W3, VB_E, ACT_NONE);
+    if (x_out) launch_attention(s, I.qkv, VB_W3, I.O, VB_E, B, N, VB_H, 64, VB_E, lens, nullptr, 0, false, /*pv_half=*/false);
+    else launch_attn_fwd(s, I.qkv, VB_W3, I.O, VB_E, I.lse, B, N, VB_H, lens, I.part);
+    vb_linear(s, I.O, VB_E, w.out, x, VB_E, I.xm, VB_E, T, VB_E, VB_E, ACT_NONE);
+    launch_layernorm(s, I.xm, VB_E, w.n2g, w.n2b, I.h2, VB_E, T, VB_E);
+    vb_linear(s, I.h2, VB_E, w.ff1, nullptr, 0, I.z, 2 * VB_E, T, 2 * VB_E, VB_E, ACT_NONE);
+    launch_gelu(s, I.z, 2 * VB_E, I.g, 2 * VB_E, T, 2 * VB_E, 0);
+    if (x_out) vb_linear(s, I.g, 2 * VB_E, w.ff2, I.xm, VB_E, x_out, VB_E, T, VB_E, 2 * VB_E, ACT_NONE);
+}
+
+size_t vb_workspace_bytes(int64_t B, int64_t N) {
+    const int64_t T = B * N;
+    size_t b = 4 * vb_al(T * VB_E) + 2 * vb_al(T * VB_F);                                         // boundaries, embedding
+    b += vb_al(T * VB_E) + vb_al(T * 192) + vb_al(T * VB_E) + 2 * vb_al(T * 128);               // head
+    b += vb_al(T * VB_E) + vb_al(T * VB_W3) + vb_al(T * VB_E) + vb_al(T * VB_H) + 2 * vb_al(T * VB_E) + 2 * vb_al(T * 2 * VB_E);  // interior
+    b += vb_al(T * VB_E) + vb_al(T * 2 * VB_E) + vb_al(T * VB_E) + vb_al(T * VB_W3) + vb_al(T * VB_H);                          // gradients
+    b += vb_al(vb_part_floats(T)) + vb_al((size_t)2 * VB_E * VB_E) + vb_al(ab_part_floats(B, (int)N, VB_H));
+    return b + 4096;
+}
+
+}  // namespace
+}  // namespace mcr
+
+using namespace mcr;
+
+extern "C" {
+
+// ---- building blocks ---------------------------------------------------------------------------------------------------------------
+size_t mcr_attention_backward_workspace_bytes(int64_t S, int64_t L, int n_heads, int v_dim) {
+    const int64_t T = S * L;
+    return vb_al(T * v_dim) + 2 * vb_al(T * n_heads) + vb_al(ab_part_floats(S, (int)L, n_heads)) + 1024;
+}
+
+int mcr_attention_backward(const float* qkv, int64_t ldq, const float* d_out, int64_t ld_dout, float* d_qkv, int64_t ld_dqkv, int64_t S,
+                           int64_t L, int n_heads, int qk_dim, int v_dim, const int* lens, void* workspace, size_t workspace_bytes,
+                           void* stream) {
+    const char* who = "mcr_attention_backward";
+    MCR_REQUIRE(qkv && d_out && d_qkv, "%s: null pointer", who);
+    MCR_REQUIRE(n_heads > 0 && qk_dim == AB_DQK * n_heads && v_dim == AB_DV * n_heads,
+                "%s: per-head widths must be 16 (q, k) and 64 (v), got qk_dim %d, v_dim %d for %d heads", who, qk_dim, v_dim, n_heads);
+    MCR_REQUIRE(S > 0 && L > 0 && S <= 65535 && L <= (1 << 30), "%s: bad problem size S=%ld L=%ld", who, (long)S, (long)L);
+    MCR_REQUIRE(ldq >= 2 * qk_dim + v_dim && ldq % 4 == 0 && ld_dout >= v_dim && ld_dout % 4 == 0 && ld_dqkv >= 2 * qk_dim + v_dim &&
+                    ld_dqkv % 4 == 0,
+                "%s: leading dimensions must cover the rows and be multiples of 4", who);
+    MCR_REQUIRE(((uintptr_t)qkv | (uintptr_t)d_out | (uintptr_t)d_qkv) % 16 == 0, "%s: operands must be 16-byte aligned", who);
+    MCR_REQUIRE(workspace && workspace_bytes >= mcr_attention_backward_workspace_bytes(S, L, n_heads, v_dim), "%s: workspace too small", who);
+    hipStream_t s = (hipStream_t)stream;
+    VbArena a{(char*)workspace};
+    const int64_t T = S * L;
+    float* O = a.f(T * v_dim);
+    float* lse = a.f(T * n_heads);
+    float* delta = a.f(T * n_heads);
+    float* part = a.f(ab_part_floats(S, (int)L, n_heads));
+    launch_attn_fwd(s, qkv, ldq, O, v_dim, lse, S, (int)L, n_heads, lens, part);
+    launch_attn_bwd(s, qkv, ldq, O, v_dim, lse, d_out, ld_dout, delta, d_qkv, ld_dqkv, S, (int)L, n_heads, lens, part);
+    MCR_LAUNCH_CHECK(who);
+    return 0;
+}
+
+size_t mcr_linear_backward_workspace_bytes(int64_t M, int N, int K) {
+    return vb_al((size_t)M * N) + vb_al(vb_gradw_floats(M, N, K)) + vb_al((size_t)N * K) + 1024;
+}
+
+int mcr_linear_backward(const float* X, int64_t ldx, const float* W, const float* Z, int64_t ldz, const float* dY, int64_t ldy, int64_t M, int N,
+                        int K, int gelu, float* dX, int64_t ld_dx, int accumulate_dx, float* dW, float* db, void* workspace,
+                        size_t workspace_bytes, void* stream) {
+    const char* who = "mcr_linear_backward";
+    MCR_REQUIRE(dY && (!dX || W) && (!dW || X) && (!gelu || Z), "%s: null pointer", who);
+    MCR_REQUIRE(M > 0 && N > 0 && K > 0 && M <= (1ll << 31), "%s: bad problem size M=%ld N=%d K=%d", who, (long)M, N, K);
+    MCR_REQUIRE(workspace && workspace_bytes >= mcr_linear_backward_workspace_bytes(M, N, K), "%s: workspace too small", who);
+    hipStream_t s = (hipStream_t)stream;
+    VbArena a{(char*)workspace};
+    float* dz = a.f((size_t)M * N);
+    float* part = a.f(vb_gradw_floats(M, N, K));
+    float* wt = a.f((size_t)N * K);
+    const float* g = dY;
+    int64_t ldg = ldy;
+    if (gelu) {
+        launch_copy2d(s, dY, ldy, dz, N, M, N);
+        launch_gelu(s, Z, ldz, dz, N, M, N, 1);
+        g = dz;
+        ldg = N;
+    }
+    if (dX) gemm_dx(s, g, ldg, W, K, dX, ld_dx, M, N, K, accumulate_dx != 0, wt);
+    gemm_dw(s, g, ldg, X, ldx, M, N, K, dW, db, part);
+    MCR_LAUNCH_CHECK(who);
+    return 0;
+}
+
+size_t mcr_layernorm_backward_workspace_bytes(int64_t M, int E) { return vb_al(vb_ln_part_floats(M, E)) + 1024; }
+
+int mcr_layernorm_backward(const float* X, int64_t ldx, const float* gamma, const float* dY, int64_t ldy, int64_t M, int E, float* dX, int64_t ld_dx,
+                           int accumulate_dx, float* d_gamma, float* d_beta, void* workspace, size_t workspace_bytes, void* stream) {
+    const char* who = "mcr_layernorm_backward";
+    MCR_REQUIRE(X && gamma && dY && dX, "%s: null pointer", who);
+    MCR_REQUIRE(E == 64 || E == 128 || E == 256 || E == 512, "%s: E must be 64, 128, 256 or 512 (got %d)", who, E);
+    MCR_REQUIRE(M > 0, "%s: empty problem", who);
+    MCR_REQUIRE(workspace && workspace_bytes >= mcr_layernorm_backward_workspace_bytes(M, E), "%s: workspace too small", who);
+    launch_ln_bwd((hipStream_t)stream, X, ldx, gamma, dY, ldy, dX, ld_dx, accumulate_dx != 0, d_gamma, d_beta, (float*)workspace, M, E);
+    MCR_LAUNCH_CHECK(who);
+    return 0;
+}
+
+int mcr_colmax_backward(const float* X, int64_t ldx, const float* d_bcast, int64_t ldg, float* dX, int64_t ld_dx, int64_t S, int64_t L, int E,
+                        const int* lens, void* stream) {
+    const char* who = "mcr_colmax_backward";
+    MCR_REQUIRE(X && d_bcast && dX, "%s: null pointer", who);
+    MCR_REQUIRE(S > 0 && L > 0 && E > 0 && S <= 65535 && L <= (1 << 30), "%s: bad problem size", who);
+    launch_colmax_bwd((hipStream_t)stream, X, ldx, d_bcast, ldg, dX, ld_dx, S, (int)L, E, lens);
+    MCR_LAUNCH_CHECK(who);
+    return 0;
+}
+
+// ---- SconeVis ------------------------------------------------------------------------------------------------------------------------
+size_t mcr_scone_vis_backward_workspace_bytes(int64_t B, int64_t N) { return (B > 0 && N > 0) ? vb_workspace_bytes(B, N) : 0; }
+
+int mcr_scone_vis_backward(const float* pts, const float* view_harmonics, const float* d_out, int64_t B, int64_t N, const float* const* weights,
+                           int n_weights, const int* lengths, float* const* d_weights, float* d_pts, float* d_view_harmonics, void* workspace,
+                           size_t workspace_bytes, void* stream) {
+    const char* who = "mcr_scone_vis_backward";
+    MCR_REQUIRE(pts && view_harmonics && d_out && weights, "%s: null pointer", who);
+    MCR_REQUIRE(n_weights == VB_NW || n_weights == VB_NW + 12 || n_weights == VB_NW + 17,
+                "%s: expected %d weight pointers (+ 12 or 17 plane pointers), got %d", who, VB_NW, n_weights);
+    MCR_REQUIRE(B > 0 && N > 0 && B <= 65535 && N <= (1 << 24), "%s: bad problem size B=%ld N=%ld", who, (long)B, (long)N);
+    MCR_REQUIRE(workspace && workspace_bytes >= vb_workspace_bytes(B, N), "%s: workspace too small", who);
+    for (int i = 0; i < VB_NW; ++i) MCR_REQUIRE(weights[i], "%s: weight %d is null", who, i);
+    if (d_weights)
+        for (int i = 0; i < VB_NW; ++i) MCR_REQUIRE(d_weights[i], "%s: d_weights[%d] is null", who, i);
+    MCR_REQUIRE(((uintptr_t)pts | (uintptr_t)view_harmonics | (uintptr_t)d_out) % 16 == 0, "%s: operands must be 16-byte aligned", who);
+    if (!d_weights && !d_pts && !d_view_harmonics) return 0;
+    hipStream_t s = (hipStream_t)stream;
+    const VbNet w = vb_read(weights);
+    float* const* dw = d_weights;
+    const int iN = (int)N;
+    const int64_t T = B * N;
+    VbArena a{(char*)workspace};
+    float* X[4];
+    for (int e = 0; e < 4; ++e) X[e] = a.f(T * VB_E);
+    float* z1 = a.f(T * VB_F);
+    float* g1 = a.f(T * VB_F);
+    float* hn = a.f(T * VB_E);
+    float* zf1 = a.f(T * 192);
+    float* c2 = a.f(T * VB_E);
+    float* zf2 = a.f(T * 128);
+    float* gf2 = a.f(T * 128);
+    VbInterior I;
+    I.h1 = a.f(T * VB_E); I.qkv = a.f(T * VB_W3); I.O = a.f(T * VB_E); I.lse = a.f(T * VB_H);
+    I.xm = a.f(T * VB_E); I.h2 = a.f(T * VB_E); I.z = a.f(T * 2 * VB_E); I.g = a.f(T * 2 * VB_E);
+    float* dX = a.f(T * VB_E);
+    float* dH = a.f(T * 2 * VB_E);
+    float* dA = a.f(T * VB_E);
+    float* dQKV = a.f(T * VB_W3);
+    float* delta = a.f(T * VB_H);
+    float* part = a.f(vb_part_floats(T));
+    float* wt = a.f((size_t)2 * VB_E * VB_E);                                              // transposed weight (dX products)
+    I.part = a.f(ab_part_floats(B, iN, VB_H));
+    auto DW = [&](int i) { return dw ? dw[i] : nullptr; };
+
+    // ---- forward of the fp32 network: boundaries X0..X3, the embedding's and the head's pre-activations
+    vb_linear(s, pts, 4, w.l1, nullptr, 0, z1, VB_F, T, VB_F, 4, ACT_NONE);
+    launch_gelu(s, z1, VB_F, g1, VB_F, T, VB_F, 0);
+    vb_linear(s, g1, VB_F, w.l2, nullptr, 0, X[0], VB_E, T, VB_F, VB_F, ACT_NONE);
+    launch_colmax_broadcast(s, X[0], VB_E, X[0] + VB_F, VB_E, B, iN, VB_F, lengths, pts, 4, 4, X[0] + 2 * VB_F);
+    for (int e = 0; e < 3; ++e) vb_encoder_fwd(s, w.enc[e], X[e], X[e + 1], I, B, iN, lengths);
+    launch_layernorm(s, X[3], VB_E, w.ng, w.nb, hn, VB_E, T, VB_E);
+    vb_linear(s, hn, VB_E, w.fc1, nullptr, 0, zf1, 192, T, 192, VB_E, ACT_NONE);
+    launch_gelu(s, zf1, 192, c2, VB_E, T, 192, 0);
+    launch_copy2d(s, view_harmonics, 64, c2 + 192, VB_E, T, 64);
+    vb_linear(s, c2, VB_E, w.fc2, nullptr, 0, zf2, 128, T, 128, VB_E, ACT_NONE);
+    launch_gelu(s, zf2, 128, gf2, 128, T, 128, 0);
+
+    // ---- head (SconeVis.py:143-152), backwards
+    gemm_dw(s, d_out, 64, gf2, 128, T, 64, 128, DW(46), DW(47), part);                 // fc3
+    gemm_dx(s, d_out, 64, w.fc3.w, 128, dH, 128, T, 64, 128, false, wt);
+    launch_gelu(s, zf2, 128, dH, 128, T, 128, 1);                                          // fc2
+    gemm_dw(s, dH, 128, c2, VB_E, T, 128, VB_E, DW(44), DW(45), part);
+    gemm_dx(s, dH, 128, w.fc2.w, VB_E, dA, VB_E, T, 128, VB_E, false, wt);
+    if (d_view_harmonics) launch_copy2d(s, dA + 192, VB_E, d_view_harmonics, 64, T, 64);
+    if (!d_weights && !d_pts) { MCR_LAUNCH_CHECK(who); return 0; }
+    launch_gelu(s, zf1, 192, dA, VB_E, T, 192, 1);                                         // fc1
+    gemm_dw(s, dA, VB_E, hn, VB_E, T, 192, VB_E, DW(42), DW(43), part);
+    gemm_dx(s, dA, VB_E, w.fc1.w, VB_E, dH, VB_E, T, 192, VB_E, false, wt);
+    launch_ln_bwd(s, X[3], VB_E, w.ng, dH, VB_E, dX, VB_E, false, DW(40), DW(41), part, T, VB_E);   // norm
+
+    // ---- encoders (Attention.py:278-300), last to first; dX holds the gradient of the encoder's output
+    for (int e = 2; e >= 0; --e) {
+        const VbEnc& we = w.enc[e];
+        const int o = 4 + 12 * e;
+        vb_encoder_fwd(s, we, X[e], nullptr, I, B, iN, lengths);                          // the interior, from the boundary
+        gemm_dw(s, dX, VB_E, I.g, 2 * VB_E, T, VB_E, 2 * VB_E, DW(o + 10), DW(o + 11), part);          // ff2
+        gemm_dx(s, dX, VB_E, we.ff2.w, 2 * VB_E, dH, 2 * VB_E, T, VB_E, 2 * VB_E, false, wt);
+        launch_gelu(s, I.z, 2 * VB_E, dH, 2 * VB_E, T, 2 * VB_E, 1);                      // ff1
+        gemm_dw(s, dH, 2 * VB_E, I.h2, VB_E, T, 2 * VB_E, VB_E, DW(o + 8), DW(o + 9), part);
+        gemm_dx(s, dH, 2 * VB_E, we.ff1.w, VB_E, dA, VB_E, T, 2 * VB_E, VB_E, false, wt);
+        launch_ln_bwd(s, I.xm, VB_E, we.n2g, dA, VB_E, dX, VB_E, true, DW(o + 6), DW(o + 7), part, T, VB_E);   // norm2 (+ residual)
+        gemm_dw(s, dX, VB_E, I.O, VB_E, T, VB_E, VB_E, DW(o + 4), DW(o + 5), part);        // out
+        gemm_dx(s, dX, VB_E, we.out.w, VB_E, dA, VB_E, T, VB_E, VB_E, false, wt);
+        launch_attn_bwd(s, I.qkv, VB_W3, I.O, VB_E, I.lse, dA, VB_E, delta, dQKV, VB_W3, B, iN, VB_H, lengths, I.part);
+        gemm_dw(s, dQKV, VB_W3, I.h1, VB_E, T, VB_W3, VB_E, DW(o + 2), DW(o + 3), part);   // qkv
+        gemm_dx(s, dQKV, VB_W3, we.qkv.w, VB_E, dA, VB_E, T, VB_W3, VB_E, false, wt);
+        launch_ln_bwd(s, X[e], VB_E, we.n1g, dA, VB_E, dX, VB_E, true, DW(o + 0), DW(o + 1), part, T, VB_E);   // norm1 (+ residual)
+    }
+
+    // ---- embedding (Attention.py:98-128): [res | cloud max of res | pts]
+    launch_colmax_bwd(s, X[0], VB_E, dX + VB_F, VB_E, dX, VB_E, B, iN, VB_F, lengths);
+    gemm_dw(s, dX, VB_E, g1, VB_F, T, VB_F, VB_F, DW(2), DW(3), part);                     // linear2
+    gemm_dx(s, dX, VB_E, w.l2.w, VB_F, dH, VB_F, T, VB_F, VB_F, false, wt);
+    launch_gelu(s, z1, VB_F, dH, VB_F, T, VB_F, 1);                                        // linear1
+    gemm_dw(s, dH, VB_F, pts, 4, T, VB_F, 4, DW(0), DW(1), part);
+    if (d_pts) {
+        launch_copy2d(s, dX + 2 * VB_F, VB_E, d_pts, 4, T, 4);
+        gemm_dx(s, dH, VB_F, w.l1.w, 4, d_pts, 4, T, VB_F, 4, true, wt);
+    }
+    MCR_LAUNCH_CHECK(who);
+    return 0;
+}
+
+}  // extern "C"

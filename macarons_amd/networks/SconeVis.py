@@ -97,6 +97,31 @@ class SconeVis(RangeGuard, nn.Module):
         t += [weight_planes(self.fc1.weight), weight_planes(self.fc2.weight), weight_planes(self.fc3.weight)]
         return t
 
+    def _grad_slots(self):
+        """(parameters, slots): every parameter of the module with its place in weight_table() -- (table index, row slice or None);
+        w_q / w_k / w_v are rows 0:64 / 64:128 / 128:384 of their encoder's packed qkv entries."""
+        slots = {id(self.embedding.linear1.weight): (0, None), id(self.embedding.linear1.bias): (1, None),
+                 id(self.embedding.linear2.weight): (2, None), id(self.embedding.linear2.bias): (3, None)}
+        for e, enc in enumerate(self.encoders):
+            o = 4 + 12 * e
+            qk = enc.mhsa.w_q.weight.shape[0]
+            rows = ((0, qk), (qk, 2 * qk), (2 * qk, 2 * qk + enc.mhsa.w_v.weight.shape[0]))
+            for lin, r in zip((enc.mhsa.w_q, enc.mhsa.w_k, enc.mhsa.w_v), rows):
+                slots[id(lin.weight)], slots[id(lin.bias)] = (o + 2, r), (o + 3, r)
+            for k, t in enumerate((enc.norm1.weight, enc.norm1.bias)):
+                slots[id(t)] = (o + k, None)
+            for k, t in enumerate((enc.mhsa.out.weight, enc.mhsa.out.bias, enc.norm2.weight, enc.norm2.bias, enc.ff.linear1.weight,
+                                   enc.ff.linear1.bias, enc.ff.linear2.weight, enc.ff.linear2.bias)):
+                slots[id(t)] = (o + 4 + k, None)
+        for k, t in enumerate((self.norm.weight, self.norm.bias, self.fc1.weight, self.fc1.bias, self.fc2.weight, self.fc2.bias,
+                               self.fc3.weight, self.fc3.bias)):
+            slots[id(t)] = (40 + k, None)
+        params = tuple(self.parameters())
+        missing = [n for n, p in self.named_parameters() if id(p) not in slots]
+        if missing:
+            raise NotImplementedError(f"SconeVis HIP backward: parameters outside the weight table: {missing}")
+        return params, tuple(slots[id(p)] for p in params)
+
     def forward(self, pts, mask=None, view_harmonics=None, lengths=None):
         """pts [n_clouds, seq_len, 4], view_harmonics [n_clouds, seq_len, 64] -> [n_clouds, seq_len, 64].
         lengths (extension, optional int32 device tensor [n_clouds]): cloud b is its first lengths[b] rows; the rest of the
@@ -146,8 +171,13 @@ class SconeVis(RangeGuard, nn.Module):
                 elif guard == "async":
                     self._post_range_check(self._range_flag)
             return res_
-        if A.needs_grad(self, pts, view_harmonics):     # trainers (pretrain_scone_vis.py:224): HIP forward, composite-torch backward
-            res = A.with_torch_backward(hip, lambda p, vh: A.scone_vis(self, p, vh, lengths), (pts, view_harmonics), self)
+        if A.needs_grad(self, pts, view_harmonics):     # trainers (pretrain_scone_vis.py:224): HIP forward, HIP backward
+            if A.scone_vis_backward_mode() == "composite":          # (env MCR_SCONE_VIS_BWD=composite: the torch backward, A/B)
+                res = A.with_torch_backward(hip, lambda p, vh: A.scone_vis(self, p, vh, lengths), (pts, view_harmonics), self)
+            else:
+                params, slots = self._grad_slots()
+                res = A.SconeVisFunction.apply(hip, lambda: self._table_cache.get(self, self.weight_table_with_planes), slots, lengths,
+                                               pts, view_harmonics, *params)
         else:
             res = hip(pts, view_harmonics)
         return res.view(n_clouds, seq_len, self.n_harmonics)

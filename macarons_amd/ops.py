@@ -446,6 +446,129 @@ def scone_vis_forward(pts, view_harmonics, weights, lengths=None):
     return out
 
 
+def scone_vis_backward(pts, view_harmonics, d_out, weights, lengths=None, need=(True, True, True)):
+    """Gradients of scone_vis_forward given d_out [B,N,64]: (d_weights, d_pts [B,N,4], d_vh [B,N,64]); `need` = (params, pts, vh)
+    selects what is computed (None for the rest).  d_weights: one tensor per entry of the 48-entry weight table (table order and
+    shapes; the packed qkv weight / bias one entry each).  The fp32 network's gradient whatever the variant (mcr_scone_vis_backward:
+    HIP kernels only, deterministic)."""
+    pts, view_harmonics = _req(pts, "pts"), _req(view_harmonics, "view_harmonics")
+    d_out = _req(d_out, "d_out")                # .contiguous(): x.sum().backward() hands in an expanded, zero-stride tensor
+    B, N, d = pts.shape
+    if d != 4 or view_harmonics.shape != (B, N, 64) or d_out.shape != (B, N, 64):
+        raise ValueError(f"SconeVis backward needs pts [B,N,4], view_harmonics and d_out [B,N,64]; got {tuple(pts.shape)}, "
+                         f"{tuple(view_harmonics.shape)}, {tuple(d_out.shape)}")
+    tensors = weights[0] if isinstance(weights, tuple) else weights
+    need_w, need_p, need_v = (bool(x) for x in need)
+    dev = pts.device
+    d_w = [torch.empty(tuple(t.shape), dtype=torch.float32, device=dev) for t in tensors[:48]] if need_w else None
+    d_pts = torch.empty((B, N, 4), dtype=torch.float32, device=dev) if need_p else None
+    d_vh = torch.empty((B, N, 64), dtype=torch.float32, device=dev) if need_v else None
+    if lengths is not None:
+        lengths = _req(lengths, "lengths", torch.int32).reshape(-1)
+        if lengths.numel() != B:
+            raise ValueError(f"lengths must hold one int32 per cloud ({B}), got {lengths.numel()}")
+    L_ = lib()
+    ws = _workspace(dev, int(L_.mcr_scone_vis_backward_workspace_bytes(c_i64(B), c_i64(N))))
+    dtab = (ctypes.c_void_p * 48)(*[t.data_ptr() for t in d_w]) if need_w else None
+    ptr = lambda t: _p(t) if t is not None else c_vp(None)
+    with torch.cuda.device(dev):
+        check(L_.mcr_scone_vis_backward(_p(pts), _p(view_harmonics), _p(d_out), c_i64(B), c_i64(N), _ptr_table(weights),
+                                        c_int(_n_weights(weights)), _p(lengths) if lengths is not None else c_vp(0),
+                                        dtab if dtab is not None else c_vp(None), ptr(d_pts), ptr(d_vh), _p(ws), c_size(ws.numel()),
+                                        _stream()), "mcr_scone_vis_backward")
+    return d_w, d_pts, d_vh
+
+
+def attention_backward(qkv, d_out, n_heads=4, lens=None):
+    """Gradient of attention_packed (per-head widths 16 / 64; lens as attention_packed_planes) with respect to the packed rows:
+    qkv [S,L,W], d_out [S,L,v_dim] -> d_qkv [S,L,W]  (mcr_attention_backward)."""
+    qkv, d_out = _req(qkv, "qkv"), _req(d_out, "d_out")
+    S, L, W = qkv.shape
+    qk_dim, v_dim = 16 * n_heads, 64 * n_heads
+    if W != 2 * qk_dim + v_dim or d_out.shape != (S, L, v_dim):
+        raise ValueError(f"attention_backward: qkv [S,L,{2 * qk_dim + v_dim}] and d_out [S,L,{v_dim}] expected")
+    if lens is not None:
+        lens = _req(lens, "lens", torch.int32).reshape(-1)
+        if lens.numel() != S:
+            raise ValueError("lens must hold one length per sequence")
+    d_qkv = torch.empty_like(qkv)
+    L_ = lib()
+    ws = _workspace(qkv.device, int(L_.mcr_attention_backward_workspace_bytes(c_i64(S), c_i64(L), c_int(n_heads), c_int(v_dim))))
+    with torch.cuda.device(qkv.device):
+        check(L_.mcr_attention_backward(_p(qkv), c_i64(W), _p(d_out), c_i64(v_dim), _p(d_qkv), c_i64(W), c_i64(S), c_i64(L), c_int(n_heads),
+                                        c_int(qk_dim), c_int(v_dim), _p(lens) if lens is not None else c_vp(0), _p(ws), c_size(ws.numel()),
+                                        _stream()), "mcr_attention_backward")
+    return d_qkv
+
+
+def linear_backward(x, weight, d_y, z=None, gelu=False, d_x=None, need=(True, True, True)):
+    """Gradient of linear(x, weight, bias, gelu) given d_y: (d_x, d_w, d_b).  z: the pre-activation (needed with gelu).  d_x given:
+    the input gradient is ADDED to it (in place), else a new tensor; `need` = (x, weight, bias).  mcr_linear_backward."""
+    x, weight, d_y = _req(x, "x"), _req(weight, "weight"), _req(d_y, "d_y")
+    x2, lead = _rows(x)
+    M, K = x2.shape
+    N = weight.shape[0]
+    if weight.dim() != 2 or weight.shape[1] != K:
+        raise ValueError(f"weight {tuple(weight.shape)} does not match input width {K}")
+    if d_y.numel() != M * N:
+        raise ValueError(f"d_y must hold {M} x {N} values, got {tuple(d_y.shape)}")
+    dy2 = d_y.reshape(M, N)
+    z2 = _req(z, "z").reshape(M, N) if gelu else None
+    need_x, need_w, need_b = (bool(v) for v in need)
+    acc = d_x is not None
+    if acc and (not d_x.is_contiguous() or d_x.dtype != torch.float32 or d_x.shape != x.shape):
+        raise ValueError("d_x must be a contiguous float32 tensor shaped like x")
+    dx = (d_x if acc else torch.empty_like(x2)) if need_x else None
+    dw = torch.empty((N, K), dtype=torch.float32, device=x.device) if need_w else None
+    db = torch.empty((N,), dtype=torch.float32, device=x.device) if need_b else None
+    ptr = lambda t: _p(t) if t is not None else c_vp(None)
+    L_ = lib()
+    ws = _workspace(x.device, int(L_.mcr_linear_backward_workspace_bytes(c_i64(M), c_int(N), c_int(K))))
+    with torch.cuda.device(x.device):
+        check(L_.mcr_linear_backward(_p(x2), c_i64(K), _p(weight), ptr(z2), c_i64(N), _p(dy2), c_i64(N), c_i64(M), c_int(N), c_int(K),
+                                     c_int(int(bool(gelu))), ptr(dx), c_i64(K), c_int(int(acc)), ptr(dw), ptr(db), _p(ws), c_size(ws.numel()),
+                                     _stream()), "mcr_linear_backward")
+    return (dx.reshape(*lead, K) if dx is not None else None), dw, db
+
+
+def layernorm_backward(x, weight, d_y, d_x=None, need=(True, True, True)):
+    """Gradient of layernorm(x, weight, bias) given d_y: (d_x, d_weight, d_bias); d_x given: added to it in place."""
+    x, weight, d_y = _req(x, "x"), _req(weight, "weight"), _req(d_y, "d_y")
+    x2, lead = _rows(x)
+    M, E = x2.shape
+    acc = d_x is not None
+    if acc and (not d_x.is_contiguous() or d_x.dtype != torch.float32 or d_x.shape != x.shape):
+        raise ValueError("d_x must be a contiguous float32 tensor shaped like x")
+    dx = d_x if acc else torch.empty_like(x2)
+    need_g, need_b = bool(need[1]), bool(need[2])
+    dg = torch.empty((E,), dtype=torch.float32, device=x.device) if need_g else None
+    db = torch.empty((E,), dtype=torch.float32, device=x.device) if need_b else None
+    ptr = lambda t: _p(t) if t is not None else c_vp(None)
+    L_ = lib()
+    ws = _workspace(x.device, int(L_.mcr_layernorm_backward_workspace_bytes(c_i64(M), c_int(E))))
+    with torch.cuda.device(x.device):
+        check(L_.mcr_layernorm_backward(_p(x2), c_i64(E), _p(weight), _p(d_y.reshape(M, E)), c_i64(E), c_i64(M), c_int(E), _p(dx), c_i64(E),
+                                        c_int(int(acc)), ptr(dg), ptr(db), _p(ws), c_size(ws.numel()), _stream()), "mcr_layernorm_backward")
+    return dx.reshape(*lead, E), dg, db
+
+
+def colmax_backward(x, d_bcast, d_x, lens=None):
+    """Gradient of the cloud-wide column max (colmax_broadcast; lens: max over the first lens[s] rows): d_x [S,L,E] += at each
+    column's arg-max row (lowest on ties) the column's d_bcast summed over all L rows.  In place; returns d_x."""
+    x, d_bcast = _req(x, "x"), _req(d_bcast, "d_bcast")
+    S, L, E = x.shape
+    if d_bcast.shape != x.shape or not d_x.is_contiguous() or d_x.shape != x.shape or d_x.dtype != torch.float32:
+        raise ValueError("colmax_backward: x, d_bcast and d_x must all be [S,L,E] (d_x contiguous float32)")
+    if lens is not None:
+        lens = _req(lens, "lens", torch.int32).reshape(-1)
+        if lens.numel() != S:
+            raise ValueError(f"lens must hold one length per sequence ({S}), got {lens.numel()}")
+    with torch.cuda.device(x.device):
+        check(lib().mcr_colmax_backward(_p(x), c_i64(E), _p(d_bcast), c_i64(E), _p(d_x), c_i64(E), c_i64(S), c_i64(L), c_int(E),
+                                        _p(lens) if lens is not None else c_vp(0), _stream()), "mcr_colmax_backward")
+    return d_x
+
+
 def nonfinite_flag_(x, flag):
     """flag (int32 device [1]) |= 1 if x holds an inf / NaN (mcr_nonfinite_flag); no read-back."""
     x = _req(x, "x")
