@@ -10,7 +10,8 @@
  * Conventions
  *   - all pointers are DEVICE pointers (HIP, gfx950) to contiguous row-major fp32 unless stated;
  *   - `stream` is a hipStream_t passed as void* (NULL = default stream); calls are asynchronous;
- *   - return 0 on success; non-zero on error, message via mcr_last_error() (thread-local);
+ *   - return 0 on success; non-zero on error, message via mcr_last_error() (thread-local): 1 = an argument check of the entry point,
+ *     2 = a HIP error, 3 = a kernel launcher refused (part of) the call after the entry's own checks -- nothing was launched for it;
  *   - no entry point allocates device memory: scratch is passed in (`*_workspace_bytes` gives size).
  */
 #ifndef MACARONS_HIP_H
@@ -108,7 +109,19 @@ int mcr_knn_offsets_segmented(const float* X, const float* pc, const int64_t* pc
  *   [q (qk_dim) | k (qk_dim) | v (v_dim)], head h owning channels [h*d,(h+1)*d); mask = None; S sequences of
  *   L consecutive rows; scores are divided by sqrt(qk_dim / n_heads).  Supported: 4 heads, (32,128) | (64,256).
  * mcr_colmax_broadcast: Embedding's cloud-wide max feature (Attention.py:117-121).
- * mcr_pool_max_avg: PCTransformer's max || avg pooling over the sequence (SconeOcc.py:123-126). */
+ * mcr_pool_max_avg: PCTransformer's max || avg pooling over the sequence (SconeOcc.py:123-126).
+ *
+ * Leading dimensions and alignment (floats; checked on the host: a call outside them returns non-zero and writes nothing):
+ *   every leading dimension must cover its row (ldx >= K or E, ldy / ldr >= N or E, 2 E for mcr_pool_max_avg's output,
+ *   ldq >= 2 qk_dim + v_dim, ldo >= v_dim); rows may overlap nothing else: padding columns are neither read nor written.
+ *   mcr_linear, mcr_layernorm, mcr_colmax_broadcast, mcr_pool_max_avg: any such leading dimension, operands 4-byte aligned
+ *     (16-byte loads / stores are taken only where the operand's alignment and ld % 4 == 0 allow them; same values either way).
+ *   mcr_attention, mcr_attention_ws: any ldq / ldo, operands 4-byte aligned; the matrix-pipe kernel needs qkv 16-byte aligned and
+ *     ldq % 4 == 0, anything else (but 16-token sequences of the (32,128) layout, which have a kernel of their own) runs the
+ *     slower scalar kernel (same reference, other summation order).
+ *   mcr_attention_masked: as mcr_attention for 16-token sequences of the (32,128) layout; every other shape needs qkv 16-byte
+ *     aligned and ldq % 4 == 0 (the mask exists on the matrix-pipe kernel alone) and is refused otherwise; out / ldo: any.
+ *   mcr_attention_planes: ldq % 4 == 0, qkv and workspace 16-byte aligned (refused otherwise); out 4-byte aligned, any ldo. */
 int mcr_linear(const float* X, int64_t ldx, const float* W, const float* bias, const float* residual, int64_t ldr, float* Y,
                int64_t ldy, int64_t M, int N, int K, int gelu, void* stream);
 int mcr_layernorm(const float* X, int64_t ldx, const float* gamma, const float* beta, float* Y, int64_t ldy, int64_t M, int E,
@@ -153,7 +166,12 @@ int mcr_pool_max_avg(const float* X, int64_t ldx, float* Y, int64_t ldy, int64_t
  *   E in {64, 128, 256, 512}.  workspace: mcr_layernorm_backward_workspace_bytes(M, E).
  * mcr_colmax_backward: for mcr_colmax_broadcast (lens as above, may be NULL: the max over the first lens[s] rows): for every
  *   (sequence, column c < E) dX[row*, c] += sum over ALL L rows of d_bcast[row, c], row* = the lowest valid row holding the max
- *   (torch.max(dim)'s choice on ties). */
+ *   (torch.max(dim)'s choice on ties).
+ * Leading dimensions and alignment (checked on the host: a call outside them returns non-zero and writes nothing): every leading
+ *   dimension must cover its row.  mcr_attention_backward: ldq, ld_dout, ld_dqkv multiples of 4; qkv, d_out, d_qkv and workspace
+ *   16-byte aligned.  mcr_linear_backward, mcr_layernorm_backward, mcr_colmax_backward: any leading dimension >= the row, operands
+ *   and workspace 4-byte aligned (scalar accesses throughout).  mcr_linear_backward reads X for db as well as for dW (db rides on
+ *   the dW product): X may be NULL only when both are. */
 size_t mcr_attention_backward_workspace_bytes(int64_t S, int64_t L, int n_heads, int v_dim);
 int mcr_attention_backward(const float* qkv, int64_t ldq, const float* d_out, int64_t ld_dout, float* d_qkv, int64_t ld_dqkv, int64_t S,
                            int64_t L, int n_heads, int qk_dim, int v_dim, const int* lens, void* workspace, size_t workspace_bytes,

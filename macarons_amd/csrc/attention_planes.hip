@@ -417,9 +417,9 @@ void launch_attention_planes(hipStream_t s, const void* Ph_, const void* Pl_, in
                              int split_mode, int n_planes) {
     if (S <= 0 || L <= 0) return;
     const int dq = DQK / H, dv = DV / H;
-    if ((int64_t)L * ldp >= ((int64_t)1 << 31)) { set_error("launch_attention_planes: sequence too long for 32-bit row offsets"); return; }
+    if ((int64_t)L * ldp >= ((int64_t)1 << 31)) { refuse("launch_attention_planes: sequence too long for 32-bit row offsets"); return; }
     if (!attention_planes_applicable(H, DQK, DV, ldp) || (reinterpret_cast<uintptr_t>(Ph_) & 15) || (n_planes != 1 && (reinterpret_cast<uintptr_t>(Pl_) & 15))) {
-        set_error("launch_attention_planes: unsupported head dims / alignment (dq=%d dv=%d ldp=%lld)", dq, dv, (long long)ldp);
+        refuse("launch_attention_planes: unsupported head dims / alignment (dq=%d dv=%d ldp=%lld)", dq, dv, (long long)ldp);
         return;
     }
     const _Float16 *Ph = (const _Float16*)Ph_, *Pl = (const _Float16*)Pl_;

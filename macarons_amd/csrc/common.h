@@ -9,6 +9,9 @@ namespace mcr {
 
 // ---- error plumbing (C-ABI returns int; message kept per thread) -----------------------------------
 void set_error(const char* fmt, ...);
+// A launcher (void: it sits inside chains of launches) that cannot run its call says so here and returns without launching; the
+// entry point's next MCR_LAUNCH_CHECK then returns 3 with this message, whatever hipGetLastError() holds.
+void refuse(const char* fmt, ...);
 int check_hip(hipError_t e, const char* what);
 
 #define MCR_REQUIRE(cond, ...)                       \

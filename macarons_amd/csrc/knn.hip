@@ -1191,8 +1191,8 @@ void launch_knn16_segmented(hipStream_t s, const float* X, const float* pc, cons
         if (!lds_set[dev_id]) {
             if (hipFuncSetAttribute((const void*)knn_split_merge_kernel<16>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                     8 * 64 * 17 * 8 + 64 * 16 * 3 * 4) != hipSuccess) {
-                // (the HIP error stays pending: the caller's MCR_LAUNCH_CHECK returns it -- offsets_out was not written)
-                set_error("launch_knn16_segmented: cannot reserve %d bytes of LDS for the merge kernel on device %d", 8 * 64 * 17 * 8 + 64 * 16 * 3 * 4,
+                // (the caller's MCR_LAUNCH_CHECK returns the refusal -- offsets_out was not written)
+                refuse("launch_knn16_segmented: cannot reserve %d bytes of LDS for the merge kernel on device %d", 8 * 64 * 17 * 8 + 64 * 16 * 3 * 4,
                           dev_id);
                 return;
             }

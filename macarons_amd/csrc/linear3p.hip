@@ -525,7 +525,7 @@ static void launch_linear3p_np(hipStream_t s, const void* Xh, const void* Xl, in
     _Float16 *yh = (_Float16*)Yh, *yl = (_Float16*)Yl;
     const float* nf = nullptr;
     if (once_on && M <= 4096 && !row_bias && (K == 128 || K % LPO_KS == 0)) {
-        if (!(Yh ? lpo_reserve<LP_PLANES, NP>() : lpo_reserve<LP_F32, NP>())) { set_error("launch_linear3p: cannot reserve %d bytes of LDS", LPO_LDS_BYTES); return; }
+        if (!(Yh ? lpo_reserve<LP_PLANES, NP>() : lpo_reserve<LP_F32, NP>())) { refuse("launch_linear3p: cannot reserve %d bytes of LDS", LPO_LDS_BYTES); return; }
         dim3 g((unsigned)(cdiv(M, LPO_T) * cdiv(N, LPO_T)));
         if (Yh)
             hipLaunchKernelGGL((linear3p_once_kernel<LP_PLANES, NP>), g, dim3(256), LPO_LDS_BYTES, s, xh, xl, (long long)ldx, wh, wl, (long long)ldw, bias,
@@ -536,7 +536,7 @@ static void launch_linear3p_np(hipStream_t s, const void* Xh, const void* Xl, in
         return;
     }
     if (small_mode == 2 || (small_mode == 1 && K <= 512)) {
-        if (!(Yh ? lp_reserve<LP_PLANES, true, NP>() : lp_reserve<LP_F32, true, NP>())) { set_error("launch_linear3p: cannot reserve %d bytes of LDS", LPS_LDS_BYTES); return; }
+        if (!(Yh ? lp_reserve<LP_PLANES, true, NP>() : lp_reserve<LP_F32, true, NP>())) { refuse("launch_linear3p: cannot reserve %d bytes of LDS", LPS_LDS_BYTES); return; }
         dim3 g((unsigned)(cdiv(cdiv(M, 128), 8) * 8 * cdiv(N, 128)));
         if (Yh)
             hipLaunchKernelGGL((linear3p_kernel<LP_PLANES, true, NP>), g, dim3(256), LPS_LDS_BYTES, s, xh, xl, (long long)ldx, wh, wl, (long long)ldw, bias,
@@ -547,7 +547,7 @@ static void launch_linear3p_np(hipStream_t s, const void* Xh, const void* Xl, in
                                nf, nf, 0, R, (long long)ldr);
         return;
     }
-    if (!(Yh ? lp_reserve<LP_PLANES, false, NP>() : lp_reserve<LP_F32, false, NP>())) { set_error("launch_linear3p: cannot reserve %d bytes of LDS", LP_LDS_BYTES); return; }
+    if (!(Yh ? lp_reserve<LP_PLANES, false, NP>() : lp_reserve<LP_F32, false, NP>())) { refuse("launch_linear3p: cannot reserve %d bytes of LDS", LP_LDS_BYTES); return; }
     dim3 grid((unsigned)(cdiv(cdiv(M, 256), 8) * 8 * cdiv(N, 128)));             // 1-D: see the XCD-aware block order in the kernel
     if (Yh)
         hipLaunchKernelGGL((linear3p_kernel<LP_PLANES, false, NP>), grid, dim3(512), LP_LDS_BYTES, s, xh, xl, (long long)ldx, wh, wl, (long long)ldw, bias,
@@ -575,7 +575,7 @@ bool linear3p_dot_applicable(int N, int K, int64_t ldx, int64_t ldw) { return N 
 template <int NP>
 static void launch_linear3p_dot_np(hipStream_t s, const void* Xh, const void* Xl, int64_t ldx, const void* Wh, const void* Wl, int64_t ldw,
                                    const float* bias, int64_t M, int K, int act, float wscale_inv, const float* v, const float* c, int act2, float* out) {
-    if (!lp_reserve<LP_DOT, false, NP>()) { set_error("launch_linear3p_dot: cannot reserve %d bytes of LDS", LP_LDS_BYTES); return; }
+    if (!lp_reserve<LP_DOT, false, NP>()) { refuse("launch_linear3p_dot: cannot reserve %d bytes of LDS", LP_LDS_BYTES); return; }
     dim3 grid((unsigned)(cdiv(cdiv(M, 128), 8) * 8));
     hipLaunchKernelGGL((linear3p_kernel<LP_DOT, false, NP>), grid, dim3(512), LP_LDS_BYTES, s, (const _Float16*)Xh, (const _Float16*)Xl, (long long)ldx,
                        (const _Float16*)Wh, (const _Float16*)Wl, (long long)ldw, bias, (const float*)nullptr, 1ll, (const int*)nullptr, out,

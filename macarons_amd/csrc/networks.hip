@@ -379,6 +379,7 @@ int mcr_layernorm(const float* X, int64_t ldx, const float* gamma, const float* 
                   void* stream) {
     MCR_REQUIRE(X && gamma && beta && Y, "mcr_layernorm: null pointer");
     MCR_REQUIRE(M > 0 && E > 0 && E <= 512, "mcr_layernorm: need 0 < E <= 512 (got %d)", E);
+    MCR_REQUIRE(ldx >= E && ldy >= E, "mcr_layernorm: leading dimension too small");
     launch_layernorm((hipStream_t)stream, X, ldx, gamma, beta, Y, ldy, M, E);
     MCR_LAUNCH_CHECK("mcr_layernorm");
     return 0;
@@ -393,6 +394,7 @@ int mcr_attention(const float* qkv, int64_t ldq, float* out, int64_t ldo, int64_
                 "mcr_attention: supported head layouts are 4 heads with (qk,v) = (32,128) or (64,256); got %d heads (%d,%d)",
                 n_heads, qk_dim, v_dim);
     MCR_REQUIRE(L == 16 || S <= 65535, "mcr_attention: too many long sequences");
+    MCR_REQUIRE(ldq >= 2 * qk_dim + v_dim && ldo >= v_dim, "mcr_attention: leading dimension too small");
     launch_attention((hipStream_t)stream, qkv, ldq, out, ldo, S, (int)L, n_heads, qk_dim, v_dim, nullptr, nullptr, 0, false, attn_pv_half());
     MCR_LAUNCH_CHECK("mcr_attention");
     return 0;
@@ -409,6 +411,7 @@ int mcr_attention_masked(const float* qkv, int64_t ldq, float* out, int64_t ldo,
                 n_heads, qk_dim, v_dim);
     MCR_REQUIRE(mask_seq_stride >= 0 && mask_head_stride >= 0 && mask_query_stride >= 0, "mcr_attention_masked: negative mask stride");
     MCR_REQUIRE(L == 16 || S <= 32767, "mcr_attention_masked: too many long sequences");
+    MCR_REQUIRE(ldq >= 2 * qk_dim + v_dim && ldo >= v_dim, "mcr_attention_masked: leading dimension too small");
     launch_attention((hipStream_t)stream, qkv, ldq, out, ldo, S, (int)L, n_heads, qk_dim, v_dim, nullptr, (float*)workspace,
                      workspace ? workspace_bytes / sizeof(float) : 0, false, false, mask, mask_seq_stride, mask_head_stride, mask_query_stride);
     MCR_LAUNCH_CHECK("mcr_attention_masked");
@@ -428,6 +431,7 @@ int mcr_attention_ws(const float* qkv, int64_t ldq, float* out, int64_t ldo, int
                 "mcr_attention_ws: supported head layouts are 4 heads with (qk,v) = (32,128) or (64,256); got %d heads (%d,%d)",
                 n_heads, qk_dim, v_dim);
     MCR_REQUIRE(L == 16 || S <= 32767, "mcr_attention_ws: too many long sequences");
+    MCR_REQUIRE(ldq >= 2 * qk_dim + v_dim && ldo >= v_dim, "mcr_attention_ws: leading dimension too small");
     launch_attention((hipStream_t)stream, qkv, ldq, out, ldo, S, (int)L, n_heads, qk_dim, v_dim, nullptr, (float*)workspace,
                      workspace ? workspace_bytes / sizeof(float) : 0, false, attn_pv_half());
     MCR_LAUNCH_CHECK("mcr_attention_ws");
@@ -446,6 +450,10 @@ int mcr_attention_planes(const float* qkv, int64_t ldq, float* out, int64_t ldo,
                 "mcr_attention_planes: supported head layouts are 4 heads with (qk,v) = (32,128) or (64,256); got %d heads (%d,%d)",
                 n_heads, qk_dim, v_dim);
     MCR_REQUIRE(workspace_bytes >= mcr_attention_planes_workspace_bytes(S, L, n_heads, qk_dim, v_dim), "mcr_attention_planes: workspace too small");
+    MCR_REQUIRE(ldq >= 2 * qk_dim + v_dim && ldo >= v_dim, "mcr_attention_planes: leading dimension too small");
+    // the rows are split into planes four floats at a time (split_to_planes_kernel: 16-byte loads), the planes read by 16-byte DMA
+    MCR_REQUIRE(ldq % 4 == 0 && ((uintptr_t)qkv | (uintptr_t)workspace) % 16 == 0,
+                "mcr_attention_planes: ldq must be a multiple of 4, qkv and workspace 16-byte aligned");
     const int W3 = 2 * qk_dim + v_dim;
     const int64_t T = S * L;
     _Float16* ph = reinterpret_cast<_Float16*>(workspace);
@@ -460,6 +468,7 @@ int mcr_attention_planes(const float* qkv, int64_t ldq, float* out, int64_t ldo,
 
 int mcr_colmax_broadcast(const float* X, int64_t ldx, float* Y, int64_t ldy, int64_t S, int64_t L, int E, void* stream) {
     MCR_REQUIRE(X && Y && S > 0 && L > 0 && E > 0, "mcr_colmax_broadcast: bad arguments");
+    MCR_REQUIRE(ldx >= E && ldy >= E, "mcr_colmax_broadcast: leading dimension too small");
     launch_colmax_broadcast((hipStream_t)stream, X, ldx, Y, ldy, S, (int)L, E);
     MCR_LAUNCH_CHECK("mcr_colmax_broadcast");
     return 0;
@@ -467,6 +476,7 @@ int mcr_colmax_broadcast(const float* X, int64_t ldx, float* Y, int64_t ldy, int
 
 int mcr_pool_max_avg(const float* X, int64_t ldx, float* Y, int64_t ldy, int64_t S, int64_t L, int E, void* stream) {
     MCR_REQUIRE(X && Y && S > 0 && L > 0 && E > 0, "mcr_pool_max_avg: bad arguments");
+    MCR_REQUIRE(ldx >= E && ldy >= 2 * (int64_t)E, "mcr_pool_max_avg: leading dimension too small");
     launch_pool_max_avg((hipStream_t)stream, X, ldx, Y, ldy, S, (int)L, E);
     MCR_LAUNCH_CHECK("mcr_pool_max_avg");
     return 0;

@@ -1066,7 +1066,7 @@ void launch_attention(hipStream_t s, const float* qkv, int64_t ldq, float* out, 
         return;
     }
     if (lens || mask) {
-        set_error("launch_attention: per-sequence lengths / masks need the MFMA kernel (16-byte aligned qkv, head dims (8,32) or (16,64))");
+        refuse("launch_attention: per-sequence lengths / masks need the MFMA kernel (16-byte aligned qkv, head dims (8,32) or (16,64))");
         return;
     }
     if (dq == 8 && dv == 32)
@@ -1076,7 +1076,7 @@ void launch_attention(hipStream_t s, const float* qkv, int64_t ldq, float* out, 
         hipLaunchKernelGGL((attention_flash_kernel<16, 64, KS>), grid, dim3(64 * KS), 0, s, qkv, (long long)ldq, out,
                            (long long)ldo, L, H);
     else
-        set_error("launch_attention: unsupported head dims dq=%d dv=%d", dq, dv);
+        refuse("launch_attention: unsupported head dims dq=%d dv=%d", dq, dv);
 }
 
 // =====================================================================================================

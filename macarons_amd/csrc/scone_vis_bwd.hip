@@ -839,6 +839,7 @@ int mcr_attention_backward(const float* qkv, int64_t ldq, const float* d_out, in
                 "%s: leading dimensions must cover the rows and be multiples of 4", who);
     MCR_REQUIRE(((uintptr_t)qkv | (uintptr_t)d_out | (uintptr_t)d_qkv) % 16 == 0, "%s: operands must be 16-byte aligned", who);
     MCR_REQUIRE(workspace && workspace_bytes >= mcr_attention_backward_workspace_bytes(S, L, n_heads, v_dim), "%s: workspace too small", who);
+    MCR_REQUIRE((uintptr_t)workspace % 16 == 0, "%s: workspace must be 16-byte aligned", who);
     hipStream_t s = (hipStream_t)stream;
     VbArena a{(char*)workspace};
     const int64_t T = S * L;
@@ -860,8 +861,9 @@ int mcr_linear_backward(const float* X, int64_t ldx, const float* W, const float
                         int K, int gelu, float* dX, int64_t ld_dx, int accumulate_dx, float* dW, float* db, void* workspace,
                         size_t workspace_bytes, void* stream) {
     const char* who = "mcr_linear_backward";
-    MCR_REQUIRE(dY && (!dX || W) && (!dW || X) && (!gelu || Z), "%s: null pointer", who);
+    MCR_REQUIRE(dY && (!dX || W) && ((!dW && !db) || X) && (!gelu || Z), "%s: null pointer", who);   // (db rides on the dW product: it reads X too)
     MCR_REQUIRE(M > 0 && N > 0 && K > 0 && M <= (1ll << 31), "%s: bad problem size M=%ld N=%d K=%d", who, (long)M, N, K);
+    MCR_REQUIRE(ldy >= N && (!gelu || ldz >= N) && (!dX || ld_dx >= K) && ((!dW && !db) || ldx >= K), "%s: leading dimension too small", who);
     MCR_REQUIRE(workspace && workspace_bytes >= mcr_linear_backward_workspace_bytes(M, N, K), "%s: workspace too small", who);
     hipStream_t s = (hipStream_t)stream;
     VbArena a{(char*)workspace};
@@ -890,6 +892,7 @@ int mcr_layernorm_backward(const float* X, int64_t ldx, const float* gamma, cons
     MCR_REQUIRE(X && gamma && dY && dX, "%s: null pointer", who);
     MCR_REQUIRE(E == 64 || E == 128 || E == 256 || E == 512, "%s: E must be 64, 128, 256 or 512 (got %d)", who, E);
     MCR_REQUIRE(M > 0, "%s: empty problem", who);
+    MCR_REQUIRE(ldx >= E && ldy >= E && ld_dx >= E, "%s: leading dimension too small", who);
     MCR_REQUIRE(workspace && workspace_bytes >= mcr_layernorm_backward_workspace_bytes(M, E), "%s: workspace too small", who);
     launch_ln_bwd((hipStream_t)stream, X, ldx, gamma, dY, ldy, dX, ld_dx, accumulate_dx != 0, d_gamma, d_beta, (float*)workspace, M, E);
     MCR_LAUNCH_CHECK(who);
@@ -901,6 +904,7 @@ int mcr_colmax_backward(const float* X, int64_t ldx, const float* d_bcast, int64
     const char* who = "mcr_colmax_backward";
     MCR_REQUIRE(X && d_bcast && dX, "%s: null pointer", who);
     MCR_REQUIRE(S > 0 && L > 0 && E > 0 && S <= 65535 && L <= (1 << 30), "%s: bad problem size", who);
+    MCR_REQUIRE(ldx >= E && ldg >= E && ld_dx >= E, "%s: leading dimension too small", who);
     launch_colmax_bwd((hipStream_t)stream, X, ldx, d_bcast, ldg, dX, ld_dx, S, (int)L, E, lens);
     MCR_LAUNCH_CHECK(who);
     return 0;

@@ -12,6 +12,7 @@ from conftest import golden, rel_err
 sys.path.insert(0, os.path.join(os.path.dirname(__file__), "golden"))
 import weights  # noqa: E402
 from oracle import nets  # noqa: E402
+from _strided import attention_ref, linear_ref  # noqa: E402  (the fp64 references of the building blocks)
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-4
@@ -57,11 +58,7 @@ def test_linear_vs_numpy(dev, M, N, K, gelu, res):
     b = rng.standard_normal(N).astype(np.float32)
     r = rng.standard_normal((M, N)).astype(np.float32)
     y = ops.linear(T(x, dev), T(w, dev), T(b, dev), gelu=gelu, residual=T(r, dev) if res else None).cpu().numpy()
-    ref = x.astype(np.float64) @ w.astype(np.float64).T + b
-    if gelu:
-        ref = nets.gelu(ref)
-    if res:
-        ref = ref + r
+    ref = linear_ref(x, w, b, gelu, r if res else None)
     assert np.abs(y - ref).max() < 2e-5 * max(1.0, np.abs(ref).max())
 
 
@@ -73,12 +70,7 @@ def test_long_sequence_attention_vs_numpy(dev, S, L, H, qk, v):
     rng = np.random.default_rng(S * 1000 + L)
     qkv = rng.standard_normal((S, L, 2 * qk + v)).astype(np.float32)
     y = ops.attention_packed(T(qkv, dev), H, qk, v).cpu().numpy()
-    x = qkv.astype(np.float64)
-    hs = lambda t, d: t.reshape(S, L, H, d).transpose(0, 2, 1, 3)
-    q, k, vv = hs(x[..., :qk], qk // H), hs(x[..., qk:2 * qk], qk // H), hs(x[..., 2 * qk:], v // H)
-    sc = q @ k.transpose(0, 1, 3, 2) / np.sqrt(qk // H)
-    sc = np.exp(sc - sc.max(-1, keepdims=True))
-    ref = ((sc / sc.sum(-1, keepdims=True)) @ vv).transpose(0, 2, 1, 3).reshape(S, L, v)
+    ref = attention_ref(qkv, H, qk, v)
     assert np.abs(y - ref).max() < 2e-5 * max(1.0, np.abs(ref).max())
 
 
