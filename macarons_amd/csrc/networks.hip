@@ -9,7 +9,10 @@
 //   macarons/networks/SconeOcc.py:250-347   SconeOcc.forward
 // Only the reference's default architecture hyper-parameters are implemented on the HIP path (every call site
 // uses them); the Python host classes refuse other configurations loudly.
+// The weight tables the entries read and the arena their workspaces are carved from are described once, in net_layout.h; each
+// entry's scratch is a struct with one carve function below, which its *_workspace_bytes measures.
 #include "nn_kernels.h"
+#include "net_layout.h"
 #include <cstdlib>
 #include <algorithm>
 #include <map>
@@ -17,45 +20,6 @@
 #include <utility>
 
 namespace mcr {
-
-// ---- weight tables (arrays of device pointers, order documented in include/macarons_hip.h) ------------------
-struct LinW { const float* w; const float* b; };
-struct EncW {                       // 12 pointers
-    const float *n1g, *n1b;         // norm1
-    LinW qkv;                       // rows of w_q, w_k, w_v stacked: [2*dqk + dv, E]
-    LinW out;
-    const float *n2g, *n2b;         // norm2
-    LinW ff1, ff2;
-    // optional (NULL: split per call): the four weight matrices as fp16 hi/lo planes [2][N][K] of W * 2^8, built by the host once per
-    // parameter version (networks/packing.py: encoder_weight_planes) -- pointers 4 per encoder appended to the weight table
-    const void *p_qkv = nullptr, *p_out = nullptr, *p_ff1 = nullptr, *p_ff2 = nullptr;
-};
-static void read_enc_planes(const float* const*& p, EncW& e) {
-    e.p_qkv = *p++; e.p_out = *p++; e.p_ff1 = *p++; e.p_ff2 = *p++;
-}
-static EncW read_enc(const float* const*& p) {
-    EncW e;
-    e.n1g = *p++; e.n1b = *p++;
-    e.qkv.w = *p++; e.qkv.b = *p++;
-    e.out.w = *p++; e.out.b = *p++;
-    e.n2g = *p++; e.n2b = *p++;
-    e.ff1.w = *p++; e.ff1.b = *p++;
-    e.ff2.w = *p++; e.ff2.b = *p++;
-    return e;
-}
-
-// bump allocator over the caller's workspace (256-B aligned blocks)
-struct Arena {
-    char* base; size_t cap, off;
-    float* f(size_t n_floats) {
-        size_t bytes = (n_floats * sizeof(float) + 255) & ~(size_t)255;
-        float* p = reinterpret_cast<float*>(base + off);
-        off += bytes;
-        return p;
-    }
-    bool ok() const { return off <= cap; }
-};
-static size_t al(size_t n_floats) { return (n_floats * sizeof(float) + 255) & ~(size_t)255; }
 
 // 1: local_pct.hip exact-fp32 MFMA; 5: local_pct5.hip split-precision bf16 hi/mid/lo (6 MFMAs per product, whole fp32
 // range); 6 (default): local_pct6.hip two-term fp16 split (3 MFMAs per product); 7 (OPT-IN, per call only -- never a process
@@ -215,33 +179,25 @@ static void run_encoder(hipStream_t s, const EncW& w, float* x, float* h, float*
 }
 
 // ---- PCTransformer (SconeOcc.py:45-130): S sequences of L points (pts_dim 3), E = 128, 2 encoders, 4 heads ----
-constexpr int PCT_E = 128, PCT_INNER = 125, PCT_NW = 4 + 2 * 12 + 2 + 2;
-struct PctW { LinW l1, l2; EncW enc[2]; const float *ng, *nb; LinW lin0;
-              const void *p_l2 = nullptr; const float* b_l2p = nullptr; const void* p_lin0 = nullptr; };   // host-built planes of the end layers (optional)
-static void read_pct_end_planes(const float* const*& p, PctW& w) {
-    w.p_l2 = *p++; w.b_l2p = *p++; w.p_lin0 = *p++;
-}
-static PctW read_pct(const float* const*& p) {
-    PctW w;
-    w.l1.w = *p++; w.l1.b = *p++; w.l2.w = *p++; w.l2.b = *p++;
-    w.enc[0] = read_enc(p); w.enc[1] = read_enc(p);
-    w.ng = *p++; w.nb = *p++;
-    w.lin0.w = *p++; w.lin0.b = *p++;
+constexpr int PCT_E = 128, PCT_INNER = 125;
+// The scratch of a stack of encoders of width E over T tokens (PCTransformer: E = 128; SconeVis: E = 256): the residual stream x and
+// the encoder's h [T, E], qkv [T, 2*dqk + E] (dqk = E / 4), ff [T, 2E]
+struct EncScratch { float *x, *h, *qkv, *ff; };
+static EncScratch carve_enc(Arena& a, int64_t T, int E) {
+    EncScratch w;
+    w.x = a.f(T * E);
+    w.h = a.f(T * E);
+    w.qkv = a.f(T * (E + E / 2));
+    w.ff = a.f(T * 2 * E);
     return w;
-}
-static size_t pct_ws_bytes(int64_t T) {
-    return al(T * PCT_E) * 2 + al(T * (PCT_E + 64)) + al(T * 2 * PCT_E);
 }
 // feat[s*ld_feat + 0 : feature_dim] ; feature_dim = 2 * half (max || avg)
 // lens (optional, device int per sequence): sequence s consists of its first lens[s] rows (zero-padded batch of clouds of
 // different sizes): attention keys and the pooling stop there
 static void run_pct(hipStream_t s, const PctW& w, const float* pc, float* feat, int64_t ld_feat, int64_t S, int L, int half,
-                    Arena& a, const int* lens = nullptr) {
+                    const EncScratch& ws, const int* lens = nullptr) {
     const int64_t T = S * L;
-    float* x = a.f(T * PCT_E);
-    float* h = a.f(T * PCT_E);
-    float* qkv = a.f(T * (PCT_E + 64));
-    float* ff = a.f(T * 2 * PCT_E);
+    float *x = ws.x, *h = ws.h, *qkv = ws.qkv, *ff = ws.ff;
     const bool planes = ends_planes(L, PCT_E) && half % 4 == 0;
     const float inv = 1.0f / 256.0f;
     const int np = matrix_planes();                       // 1 on variant 7: the GEMMs below read / write the high planes alone
@@ -438,8 +394,16 @@ int mcr_attention_ws(const float* qkv, int64_t ldq, float* out, int64_t ldo, int
     return 0;
 }
 
+// planes [2][T][W3] fp16 (the bytes of the fp32 rows) + key-split scratch
+struct AttnPlanesScratch { _Float16* planes; float* split; };
+static AttnPlanesScratch carve_attention_planes(Arena& a, int64_t S, int64_t L, int n_heads, int qk_dim, int v_dim) {
+    AttnPlanesScratch w;
+    w.planes = reinterpret_cast<_Float16*>(a.f((size_t)S * L * (2 * qk_dim + v_dim)));
+    w.split = a.f(attention_split_floats(S, (int)L, n_heads, v_dim));
+    return w;
+}
 size_t mcr_attention_planes_workspace_bytes(int64_t S, int64_t L, int n_heads, int qk_dim, int v_dim) {
-    return al((size_t)S * L * (2 * qk_dim + v_dim)) + attention_split_floats(S, (int)L, n_heads, v_dim) * sizeof(float);   // planes (the bytes of the fp32 rows) + key-split scratch
+    return measure(carve_attention_planes, S, L, n_heads, qk_dim, v_dim);
 }
 
 int mcr_attention_planes(const float* qkv, int64_t ldq, float* out, int64_t ldo, int64_t S, int64_t L, int n_heads, int qk_dim, int v_dim,
@@ -456,11 +420,12 @@ int mcr_attention_planes(const float* qkv, int64_t ldq, float* out, int64_t ldo,
                 "mcr_attention_planes: ldq must be a multiple of 4, qkv and workspace 16-byte aligned");
     const int W3 = 2 * qk_dim + v_dim;
     const int64_t T = S * L;
-    _Float16* ph = reinterpret_cast<_Float16*>(workspace);
-    _Float16* pl = ph + (size_t)T * W3;
-    float* split_ws = reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + al((size_t)T * W3));
+    Arena a{(char*)workspace, workspace_bytes};
+    const AttnPlanesScratch ws = carve_attention_planes(a, S, L, n_heads, qk_dim, v_dim);
+    MCR_REQUIRE(a.ok(), "mcr_attention_planes: workspace too small");
+    _Float16 *ph = ws.planes, *pl = ph + (size_t)T * W3;
     launch_split_to_planes((hipStream_t)stream, qkv, ldq, ph, pl, W3, T, W3);
-    launch_attention_planes((hipStream_t)stream, ph, pl, W3, out, ldo, nullptr, nullptr, 0, S, (int)L, n_heads, qk_dim, v_dim, lens, split_ws,
+    launch_attention_planes((hipStream_t)stream, ph, pl, W3, out, ldo, nullptr, nullptr, 0, S, (int)L, n_heads, qk_dim, v_dim, lens, ws.split,
                             attention_split_floats(S, (int)L, n_heads, v_dim), split_mode);
     MCR_LAUNCH_CHECK("mcr_attention_planes");
     return 0;
@@ -532,70 +497,54 @@ int mcr_local_pct_forward(const float* offsets, float* features, int64_t ld_feat
 }
 
 // ---------------------------------------------------------------------------------------------------------
-size_t mcr_pc_transformer_workspace_bytes(int64_t S, int64_t L) { return pct_ws_bytes(S * L) + 4096; }
+constexpr size_t PCT_WS_SLACK = 4096;
+size_t mcr_pc_transformer_workspace_bytes(int64_t S, int64_t L) { return measure(carve_enc, S * L, PCT_E) + PCT_WS_SLACK; }
 
 int mcr_pc_transformer_forward(const float* pc, float* features, int64_t S, int64_t L, int feature_dim,
                                const float* const* weights, int n_weights, void* workspace, size_t workspace_bytes,
                                void* stream) {
     VariantScope variant_scope_;
     MCR_REQUIRE(pc && features && weights, "mcr_pc_transformer_forward: null pointer");
-    MCR_REQUIRE(n_weights == PCT_NW || n_weights == PCT_NW + 8 || n_weights == PCT_NW + 11,
-                "mcr_pc_transformer_forward: expected %d weight pointers (+ 8 or 11 plane pointers), got %d", PCT_NW, n_weights);
+    if (check_table("mcr_pc_transformer_forward", PCT_TABLE, weights, n_weights, n_weights)) return 1;
     MCR_REQUIRE(S > 0 && L > 0, "mcr_pc_transformer_forward: empty problem");
     MCR_REQUIRE(feature_dim == 256 || feature_dim == 512, "mcr_pc_transformer_forward: feature_dim must be 256 or 512");
     MCR_REQUIRE(L == 16 || S <= 65535, "mcr_pc_transformer_forward: too many long sequences");
     MCR_REQUIRE(workspace && workspace_bytes >= mcr_pc_transformer_workspace_bytes(S, L),
                 "mcr_pc_transformer_forward: workspace too small");
-    for (int i = 0; i < n_weights; ++i) MCR_REQUIRE(weights[i], "mcr_pc_transformer_forward: weight %d is null", i);
-    const float* const* p = weights;
-    PctW w = read_pct(p);
-    if (n_weights >= PCT_NW + 8) { read_enc_planes(p, w.enc[0]); read_enc_planes(p, w.enc[1]); }
-    if (n_weights == PCT_NW + 11) read_pct_end_planes(p, w);
-    Arena a{(char*)workspace, workspace_bytes, 0};
-    run_pct((hipStream_t)stream, w, pc, features, feature_dim, S, (int)L, feature_dim / 2, a);
+    PctW w = read_pct(weights);
+    read_pct_tails(w, PCT_TABLE, weights, n_weights);
+    Arena a{(char*)workspace, workspace_bytes};
+    const EncScratch ws = carve_enc(a, S * L, PCT_E);
+    MCR_REQUIRE(a.ok(), "mcr_pc_transformer_forward: workspace too small");
+    run_pct((hipStream_t)stream, w, pc, features, feature_dim, S, (int)L, feature_dim / 2, ws);
     MCR_LAUNCH_CHECK("mcr_pc_transformer_forward");
     return 0;
 }
 
 // ---------------------------------------------------------------------------------------------------------
 // SconeVis.forward (SconeVis.py:121-162): E = 256, 3 encoders, 4 heads, view_state_mode "end".
-constexpr int VIS_E = 256, VIS_F = 126, VIS_NW = 4 + 3 * 12 + 2 + 6;
+constexpr int VIS_E = 256, VIS_F = 126;
+constexpr size_t VIS_WS_SLACK = 4096;
 
-size_t mcr_scone_vis_workspace_bytes(int64_t B, int64_t N) {
-    const int64_t T = B * N;
-    return al(T * VIS_E) * 2 + al(T * (VIS_E + 128)) + al(T * 2 * VIS_E) + 4096;
-}
+size_t mcr_scone_vis_workspace_bytes(int64_t B, int64_t N) { return measure(carve_enc, B * N, VIS_E) + VIS_WS_SLACK; }
 
 int mcr_scone_vis_forward(const float* pts, const float* view_harmonics, float* out, int64_t B, int64_t N,
                           const float* const* weights, int n_weights, const int* lengths, void* workspace,
                           size_t workspace_bytes, void* stream) {
     VariantScope variant_scope_;
     MCR_REQUIRE(pts && view_harmonics && out && weights, "mcr_scone_vis_forward: null pointer");
-    MCR_REQUIRE(n_weights == VIS_NW || n_weights == VIS_NW + 12 || n_weights == VIS_NW + 17,
-                "mcr_scone_vis_forward: expected %d weight pointers (+ 12 or 17 plane pointers), got %d", VIS_NW, n_weights);
+    if (check_table("mcr_scone_vis_forward", VIS_TABLE, weights, n_weights, n_weights)) return 1;
     MCR_REQUIRE(B > 0 && N > 0 && B <= 65535, "mcr_scone_vis_forward: bad problem size B=%ld N=%ld", (long)B, (long)N);
     MCR_REQUIRE(workspace && workspace_bytes >= mcr_scone_vis_workspace_bytes(B, N), "mcr_scone_vis_forward: workspace too small");
-    for (int i = 0; i < n_weights; ++i) MCR_REQUIRE(weights[i], "mcr_scone_vis_forward: weight %d is null", i);
     hipStream_t s = (hipStream_t)stream;
-    const float* const* p = weights;
-    LinW l1{p[0], p[1]}, l2{p[2], p[3]};
-    p += 4;
-    EncW enc[3] = {read_enc(p), read_enc(p), read_enc(p)};
-    const float *ng = *p++, *nb = *p++;
-    LinW fc1{p[0], p[1]}, fc2{p[2], p[3]}, fc3{p[4], p[5]};
-    p += 6;
-    if (n_weights >= VIS_NW + 12)
-        for (int e = 0; e < 3; ++e) read_enc_planes(p, enc[e]);
-    const void *hp_l2 = nullptr, *hp_fc1 = nullptr, *hp_fc2 = nullptr, *hp_fc3 = nullptr;     // host-built planes of the end layers (optional)
-    const float* hb_l2 = nullptr;
-    if (n_weights == VIS_NW + 17) { hp_l2 = p[0]; hb_l2 = p[1]; hp_fc1 = p[2]; hp_fc2 = p[3]; hp_fc3 = p[4]; p += 5; }
+    const VisW w = read_vis_table(weights, n_weights);
+    const LinW &l1 = w.l1, &l2 = w.l2, &fc1 = w.fc1, &fc2 = w.fc2, &fc3 = w.fc3;
 
     const int64_t T = B * N;
-    Arena a{(char*)workspace, workspace_bytes, 0};
-    float* x = a.f(T * VIS_E);
-    float* h = a.f(T * VIS_E);
-    float* qkv = a.f(T * (VIS_E + 128));
-    float* ff = a.f(T * 2 * VIS_E);
+    Arena a{(char*)workspace, workspace_bytes};
+    const EncScratch ws = carve_enc(a, T, VIS_E);
+    MCR_REQUIRE(a.ok(), "mcr_scone_vis_forward: workspace too small");
+    float *x = ws.x, *h = ws.h, *qkv = ws.qkv, *ff = ws.ff;
     const bool planes = ends_planes((int)N, VIS_E);
     const float inv = 1.0f / 256.0f;
     const int np = matrix_planes();                       // 1 on variant 7: the GEMMs below read / write the high planes alone
@@ -606,8 +555,8 @@ int mcr_scone_vis_forward(const float* pts, const float* view_harmonics, float* 
         // columns 126, 127 = 0 + 0 are overwritten by the cloud-wide max below)
         _Float16* x1l = hh + (size_t)T * 128;
         launch_linear_smallk_planes(s, pts, 4, l1.w, l1.b, hh, x1l, 128, T, VIS_F, 4, ACT_GELU, 128);
-        const _Float16* wp = (const _Float16*)hp_l2;                                            // host-built (once per parameter version) ...
-        const float* bp = hb_l2;
+        const _Float16* wp = (const _Float16*)w.p_l2;                                            // host-built (once per parameter version) ...
+        const float* bp = w.b_l2p;
         if (!wp) {                                                                              // ... or padded here, per call
             float* bq = ff + (size_t)128 * 128;
             launch_pad_weights(s, l2.w, VIS_F, l2.b, ff, bq, VIS_F, VIS_F, 128, 128);
@@ -620,12 +569,12 @@ int mcr_scone_vis_forward(const float* pts, const float* view_harmonics, float* 
         launch_linear(s, h, VIS_F, l2.w, l2.b, nullptr, 0, x, VIS_E, T, VIS_F, VIS_F, ACT_NONE, nullptr, 0, 0, N);
     }
     launch_colmax_broadcast(s, x, VIS_E, x + VIS_F, VIS_E, B, (int)N, VIS_F, lengths, pts, 4, 4, x + 2 * VIS_F);   // (+ the raw input columns)
-    for (int e = 0; e < 3; ++e) run_encoder(s, enc[e], x, h, qkv, ff, B, (int)N, VIS_E, 4, lengths);   // SconeVis.py:139-140
+    for (int e = 0; e < 3; ++e) run_encoder(s, w.enc[e], x, h, qkv, ff, B, (int)N, VIS_E, 4, lengths);   // SconeVis.py:139-140
     if (planes) {
         // :143-152 on planes: LayerNorm -> planes; fc1 (GELU) writes columns 0..191 of the next operand's planes, the view harmonics are
         // split into columns 192..255; fc2 (GELU) writes planes; fc3 leaves fp32.  Weight planes: split per call into the idle qkv region
-        launch_layernorm_planes(s, x, VIS_E, ng, nb, hh, np == 1 ? nullptr : hl, VIS_E, T, VIS_E);
-        const _Float16 *w1 = (const _Float16*)hp_fc1, *w2 = (const _Float16*)hp_fc2, *w3 = (const _Float16*)hp_fc3;
+        launch_layernorm_planes(s, x, VIS_E, w.ng, w.nb, hh, np == 1 ? nullptr : hl, VIS_E, T, VIS_E);
+        const _Float16 *w1 = (const _Float16*)w.p_fc1, *w2 = (const _Float16*)w.p_fc2, *w3 = (const _Float16*)w.p_fc3;
         if (!w1) {
             _Float16* q1 = reinterpret_cast<_Float16*>(qkv);
             _Float16* q2 = q1 + (size_t)2 * 192 * VIS_E;
@@ -645,7 +594,7 @@ int mcr_scone_vis_forward(const float* pts, const float* view_harmonics, float* 
         launch_linear3p(s, hh, gl, 128, w3, w3 + (size_t)64 * 128, 128, fc3.b, out, nullptr, nullptr, 64, T, 64, 128, ACT_NONE, inv, nullptr, 0, nullptr,
                         nullptr, 0, np);
     } else {
-        launch_layernorm(s, x, VIS_E, ng, nb, h, VIS_E, T, VIS_E);                                   // :143
+        launch_layernorm(s, x, VIS_E, w.ng, w.nb, h, VIS_E, T, VIS_E);                                   // :143
         // fc1 256->192 GELU, || view_harmonics (64), fc2 256->128 GELU, fc3 128->64                  (:146-152)
         launch_linear(s, h, VIS_E, fc1.w, fc1.b, nullptr, 0, ff, VIS_E, T, 192, VIS_E, ACT_GELU, nullptr, 0, 0, head_route(N));
         launch_copy2d(s, view_harmonics, 64, ff + 192, VIS_E, T, 64);
@@ -661,22 +610,33 @@ int mcr_scone_vis_forward(const float* pts, const float* view_harmonics, float* 
 // torch's CPU generator exactly like the reference: randperm at :269 and :311):
 //   pc_global [B, Lg, 3]            Lg = min(M, 2048)
 //   pc_scale[i] [B, M_i, 3], i < 3  the cloud seen by scale i (M_0 = M, then M_i = M_{i-1} // ds_factor)
-constexpr int OCC_NW = PCT_NW * 4 + 6 + 6, OCC_CHUNK = 16384;
+constexpr int OCC_CHUNK = 16384;
+// per-query feature row: [ local 3x256 | x-embedding 512 | view harmonics 64 ] = 1344   (cat at SconeOcc.py:333
+// is (global 512, local 768, x 512, harmonics 64); the per-cloud global part is folded into a row bias)
+constexpr int FEAT = 1344;
+constexpr size_t OCC_WS_SLACK = 8192 + 2 * 1024, OCC_RAGGED_WS_SLACK = 8192 + 1024;
 
-size_t mcr_scone_occ_workspace_bytes(int64_t B, int64_t Q, int64_t Lg) {
-    const int64_t qc = std::min<int64_t>(Q, OCC_CHUNK);
-    size_t local = pct_ws_bytes(qc * 16) + al(qc * 16 * 3) + al(qc * 16) + al(qc * 16 * 2) + 1024;
-    local = std::max(local, al(B * Q * 16 * 3) + al(Q * 16) + al(Q * 16 * 2) + 1024);  // fused path: kNN outputs for all B x Q rows
-    size_t glob = pct_ws_bytes(B * Lg);
-    size_t head = al(B * Q * 1344) + al(B * Q * 512) + al(B * Q * 256) + al(B * 512) * 2;
-    head += linear3h_planes_bytes(512, 1344);        // split weight planes of the largest head layer (reused layer after layer)
-    // grid-pruned kNN (knn.hip: K1-grid): the query order of all clouds + one sorted candidate copy (the largest admissible cloud)
-    const size_t knn_grid = knn_grid_query_bytes(B, Q) + 3 * knn_grid_cloud_bytes(B, 16384) + knn_grid_park_bytes() + 1024;
-    return local + glob + head + knn_grid + 8192;          // local and global paths run concurrently (two streams): disjoint scratch
+// ---- what the dense and the ragged entry share: the workspace's front, the side stream, everything behind the local features ----
+// The head's scratch over T query rows in G groups (clouds / jobs): the workspace of both entries starts with it, the global
+// transformer's scratch follows (local and global paths run concurrently, on two streams: disjoint scratch).
+struct OccHead {
+    float *feat, *h1, *h2, *gfeat, *gbias;
+    void* wplanes;                                        // split weight planes of the largest head layer (reused layer after layer)
+    // variant 6 with all three fused transformers: the head runs on fp16 hi/lo planes end to end (run_head_planes); the feature
+    // buffer then holds planes [2][T][1344] fp16 instead of fp32 [T][1344]
+    _Float16* featP() const { return reinterpret_cast<_Float16*>(feat); }
+    HeadScratch planes() const { return HeadScratch{featP(), reinterpret_cast<_Float16*>(h1), h2, wplanes}; }
+};
+static OccHead carve_occ_head(Arena& a, int64_t T, int64_t G) {
+    OccHead w;
+    w.feat = a.f(T * FEAT);
+    w.h1 = a.f(T * 512);
+    w.h2 = a.f(T * 256);
+    w.gfeat = a.f(G * 512);
+    w.gbias = a.f(G * 512);
+    w.wplanes = a.bytes(linear3h_planes_bytes(512, 1344));
+    return w;
 }
-
-int mcr_knn_points(const float* X, const float* pc, int64_t* idx, float* dists, float* pts, int64_t B, int64_t Q, int64_t M,
-                   int k, int subtract_query, void* stream);
 
 // The global feature (a chain of ~20 small launches on 2048 tokens, ~0.3 ms of mostly latency) depends on nothing the local
 // path produces and is needed only by the first head layer: it runs on a side stream beside the kNN / local-transformer
@@ -704,22 +664,134 @@ static OccSide* occ_side(hipStream_t caller, int slot = 0) {
     }
     return &x;
 }
+// fork the side stream off s: the stream the side work goes to -- s itself, and side = NULL, when there is none or the fork failed
+static hipStream_t fork_side(hipStream_t s, OccSide*& side) {
+    if (side && hipEventRecord(side->fork, s) == hipSuccess && hipStreamWaitEvent(side->s, side->fork, 0) == hipSuccess) return side->s;
+    side = nullptr;
+    return s;
+}
+// every way out of an entry joins the side stream again (error returns included: a dangling fork would poison a capture and
+// let side-stream work outlive the caller's workspace): the guard exists before anything is queued on the side stream, and on an
+// early return it records the join itself
+struct SideJoin {
+    OccSide* side; hipStream_t s; bool recorded = false, joined = false;
+    ~SideJoin() {
+        if (!side || joined) return;
+        if (!recorded) (void)hipEventRecord(side->join, side->s);
+        (void)hipStreamWaitEvent(s, side->join, 0);
+    }
+};
 
-int mcr_scone_occ_forward_phase(const float* pc_global, int64_t Lg, const float* const* pc_scale, const int64_t* M_scale,
-                                const float* x, const float* view_harmonics, float* out, int64_t B, int64_t Q,
-                                const float* const* weights, int n_weights, const float* const* local_blobs,
-                                const void* const* head_planes, const float* head_inv_scales, int* range_flag, void* workspace,
-                                size_t workspace_bytes, int phase, void* stream);
-int mcr_scone_occ_forward(const float* pc_global, int64_t Lg, const float* const* pc_scale, const int64_t* M_scale,
-                          const float* x, const float* view_harmonics, float* out, int64_t B, int64_t Q,
-                          const float* const* weights, int n_weights, const float* const* local_blobs,
-                          const void* const* head_planes, const float* head_inv_scales, int* range_flag, void* workspace,
-                          size_t workspace_bytes, void* stream) {
-    return mcr_scone_occ_forward_phase(pc_global, Lg, pc_scale, M_scale, x, view_harmonics, out, B, Q, weights, n_weights, local_blobs,
-                                       head_planes, head_inv_scales, range_flag, workspace, workspace_bytes, 0, stream);
+// the global feature of G clouds (SconeOcc.py:269-277) and its contribution to linear1: gbias[b, n] = sum_k gfeat[b, k] * W1[n, k]
+// (columns 0..511 of linear1.weight)
+static void run_global(hipStream_t gs, const OccW& w, const float* pc_global, int64_t G, int64_t Lg, const int* lens, const EncScratch& glob,
+                       const OccHead& hd) {
+    run_pct(gs, w.global, pc_global, hd.gfeat, 512, G, (int)Lg, 256, glob, lens);
+    launch_linear(gs, hd.gfeat, 512, w.lin1.w, nullptr, nullptr, 0, hd.gbias, 512, G, 512, 512, ACT_NONE, nullptr, 0, 1856, 1);
 }
 
-// The same in two calls on one stream and ONE workspace.  Phase 1 = what needs neither the view harmonics nor any hidden draw: the
+// The large layers of the fp32-input head run on the matrix path of the selected variant -- 6: fp16 x 3 with the weights split once
+// per call into `wplanes`; 5: bf16 x 6 (exact hi/mid/lo); 1: exact fp32 MFMA -- chosen by the variant and the layer alone, never by
+// the number of rows: a query's occupancy must not depend on how many other queries share the launch (query shards of the
+// multi-GPU step, chunks, scene batches and the single call agree bit for bit).
+// which: 0 xe2, 1 xe3, 2 lin1 (columns 512..1855), 3 lin2 -- the order of the host's pre-split planes (variant 6)
+// rb (optional): the row bias, grouped by rows_per_group (dense: rows of one cloud) or by row_group (ragged: the job of each row)
+static void head_linear(hipStream_t s, int which, const float* X, int64_t ldx, const float* W, int64_t ldw, const float* b, float* Y, int64_t ldy,
+                        int64_t M, int N, int K, const float* rb, int64_t rows_per_group, const int* row_group, const void* const* head_planes,
+                        const float* head_inv_scales, void* wplanes) {
+    const int variant = g_local_pct_variant;
+    const int64_t ANY_M = (int64_t)1 << 40;
+    if ((variant == 6 || variant == 7) && linear3h_applicable(X, ldx, W, ldw, ANY_M, N, K)) {
+        const bool pre = head_planes && head_planes[which] && head_inv_scales[which] > 0.f;
+        launch_linear3h(s, X, ldx, W, ldw, pre ? const_cast<void*>(head_planes[which]) : wplanes, b, nullptr, 0, Y, ldy, M, N, K, ACT_GELU, rb,
+                        rows_per_group, pre ? head_inv_scales[which] : 0.f, row_group);
+    } else if (variant == 5 && linear3_applicable(X, ldx, W, ldw, ANY_M, N, K))
+        launch_linear3(s, X, ldx, W, b, nullptr, 0, Y, ldy, M, N, K, ACT_GELU, rb, rows_per_group, ldw, row_group);
+    else
+        launch_linear(s, X, ldx, W, b, nullptr, 0, Y, ldy, M, N, K, ACT_GELU, rb, rows_per_group, ldw, /*route_rows=*/1, row_group);
+}
+
+// Everything behind the local features: x embedding, the join with the side stream (the global feature is needed from the first
+// head layer on), head MLP, range guard.  planes: on fp16 planes end to end (x_done: its x embedding has been queued elsewhere).
+static int run_occ_head(const char* who, hipStream_t s, const OccW& w, const float* x, const float* view_harmonics, int64_t T, const OccHead& hd,
+                        int64_t rows_per_group, const int* row_group, const void* const* head_planes, const float* head_inv_scales, bool planes,
+                        bool x_done, OccSide* side, SideJoin& side_join, int* range_flag, float* out) {
+    bool join_failed = false;
+    auto join = [&]() {
+        if (side) {
+            side_join.joined = true;
+            join_failed = hipStreamWaitEvent(s, side->join, 0) != hipSuccess;
+        }
+    };
+    if (planes)
+        run_head_planes(s, x, view_harmonics, T, w.xe1, w.xe2, w.xe3, w.lin1, w.lin2, w.lin3, hd.gbias, rows_per_group, row_group, head_planes,
+                        head_inv_scales, hd.planes(), out, join, x_done);
+    else {
+        // ---- x embedding 3 -> 128 -> 256 -> 512, GELU each (SconeOcc.py:35-42) ----
+        launch_linear(s, x, 3, w.xe1.w, w.xe1.b, nullptr, 0, hd.h2, 128, T, 128, 3, ACT_GELU, nullptr, 0, 0, 1);
+        head_linear(s, 0, hd.h2, 128, w.xe2.w, 128, w.xe2.b, hd.h1, 256, T, 256, 128, nullptr, 0, nullptr, head_planes, head_inv_scales, hd.wplanes);
+        head_linear(s, 1, hd.h1, 256, w.xe3.w, 256, w.xe3.b, hd.feat + 768, FEAT, T, 512, 256, nullptr, 0, nullptr, head_planes, head_inv_scales, hd.wplanes);
+        launch_copy2d(s, view_harmonics, 64, hd.feat + 1280, FEAT, T, 64);
+        // ---- head MLP 1856 -> 512 -> 256 -> 1, GELU after every layer incl. the last (SconeOcc.py:334-345) ----
+        join();
+        MCR_REQUIRE(!join_failed, "%s: side stream (join)", who);
+        head_linear(s, 2, hd.feat, FEAT, w.lin1.w + 512, 1856, w.lin1.b, hd.h1, 512, T, 512, FEAT, hd.gbias, rows_per_group, row_group, head_planes,
+                    head_inv_scales, hd.wplanes);
+        head_linear(s, 3, hd.h1, 512, w.lin2.w, 512, w.lin2.b, hd.h2, 256, T, 256, 512, nullptr, 0, nullptr, head_planes, head_inv_scales, hd.wplanes);
+        launch_linear(s, hd.h2, 256, w.lin3.w, w.lin3.b, nullptr, 0, out, 1, T, 1, 256, ACT_GELU, nullptr, 0, 0, 1);
+    }
+    MCR_REQUIRE(!join_failed, "%s: side stream (join)", who);
+    // range guard of the fp16 split path: an activation beyond the fp16 range (|x| >= 65520) becomes inf in its high plane and
+    // reaches the output as a non-finite occupancy (inf - inf in the accumulators, NaN through LayerNorm / soft-max / the mean
+    // pooling); the caller re-runs on the full-range variant 5 when the flag comes back set
+    if (range_flag) launch_nonfinite_flag(s, out, T, range_flag);
+    MCR_LAUNCH_CHECK(who);
+    return 0;
+}
+
+// ---- the dense entry's workspace: head | grid kNN | global transformer | scratch ----
+// `scratch` is what is left behind the rest; every (cloud, scale) launch of the local path carves it anew: the [rows,16,3] offsets
+// of its queries (only the offsets are consumed, SconeOcc.py:297-298: indices and distances are not written) and, on the
+// layer-by-layer path through HBM, the transformer's scratch over rows sequences of 16 points
+struct OccLocal { float* offs; EncScratch pct; };
+static OccLocal carve_occ_local(Arena& a, int64_t rows, bool layer_by_layer) {
+    OccLocal w{};
+    w.offs = a.f(rows * 16 * 3);
+    if (layer_by_layer) w.pct = carve_enc(a, rows * 16, PCT_E);
+    return w;
+}
+struct OccScratch {
+    OccHead head;
+    // grid-pruned kNN (knn.hip: K1-grid): the query order of all clouds + one sorted candidate copy per scale (the largest admissible cloud)
+    char *knn_q, *knn_c, *knn_park;
+    size_t knn_c_bytes;
+    EncScratch glob;
+    Arena scratch;
+};
+static OccScratch carve_occ(Arena& a, int64_t B, int64_t Q, int64_t Lg) {
+    OccScratch w;
+    w.head = carve_occ_head(a, B * Q, B);
+    w.knn_c_bytes = knn_grid_cloud_bytes(B, 16384);
+    w.knn_q = (char*)a.bytes(knn_grid_query_bytes(B, Q));
+    w.knn_c = (char*)a.bytes(3 * w.knn_c_bytes);
+    w.knn_park = (char*)a.bytes(knn_grid_park_bytes());
+    w.glob = carve_enc(a, B * Lg, PCT_E);
+    w.scratch = a.rest();
+    return w;
+}
+size_t mcr_scone_occ_workspace_bytes(int64_t B, int64_t Q, int64_t Lg) {
+    // this function knows neither the variant nor whether the fused blobs are given, so `scratch` covers the largest of the forms a
+    // call of these dimensions can take: the offsets of all B x Q rows (fused path, a batch of clouds in one launch), one cloud's
+    // (fused path, per cloud), or the layer-by-layer path over a chunk of queries
+    const size_t local = std::max({measure(carve_occ_local, B * Q, false), measure(carve_occ_local, Q, false),
+                                   measure(carve_occ_local, std::min<int64_t>(Q, OCC_CHUNK), true)});
+    return measure(carve_occ, B, Q, Lg) + local + OCC_WS_SLACK;
+}
+
+int mcr_knn_points(const float* X, const float* pc, int64_t* idx, float* dists, float* pts, int64_t B, int64_t Q, int64_t M,
+                   int k, int subtract_query, void* stream);
+
+// mcr_scone_occ_forward (phase 0: the single call, below) or the same in two calls on one stream and ONE workspace.  Phase 1 = what needs neither the view harmonics nor any hidden draw: the
 // query order of the grid search, scale 0 (the whole cloud: search + local transformer) -- it reads x, pc_scale[0] and M_scale[0..2]
 // only (the sizes of the down-sampled clouds are known before they are drawn) and is the first long kernel of an NBV step, so a
 // caller queues it BEFORE it builds the view state, the harmonics and the down-sampled clouds: the host work of those hides behind
@@ -730,79 +802,44 @@ int mcr_scone_occ_forward_phase(const float* pc_global, int64_t Lg, const float*
                                 const float* const* weights, int n_weights, const float* const* local_blobs,
                                 const void* const* head_planes, const float* head_inv_scales, int* range_flag, void* workspace,
                                 size_t workspace_bytes, int phase, void* stream) {
+    const char* who = "mcr_scone_occ_forward";
     VariantScope variant_scope_;
     MCR_REQUIRE(phase >= 0 && phase <= 2, "mcr_scone_occ_forward: phase must be 0, 1 or 2");
     const bool early = phase != 2, late = phase != 1;
     MCR_REQUIRE(pc_scale && M_scale && x && weights && (!late || (pc_global && view_harmonics && out)), "mcr_scone_occ_forward: null pointer");
     MCR_REQUIRE(!head_planes || head_inv_scales, "mcr_scone_occ_forward: head_planes need head_inv_scales");
-    MCR_REQUIRE(n_weights == OCC_NW || n_weights == OCC_NW + 8 || n_weights == OCC_NW + 11,
-                "mcr_scone_occ_forward: expected %d weight pointers (+ 8 or 11 plane pointers), got %d", OCC_NW, n_weights);
+    if (check_table(who, OCC_TABLE, weights, n_weights, n_weights)) return 1;
     MCR_REQUIRE(B > 0 && Q > 0 && Lg > 0 && B <= 65535, "mcr_scone_occ_forward: bad problem size");
     MCR_REQUIRE(workspace && workspace_bytes >= mcr_scone_occ_workspace_bytes(B, Q, Lg), "mcr_scone_occ_forward: workspace too small");
-    for (int i = 0; i < n_weights; ++i) MCR_REQUIRE(weights[i], "mcr_scone_occ_forward: weight %d is null", i);
     for (int i = 0; i < 3; ++i)
         MCR_REQUIRE((pc_scale[i] || (!late && i > 0)) && M_scale[i] >= 16, "mcr_scone_occ_forward: scale %d has %ld points (< k = 16)", i,
                     (long)M_scale[i]);
     hipStream_t s = (hipStream_t)stream;
-    const float* const* p = weights;
-    PctW wg = read_pct(p);
-    const PctW wl[3] = {read_pct(p), read_pct(p), read_pct(p)};
-    LinW xe1{p[0], p[1]}, xe2{p[2], p[3]}, xe3{p[4], p[5]};
-    p += 6;
-    LinW lin1{p[0], p[1]}, lin2{p[2], p[3]}, lin3{p[4], p[5]};
-    p += 6;
-    if (n_weights >= OCC_NW + 8) { read_enc_planes(p, wg.enc[0]); read_enc_planes(p, wg.enc[1]); }     // the global transformer's encoders
-    if (n_weights == OCC_NW + 11) read_pct_end_planes(p, wg);                                           // ... and its end layers
-
-    Arena head{(char*)workspace, workspace_bytes, 0};
-    // per-query feature row: [ local 3x256 | x-embedding 512 | view harmonics 64 ] = 1344   (cat at SconeOcc.py:333
-    // is (global 512, local 768, x 512, harmonics 64); the per-cloud global part is folded into a row bias)
-    constexpr int FEAT = 1344;
-    float* feat = head.f(B * Q * FEAT);
-    float* h1 = head.f(B * Q * 512);
-    float* h2 = head.f(B * Q * 256);
-    float* gfeat = head.f(B * 512);
-    float* gbias = head.f(B * 512);
-    void* wplanes = head.f(linear3h_planes_bytes(512, 1344) / sizeof(float));
-    const size_t knn_q_bytes = knn_grid_query_bytes(B, Q), knn_c_bytes = knn_grid_cloud_bytes(B, 16384);
-    char* knn_q_ws = (char*)head.f((knn_q_bytes + 3) / 4);
-    char* knn_c_ws = (char*)head.f((3 * knn_c_bytes + 3) / 4);
-    char* knn_park_ws = (char*)head.f((knn_grid_park_bytes() + 3) / 4);
-    const size_t glob_bytes = pct_ws_bytes(B * Lg);
-    Arena garena{(char*)workspace + head.off, glob_bytes, 0};
-    Arena scratch{(char*)workspace + head.off + glob_bytes, workspace_bytes - head.off - glob_bytes, 0};
+    const OccW w = read_occ_table(weights, n_weights);
+    Arena arena{(char*)workspace, workspace_bytes};
+    const OccScratch ws = carve_occ(arena, B, Q, Lg);
+    MCR_REQUIRE(arena.ok(), "mcr_scone_occ_forward: workspace overflow (global)");
+    const OccHead& hd = ws.head;
+    float* feat = hd.feat;
 
     // ---- global feature (SconeOcc.py:269-277), on the side stream ----
     OccSide* side = late ? occ_side(s) : nullptr;
-    hipStream_t gs = s;
-    if (side && hipEventRecord(side->fork, s) == hipSuccess && hipStreamWaitEvent(side->s, side->fork, 0) == hipSuccess) gs = side->s;
-    else side = nullptr;
-    // every way out of this function joins the side stream again (error returns included: a dangling fork would poison a capture and
-    // let side-stream work outlive the caller's workspace): the guard exists before anything is queued on the side stream, and on an
-    // early return it records the join itself
-    struct SideJoin {
-        OccSide* side; hipStream_t s; bool recorded, joined;
-        ~SideJoin() {
-            if (!side || joined) return;
-            if (!recorded) (void)hipEventRecord(side->join, side->s);
-            (void)hipStreamWaitEvent(s, side->join, 0);
-        }
-    } side_join{side, s, false, false};
+    const hipStream_t gs = fork_side(s, side);
+    SideJoin side_join{side, s};
     // fused path: one kNN + one LDS-resident transformer launch per (cloud, scale) over ALL queries (nothing but
     // the [Q,16,3] offsets is materialised); layer-by-layer path: chunked over queries to bound its workspace.
     const bool fused_all = local_blobs && local_blobs[0] && local_blobs[1] && local_blobs[2];
     const int64_t qc = fused_all ? Q : std::min<int64_t>(Q, OCC_CHUNK);
-    // variant 6 with all three fused transformers: the head runs on fp16 hi/lo planes end to end (run_head_planes); the feature
-    // buffer then holds planes [2][T][1344] fp16 instead of fp32 [T][1344] (MCR_HEAD_PLANES=0: the fp32-input linear3h path)
+    // the planes head (OccHead::planes; MCR_HEAD_PLANES=0: the fp32-input linear3h path)
     static const bool planes_on = []() { const char* e = getenv("MCR_HEAD_PLANES"); return !(e && e[0] == '0'); }();
     const bool planes = planes_on && fused_all && fp16_planes_variant();
-    _Float16* featP = reinterpret_cast<_Float16*>(feat);
+    _Float16* featP = hd.featP();
     const int64_t Tall = B * Q;
     // the x embedding of the planes head (0.3 ms of GEMMs that need only the queries) rides on the side stream behind the global
     // transformer: its workgroups fill the machine in the holes of the local path (kNN preparation, the parked kNN groups, kernel
     // tails) instead of extending the serial tail of the step.  MCR_OCC_X_SIDE=0: on the caller's stream, after the local path.
     static const bool x_side_on = []() { const char* e = getenv("MCR_OCC_X_SIDE"); return !(e && e[0] == '0'); }();
-    const HeadScratch head_scratch{featP, reinterpret_cast<_Float16*>(h1), h2, wplanes};
+    const HeadScratch head_scratch = hd.planes();
     // ... and it needs nothing but the queries, so it is queued with the EARLY part (phase 1 / the start of the single call), where the
     // GPU is nearly idle for ~0.4 ms (query order, cloud build, the scale-0 search): behind the global transformer it only found the
     // holes between the local-transformer launches and finished 0.15 ms AFTER the last of them -- the head waited for it
@@ -821,18 +858,15 @@ int mcr_scone_occ_forward_phase(const float* pc_global, int64_t Lg, const float*
     if (x_early && early) {
         MCR_REQUIRE(hipEventRecord(xside->fork, s) == hipSuccess && hipStreamWaitEvent(xside->s, xside->fork, 0) == hipSuccess,
                     "mcr_scone_occ_forward: side stream (x embedding fork)");
-        run_x_embedding_planes(xside->s, x, nullptr, B * Q, xe1, xe2, xe3, head_planes, head_inv_scales, head_scratch);
+        run_x_embedding_planes(xside->s, x, nullptr, B * Q, w.xe1, w.xe2, w.xe3, head_planes, head_inv_scales, head_scratch);
         MCR_REQUIRE(hipEventRecord(xside->join, xside->s) == hipSuccess, "mcr_scone_occ_forward: side stream (x embedding record)");
         x_join.armed = true;
     }
     if (late) {
-        run_pct(gs, wg, pc_global, gfeat, 512, B, (int)Lg, 256, garena);
-        MCR_REQUIRE(garena.ok(), "mcr_scone_occ_forward: workspace overflow (global)");
-        // its contribution to linear1: gbias[b, n] = sum_k gfeat[b, k] * W1[n, k]  (columns 0..511 of linear1.weight)
-        launch_linear(gs, gfeat, 512, lin1.w, nullptr, nullptr, 0, gbias, 512, B, 512, 512, ACT_NONE, nullptr, 0, 1856, 1);
+        run_global(gs, w, pc_global, B, Lg, nullptr, ws.glob, hd);
         if (x_on_side && x_early)
             launch_split_to_planes(gs, view_harmonics, 64, featP + 1280, matrix_planes() == 1 ? nullptr : featP + Tall * FEAT + 1280, 1344, B * Q, 64);
-        else if (x_on_side) run_x_embedding_planes(gs, x, view_harmonics, B * Q, xe1, xe2, xe3, head_planes, head_inv_scales, head_scratch);
+        else if (x_on_side) run_x_embedding_planes(gs, x, view_harmonics, B * Q, w.xe1, w.xe2, w.xe3, head_planes, head_inv_scales, head_scratch);
     }
     if (side) {
         MCR_REQUIRE(hipEventRecord(side->join, side->s) == hipSuccess, "mcr_scone_occ_forward: side stream (record)");
@@ -848,24 +882,24 @@ int mcr_scone_occ_forward_phase(const float* pc_global, int64_t Lg, const float*
         int n_grid = 0;
         for (int sc = 0; sc < 3; ++sc)
             if (knn_grid_applicable(M_scale[sc], 16)) {
-                g_pc[n_grid] = pc_scale[sc]; g_M[n_grid] = M_scale[sc]; g_ws[n_grid] = knn_c_ws + n_grid * knn_c_bytes;
+                g_pc[n_grid] = pc_scale[sc]; g_M[n_grid] = M_scale[sc]; g_ws[n_grid] = ws.knn_c + n_grid * ws.knn_c_bytes;
                 knn_slot[sc] = n_grid++;
             }
         if (n_grid) {
             // the query order belongs to phase 1 (phase 2 finds it where phase 1 left it); every scale's cloud is built in the
             // phase that searches it -- all of them in one launch on the single call
             if (phase == 0) {
-                knn_qperm = knn_grid_order_queries(s, x, B, Q, knn_q_ws, knn_park_ws);
+                knn_qperm = knn_grid_order_queries(s, x, B, Q, ws.knn_q, ws.knn_park);
                 knn_grid_build_clouds(s, n_grid, g_pc, g_M, B, g_ws, knn_clouds);
             } else {
                 const int first = early ? 0 : (knn_slot[0] >= 0 ? 1 : 0), count = early ? (knn_slot[0] >= 0 ? 1 : 0) : n_grid - first;
                 // phase 1 opens the step on an idle GPU: the cloud build (one workgroup per cloud, 40 us) runs on the side stream beside
                 // the five small launches of the query order instead of after them
                 OccSide* bside = early && count > 0 ? occ_side(s) : nullptr;
-                if (bside && !(hipEventRecord(bside->fork, s) == hipSuccess && hipStreamWaitEvent(bside->s, bside->fork, 0) == hipSuccess)) bside = nullptr;
-                knn_grid_build_clouds(bside ? bside->s : s, count, g_pc + first, g_M + first, B, g_ws + first, knn_clouds + first);
+                const hipStream_t bs = fork_side(s, bside);
+                knn_grid_build_clouds(bs, count, g_pc + first, g_M + first, B, g_ws + first, knn_clouds + first);
                 const bool recorded = !bside || hipEventRecord(bside->join, bside->s) == hipSuccess;
-                knn_qperm = knn_grid_order_queries(s, x, B, Q, knn_q_ws, knn_park_ws, /*launch=*/early);
+                knn_qperm = knn_grid_order_queries(s, x, B, Q, ws.knn_q, ws.knn_park, /*launch=*/early);
                 const bool joined = !bside || hipStreamWaitEvent(s, bside->join, 0) == hipSuccess;        // (waits for a stale record at worst)
                 MCR_REQUIRE(recorded && joined, "mcr_scone_occ_forward: side stream (cloud build)");
             }
@@ -876,16 +910,17 @@ int mcr_scone_occ_forward_phase(const float* pc_global, int64_t Lg, const float*
         if (sc == 0 ? !early : !late) continue;
         const bool grid_knn = knn_slot[sc] >= 0;
         const KnnGridCloud knn_cloud = grid_knn ? knn_clouds[knn_slot[sc]] : KnnGridCloud{};
+        const bool fused = planes || (local_blobs && local_blobs[sc]);      // the fused LDS-resident kernel (local_pct*.hip)
         // a batch of clouds on the fused path (config 3's scene batch): ONE search and ONE transformer launch per scale over all B x Q
         // rows instead of one per cloud -- eight brute-force searches of 256 workgroups each (one wave per SIMD: every wave waits out
         // its own latencies) become one of 2048.  The rows are the same rows: same bits.  MCR_OCC_BATCH_LOCAL=0: per cloud (A/B)
         static const bool batch_local_on = []() { const char* e = getenv("MCR_OCC_BATCH_LOCAL"); return !(e && e[0] == '0'); }();
-        if (batch_local_on && B > 1 && qc == Q && (planes || (local_blobs && local_blobs[sc]))) {
-            Arena a = scratch;
-            float* offs = a.f(Tall * 16 * 3);
+        if (batch_local_on && B > 1 && qc == Q && fused) {
+            Arena a = ws.scratch;
+            float* offs = carve_occ_local(a, Tall, false).offs;
             if (a.ok()) {
                 if (grid_knn) {
-                    launch_knn16_grid(s, x, pc_scale[sc], M_scale[sc], knn_qperm, knn_cloud, 0, B, Q, nullptr, nullptr, offs, true, knn_park_ws, sc);
+                    launch_knn16_grid(s, x, pc_scale[sc], M_scale[sc], knn_qperm, knn_cloud, 0, B, Q, nullptr, nullptr, offs, true, ws.knn_park, sc);
                     MCR_LAUNCH_CHECK("knn_grid_kernel");
                 } else if (int e = mcr_knn_points(x, pc_scale[sc], nullptr, nullptr, offs, B, Q, M_scale[sc], 16, 1, stream))
                     return e;
@@ -897,12 +932,12 @@ int mcr_scone_occ_forward_phase(const float* pc_global, int64_t Lg, const float*
         for (int64_t q0 = 0; q0 < Q; q0 += qc) {
             const int64_t nq = std::min<int64_t>(qc, Q - q0);
             for (int64_t b = 0; b < B; ++b) {
-                Arena a = scratch;
-                float* offs = a.f(nq * 16 * 3);
-                MCR_REQUIRE(a.ok(), "mcr_scone_occ_forward: workspace overflow (kNN)");
-                // only the offsets are consumed (SconeOcc.py:297-298): indices and distances are not written
+                Arena a = ws.scratch;
+                const OccLocal loc = carve_occ_local(a, nq, !fused);
+                MCR_REQUIRE(a.ok(), fused ? "mcr_scone_occ_forward: workspace overflow (kNN)" : "mcr_scone_occ_forward: workspace overflow (local)");
+                float* offs = loc.offs;
                 if (grid_knn) {
-                    launch_knn16_grid(s, x, pc_scale[sc], M_scale[sc], knn_qperm, knn_cloud, b, 1, Q, nullptr, nullptr, offs, true, knn_park_ws,
+                    launch_knn16_grid(s, x, pc_scale[sc], M_scale[sc], knn_qperm, knn_cloud, b, 1, Q, nullptr, nullptr, offs, true, ws.knn_park,
                                       (int)(sc * B + b));
                     MCR_LAUNCH_CHECK("knn_grid_kernel");
                 } else if (int e = mcr_knn_points(x + (b * Q + q0) * 3, pc_scale[sc] + b * M_scale[sc] * 3, nullptr, nullptr, offs, 1, nq,
@@ -911,11 +946,10 @@ int mcr_scone_occ_forward_phase(const float* pc_global, int64_t Lg, const float*
                 if (planes)
                     run_local_pct(s, offs, nullptr, FEAT, nq, local_blobs[sc], featP + (b * Q + q0) * FEAT + sc * 256,
                                   featP + Tall * FEAT + (b * Q + q0) * FEAT + sc * 256);
-                else if (local_blobs && local_blobs[sc])      // fused LDS-resident kernel (local_pct.hip)
+                else if (fused)
                     run_local_pct(s, offs, feat + (b * Q + q0) * FEAT + sc * 256, FEAT, nq, local_blobs[sc]);
                 else                                      // layer-by-layer path through HBM
-                    run_pct(s, wl[sc], offs, feat + (b * Q + q0) * FEAT + sc * 256, FEAT, nq, 16, 128, a);
-                MCR_REQUIRE(a.ok(), "mcr_scone_occ_forward: workspace overflow (local)");
+                    run_pct(s, w.local[sc], offs, feat + (b * Q + q0) * FEAT + sc * 256, FEAT, nq, 16, 128, loc.pct);
             }
         }
     }
@@ -924,59 +958,17 @@ int mcr_scone_occ_forward_phase(const float* pc_global, int64_t Lg, const float*
         MCR_LAUNCH_CHECK("mcr_scone_occ_forward (phase 1)");
         return 0;
     }
-    // The large layers run on the matrix path of the selected variant -- 6: fp16 x 3 with the weights split once per call into
-    // `wplanes`; 5: bf16 x 6 (exact hi/mid/lo); 1: exact fp32 MFMA -- chosen by the variant and the layer alone, never by the
-    // number of rows: a query's occupancy must not depend on how many other queries share the launch (query shards of the
-    // multi-GPU step, chunks, scene batches and the single call agree bit for bit).
-    const int variant = g_local_pct_variant;
-    const int64_t ANY_M = (int64_t)1 << 40;
-    // which: 0 xe2, 1 xe3, 2 lin1 (columns 512..1855), 3 lin2 -- the order of the host's pre-split planes (variant 6)
-    auto big_linear = [&](int which, const float* X_, int64_t ldx, const float* W_, int64_t ldw, const float* b_, float* Y_, int64_t ldy,
-                          int64_t M_, int N_, int K_, const float* rb, int64_t rpg) {
-        if ((variant == 6 || variant == 7) && linear3h_applicable(X_, ldx, W_, ldw, ANY_M, N_, K_)) {
-            const bool pre = head_planes && head_planes[which] && head_inv_scales[which] > 0.f;
-            launch_linear3h(s, X_, ldx, W_, ldw, pre ? const_cast<void*>(head_planes[which]) : wplanes, b_, nullptr, 0, Y_, ldy, M_, N_, K_,
-                            ACT_GELU, rb, rpg, pre ? head_inv_scales[which] : 0.f);
-        }
-        else if (variant == 5 && linear3_applicable(X_, ldx, W_, ldw, ANY_M, N_, K_))
-            launch_linear3(s, X_, ldx, W_, b_, nullptr, 0, Y_, ldy, M_, N_, K_, ACT_GELU, rb, rpg, ldw);
-        else
-            launch_linear(s, X_, ldx, W_, b_, nullptr, 0, Y_, ldy, M_, N_, K_, ACT_GELU, rb, rpg, ldw, /*route_rows=*/1);
-    };
-    const int64_t T = B * Q;
-    if (planes) {
-        bool join_failed = false;
-        run_head_planes(s, x, view_harmonics, T, xe1, xe2, xe3, lin1, lin2, lin3, gbias, Q, nullptr, head_planes, head_inv_scales,
-                        head_scratch, out, [&]() {
-                            if (side) {
-                                side_join.joined = true;
-                                join_failed = hipStreamWaitEvent(s, side->join, 0) != hipSuccess;
-                            }
-                        }, x_on_side);
-        MCR_REQUIRE(!join_failed, "mcr_scone_occ_forward: side stream (join)");
-        if (range_flag) launch_nonfinite_flag(s, out, T, range_flag);
-        MCR_LAUNCH_CHECK("mcr_scone_occ_forward");
-        return 0;
-    }
-    // ---- x embedding 3 -> 128 -> 256 -> 512, GELU each (SconeOcc.py:35-42) ----
-    launch_linear(s, x, 3, xe1.w, xe1.b, nullptr, 0, h2, 128, T, 128, 3, ACT_GELU, nullptr, 0, 0, 1);
-    big_linear(0, h2, 128, xe2.w, 128, xe2.b, h1, 256, T, 256, 128, nullptr, 0);
-    big_linear(1, h1, 256, xe3.w, 256, xe3.b, feat + 768, FEAT, T, 512, 256, nullptr, 0);
-    launch_copy2d(s, view_harmonics, 64, feat + 1280, FEAT, T, 64);
-    // ---- head MLP 1856 -> 512 -> 256 -> 1, GELU after every layer incl. the last (SconeOcc.py:334-345) ----
-    if (side) {
-        side_join.joined = true;
-        MCR_REQUIRE(hipStreamWaitEvent(s, side->join, 0) == hipSuccess, "mcr_scone_occ_forward: side stream (join)");
-    }
-    big_linear(2, feat, FEAT, lin1.w + 512, 1856, lin1.b, h1, 512, T, 512, FEAT, gbias, Q);
-    big_linear(3, h1, 512, lin2.w, 512, lin2.b, h2, 256, T, 256, 512, nullptr, 0);
-    launch_linear(s, h2, 256, lin3.w, lin3.b, nullptr, 0, out, 1, T, 1, 256, ACT_GELU, nullptr, 0, 0, 1);
-    // range guard of the fp16 split path: an activation beyond the fp16 range (|x| >= 65520) becomes inf in its high plane and
-    // reaches the output as a non-finite occupancy (inf - inf in the accumulators, NaN through LayerNorm / soft-max / the mean
-    // pooling); the caller re-runs on the full-range variant 5 when the flag comes back set
-    if (range_flag) launch_nonfinite_flag(s, out, T, range_flag);
-    MCR_LAUNCH_CHECK("mcr_scone_occ_forward");
-    return 0;
+    return run_occ_head(who, s, w, x, view_harmonics, Tall, hd, Q, nullptr, head_planes, head_inv_scales, planes, /*x_done=*/x_on_side, side,
+                        side_join, range_flag, out);
+}
+
+int mcr_scone_occ_forward(const float* pc_global, int64_t Lg, const float* const* pc_scale, const int64_t* M_scale,
+                          const float* x, const float* view_harmonics, float* out, int64_t B, int64_t Q,
+                          const float* const* weights, int n_weights, const float* const* local_blobs,
+                          const void* const* head_planes, const float* head_inv_scales, int* range_flag, void* workspace,
+                          size_t workspace_bytes, void* stream) {
+    return mcr_scone_occ_forward_phase(pc_global, Lg, pc_scale, M_scale, x, view_harmonics, out, B, Q, weights, n_weights, local_blobs,
+                                       head_planes, head_inv_scales, range_flag, workspace, workspace_bytes, 0, stream);
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -985,32 +977,20 @@ int mcr_scone_occ_forward_phase(const float* pc_global, int64_t Lg, const float*
 // as ONE launch sequence.  Job j: global cloud pc_global[j] (Lg rows, the first global_len[j] valid), neighbourhood clouds
 // pc_scale[s][scale_off[s][j] .. scale_off[s][j+1]), queries = the rows r of x with row_job[r] == j (rows sorted by job).
 // knn_blocks: n_blocks x int4 (job, first row, rows <= mcr_knn_rows_per_block(), 0) covering every row once.
-size_t mcr_scone_occ_ragged_workspace_bytes(int64_t J, int64_t T, int64_t Lg) {
-    size_t local = al(T * 16 * 3) + al(knn16_segmented_split_floats(T)) + 1024;
-    size_t glob = pct_ws_bytes(J * Lg);
-    size_t head = al(T * 1344) + al(T * 512) + al(T * 256) + al(J * 512) * 2 + linear3h_planes_bytes(512, 1344);
-    return local + glob + head + 8192;
+// Its workspace: head | global transformer | the offsets of all T rows | the segmented search's split scratch
+struct OccRaggedScratch { OccHead head; EncScratch glob; float *offs, *knn_split; };
+static OccRaggedScratch carve_occ_ragged(Arena& a, int64_t J, int64_t T, int64_t Lg) {
+    OccRaggedScratch w;
+    w.head = carve_occ_head(a, T, J);
+    w.glob = carve_enc(a, J * Lg, PCT_E);
+    w.offs = a.f(T * 16 * 3);
+    w.knn_split = a.f(knn16_segmented_split_floats(T));
+    return w;
 }
+size_t mcr_scone_occ_ragged_workspace_bytes(int64_t J, int64_t T, int64_t Lg) { return measure(carve_occ_ragged, J, T, Lg) + OCC_RAGGED_WS_SLACK; }
 int mcr_knn_rows_per_block(void) { return knn_rows_per_block(); }
 
-int mcr_scone_occ_forward_ragged_phase(const float* pc_global, const int* global_len, int64_t Lg, const float* const* pc_scale,
-                                       const int64_t* const* scale_off, const float* x, const float* view_harmonics, const int* row_job,
-                                       const int* knn_blocks, int64_t n_blocks, float* out, int64_t J, int64_t T,
-                                       const float* const* weights, int n_weights, const float* const* local_blobs,
-                                       const void* const* head_planes, const float* head_inv_scales, int* range_flag, void* workspace,
-                                       size_t workspace_bytes, int phase, void* stream);
-int mcr_scone_occ_forward_ragged(const float* pc_global, const int* global_len, int64_t Lg, const float* const* pc_scale,
-                                 const int64_t* const* scale_off, const float* x, const float* view_harmonics, const int* row_job,
-                                 const int* knn_blocks, int64_t n_blocks, float* out, int64_t J, int64_t T,
-                                 const float* const* weights, int n_weights, const float* const* local_blobs,
-                                 const void* const* head_planes, const float* head_inv_scales, int* range_flag, void* workspace,
-                                 size_t workspace_bytes, void* stream) {
-    return mcr_scone_occ_forward_ragged_phase(pc_global, global_len, Lg, pc_scale, scale_off, x, view_harmonics, row_job, knn_blocks, n_blocks, out,
-                                              J, T, weights, n_weights, local_blobs, head_planes, head_inv_scales, range_flag, workspace,
-                                              workspace_bytes, 0, stream);
-}
-
-// The same in two calls on one stream and ONE workspace: phase 1 = everything that needs none of the hidden random draws (scale 0:
+// mcr_scone_occ_forward_ragged (phase 0: the single call, below) or the same in two calls on one stream and ONE workspace: phase 1 = everything that needs none of the hidden random draws (scale 0:
 // the whole clouds; the x embedding on the planes path), phase 2 = the rest (global transformer, scales 1 and 2, head).  The host
 // makes the draws (~60 us of torch.randperm per job) between the two calls while the GPU works on phase 1.  phase 0 = both.
 // Phase 1 reads pc_scale[0], scale_off[0], x, view_harmonics, row_job, knn_blocks, local_blobs[0]; phase 2 everything else too.
@@ -1020,58 +1000,37 @@ int mcr_scone_occ_forward_ragged_phase(const float* pc_global, const int* global
                                        const float* const* weights, int n_weights, const float* const* local_blobs,
                                        const void* const* head_planes, const float* head_inv_scales, int* range_flag, void* workspace,
                                        size_t workspace_bytes, int phase, void* stream) {
+    const char* who = "mcr_scone_occ_forward_ragged";
     VariantScope variant_scope_;
     MCR_REQUIRE(phase >= 0 && phase <= 2, "mcr_scone_occ_forward_ragged: phase must be 0, 1 or 2");
     const bool early = phase != 2, late = phase != 1;
     MCR_REQUIRE(pc_scale && scale_off && x && view_harmonics && row_job && knn_blocks && weights && (!late || (pc_global && global_len && out)),
                 "mcr_scone_occ_forward_ragged: null pointer");
-    MCR_REQUIRE(n_weights == OCC_NW || n_weights == OCC_NW + 8 || n_weights == OCC_NW + 11,
-                "mcr_scone_occ_forward_ragged: expected %d weight pointers (+ 8 or 11 plane pointers), got %d", OCC_NW, n_weights);
+    if (check_table(who, OCC_TABLE, weights, n_weights, n_weights)) return 1;
     MCR_REQUIRE(J > 0 && T > 0 && Lg > 0 && J <= 32767 && n_blocks > 0, "mcr_scone_occ_forward_ragged: bad problem size");
     MCR_REQUIRE(local_blobs && local_blobs[0] && local_blobs[1] && local_blobs[2],
                 "mcr_scone_occ_forward_ragged: needs the fused local-transformer blobs");
     MCR_REQUIRE(!head_planes || head_inv_scales, "mcr_scone_occ_forward_ragged: head_planes need head_inv_scales");
     MCR_REQUIRE(workspace && workspace_bytes >= mcr_scone_occ_ragged_workspace_bytes(J, T, Lg), "mcr_scone_occ_forward_ragged: workspace too small");
-    for (int i = 0; i < n_weights; ++i) MCR_REQUIRE(weights[i], "mcr_scone_occ_forward_ragged: weight %d is null", i);
     for (int i = 0; i < (late ? 3 : 1); ++i) MCR_REQUIRE(pc_scale[i] && scale_off[i], "mcr_scone_occ_forward_ragged: scale %d is null", i);
     hipStream_t s = (hipStream_t)stream;
-    const float* const* p = weights;
-    PctW wg = read_pct(p);
-    for (int i = 0; i < 3; ++i) (void)read_pct(p);
-    LinW xe1{p[0], p[1]}, xe2{p[2], p[3]}, xe3{p[4], p[5]};
-    p += 6;
-    LinW lin1{p[0], p[1]}, lin2{p[2], p[3]}, lin3{p[4], p[5]};
-    p += 6;
-    if (n_weights >= OCC_NW + 8) { read_enc_planes(p, wg.enc[0]); read_enc_planes(p, wg.enc[1]); }     // the global transformer's encoders
-    if (n_weights == OCC_NW + 11) read_pct_end_planes(p, wg);                                           // ... and its end layers
-
-    Arena head{(char*)workspace, workspace_bytes, 0};
-    constexpr int FEAT = 1344;
-    float* feat = head.f(T * FEAT);
-    float* h1 = head.f(T * 512);
-    float* h2 = head.f(T * 256);
-    float* gfeat = head.f(J * 512);
-    float* gbias = head.f(J * 512);
-    void* wplanes = head.f(linear3h_planes_bytes(512, 1344) / sizeof(float));
-    const size_t glob_bytes = pct_ws_bytes(J * Lg);
-    Arena garena{(char*)workspace + head.off, glob_bytes, 0};
-    Arena scratch{(char*)workspace + head.off + glob_bytes, workspace_bytes - head.off - glob_bytes, 0};
+    const OccW w = read_occ_table(weights, n_weights);
+    Arena arena{(char*)workspace, workspace_bytes};
+    const OccRaggedScratch ws = carve_occ_ragged(arena, J, T, Lg);
+    MCR_REQUIRE(arena.ok(), "mcr_scone_occ_forward_ragged: workspace overflow (kNN)");
+    const OccHead& hd = ws.head;
     static const bool planes_on = []() { const char* e = getenv("MCR_HEAD_PLANES"); return !(e && e[0] == '0'); }();
     const bool planes = planes_on && fp16_planes_variant();
-    _Float16* featP = reinterpret_cast<_Float16*>(feat);
-    const HeadScratch head_scratch{featP, reinterpret_cast<_Float16*>(h1), h2, wplanes};
-    float* offs = scratch.f(T * 16 * 3);
-    float* knn_split_ws = scratch.f(knn16_segmented_split_floats(T));
-    MCR_REQUIRE(scratch.ok(), "mcr_scone_occ_forward_ragged: workspace overflow (kNN)");
+    _Float16* featP = hd.featP();
     auto local_scale = [&](int sc) {                      // one segmented kNN + one fused transformer launch over ALL rows
         // (the whole clouds of scale 0 are the large ones: a launch with few query blocks cuts every job's candidates into slices of
         // ~2048 for more workgroups; slicing the down-sampled clouds of the coarser scales too -- 512 per slice -- measured no better)
-        launch_knn16_segmented(s, x, pc_scale[sc], (const long long*)scale_off[sc], knn_blocks, n_blocks, T, offs, knn_split_ws, sc == 0 ? 2048 : 0);
-        if (planes) run_local_pct(s, offs, nullptr, FEAT, T, local_blobs[sc], featP + sc * 256, featP + T * FEAT + sc * 256);
-        else run_local_pct(s, offs, feat + sc * 256, FEAT, T, local_blobs[sc]);
+        launch_knn16_segmented(s, x, pc_scale[sc], (const long long*)scale_off[sc], knn_blocks, n_blocks, T, ws.offs, ws.knn_split, sc == 0 ? 2048 : 0);
+        if (planes) run_local_pct(s, ws.offs, nullptr, FEAT, T, local_blobs[sc], featP + sc * 256, featP + T * FEAT + sc * 256);
+        else run_local_pct(s, ws.offs, hd.feat + sc * 256, FEAT, T, local_blobs[sc]);
     };
     if (early) {
-        if (planes && phase == 1) run_x_embedding_planes(s, x, view_harmonics, T, xe1, xe2, xe3, head_planes, head_inv_scales, head_scratch);
+        if (planes && phase == 1) run_x_embedding_planes(s, x, view_harmonics, T, w.xe1, w.xe2, w.xe3, head_planes, head_inv_scales, hd.planes());
         local_scale(0);
         if (!late) {
             MCR_LAUNCH_CHECK("mcr_scone_occ_forward_ragged (phase 1)");
@@ -1080,67 +1039,28 @@ int mcr_scone_occ_forward_ragged_phase(const float* pc_global, const int* global
     }
 
     OccSide* side = occ_side(s);
-    hipStream_t gs = s;
-    if (side && hipEventRecord(side->fork, s) == hipSuccess && hipStreamWaitEvent(side->s, side->fork, 0) == hipSuccess) gs = side->s;
-    else side = nullptr;
-    struct SideJoin {
-        OccSide* side; hipStream_t s; bool recorded, joined;
-        ~SideJoin() {
-            if (!side || joined) return;
-            if (!recorded) (void)hipEventRecord(side->join, side->s);
-            (void)hipStreamWaitEvent(s, side->join, 0);
-        }
-    } side_join{side, s, false, false};
-    run_pct(gs, wg, pc_global, gfeat, 512, J, (int)Lg, 256, garena, global_len);
-    MCR_REQUIRE(garena.ok(), "mcr_scone_occ_forward_ragged: workspace overflow (global)");
-    launch_linear(gs, gfeat, 512, lin1.w, nullptr, nullptr, 0, gbias, 512, J, 512, 512, ACT_NONE, nullptr, 0, 1856, 1);
+    const hipStream_t gs = fork_side(s, side);
+    SideJoin side_join{side, s};
+    run_global(gs, w, pc_global, J, Lg, global_len, ws.glob, hd);
     if (side) {
         MCR_REQUIRE(hipEventRecord(side->join, side->s) == hipSuccess, "mcr_scone_occ_forward_ragged: side stream (record)");
         side_join.recorded = true;
     }
     // ---- local features of scales 1 and 2 (scale 0: above) ----
     for (int sc = 1; sc < 3; ++sc) local_scale(sc);
-    if (planes) {
-        bool join_failed = false;
-        run_head_planes(s, x, view_harmonics, T, xe1, xe2, xe3, lin1, lin2, lin3, gbias, 0, row_job, head_planes, head_inv_scales,
-                        head_scratch, out, [&]() {
-                            if (side) {
-                                side_join.joined = true;
-                                join_failed = hipStreamWaitEvent(s, side->join, 0) != hipSuccess;
-                            }
-                        }, /*x_done=*/phase == 2);
-        MCR_REQUIRE(!join_failed, "mcr_scone_occ_forward_ragged: side stream (join)");
-        if (range_flag) launch_nonfinite_flag(s, out, T, range_flag);
-        MCR_LAUNCH_CHECK("mcr_scone_occ_forward_ragged");
-        return 0;
-    }
-    const int variant = g_local_pct_variant;
-    const int64_t ANY_M = (int64_t)1 << 40;
-    auto big_linear = [&](int which, const float* X_, int64_t ldx, const float* W_, int64_t ldw, const float* b_, float* Y_, int64_t ldy,
-                          int64_t M_, int N_, int K_, const float* rb, const int* rg) {
-        if ((variant == 6 || variant == 7) && linear3h_applicable(X_, ldx, W_, ldw, ANY_M, N_, K_)) {
-            const bool pre = head_planes && head_planes[which] && head_inv_scales[which] > 0.f;
-            launch_linear3h(s, X_, ldx, W_, ldw, pre ? const_cast<void*>(head_planes[which]) : wplanes, b_, nullptr, 0, Y_, ldy, M_, N_, K_,
-                            ACT_GELU, rb, 0, pre ? head_inv_scales[which] : 0.f, rg);
-        } else if (variant == 5 && linear3_applicable(X_, ldx, W_, ldw, ANY_M, N_, K_))
-            launch_linear3(s, X_, ldx, W_, b_, nullptr, 0, Y_, ldy, M_, N_, K_, ACT_GELU, rb, 0, ldw, rg);
-        else
-            launch_linear(s, X_, ldx, W_, b_, nullptr, 0, Y_, ldy, M_, N_, K_, ACT_GELU, rb, 0, ldw, /*route_rows=*/1, rg);
-    };
-    launch_linear(s, x, 3, xe1.w, xe1.b, nullptr, 0, h2, 128, T, 128, 3, ACT_GELU, nullptr, 0, 0, 1);
-    big_linear(0, h2, 128, xe2.w, 128, xe2.b, h1, 256, T, 256, 128, nullptr, nullptr);
-    big_linear(1, h1, 256, xe3.w, 256, xe3.b, feat + 768, FEAT, T, 512, 256, nullptr, nullptr);
-    launch_copy2d(s, view_harmonics, 64, feat + 1280, FEAT, T, 64);
-    if (side) {
-        side_join.joined = true;
-        MCR_REQUIRE(hipStreamWaitEvent(s, side->join, 0) == hipSuccess, "mcr_scone_occ_forward_ragged: side stream (join)");
-    }
-    big_linear(2, feat, FEAT, lin1.w + 512, 1856, lin1.b, h1, 512, T, 512, FEAT, gbias, row_job);
-    big_linear(3, h1, 512, lin2.w, 512, lin2.b, h2, 256, T, 256, 512, nullptr, nullptr);
-    launch_linear(s, h2, 256, lin3.w, lin3.b, nullptr, 0, out, 1, T, 1, 256, ACT_GELU, nullptr, 0, 0, 1);
-    if (range_flag) launch_nonfinite_flag(s, out, T, range_flag);
-    MCR_LAUNCH_CHECK("mcr_scone_occ_forward_ragged");
-    return 0;
+    return run_occ_head(who, s, w, x, view_harmonics, T, hd, 0, row_job, head_planes, head_inv_scales, planes, /*x_done=*/phase == 2, side, side_join,
+                        range_flag, out);
+}
+
+int mcr_scone_occ_forward_ragged(const float* pc_global, const int* global_len, int64_t Lg, const float* const* pc_scale,
+                                 const int64_t* const* scale_off, const float* x, const float* view_harmonics, const int* row_job,
+                                 const int* knn_blocks, int64_t n_blocks, float* out, int64_t J, int64_t T,
+                                 const float* const* weights, int n_weights, const float* const* local_blobs,
+                                 const void* const* head_planes, const float* head_inv_scales, int* range_flag, void* workspace,
+                                 size_t workspace_bytes, void* stream) {
+    return mcr_scone_occ_forward_ragged_phase(pc_global, global_len, Lg, pc_scale, scale_off, x, view_harmonics, row_job, knn_blocks, n_blocks, out,
+                                              J, T, weights, n_weights, local_blobs, head_planes, head_inv_scales, range_flag, workspace,
+                                              workspace_bytes, 0, stream);
 }
 
 }  // extern "C"

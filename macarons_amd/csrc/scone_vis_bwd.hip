@@ -23,6 +23,7 @@
 // (launch_linear routed to the fp32 MFMA kernel) in the recompute and the dX products.  The fp16 planes path is never taken, whatever the caller's variant: the result is the gradient of
 // the fp32 network at the given inputs (on variants 6 and 7 too).  No float atomics: two calls give identical bits.
 #include "nn_kernels.h"
+#include "net_layout.h"
 #include <algorithm>
 #include <cmath>
 
@@ -32,7 +33,7 @@ namespace {
 
 typedef float f2 __attribute__((ext_vector_type(2)));
 
-constexpr int VB_E = 256, VB_F = 126, VB_NW = 48, VB_H = 4;
+constexpr int VB_E = 256, VB_F = 126, VB_H = 4;
 constexpr int AB_DQK = 16, AB_DV = 64;                 // per-head q / k and v widths of the attention kernels
 constexpr int AB_TILE = 32;                            // keys (queries) staged per wave and step
 constexpr float AB_SCALE = 0.25f;                      // 1 / sqrt(16)
@@ -749,30 +750,7 @@ void launch_attn_bwd(hipStream_t s, const float* qkv, int64_t ldq, const float* 
 }
 
 // ---- the network -------------------------------------------------------------------------------------------------------------------
-struct VbLin { const float* w; const float* b; };
-struct VbEnc { const float *n1g, *n1b; VbLin qkv, out; const float *n2g, *n2b; VbLin ff1, ff2; };
-struct VbNet { VbLin l1, l2; VbEnc enc[3]; const float *ng, *nb; VbLin fc1, fc2, fc3; };
-
-VbNet vb_read(const float* const* p) {
-    VbNet n;
-    n.l1 = {p[0], p[1]};
-    n.l2 = {p[2], p[3]};
-    for (int e = 0; e < 3; ++e) {
-        const float* const* q = p + 4 + 12 * e;
-        n.enc[e] = {q[0], q[1], {q[2], q[3]}, {q[4], q[5]}, q[6], q[7], {q[8], q[9]}, {q[10], q[11]}};
-    }
-    n.ng = p[40]; n.nb = p[41];
-    n.fc1 = {p[42], p[43]}; n.fc2 = {p[44], p[45]}; n.fc3 = {p[46], p[47]};
-    return n;
-}
-
-inline size_t vb_al(size_t n_floats) { return (n_floats * sizeof(float) + 255) & ~(size_t)255; }
-
-struct VbArena {
-    char* base; size_t off = 0;
-    float* f(size_t n) { float* p = reinterpret_cast<float*>(base + off); off += vb_al(n); return p; }
-};
-
+// (the weight table and the arena of the workspace: net_layout.h)
 // the encoder's interior, rebuilt from its input x: what its backward reads
 struct VbInterior { float *h1, *qkv, *O, *lse, *xm, *h2, *z, *g, *part; };   // part: the attention's split scratch
 constexpr int VB_W3 = 2 * 64 + VB_E;                             // packed q | k | v width
@@ -783,14 +761,14 @@ size_t vb_part_floats(int64_t T) {
 }
 
 // the fp32 GEMMs of the forward (launch_linear routed on one row: never the split-precision kernels)
-void vb_linear(hipStream_t s, const float* X, int64_t ldx, const VbLin& w, const float* R, int64_t ldr, float* Y, int64_t ldy, int64_t T,
+void vb_linear(hipStream_t s, const float* X, int64_t ldx, const LinW& w, const float* R, int64_t ldr, float* Y, int64_t ldy, int64_t T,
                int N, int K, int act) {
     launch_linear(s, X, ldx, w.w, w.b, R, ldr, Y, ldy, T, N, K, act, nullptr, 0, 0, 1);
 }
 
 // x_out = Encoder(x) (x_out NULL: the interior for the backward, LSE included).  The boundary pass (x_out given) needs no LSE: it takes
 // the forward's exact-fp32 MFMA attention (launch_attention, fp32 P V)
-void vb_encoder_fwd(hipStream_t s, const VbEnc& w, const float* x, float* x_out, const VbInterior& I, int64_t B, int N, const int* lens) {
+void vb_encoder_fwd(hipStream_t s, const EncW& w, const float* x, float* x_out, const VbInterior& I, int64_t B, int N, const int* lens) {
     const int64_t T = B * N;
     launch_layernorm(s, x, VB_E, w.n1g, w.n1b, I.h1, VB_E, T, VB_E);
     vb_linear(s, I.h1, VB_E, w.qkv, nullptr, 0, I.qkv, VB_W3, T, VB_W3, VB_E, ACT_NONE);
@@ -803,15 +781,52 @@ void vb_encoder_fwd(hipStream_t s, const VbEnc& w, const float* x, float* x_out,
     if (x_out) vb_linear(s, I.g, 2 * VB_E, w.ff2, I.xm, VB_E, x_out, VB_E, T, VB_E, 2 * VB_E, ACT_NONE);
 }
 
-size_t vb_workspace_bytes(int64_t B, int64_t N) {
+// The workspace of mcr_scone_vis_backward over T = B * N tokens
+struct VbScratch {
+    float* X[VIS_N_ENC + 1];                               // the residual stream at the encoder boundaries
+    float *z1, *g1;                                        // the embedding's pre-activation and its GELU
+    float *hn, *zf1, *c2, *zf2, *gf2;                      // head: final LayerNorm, fc1 pre-activation, [GELU(fc1) | harmonics], fc2 pre-activation, its GELU
+    VbInterior I;                                          // one encoder's interior (the three share it)
+    float *dX, *dH, *dA, *dQKV, *delta;                    // gradients
+    float *part, *wt;                                      // slabs / column partials of the weight gradients; transposed weight (dX products)
+};
+VbScratch carve_vb(Arena& a, int64_t B, int64_t N) {
     const int64_t T = B * N;
-    size_t b = 4 * vb_al(T * VB_E) + 2 * vb_al(T * VB_F);                                         // boundaries, embedding
-    b += vb_al(T * VB_E) + vb_al(T * 192) + vb_al(T * VB_E) + 2 * vb_al(T * 128);               // head
-    b += vb_al(T * VB_E) + vb_al(T * VB_W3) + vb_al(T * VB_E) + vb_al(T * VB_H) + 2 * vb_al(T * VB_E) + 2 * vb_al(T * 2 * VB_E);  // interior
-    b += vb_al(T * VB_E) + vb_al(T * 2 * VB_E) + vb_al(T * VB_E) + vb_al(T * VB_W3) + vb_al(T * VB_H);                          // gradients
-    b += vb_al(vb_part_floats(T)) + vb_al((size_t)2 * VB_E * VB_E) + vb_al(ab_part_floats(B, (int)N, VB_H));
-    return b + 4096;
+    VbScratch w;
+    for (float*& x : w.X) x = a.f(T * VB_E);
+    w.z1 = a.f(T * VB_F); w.g1 = a.f(T * VB_F);
+    w.hn = a.f(T * VB_E); w.zf1 = a.f(T * 192); w.c2 = a.f(T * VB_E); w.zf2 = a.f(T * 128); w.gf2 = a.f(T * 128);
+    VbInterior& I = w.I;
+    I.h1 = a.f(T * VB_E); I.qkv = a.f(T * VB_W3); I.O = a.f(T * VB_E); I.lse = a.f(T * VB_H);
+    I.xm = a.f(T * VB_E); I.h2 = a.f(T * VB_E); I.z = a.f(T * 2 * VB_E); I.g = a.f(T * 2 * VB_E);
+    w.dX = a.f(T * VB_E); w.dH = a.f(T * 2 * VB_E); w.dA = a.f(T * VB_E); w.dQKV = a.f(T * VB_W3); w.delta = a.f(T * VB_H);
+    w.part = a.f(vb_part_floats(T));
+    w.wt = a.f((size_t)2 * VB_E * VB_E);
+    I.part = a.f(ab_part_floats(B, (int)N, VB_H));
+    return w;
 }
+constexpr size_t VB_WS_SLACK = 4096, VB_BLOCK_WS_SLACK = 1024;
+
+// ... and of the three building blocks
+struct AttnBwdScratch { float *O, *lse, *delta, *part; };
+AttnBwdScratch carve_attention_backward(Arena& a, int64_t S, int64_t L, int n_heads, int v_dim) {
+    const int64_t T = S * L;
+    AttnBwdScratch w;
+    w.O = a.f(T * v_dim);
+    w.lse = a.f(T * n_heads);
+    w.delta = a.f(T * n_heads);
+    w.part = a.f(ab_part_floats(S, (int)L, n_heads));
+    return w;
+}
+struct LinBwdScratch { float *dz, *part, *wt; };
+LinBwdScratch carve_linear_backward(Arena& a, int64_t M, int N, int K) {
+    LinBwdScratch w;
+    w.dz = a.f((size_t)M * N);
+    w.part = a.f(vb_gradw_floats(M, N, K));
+    w.wt = a.f((size_t)N * K);
+    return w;
+}
+float* carve_layernorm_backward(Arena& a, int64_t M, int E) { return a.f(vb_ln_part_floats(M, E)); }
 
 }  // namespace
 }  // namespace mcr
@@ -822,8 +837,7 @@ extern "C" {
 
 // ---- building blocks ---------------------------------------------------------------------------------------------------------------
 size_t mcr_attention_backward_workspace_bytes(int64_t S, int64_t L, int n_heads, int v_dim) {
-    const int64_t T = S * L;
-    return vb_al(T * v_dim) + 2 * vb_al(T * n_heads) + vb_al(ab_part_floats(S, (int)L, n_heads)) + 1024;
+    return measure(carve_attention_backward, S, L, n_heads, v_dim) + VB_BLOCK_WS_SLACK;
 }
 
 int mcr_attention_backward(const float* qkv, int64_t ldq, const float* d_out, int64_t ld_dout, float* d_qkv, int64_t ld_dqkv, int64_t S,
@@ -841,20 +855,17 @@ int mcr_attention_backward(const float* qkv, int64_t ldq, const float* d_out, in
     MCR_REQUIRE(workspace && workspace_bytes >= mcr_attention_backward_workspace_bytes(S, L, n_heads, v_dim), "%s: workspace too small", who);
     MCR_REQUIRE((uintptr_t)workspace % 16 == 0, "%s: workspace must be 16-byte aligned", who);
     hipStream_t s = (hipStream_t)stream;
-    VbArena a{(char*)workspace};
-    const int64_t T = S * L;
-    float* O = a.f(T * v_dim);
-    float* lse = a.f(T * n_heads);
-    float* delta = a.f(T * n_heads);
-    float* part = a.f(ab_part_floats(S, (int)L, n_heads));
-    launch_attn_fwd(s, qkv, ldq, O, v_dim, lse, S, (int)L, n_heads, lens, part);
-    launch_attn_bwd(s, qkv, ldq, O, v_dim, lse, d_out, ld_dout, delta, d_qkv, ld_dqkv, S, (int)L, n_heads, lens, part);
+    Arena a{(char*)workspace, workspace_bytes};
+    const AttnBwdScratch ws = carve_attention_backward(a, S, L, n_heads, v_dim);
+    MCR_REQUIRE(a.ok(), "%s: workspace overflow", who);
+    launch_attn_fwd(s, qkv, ldq, ws.O, v_dim, ws.lse, S, (int)L, n_heads, lens, ws.part);
+    launch_attn_bwd(s, qkv, ldq, ws.O, v_dim, ws.lse, d_out, ld_dout, ws.delta, d_qkv, ld_dqkv, S, (int)L, n_heads, lens, ws.part);
     MCR_LAUNCH_CHECK(who);
     return 0;
 }
 
 size_t mcr_linear_backward_workspace_bytes(int64_t M, int N, int K) {
-    return vb_al((size_t)M * N) + vb_al(vb_gradw_floats(M, N, K)) + vb_al((size_t)N * K) + 1024;
+    return measure(carve_linear_backward, M, N, K) + VB_BLOCK_WS_SLACK;
 }
 
 int mcr_linear_backward(const float* X, int64_t ldx, const float* W, const float* Z, int64_t ldz, const float* dY, int64_t ldy, int64_t M, int N,
@@ -866,10 +877,10 @@ int mcr_linear_backward(const float* X, int64_t ldx, const float* W, const float
     MCR_REQUIRE(ldy >= N && (!gelu || ldz >= N) && (!dX || ld_dx >= K) && ((!dW && !db) || ldx >= K), "%s: leading dimension too small", who);
     MCR_REQUIRE(workspace && workspace_bytes >= mcr_linear_backward_workspace_bytes(M, N, K), "%s: workspace too small", who);
     hipStream_t s = (hipStream_t)stream;
-    VbArena a{(char*)workspace};
-    float* dz = a.f((size_t)M * N);
-    float* part = a.f(vb_gradw_floats(M, N, K));
-    float* wt = a.f((size_t)N * K);
+    Arena a{(char*)workspace, workspace_bytes};
+    const LinBwdScratch ws = carve_linear_backward(a, M, N, K);
+    MCR_REQUIRE(a.ok(), "%s: workspace overflow", who);
+    float* dz = ws.dz;
     const float* g = dY;
     int64_t ldg = ldy;
     if (gelu) {
@@ -878,13 +889,13 @@ int mcr_linear_backward(const float* X, int64_t ldx, const float* W, const float
         g = dz;
         ldg = N;
     }
-    if (dX) gemm_dx(s, g, ldg, W, K, dX, ld_dx, M, N, K, accumulate_dx != 0, wt);
-    gemm_dw(s, g, ldg, X, ldx, M, N, K, dW, db, part);
+    if (dX) gemm_dx(s, g, ldg, W, K, dX, ld_dx, M, N, K, accumulate_dx != 0, ws.wt);
+    gemm_dw(s, g, ldg, X, ldx, M, N, K, dW, db, ws.part);
     MCR_LAUNCH_CHECK(who);
     return 0;
 }
 
-size_t mcr_layernorm_backward_workspace_bytes(int64_t M, int E) { return vb_al(vb_ln_part_floats(M, E)) + 1024; }
+size_t mcr_layernorm_backward_workspace_bytes(int64_t M, int E) { return measure(carve_layernorm_backward, M, E) + VB_BLOCK_WS_SLACK; }
 
 int mcr_layernorm_backward(const float* X, int64_t ldx, const float* gamma, const float* dY, int64_t ldy, int64_t M, int E, float* dX, int64_t ld_dx,
                            int accumulate_dx, float* d_gamma, float* d_beta, void* workspace, size_t workspace_bytes, void* stream) {
@@ -894,7 +905,10 @@ int mcr_layernorm_backward(const float* X, int64_t ldx, const float* gamma, cons
     MCR_REQUIRE(M > 0, "%s: empty problem", who);
     MCR_REQUIRE(ldx >= E && ldy >= E && ld_dx >= E, "%s: leading dimension too small", who);
     MCR_REQUIRE(workspace && workspace_bytes >= mcr_layernorm_backward_workspace_bytes(M, E), "%s: workspace too small", who);
-    launch_ln_bwd((hipStream_t)stream, X, ldx, gamma, dY, ldy, dX, ld_dx, accumulate_dx != 0, d_gamma, d_beta, (float*)workspace, M, E);
+    Arena a{(char*)workspace, workspace_bytes};
+    float* part = carve_layernorm_backward(a, M, E);
+    MCR_REQUIRE(a.ok(), "%s: workspace overflow", who);
+    launch_ln_bwd((hipStream_t)stream, X, ldx, gamma, dY, ldy, dX, ld_dx, accumulate_dx != 0, d_gamma, d_beta, part, M, E);
     MCR_LAUNCH_CHECK(who);
     return 0;
 }
@@ -911,49 +925,33 @@ int mcr_colmax_backward(const float* X, int64_t ldx, const float* d_bcast, int64
 }
 
 // ---- SconeVis ------------------------------------------------------------------------------------------------------------------------
-size_t mcr_scone_vis_backward_workspace_bytes(int64_t B, int64_t N) { return (B > 0 && N > 0) ? vb_workspace_bytes(B, N) : 0; }
+size_t mcr_scone_vis_backward_workspace_bytes(int64_t B, int64_t N) { return (B > 0 && N > 0) ? measure(carve_vb, B, N) + VB_WS_SLACK : 0; }
 
 int mcr_scone_vis_backward(const float* pts, const float* view_harmonics, const float* d_out, int64_t B, int64_t N, const float* const* weights,
                            int n_weights, const int* lengths, float* const* d_weights, float* d_pts, float* d_view_harmonics, void* workspace,
                            size_t workspace_bytes, void* stream) {
     const char* who = "mcr_scone_vis_backward";
     MCR_REQUIRE(pts && view_harmonics && d_out && weights, "%s: null pointer", who);
-    MCR_REQUIRE(n_weights == VB_NW || n_weights == VB_NW + 12 || n_weights == VB_NW + 17,
-                "%s: expected %d weight pointers (+ 12 or 17 plane pointers), got %d", who, VB_NW, n_weights);
+    if (check_table(who, VIS_TABLE, weights, n_weights, VIS_NW)) return 1;                  // (a planes tail is accepted and ignored)
     MCR_REQUIRE(B > 0 && N > 0 && B <= 65535 && N <= (1 << 24), "%s: bad problem size B=%ld N=%ld", who, (long)B, (long)N);
-    MCR_REQUIRE(workspace && workspace_bytes >= vb_workspace_bytes(B, N), "%s: workspace too small", who);
-    for (int i = 0; i < VB_NW; ++i) MCR_REQUIRE(weights[i], "%s: weight %d is null", who, i);
+    MCR_REQUIRE(workspace && workspace_bytes >= mcr_scone_vis_backward_workspace_bytes(B, N), "%s: workspace too small", who);
     if (d_weights)
-        for (int i = 0; i < VB_NW; ++i) MCR_REQUIRE(d_weights[i], "%s: d_weights[%d] is null", who, i);
+        for (int i = 0; i < VIS_NW; ++i) MCR_REQUIRE(d_weights[i], "%s: d_weights[%d] is null", who, i);
     MCR_REQUIRE(((uintptr_t)pts | (uintptr_t)view_harmonics | (uintptr_t)d_out) % 16 == 0, "%s: operands must be 16-byte aligned", who);
     if (!d_weights && !d_pts && !d_view_harmonics) return 0;
     hipStream_t s = (hipStream_t)stream;
-    const VbNet w = vb_read(weights);
-    float* const* dw = d_weights;
+    const VisW w = read_vis_table(weights, VIS_NW);
     const int iN = (int)N;
     const int64_t T = B * N;
-    VbArena a{(char*)workspace};
-    float* X[4];
-    for (int e = 0; e < 4; ++e) X[e] = a.f(T * VB_E);
-    float* z1 = a.f(T * VB_F);
-    float* g1 = a.f(T * VB_F);
-    float* hn = a.f(T * VB_E);
-    float* zf1 = a.f(T * 192);
-    float* c2 = a.f(T * VB_E);
-    float* zf2 = a.f(T * 128);
-    float* gf2 = a.f(T * 128);
-    VbInterior I;
-    I.h1 = a.f(T * VB_E); I.qkv = a.f(T * VB_W3); I.O = a.f(T * VB_E); I.lse = a.f(T * VB_H);
-    I.xm = a.f(T * VB_E); I.h2 = a.f(T * VB_E); I.z = a.f(T * 2 * VB_E); I.g = a.f(T * 2 * VB_E);
-    float* dX = a.f(T * VB_E);
-    float* dH = a.f(T * 2 * VB_E);
-    float* dA = a.f(T * VB_E);
-    float* dQKV = a.f(T * VB_W3);
-    float* delta = a.f(T * VB_H);
-    float* part = a.f(vb_part_floats(T));
-    float* wt = a.f((size_t)2 * VB_E * VB_E);                                              // transposed weight (dX products)
-    I.part = a.f(ab_part_floats(B, iN, VB_H));
-    auto DW = [&](int i) { return dw ? dw[i] : nullptr; };
+    Arena a{(char*)workspace, workspace_bytes};
+    const VbScratch ws = carve_vb(a, B, N);
+    MCR_REQUIRE(a.ok(), "%s: workspace overflow", who);
+    float* const* X = ws.X;
+    float *z1 = ws.z1, *g1 = ws.g1, *hn = ws.hn, *zf1 = ws.zf1, *c2 = ws.c2, *zf2 = ws.zf2, *gf2 = ws.gf2;
+    const VbInterior& I = ws.I;
+    float *dX = ws.dX, *dH = ws.dH, *dA = ws.dA, *dQKV = ws.dQKV, *delta = ws.delta, *part = ws.part, *wt = ws.wt;
+    // where the gradient of the table's entry `slot` goes (d_weights has the table's order and slot names: net_layout.h)
+    auto DW = [&](int slot) { return d_weights ? d_weights[slot] : nullptr; };
 
     // ---- forward of the fp32 network: boundaries X0..X3, the embedding's and the head's pre-activations
     vb_linear(s, pts, 4, w.l1, nullptr, 0, z1, VB_F, T, VB_F, 4, ACT_NONE);
@@ -969,43 +967,43 @@ int mcr_scone_vis_backward(const float* pts, const float* view_harmonics, const 
     launch_gelu(s, zf2, 128, gf2, 128, T, 128, 0);
 
     // ---- head (SconeVis.py:143-152), backwards
-    gemm_dw(s, d_out, 64, gf2, 128, T, 64, 128, DW(46), DW(47), part);                 // fc3
+    gemm_dw(s, d_out, 64, gf2, 128, T, 64, 128, DW(VIS_FC3 + LIN_W), DW(VIS_FC3 + LIN_B), part);                 // fc3
     gemm_dx(s, d_out, 64, w.fc3.w, 128, dH, 128, T, 64, 128, false, wt);
     launch_gelu(s, zf2, 128, dH, 128, T, 128, 1);                                          // fc2
-    gemm_dw(s, dH, 128, c2, VB_E, T, 128, VB_E, DW(44), DW(45), part);
+    gemm_dw(s, dH, 128, c2, VB_E, T, 128, VB_E, DW(VIS_FC2 + LIN_W), DW(VIS_FC2 + LIN_B), part);
     gemm_dx(s, dH, 128, w.fc2.w, VB_E, dA, VB_E, T, 128, VB_E, false, wt);
     if (d_view_harmonics) launch_copy2d(s, dA + 192, VB_E, d_view_harmonics, 64, T, 64);
     if (!d_weights && !d_pts) { MCR_LAUNCH_CHECK(who); return 0; }
     launch_gelu(s, zf1, 192, dA, VB_E, T, 192, 1);                                         // fc1
-    gemm_dw(s, dA, VB_E, hn, VB_E, T, 192, VB_E, DW(42), DW(43), part);
+    gemm_dw(s, dA, VB_E, hn, VB_E, T, 192, VB_E, DW(VIS_FC1 + LIN_W), DW(VIS_FC1 + LIN_B), part);
     gemm_dx(s, dA, VB_E, w.fc1.w, VB_E, dH, VB_E, T, 192, VB_E, false, wt);
-    launch_ln_bwd(s, X[3], VB_E, w.ng, dH, VB_E, dX, VB_E, false, DW(40), DW(41), part, T, VB_E);   // norm
+    launch_ln_bwd(s, X[3], VB_E, w.ng, dH, VB_E, dX, VB_E, false, DW(VIS_NG), DW(VIS_NB), part, T, VB_E);   // norm
 
     // ---- encoders (Attention.py:278-300), last to first; dX holds the gradient of the encoder's output
     for (int e = 2; e >= 0; --e) {
-        const VbEnc& we = w.enc[e];
-        const int o = 4 + 12 * e;
+        const EncW& we = w.enc[e];
+        const int o = VIS_ENC + ENC_NW * e;                               // the encoder's block of the table
         vb_encoder_fwd(s, we, X[e], nullptr, I, B, iN, lengths);                          // the interior, from the boundary
-        gemm_dw(s, dX, VB_E, I.g, 2 * VB_E, T, VB_E, 2 * VB_E, DW(o + 10), DW(o + 11), part);          // ff2
+        gemm_dw(s, dX, VB_E, I.g, 2 * VB_E, T, VB_E, 2 * VB_E, DW(o + ENC_FF2 + LIN_W), DW(o + ENC_FF2 + LIN_B), part);          // ff2
         gemm_dx(s, dX, VB_E, we.ff2.w, 2 * VB_E, dH, 2 * VB_E, T, VB_E, 2 * VB_E, false, wt);
         launch_gelu(s, I.z, 2 * VB_E, dH, 2 * VB_E, T, 2 * VB_E, 1);                      // ff1
-        gemm_dw(s, dH, 2 * VB_E, I.h2, VB_E, T, 2 * VB_E, VB_E, DW(o + 8), DW(o + 9), part);
+        gemm_dw(s, dH, 2 * VB_E, I.h2, VB_E, T, 2 * VB_E, VB_E, DW(o + ENC_FF1 + LIN_W), DW(o + ENC_FF1 + LIN_B), part);
         gemm_dx(s, dH, 2 * VB_E, we.ff1.w, VB_E, dA, VB_E, T, 2 * VB_E, VB_E, false, wt);
-        launch_ln_bwd(s, I.xm, VB_E, we.n2g, dA, VB_E, dX, VB_E, true, DW(o + 6), DW(o + 7), part, T, VB_E);   // norm2 (+ residual)
-        gemm_dw(s, dX, VB_E, I.O, VB_E, T, VB_E, VB_E, DW(o + 4), DW(o + 5), part);        // out
+        launch_ln_bwd(s, I.xm, VB_E, we.n2g, dA, VB_E, dX, VB_E, true, DW(o + ENC_N2G), DW(o + ENC_N2B), part, T, VB_E);   // norm2 (+ residual)
+        gemm_dw(s, dX, VB_E, I.O, VB_E, T, VB_E, VB_E, DW(o + ENC_OUT + LIN_W), DW(o + ENC_OUT + LIN_B), part);        // out
         gemm_dx(s, dX, VB_E, we.out.w, VB_E, dA, VB_E, T, VB_E, VB_E, false, wt);
         launch_attn_bwd(s, I.qkv, VB_W3, I.O, VB_E, I.lse, dA, VB_E, delta, dQKV, VB_W3, B, iN, VB_H, lengths, I.part);
-        gemm_dw(s, dQKV, VB_W3, I.h1, VB_E, T, VB_W3, VB_E, DW(o + 2), DW(o + 3), part);   // qkv
+        gemm_dw(s, dQKV, VB_W3, I.h1, VB_E, T, VB_W3, VB_E, DW(o + ENC_QKV + LIN_W), DW(o + ENC_QKV + LIN_B), part);   // qkv
         gemm_dx(s, dQKV, VB_W3, we.qkv.w, VB_E, dA, VB_E, T, VB_W3, VB_E, false, wt);
-        launch_ln_bwd(s, X[e], VB_E, we.n1g, dA, VB_E, dX, VB_E, true, DW(o + 0), DW(o + 1), part, T, VB_E);   // norm1 (+ residual)
+        launch_ln_bwd(s, X[e], VB_E, we.n1g, dA, VB_E, dX, VB_E, true, DW(o + ENC_N1G), DW(o + ENC_N1B), part, T, VB_E);   // norm1 (+ residual)
     }
 
     // ---- embedding (Attention.py:98-128): [res | cloud max of res | pts]
     launch_colmax_bwd(s, X[0], VB_E, dX + VB_F, VB_E, dX, VB_E, B, iN, VB_F, lengths);
-    gemm_dw(s, dX, VB_E, g1, VB_F, T, VB_F, VB_F, DW(2), DW(3), part);                     // linear2
+    gemm_dw(s, dX, VB_E, g1, VB_F, T, VB_F, VB_F, DW(VIS_L2 + LIN_W), DW(VIS_L2 + LIN_B), part);                     // linear2
     gemm_dx(s, dX, VB_E, w.l2.w, VB_F, dH, VB_F, T, VB_F, VB_F, false, wt);
     launch_gelu(s, z1, VB_F, dH, VB_F, T, VB_F, 1);                                        // linear1
-    gemm_dw(s, dH, VB_F, pts, 4, T, VB_F, 4, DW(0), DW(1), part);
+    gemm_dw(s, dH, VB_F, pts, 4, T, VB_F, 4, DW(VIS_L1 + LIN_W), DW(VIS_L1 + LIN_B), part);
     if (d_pts) {
         launch_copy2d(s, dX + 2 * VB_F, VB_E, d_pts, 4, T, 4);
         gemm_dx(s, dH, VB_F, w.l1.w, 4, d_pts, 4, T, VB_F, 4, true, wt);

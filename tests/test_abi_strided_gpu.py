@@ -10,6 +10,10 @@ call's bit for bit.  Operands the header calls unsupported must be REFUSED: non-
 Tolerances are the project's: forward blocks |y - ref|.max() < 2e-5 * max(1, |ref|.max()) (test_linear_vs_numpy), backward blocks
 BLOCK_TOL = 2e-5 on max|got - ref| / max|ref| per tensor (test_scone_vis_backward_gpu.py), column max bit-exact, mean 1e-6.
 Every measured error is printed with the ERR prefix.
+
+Last section: the five NETWORK entry points (PCTransformer, SconeVis forward and backward, SconeOcc dense and ragged, single call and
+two phases) in a workspace of EXACTLY the bytes their size functions return, guarded on both sides, bit-equal to the call through
+ops.* (which allocates 10 % more), and refused when the workspace is 4 bytes shorter.
 """
 import ctypes
 import itertools
@@ -723,3 +727,239 @@ def test_colmax_backward(dev, L, E):
         for ldx, ldg, ldd in ((E - 1, E, E), (E, E - 1, E), (E, E, E - 1)):
             rc = L_().mcr_colmax_backward(P(X), I64(ldx), P(X), I64(ldg), P(DX), I64(ldd), I64(S), I64(L), CI(E), VP(None), stream())
             refused(rc, f"mcr_colmax_backward ld {ldx, ldg, ldd}", "leading dimension too small", [DX])
+
+
+# =====================================================================================================================================
+# The network entry points in a workspace of exactly the size they ask for
+# =====================================================================================================================================
+# entry -> (its size function, the positions of that function's arguments among the entry's, the position of `workspace` (the byte
+# count follows it), the position of `phase` or None, outputs: position -> (rows, cols) from the arguments)
+def _vis_rows(a):
+    return a[3].value * a[4].value
+
+
+NET_ENTRIES = {
+    "mcr_pc_transformer_forward": ("mcr_pc_transformer_workspace_bytes", (2, 3), 7, None, lambda a: {1: (a[2].value, a[4].value)}),
+    "mcr_scone_vis_forward": ("mcr_scone_vis_workspace_bytes", (3, 4), 8, None, lambda a: {2: (_vis_rows(a), 64)}),
+    "mcr_scone_vis_backward": ("mcr_scone_vis_backward_workspace_bytes", (3, 4), 11, None, lambda a: {9: (_vis_rows(a), 4), 10: (_vis_rows(a), 64)}),
+    "mcr_scone_occ_forward_phase": ("mcr_scone_occ_workspace_bytes", (7, 8, 1), 15, 17, lambda a: {6: (a[7].value * a[8].value, 1)}),
+    "mcr_scone_occ_forward_ragged_phase": ("mcr_scone_occ_ragged_workspace_bytes", (11, 12, 2), 19, 21, lambda a: {10: (a[12].value, 1)}),
+}
+VIS_D_WEIGHTS = 8                                      # mcr_scone_vis_backward: the table of 48 gradient pointers
+_ENC_SHAPES = [(1, 256), (1, 256), (384, 256), (1, 384), (256, 256), (1, 256), (1, 256), (1, 256), (512, 256), (1, 512), (256, 512), (1, 256)]
+VIS_TABLE_SHAPES = [(126, 4), (1, 126), (126, 126), (1, 126)] + 3 * _ENC_SHAPES + \
+                   [(1, 256), (1, 256), (192, 256), (1, 192), (128, 256), (1, 128), (64, 128), (1, 64)]       # include/macarons_hip.h: SCONE_VIS (48)
+
+
+def _is_null(p):
+    return p is None or getattr(p, "value", 1) in (None, 0)
+
+
+class ExactWorkspaces:
+    """Stands in front of the network entry points of the loaded library.  Every call that reaches one of them (through ops.*, with the
+    operands ops.* made) goes through unchanged and is then REPEATED through ctypes, same operands, same variant, with
+      - a workspace of exactly the bytes the entry's size function returns, inside a guarded, NaN-filled arena, and outputs in
+        guarded arenas of their own: return code 0, guards intact; the outputs are kept (`calls`) for the bit comparison with
+        what ops.* returned;
+      - a workspace 4 bytes shorter: the entry must refuse (code 1, "workspace too small", outputs untouched).
+    The two calls of a two-phase forward share one exact workspace, as the header asks."""
+
+    def __init__(self, monkeypatch, dev):
+        from macarons_amd import ops
+        self.ops, self.dev, self.lib = ops, dev, L_()
+        self.real = {name: getattr(self.lib, name) for name in NET_ENTRIES}
+        self.kept = {}                                 # entry -> the exact workspace of its current forward
+        self.calls = []                                # (entry, phase, {position: packed output})
+        for name in NET_ENTRIES:
+            monkeypatch.setattr(self.lib, name, lambda *a, _n=name: self._call(_n, a), raising=False)
+
+    def _repeat(self, name, args, ws, outs):
+        a = list(args)
+        wpos = NET_ENTRIES[name][2]
+        a[wpos], a[wpos + 1] = P(ws), SZ(ws.n_bytes)
+        for pos, arena in outs.items():
+            a[pos] = (VP * len(arena))(*[x.ptr for x in arena]) if isinstance(arena, list) else P(arena)
+        self.lib.mcr_call_variant(CI(getattr(self.ops._tls, "variant", 0)))
+        rc = self.real[name](*a)
+        torch.cuda.synchronize()
+        return rc
+
+    def _outs(self, name, args):
+        outs = {pos: Arena(r, c, device=self.dev) for pos, (r, c) in NET_ENTRIES[name][4](args).items() if not _is_null(args[pos])}
+        if name == "mcr_scone_vis_backward" and not _is_null(args[VIS_D_WEIGHTS]):
+            outs[VIS_D_WEIGHTS] = [Arena(r, c, device=self.dev) for r, c in VIS_TABLE_SHAPES]
+        return outs
+
+    def _call(self, name, args):
+        rc = self.real[name](*args)
+        if rc != 0:
+            return rc
+        size_fn, size_pos, wpos, ppos, _ = NET_ENTRIES[name]
+        phase = args[ppos].value if ppos is not None else 0
+        tag = f"{name} phase {phase} variant {self.ops.current_variant()} sizes {[args[i].value for i in size_pos]}"
+        n = int(getattr(self.lib, size_fn)(*[args[i] for i in size_pos]))
+        if phase != 2:
+            self.kept[name] = Workspace(n, self.dev)
+        ws = self.kept[name]
+        assert ws.n_bytes == n, f"{tag}: phase 2 asks for {n} bytes, phase 1 asked for {ws.n_bytes}"
+        outs = self._outs(name, args)
+        rc2 = self._repeat(name, args, ws, outs)
+        assert rc2 == 0, f"{tag}: rc {rc2} in a workspace of exactly {n} bytes: {last_error()}"
+        ws.check_guard(tag + " workspace")
+        flat = [x for v in outs.values() for x in (v if isinstance(v, list) else [v])]
+        for x in flat:
+            x.check_guard(tag + " output")
+        self.calls.append((name, phase, {pos: ([x.packed() for x in v] if isinstance(v, list) else v.packed()) for pos, v in outs.items()}))
+        short, outs = Workspace(n - 4, self.dev), self._outs(name, args)
+        rc3 = self._repeat(name, args, short, outs)
+        refused(rc3, tag + f" in {n - 4} bytes", "workspace too small", [short] + [x for v in outs.values() for x in (v if isinstance(v, list) else [v])])
+        assert rc3 == 1, f"{tag}: a short workspace returned {rc3}"
+        print(f"EXACT {tag}: {n} bytes")
+        return rc
+
+    def take(self, name, phase=None):
+        """The kept outputs of the calls of `name` since the last take (those of `phase` only, if given)."""
+        got = [o for (n_, ph, o) in self.calls if n_ == name and (phase is None or ph == phase)]
+        self.calls = []
+        return got
+
+
+def same_bits(a, b):
+    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
+    return a.size == b.size and np.array_equal(a.reshape(-1).view(np.int32), b.reshape(-1).view(np.int32))
+
+
+def _golden_module(cls, seed, dev):
+    import os
+    import sys
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden"))
+    import weights
+    m = cls()
+    sd = weights.make_state_dict(weights.shapes_of(m), seed)
+    m.load_state_dict({k: torch.from_numpy(v) for k, v in sd.items()}, strict=True)
+    return m.to(dev).eval()
+
+
+def _to(x, dev):
+    return torch.from_numpy(np.ascontiguousarray(x)).to(dev)
+
+
+NET_VARIANTS = [1, 5, 6, 7]
+
+
+@pytest.mark.parametrize("variant", NET_VARIANTS)
+def test_exact_workspace_pc_transformer_and_scone_occ(dev, monkeypatch, variant):
+    """mcr_pc_transformer_forward, mcr_scone_occ_forward (single call; phases 1 + 2; a batch of clouds; the layer-by-layer path) on the
+    golden weights and sizes, each in a workspace of exactly its stated size (ExactWorkspaces)."""
+    from conftest import golden
+    from macarons_amd import ops
+    from macarons_amd.networks import SconeOcc
+    m = _golden_module(SconeOcc, 2, dev)
+    g = golden("scone_occ")
+    spy = ExactWorkspaces(monkeypatch, dev)
+    with torch.no_grad(), ops.variant(variant):
+        for tag in ("m100_q17", "m1024_q300", "m4096_q512"):
+            perms = [torch.from_numpy(g[f"{tag}_perm{i}"].astype(np.int64)) for i in range(3)]
+            pc, x, vh = _to(g[f"{tag}_pc"], dev), _to(g[f"{tag}_x"], dev), _to(g[f"{tag}_vh"], dev)
+            gf = m.global_transformer(pc[:, perms[0].to(dev)].contiguous()).cpu().numpy()
+            (o,) = spy.take("mcr_pc_transformer_forward")
+            assert same_bits(o[1], gf), f"{tag}: mcr_pc_transformer_forward in an exact workspace differs from ops.pc_transformer_forward"
+            y = m(pc, x, vh, perms=perms).cpu().numpy()
+            (o,) = spy.take("mcr_scone_occ_forward_phase", 0)
+            assert same_bits(o[6], y), f"{tag}: single call"
+            if min(m.scale_sizes(pc.shape[1])) < m.k_for_knn:        # (m100: its coarsest cloud is below k, forward_begin does not apply)
+                continue
+            h = m.forward_begin(pc, x)
+            assert h is not None
+            y2 = m(pc, x, vh, perms=perms, begun=h).cpu().numpy()
+            got = spy.take("mcr_scone_occ_forward_phase")
+            assert len(got) == 2 and not got[0] and same_bits(got[1][6], y2) and same_bits(y2, y), f"{tag}: phases 1 + 2"
+        # a batch of clouds (one search and one transformer launch per scale over all rows), Q beyond one chunk of the layer-by-layer path
+        rng = np.random.default_rng(5)
+        pc = _to(rng.uniform(-.4, .4, (2, 1500, 3)).astype(np.float32), dev)
+        x = _to(rng.uniform(-.5, .5, (2, 16385, 3)).astype(np.float32), dev)
+        vh = _to((rng.standard_normal((2, 16385, 64)) * .3).astype(np.float32), dev)
+        torch.manual_seed(5)
+        perms = m.draw_perms(1500)
+        y = m(pc, x, vh, perms=perms).cpu().numpy()
+        (o,) = spy.take("mcr_scone_occ_forward_phase", 0)
+        assert same_bits(o[6], y), "batch of two clouds"
+        m.fused_local = False
+        y = m(pc, x, vh, perms=perms).cpu().numpy()
+        (o,) = spy.take("mcr_scone_occ_forward_phase", 0)
+        assert same_bits(o[6], y), "layer-by-layer path"
+
+
+@pytest.mark.parametrize("variant", NET_VARIANTS)
+def test_exact_workspace_scone_occ_ragged(dev, monkeypatch, variant):
+    """mcr_scone_occ_forward_ragged: phases 1 + 2 (SconeOcc.forward_ragged), then the single call on the operands of that phase 2."""
+    from macarons_amd import ops
+    from macarons_amd.networks import SconeOcc
+    m = _golden_module(SconeOcc, 2, dev)
+    rng = np.random.default_rng(12)
+    sizes_m, sizes_q = [100, 3000, 65, 2048, 900], [17, 300, 1, 129, 4097]
+    pc = _to(np.concatenate([rng.uniform(-.4, .4, (n, 3)).astype(np.float32) for n in sizes_m]), dev)
+    x = _to(np.concatenate([rng.uniform(-.5, .5, (q, 3)).astype(np.float32) for q in sizes_q]), dev)
+    vh = _to(np.concatenate([(rng.standard_normal((q, 64)) * .3).astype(np.float32) for q in sizes_q]), dev)
+    torch.manual_seed(21)
+    perms = [m.draw_perms(n) for n in sizes_m]
+    spy = ExactWorkspaces(monkeypatch, dev)
+    real, last = ops.scone_occ_forward_ragged, {}
+
+    def keep(*a, **k):                                  # the operands the module made for its last call (they stay alive here)
+        last["a"], last["k"] = a, k
+        return real(*a, **k)
+    monkeypatch.setattr(ops, "scone_occ_forward_ragged", keep)
+    with torch.no_grad(), ops.variant(variant):
+        y = m.forward_ragged(pc, sizes_m, x, vh, sizes_q, perms=perms).cpu().numpy()
+        got = spy.take("mcr_scone_occ_forward_ragged_phase")
+        assert [len(o) for o in got] == [0, 1] and same_bits(got[1][10], y), "phases 1 + 2"
+        assert last["k"]["phase"] == 2
+        y0 = real(*last["a"], **{**last["k"], "phase": 0, "out": None}).cpu().numpy()
+        (o,) = spy.take("mcr_scone_occ_forward_ragged_phase", 0)
+        assert same_bits(o[10], y0) and same_bits(y0, y), "single call"
+
+
+@pytest.mark.parametrize("variant", NET_VARIANTS)
+def test_exact_workspace_scone_vis_forward(dev, monkeypatch, variant):
+    from conftest import golden
+    from macarons_amd import ops
+    from macarons_amd.networks import SconeVis
+    m = _golden_module(SconeVis, 1, dev)
+    g = golden("scone_vis")
+    spy = ExactWorkspaces(monkeypatch, dev)
+    with torch.no_grad(), ops.variant(variant):
+        for key in ("16", "333", "2048", "b3"):
+            y = m(_to(g[f"pts_{key}"], dev), view_harmonics=_to(g[f"vh_{key}"], dev)).cpu().numpy()
+            (o,) = spy.take("mcr_scone_vis_forward")
+            assert same_bits(o[2], y), key
+        lengths = torch.tensor([700, 2048, 1], dtype=torch.int32, device=dev)
+        pts, vh = _to(np.tile(g["pts_2048"], (3, 1, 1)), dev), _to(np.tile(g["vh_2048"], (3, 1, 1)), dev)
+        y = m(pts, view_harmonics=vh, lengths=lengths).cpu().numpy()
+        (o,) = spy.take("mcr_scone_vis_forward")
+        assert same_bits(o[2], y), "padded batch with lengths"
+
+
+@pytest.mark.parametrize("B,N,with_lengths", [(1, 333, False), (1, 2048, False), (3, 700, True)])
+def test_exact_workspace_scone_vis_backward(dev, monkeypatch, B, N, with_lengths):
+    """mcr_scone_vis_backward takes no variant (the fp32 network's gradient on every one): all three gradients, then each alone."""
+    from macarons_amd import ops
+    from macarons_amd.networks import SconeVis
+    m = _golden_module(SconeVis, 1, dev)
+    rng = np.random.default_rng(B * N)
+    pts = _to(rng.uniform(-.5, .5, (B, N, 4)).astype(np.float32), dev)
+    vh = _to((rng.standard_normal((B, N, 64)) * .3).astype(np.float32), dev)
+    d_out = _to(rng.standard_normal((B, N, 64)).astype(np.float32), dev)
+    lengths = torch.tensor([N, N // 2, 1][:B], dtype=torch.int32, device=dev) if with_lengths else None
+    spy = ExactWorkspaces(monkeypatch, dev)
+    for need in ((True, True, True), (True, False, False), (False, True, False), (False, False, True)):
+        d_w, d_pts, d_vh = ops.scone_vis_backward(pts, vh, d_out, m.weight_table(), lengths, need=need)
+        (o,) = spy.take("mcr_scone_vis_backward")
+        assert set(o) == {p for p, asked in zip((VIS_D_WEIGHTS, 9, 10), need) if asked}, need
+        if need[0]:
+            for i, (got, ref) in enumerate(zip(o[VIS_D_WEIGHTS], d_w)):
+                assert same_bits(got, ref.cpu().numpy()), f"need {need}: d_weights[{i}]"
+        if need[1]:
+            assert same_bits(o[9], d_pts.cpu().numpy()), f"need {need}: d_pts"
+        if need[2]:
+            assert same_bits(o[10], d_vh.cpu().numpy()), f"need {need}: d_view_harmonics"
