@@ -4,13 +4,9 @@
 // pytorch3d knn_gather, which materialises the dense [B,Q,M] distance matrix: 4 GB at Q=100k, M=10k) and the
 // offset step of macarons/networks/SconeOcc.py:297-298 (neighbours minus the query).
 //
-// One lane owns one query and keeps its k best (d2, index) pairs sorted in VGPRs; surface points stream
-// through LDS in tiles (one broadcast ds_read_b128 per candidate per wave).  A workgroup = 2 query tiles of 64 x 2
-// waves per tile; the two waves of a tile each scan every other candidate (Q/64 waves alone cannot fill 1024 SIMDs)
-// and their sorted lists are merged through LDS at the end.  A 4-way split was measured first: every extra split
-// re-pays the ~16 ln(M/16) list insertions per lane, and its 6252 waves at 3 blocks/CU needed 2.03 rounds of the chip
-// = 3; this shape needs 40 KB of LDS (4 blocks/CU) and 782 blocks = 0.76 rounds at Q = 100k with 35 % fewer
-// instructions.  Candidates are taken 4 at a time (independent distance computations, one branch per batch).  Convention (shared with
+// Every kernel here keeps a query's k best (d2, index) pairs sorted in VGPRs while the surface points stream through LDS in tiles;
+// the distances that FILTER are evaluated on the matrix pipe (K1-mfma below), the ones that are kept are recomputed exactly.
+// A workgroup serves 128 queries, 32 per wave.  Convention (shared with
 // oracle/knn.py, see there why the reference's own tie order is unspecified):
 //   d2 = (dx*dx + dy*dy) + dz*dz in fp32 with every product and sum rounded (no FMA contraction),
 //   ascending by (d2, index): ties go to the lower index;  dists = sqrt(d2), correctly rounded.
@@ -22,11 +18,7 @@
 namespace mcr {
 
 constexpr int KNN_BLOCK = 256;
-constexpr int KNN_WAVES = KNN_BLOCK / MCR_WAVE;
-constexpr int KNN_SPLIT = 2;                       // waves sharing one 64-query tile
-constexpr int KNN_QT = KNN_WAVES / KNN_SPLIT;      // query tiles per workgroup
-constexpr int KNN_TILE = 1536;     // surface points per LDS tile (24 KB as float4); multiple of 16
-constexpr int KNN_QCAP = 8;        // per-lane queue of accepted candidates (LDS, [slot][thread])
+constexpr int KNN_BLOCK_ROWS = 128;                // queries per workgroup of the brute-force kernel
 
 // Insert (d2, idx) into the ascending list: slot j takes its upper neighbour if that one must move down,
 // the new element if it lands here, else keeps its value (one v_cmp + four v_cndmask per slot, no branches).
@@ -70,150 +62,17 @@ __device__ __forceinline__ float knn_d2(float qx, float qy, float qz, const floa
     return s + zz;
 }
 
-// grid = (ceil(Q/128), B); block = 2 query tiles x 2 waves
-template <int K, bool OFFSETS>
-__global__ __launch_bounds__(KNN_BLOCK) void knn_kernel(const float* __restrict__ X, const float* __restrict__ pc,
-                                                        long long* __restrict__ out_idx, float* __restrict__ out_dist,
-                                                        float* __restrict__ out_pts, int Q, int M, const int4* __restrict__ blocks,
-                                                        const long long* __restrict__ pc_off) {
-    // 40 KB: [tile 24 KB][queue distances 8 KB][queue indices 8 KB]; the first 32 KB are reused as the merge buffer
-    __shared__ __attribute__((aligned(16))) char smem[KNN_TILE * 16 + 2 * KNN_QCAP * KNN_BLOCK * 4];
-    float4* s_pc = reinterpret_cast<float4*>(smem);
-    float* s_qd = reinterpret_cast<float*>(smem + KNN_TILE * 16);
-    int* s_qi = reinterpret_cast<int*>(smem + KNN_TILE * 16 + KNN_QCAP * KNN_BLOCK * 4);
-    static_assert(KNN_WAVES * K * MCR_WAVE * 8 <= KNN_TILE * 16 + KNN_QCAP * KNN_BLOCK * 4, "merge buffer does not fit");
-    const int b = blockIdx.y;
-    const int lane = threadIdx.x & (MCR_WAVE - 1);
-    const int wave = threadIdx.x / MCR_WAVE;
-    const int qt = wave / KNN_SPLIT, part = wave % KNN_SPLIT;
-    // segmented form (blocks != NULL): workgroup i serves queries [blocks[i].y, blocks[i].y + blocks[i].z) (at most 128 rows of X,
-    // all of job blocks[i].x) against that job's own candidate cloud pc[pc_off[job] .. pc_off[job + 1]) -- many clouds of different
-    // sizes in one launch (the per-cell clouds of the occupancy-field pass); neighbour indices are relative to the job's cloud
-    int q_first = blockIdx.x * KNN_QT * MCR_WAVE, q_end = Q;
-    const float* pcb = pc + (size_t)b * M * 3;
-    if (blocks) {
-        const int4 bk = blocks[blockIdx.x];
-        q_first = bk.y; q_end = bk.y + bk.z;
-        pcb = pc + (size_t)pc_off[bk.x] * 3;
-        M = (int)(pc_off[bk.x + 1] - pc_off[bk.x]);
-    }
-    const int q = q_first + qt * MCR_WAVE + lane;
-    const bool valid = q < q_end;
-    const float* xq = X + ((size_t)b * Q + (valid ? q : q_end - 1)) * 3;
-    const float qx = xq[0], qy = xq[1], qz = xq[2];
-
-    float bd[K];
-    int bi[K];
-#pragma unroll
-    for (int j = 0; j < K; ++j) { bd[j] = __builtin_inff(); bi[j] = 0x7fffffff; }
-
-    // Accepted candidates are first pushed to a small per-lane LDS queue (a predicated ds_write) and inserted
-    // into the sorted register list in batches: the ~90-instruction insertion then runs once per ~KNN_QCAP
-    // accepted candidates of the fastest-filling lane instead of once per candidate any lane accepts.  The
-    // filter threshold tau is the (possibly stale, hence larger) current k-th distance: never a false reject.
-    float tau = __builtin_inff();
-    int cnt = 0;
-    float* q_d = s_qd + threadIdx.x;
-    int* q_i = s_qi + threadIdx.x;
-    auto flush = [&]() {
-        int maxc = cnt;
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) maxc = max(maxc, __shfl_xor(maxc, o, 64));
-        for (int sidx = 0; sidx < maxc; ++sidx)
-            if (sidx < cnt) knn_insert<K>(bd, bi, q_d[sidx * KNN_BLOCK], q_i[sidx * KNN_BLOCK]);
-        tau = bd[K - 1];
-        cnt = 0;
-    };
-    auto push = [&](float d, int idx) {
-        if (d < tau) {
-            q_d[cnt * KNN_BLOCK] = d;
-            q_i[cnt * KNN_BLOCK] = idx;
-            ++cnt;
-        }
-    };
-
-    for (int t0 = 0; t0 < M; t0 += KNN_TILE) {
-        const int nt = min(KNN_TILE, M - t0);
-        const int nt_pad = (nt + 15) & ~15;
-        __syncthreads();
-        for (int i = threadIdx.x; i < nt_pad; i += KNN_BLOCK) {
-            if (i < nt) {
-                const float* p = pcb + (size_t)(t0 + i) * 3;
-                s_pc[i] = make_float4(p[0], p[1], p[2], 0.f);
-            } else {
-                s_pc[i] = make_float4(3e18f, 3e18f, 3e18f, 0.f);        // d2 = +inf: never accepted
-            }
-        }
-        __syncthreads();
-        // the wave scans candidates i = part, part + SPLIT, ... of the tile, 4 per iteration
-        for (int i = part; i < nt_pad; i += 4 * KNN_SPLIT) {
-            const float4 p0 = s_pc[i], p1 = s_pc[i + KNN_SPLIT], p2 = s_pc[i + 2 * KNN_SPLIT], p3 = s_pc[i + 3 * KNN_SPLIT];
-            const float d0 = knn_d2(qx, qy, qz, p0), d1 = knn_d2(qx, qy, qz, p1);
-            const float d2 = knn_d2(qx, qy, qz, p2), d3 = knn_d2(qx, qy, qz, p3);
-            // once the lists have warmed up almost every batch is rejected by every lane: one wave-uniform test on the batch
-            // minimum then skips the four predicated pushes
-            if (__any(fminf(fminf(d0, d1), fminf(d2, d3)) < tau)) {
-                push(d0, t0 + i);
-                push(d1, t0 + i + KNN_SPLIT);
-                push(d2, t0 + i + 2 * KNN_SPLIT);
-                push(d3, t0 + i + 3 * KNN_SPLIT);
-                if (__any(cnt > KNN_QCAP - 4)) flush();
-            }
-        }
-    }
-    flush();
-    // ---- merge of the tile's KNN_SPLIT sorted lists (lexicographic on (d2, index)) ----------------------------
-    __syncthreads();
-    float* m_d = reinterpret_cast<float*>(smem);                        // [wave][K][lane]
-    int* m_i = reinterpret_cast<int*>(smem) + KNN_WAVES * K * MCR_WAVE;
-#pragma unroll
-    for (int j = 0; j < K; ++j) {
-        m_d[(wave * K + j) * MCR_WAVE + lane] = bd[j];
-        m_i[(wave * K + j) * MCR_WAVE + lane] = bi[j];
-    }
-    __syncthreads();
-    if (part != 0 || !valid) return;
-    m_d += qt * KNN_SPLIT * K * MCR_WAVE;                               // this tile's lists
-    m_i += qt * KNN_SPLIT * K * MCR_WAVE;
-    int head[KNN_SPLIT];
-#pragma unroll
-    for (int w = 0; w < KNN_SPLIT; ++w) head[w] = 0;
-    const size_t o = ((size_t)b * Q + q) * K;
-    for (int j = 0; j < K; ++j) {
-        float best_d = __builtin_inff();
-        int best_i = 0x7fffffff, best_w = 0;
-#pragma unroll
-        for (int w = 0; w < KNN_SPLIT; ++w) {
-            const int h = head[w] < K ? head[w] : K - 1;
-            const float d = head[w] < K ? m_d[(w * K + h) * MCR_WAVE + lane] : __builtin_inff();
-            const int id = head[w] < K ? m_i[(w * K + h) * MCR_WAVE + lane] : 0x7fffffff;
-            const bool better = d < best_d || (d == best_d && id < best_i);
-            best_d = better ? d : best_d;
-            best_i = better ? id : best_i;
-            best_w = better ? w : best_w;
-        }
-#pragma unroll
-        for (int w = 0; w < KNN_SPLIT; ++w) head[w] += (best_w == w) ? 1 : 0;
-        if (out_idx) out_idx[o + j] = (long long)best_i;
-        if (out_dist) out_dist[o + j] = sqrt_cr(best_d);
-        const float* p = pcb + (size_t)best_i * 3;
-        out_pts[(o + j) * 3 + 0] = OFFSETS ? p[0] - qx : p[0];
-        out_pts[(o + j) * 3 + 1] = OFFSETS ? p[1] - qy : p[1];
-        out_pts[(o + j) * 3 + 2] = OFFSETS ? p[2] - qz : p[2];
-    }
-}
-
 // ---------------------------------------------------------------------------------------------------------
-// K1-mfma: the same search with the distances on the matrix pipe.  A wave owns 32 queries; for 32 candidates at a time two
+// K1-mfma: the brute-force search with the distances on the matrix pipe.  A wave owns 32 queries; for 32 candidates at a time two
 // v_mfma_f32_32x32x2_f32 evaluate  s[c][q] = |p_c|^2 - 2 x_q . p_c  (A row c = (p.x, p.y, p.z, |p|^2), B column q =
 // (-2x.x, -2x.y, -2x.z, 1); the fp32 MFMA is bit for bit a k-ordered fmaf chain) -- 1024 candidate-query pairs per 128 pipe
-// cycles, 3.7x the vector form (11 instructions per 64 pairs), and the vector ALU is left with the selection.  Lane (q, h) gets 16
+// cycles, 3.7x a vector-ALU evaluation (11 instructions per 64 pairs), and the vector ALU is left with the selection.  Lane (q, h) gets 16
 // of the 32 candidates (rows (r & 3) + 8 (r >> 2) + 4 h) of ITS query, so a query's list is kept in two halves (merged at the
-// end, like the two-wave split of the vector kernel).  s + |x|^2 is NOT the convention's distance (different rounding): it only
+// end).  s + |x|^2 is NOT the convention's distance (different rounding): it only
 // FILTERS.  A candidate passes when s < tau - |x|^2 + eps (tau = the lane's current, possibly stale, k-th EXACT distance; eps =
 // 2^-20 (|x| + max|p|)^2 covers both forms' rounding 16 times over, so no true neighbour is ever rejected); its index goes to
 // the lane's LDS queue; at a flush the exact (dx^2 + dy^2) + dz^2 is recomputed from the coordinates and inserted with the same
-// strict compare -- the output is bit-identical to the vector kernel's (and oracle/knn.py's).
+// strict compare -- the output is bit-identical to an exact scan in index order (oracle/knn.py).
 constexpr int KM_TILE = 1024;      // candidates per LDS tile (SoA x | y | z | |p|^2: 16 KB)
 constexpr int KM_QCAP = 32;        // queued candidate indices per lane (32 KB as [slot][thread])
 
@@ -237,7 +96,10 @@ __global__ __launch_bounds__(KNN_BLOCK) void knn_mfma_kernel(const float* __rest
     const int j = lane & 31, h = lane >> 5;
     int q_first = blockIdx.x * 128, q_end = Q;
     const float* pcb = pc + (size_t)b * M * 3;
-    if (blocks) {                                  // segmented form: see knn_kernel
+    // segmented form (blocks != NULL): workgroup i serves queries [blocks[i].y, blocks[i].y + blocks[i].z) (at most 128 rows of X,
+    // all of job blocks[i].x) against that job's own candidate cloud pc[pc_off[job] .. pc_off[job + 1]) -- many clouds of different
+    // sizes in one launch (the per-cell clouds of the occupancy-field pass); neighbour indices are relative to the job's cloud
+    if (blocks) {
         const int4 bk = blocks[blockIdx.x];
         q_first = bk.y; q_end = bk.y + bk.z;
         pcb = pc + (size_t)pc_off[bk.x] * 3;
@@ -427,7 +289,7 @@ __global__ __launch_bounds__(KNN_BLOCK) void knn_mfma_kernel(const float* __rest
 // Exactness: a candidate in a skipped sub-tile has (real) distance^2 >= lb > R^2 >= the true 16th distance of every query of
 // the wave (any 16 candidates bound it from above); lb is compared after a relative guard of 1e-5 (its own fp32 rounding is
 // ~2e-7).  Everything that is visited goes through the same filter + exact fp32 (dx^2 + dy^2) + dz^2 + insert as before, so the
-// output is bit-identical to knn_kernel / knn_mfma_kernel and oracle/knn.py (tests/test_knn_gpu.py, incl. heavy ties).
+// output is bit-identical to knn_mfma_kernel and oracle/knn.py (tests/test_knn_gpu.py, incl. heavy ties).
 constexpr int KG_GP_BITS = 4, KG_GQ_BITS = 5, KG_GP = 1 << KG_GP_BITS, KG_GQ = 1 << KG_GQ_BITS;      // cells per axis: candidate grid, query grid
 constexpr int KG_MIN_M = 1024, KG_MAX_M = 16384;
 constexpr int KG_BUILD_BLOCK = 1024;
@@ -1135,18 +997,10 @@ __global__ __launch_bounds__(64) void knn_split_merge_kernel(const float* __rest
 template <int K>
 static void launch_knn(bool offsets, dim3 grid, hipStream_t s, const float* X, const float* pc, long long* idx, float* dist,
                        float* pts, int Q, int M, const int4* blocks = nullptr, const long long* pc_off = nullptr) {
-    static const bool use_mfma = []() { const char* e = getenv("MCR_KNN_MFMA"); return !(e && e[0] == '0'); }();   // dev A/B knob
-    if (use_mfma) {                                // distances on the matrix pipe (bit-identical results); same grid: 128 queries per block
-        if (offsets)
-            hipLaunchKernelGGL((knn_mfma_kernel<K, true>), grid, dim3(KNN_BLOCK), 0, s, X, pc, idx, dist, pts, Q, M, blocks, pc_off);
-        else
-            hipLaunchKernelGGL((knn_mfma_kernel<K, false>), grid, dim3(KNN_BLOCK), 0, s, X, pc, idx, dist, pts, Q, M, blocks, pc_off);
-        return;
-    }
     if (offsets)
-        hipLaunchKernelGGL((knn_kernel<K, true>), grid, dim3(KNN_BLOCK), 0, s, X, pc, idx, dist, pts, Q, M, blocks, pc_off);
+        hipLaunchKernelGGL((knn_mfma_kernel<K, true>), grid, dim3(KNN_BLOCK), 0, s, X, pc, idx, dist, pts, Q, M, blocks, pc_off);
     else
-        hipLaunchKernelGGL((knn_kernel<K, false>), grid, dim3(KNN_BLOCK), 0, s, X, pc, idx, dist, pts, Q, M, blocks, pc_off);
+        hipLaunchKernelGGL((knn_mfma_kernel<K, false>), grid, dim3(KNN_BLOCK), 0, s, X, pc, idx, dist, pts, Q, M, blocks, pc_off);
 }
 
 }  // namespace mcr
@@ -1157,7 +1011,7 @@ using namespace mcr;
 // row, number of rows <= 128, 0); job j's candidates are pc[pc_off[j] .. pc_off[j+1]).  Every job needs >= 16 candidates.
 namespace mcr {
 // split_ws (optional, knn16_segmented_split_floats(T) floats): lets a launch with few query blocks split every job's candidates over
-// up to KNN_SEG_SPLIT workgroups per block (+ one merge launch); same neighbours in the same order.  MCR_KNN_SEG_SPLIT=0: never (A/B)
+// up to KNN_SEG_SPLIT workgroups per block (+ one merge launch); same neighbours in the same order.
 #ifndef MCR_KNN_SEG_SPLIT_MAX
 #define MCR_KNN_SEG_SPLIT_MAX 8
 #endif
@@ -1169,20 +1023,16 @@ size_t knn16_segmented_split_floats(int64_t T) { return (size_t)KNN_SEG_SPLIT * 
 void launch_knn16_segmented(hipStream_t s, const float* X, const float* pc, const long long* pc_off, const int* blocks,
                             int64_t n_blocks, int64_t T, float* offsets_out, float* split_ws, int slice) {
     if (n_blocks <= 0) return;
-    static const bool split_on = []() { const char* e = getenv("MCR_KNN_SEG_SPLIT"); return !(e && e[0] == '0'); }();
-    static const bool use_mfma = []() { const char* e = getenv("MCR_KNN_MFMA"); return !(e && e[0] == '0'); }();
-    // four waves per block: ~3 waves per SIMD need 768 blocks
-    // slice: candidates per slice of a job (0: the launch is not split); MCR_KNN_SEG_CAND=0: one slice count for every job instead (A/B)
-    static const bool per_job = []() { const char* e = getenv("MCR_KNN_SEG_CAND"); return !(e && e[0] == '0'); }();
-    const int seg_cand = per_job ? slice : 0;
+    // four waves per block: ~3 waves per SIMD need 768 blocks; a sliced launch aims at four times as many, since a job's small cloud
+    // fills fewer slices than the largest one's
+    // slice: candidates per slice of a job (0: the launch is not split)
     int n_split = 1;
-    if (split_on && use_mfma && split_ws && slice > 0)
-        n_split = (int)std::min<int64_t>(KNN_SEG_SPLIT, std::max<int64_t>(1, (seg_cand > 0 ? 4 * MCR_KNN_SEG_TARGET : MCR_KNN_SEG_TARGET) / n_blocks));
+    if (split_ws && slice > 0) n_split = (int)std::min<int64_t>(KNN_SEG_SPLIT, std::max<int64_t>(1, 4 * MCR_KNN_SEG_TARGET / n_blocks));
     if (n_split > 1) {
         unsigned long long* part = reinterpret_cast<unsigned long long*>(split_ws);
         hipLaunchKernelGGL((knn_mfma_kernel<16, true>), dim3((unsigned)n_blocks, (unsigned)n_split), dim3(KNN_BLOCK), 0, s, X, pc,
                            (long long*)nullptr, (float*)nullptr, offsets_out, (int)T, 0, reinterpret_cast<const int4*>(blocks), pc_off, n_split, part,
-                           seg_cand);
+                           slice);
         const size_t merge_lds = (size_t)n_split * 64 * 17 * 8 + 64 * 16 * 3 * 4;                    // <= 81 920 bytes at 8 slices
         // the opt-in to > 64 KB of dynamic LDS is a per-DEVICE attribute of the function: set once for every device this process drives
         static bool lds_set[64] = {};
@@ -1199,21 +1049,19 @@ void launch_knn16_segmented(hipStream_t s, const float* X, const float* pc, cons
             lds_set[dev_id] = true;
         }
         hipLaunchKernelGGL((knn_split_merge_kernel<16>), dim3((unsigned)n_blocks, 2), dim3(64), merge_lds, s, X, pc, pc_off,
-                           reinterpret_cast<const int4*>(blocks), (const unsigned long long*)part, n_split, (int)T, offsets_out, seg_cand);
+                           reinterpret_cast<const int4*>(blocks), (const unsigned long long*)part, n_split, (int)T, offsets_out, slice);
         return;
     }
     launch_knn<16>(true, dim3((unsigned)n_blocks, 1), s, X, pc, nullptr, nullptr, offsets_out, (int)T, 0,
                    reinterpret_cast<const int4*>(blocks), pc_off);
 }
-constexpr int knn_block_rows() { return MCR_WAVE * KNN_QT; }
-int knn_rows_per_block() { return knn_block_rows(); }
+int knn_rows_per_block() { return KNN_BLOCK_ROWS; }
 }  // namespace mcr
 
 namespace mcr {
 static inline size_t kg_al(size_t n) { return (n + 255) & ~(size_t)255; }
 bool knn_grid_applicable(int64_t M, int k) {
-    static const bool on = []() { const char* e = getenv("MCR_KNN_GRID"); return !(e && e[0] == '0'); }();      // dev A/B knob
-    return on && k == 16 && M >= KG_MIN_M && M <= KG_MAX_M;
+    return k == 16 && M >= KG_MIN_M && M <= KG_MAX_M;
 }
 size_t knn_grid_query_bytes(int64_t B, int64_t Q) {
     return kg_al(B * 8 * 4) + kg_al((size_t)B * KG_QCELLS * 4) + 3 * kg_al((size_t)B * Q * 4);
@@ -1278,8 +1126,7 @@ void launch_knn16_grid(hipStream_t s, const float* X, const float* pc, int64_t M
     long long* i64 = (long long*)idx;             // the outputs are those of cloud b_first already
     float* d = dist;
     float* o = pts;
-    static const bool park_on = []() { const char* e = getenv("MCR_KNN_PARK"); return !(e && e[0] == '0'); }();          // dev A/B knob
-    int* def_count = park_ws && park_on && launch >= 0 && launch < 64 ? (int*)park_ws + launch : nullptr;
+    int* def_count = park_ws && launch >= 0 && launch < 64 ? (int*)park_ws + launch : nullptr;
     char* def_scratch = park_ws ? (char*)park_ws + 256 : nullptr;
     dim3 grid((unsigned)cdiv(Q, 32), (unsigned)n_b);
     const int n_sub = (int)(c.cand_stride / 32);
@@ -1304,17 +1151,16 @@ extern "C" int mcr_knn_points(const float* X, const float* pc, int64_t* idx, flo
     MCR_REQUIRE(k <= M, "mcr_knn_points: k=%d exceeds the number of points M=%ld (torch.topk would raise)", k, (long)M);
     MCR_REQUIRE(B <= 65535 && Q < (1ll << 31) && M < (1ll << 31), "mcr_knn_points: problem too large");
     hipStream_t s = (hipStream_t)stream;
-    dim3 grid((unsigned)cdiv(Q, MCR_WAVE * KNN_QT), (unsigned)B);
+    dim3 grid((unsigned)cdiv(Q, KNN_BLOCK_ROWS), (unsigned)B);
     long long* i64 = (long long*)idx;
     switch (k) {
         case 1: launch_knn<1>(subtract_query, grid, s, X, pc, i64, dists, pts, (int)Q, (int)M); break;
         case 4: launch_knn<4>(subtract_query, grid, s, X, pc, i64, dists, pts, (int)Q, (int)M); break;
         case 8: launch_knn<8>(subtract_query, grid, s, X, pc, i64, dists, pts, (int)Q, (int)M); break;
         case 16: launch_knn<16>(subtract_query, grid, s, X, pc, i64, dists, pts, (int)Q, (int)M); break;
-        
         default: MCR_REQUIRE(false, "mcr_knn_points: k must be one of 1,4,8,16 (got %d)", k);
     }
-    MCR_LAUNCH_CHECK("knn_kernel");
+    MCR_LAUNCH_CHECK("knn_mfma_kernel");
     return 0;
 }
 

@@ -152,6 +152,7 @@ bool linear3_applicable(const float* X, int64_t ldx, const float* W, int64_t ldw
     return linear3_shape_ok(X, ldx, W, ldw, N, K) && cdiv(M, L3G_BM) * cdiv(N, L3G_BN_BIG) >= 256;
 }
 
+constexpr int64_t L3_XCD_MIN_ROW_BLOCKS = 64;             // row blocks from which a launch takes the XCD-aware block order
 void launch_linear3(hipStream_t s, const float* X, int64_t ldx, const float* W, const float* bias, const float* R, int64_t ldr,
                     float* Y, int64_t ldy, int64_t M, int N, int K, int act, const float* row_bias, int64_t rows_per_group,
                     int64_t ldw, const int* row_group) {
@@ -160,14 +161,11 @@ void launch_linear3(hipStream_t s, const float* X, int64_t ldx, const float* W, 
     // widest column tile that still gives the chip ~2 blocks per CU (performance only: see the note on L3G_NT above); the short-K
     // GEMMs of the encoders (K = 256 / 512: eight or sixteen chunks between an exposed first load and the epilogue) run better on
     // 64-column blocks, four per CU, than on 128-column ones, three per CU (SconeVis on 30 x 2048 tokens: 3.80 vs 4.11 ms); the
-    // head's K = 1344 the other way round.  MCR_L3_SHORTK=0: 128-column blocks whatever K is (A/B)
-    static const bool shortk = []() { const char* e = getenv("MCR_L3_SHORTK"); return !(e && e[0] == '0'); }();
-    int nt = shortk && K <= 512 ? 2 : 4;
+    // head's K = 1344 the other way round.
+    int nt = K <= 512 ? 2 : 4;
     while (nt > 1 && mb * cdiv(N, nt * 32) < 512) nt >>= 1;
-    // XCD-aware block order for the batch-sized launches (SconeVis on 30 x 2048 tokens: 3.77 -> 3.53 ms); MCR_L3_XCD=0: never (A/B)
-    static const bool xcd_on = []() { const char* e = getenv("MCR_L3_XCD"); return !(e && e[0] == '0'); }();
-    static const int xcd_min = []() { const char* e = getenv("MCR_L3_XCD_MIN"); return e ? atoi(e) : 64; }();
-    const int xo = xcd_on && mb >= xcd_min;
+    // XCD-aware block order for the batch-sized launches (SconeVis on 30 x 2048 tokens: 3.77 -> 3.53 ms)
+    const int xo = mb >= L3_XCD_MIN_ROW_BLOCKS;
 #define MCR_L3(NT)                                                                                                              \
     hipLaunchKernelGGL((linear3_kernel<NT>), dim3((unsigned)((xo ? cdiv(mb, 8) * 8 : mb) * cdiv(N, NT * 32))), dim3(256), 0, s, X, \
                        (long long)ldx, W, (long long)ldw, bias, row_bias, rpg, R, (long long)ldr, Y, (long long)ldy,            \

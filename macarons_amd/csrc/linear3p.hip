@@ -517,14 +517,11 @@ static void launch_linear3p_np(hipStream_t s, const void* Xh, const void* Xl, in
                                const float* bias, float* Y, void* Yh, void* Yl, int64_t ldy, int64_t M, int N, int K, int act, float wscale_inv,
                                const float* row_bias, int64_t rows_per_group, const int* row_group, const float* R, int64_t ldr) {
     const long long rpg = rows_per_group > 0 ? rows_per_group : 1;
-    // short K: the two-blocks-per-CU form (same bits); MCR_L3P_SMALL=0: the large tile whatever K is (A/B), =2: the small one always
-    static const int small_mode = []() { const char* e = getenv("MCR_L3P_SMALL"); return e ? atoi(e) : 1; }();
-    // a few thousand rows: the one-shot form (same bits); MCR_L3P_ONCE=0: off (A/B)
-    static const bool once_on = []() { const char* e = getenv("MCR_L3P_ONCE"); return !(e && e[0] == '0'); }();
+    // three forms, the same bits: a few thousand rows take the one-shot form, short K the two-blocks-per-CU form, the rest the large tile
     const _Float16 *xh = (const _Float16*)Xh, *xl = (const _Float16*)Xl, *wh = (const _Float16*)Wh, *wl = (const _Float16*)Wl;
     _Float16 *yh = (_Float16*)Yh, *yl = (_Float16*)Yl;
     const float* nf = nullptr;
-    if (once_on && M <= 4096 && !row_bias && (K == 128 || K % LPO_KS == 0)) {
+    if (M <= 4096 && !row_bias && (K == 128 || K % LPO_KS == 0)) {
         if (!(Yh ? lpo_reserve<LP_PLANES, NP>() : lpo_reserve<LP_F32, NP>())) { refuse("launch_linear3p: cannot reserve %d bytes of LDS", LPO_LDS_BYTES); return; }
         dim3 g((unsigned)(cdiv(M, LPO_T) * cdiv(N, LPO_T)));
         if (Yh)
@@ -535,7 +532,7 @@ static void launch_linear3p_np(hipStream_t s, const void* Xh, const void* Xl, in
                                (_Float16*)nullptr, (_Float16*)nullptr, (long long)ldy, (long long)M, N, K, act, wscale_inv, R, (long long)ldr);
         return;
     }
-    if (small_mode == 2 || (small_mode == 1 && K <= 512)) {
+    if (K <= 512) {
         if (!(Yh ? lp_reserve<LP_PLANES, true, NP>() : lp_reserve<LP_F32, true, NP>())) { refuse("launch_linear3p: cannot reserve %d bytes of LDS", LPS_LDS_BYTES); return; }
         dim3 g((unsigned)(cdiv(cdiv(M, 128), 8) * 8 * cdiv(N, 128)));
         if (Yh)
@@ -571,7 +568,7 @@ void launch_linear3p(hipStream_t s, const void* Xh, const void* Xl, int64_t ldx,
 }
 
 // out[m] = act2( act(X W^T * wscale_inv + bias)[m][:] . v + c ) for a 256-feature layer (N == 256): two layers, one launch
-bool linear3p_dot_applicable(int N, int K, int64_t ldx, int64_t ldw) { return N == 256 && K % LP_BK == 0 && K >= LP_BK && ldx % 8 == 0 && ldw % 8 == 0; }
+// (K a multiple of LP_BK, ldx and ldw multiples of 8: the SconeOcc head's 512 -> 256 -> 1 tail is the caller)
 template <int NP>
 static void launch_linear3p_dot_np(hipStream_t s, const void* Xh, const void* Xl, int64_t ldx, const void* Wh, const void* Wl, int64_t ldw,
                                    const float* bias, int64_t M, int K, int act, float wscale_inv, const float* v, const float* c, int act2, float* out) {

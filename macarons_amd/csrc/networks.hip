@@ -66,42 +66,20 @@ static inline int matrix_planes() { return g_local_pct_variant == 7 ? 1 : 2; }
 // argument = "choose on the layer's shape"; its column-tile width follows the launch, which does not change a single bit) -- one
 // sequence costs the same as on the fp32 kernels, 8 or 30 sequences in one launch (scene batch, the neighbour cameras of a MACARONS
 // decision) run 1.3x faster, and a sequence's result still does not depend on how many share the launch.  Variant 1 = exact fp32
-// everywhere.  MCR_SMALL_SPLIT=0: the fp32 small-problem kernels on every variant (A/B).
-static inline int64_t seq_route(int64_t L) {
-    static const bool on = []() { const char* e = getenv("MCR_SMALL_SPLIT"); return !(e && e[0] == '0'); }();
-    return on && g_local_pct_variant >= 5 ? -L : L;
-}
+// everywhere.  The wide layers behind the encoders (SconeVis fc1 / fc2, the global transformer's lin0) take the same route.
+static inline int64_t seq_route(int64_t L) { return g_local_pct_variant >= 5 ? -L : L; }
 
-// the wide layers behind the encoders (SconeVis fc1 / fc2, the global transformer's lin0): on the encoders' matrix path;
-// MCR_HEAD_SPLIT=0: the exact-fp32 kernels, as before round 4 (A/B)
-static inline int64_t head_route(int64_t L) {
-    static const bool on = []() { const char* e = getenv("MCR_HEAD_SPLIT"); return !(e && e[0] == '0'); }();
-    return on ? seq_route(L) : L;
-}
+// long-sequence attention: P V on fp16 hi/lo pairs (nn_kernels.hip: PVH) on the fp16-split variants, fp32 MFMA on the others
+static inline bool attn_pv_half() { return fp16_planes_variant(); }
 
-// long-sequence attention: P V on fp16 hi/lo pairs (nn_kernels.hip: PVH) on the fp16-split variant; MCR_ATTN_PVH=0: fp32 MFMA (A/B)
-static inline bool attn_pv_half() {
-    static const bool on = []() { const char* e = getenv("MCR_ATTN_PVH"); return !(e && e[0] == '0'); }();
-    return on && fp16_planes_variant();
-}
-
-// Encoder GEMMs of the long-sequence networks on fp16 hi/lo PLANES (variant 6, sequences of >= 512 tokens; MCR_ENC_PLANES=0: the
-// bf16 x 6 kernels as on variant 5, A/B): the GEMM inputs are split once where they are produced -- LayerNorm writes planes, the FF's
+// Encoder GEMMs of the long-sequence networks on fp16 hi/lo PLANES (variants 6 and 7, sequences of >= 512 tokens; shorter ones take the
+// bf16 x 6 kernels as on variant 5): the GEMM inputs are split once where they are produced -- LayerNorm writes planes, the FF's
 // first GEMM writes planes, the attention output is split in one pass -- and every operand reaches LDS by DMA (linear3p.hip): no
 // split and no staging registers inside the GEMMs, three MFMAs per product instead of six.  Chosen on the sequence length alone, so a
 // cloud's result does not depend on how many clouds share the launch.  Needs |activation| < 65504 like the rest of variant 6: the
-// occupancy / harmonics that come out non-finite otherwise are what the range guards look at.
-static inline bool enc_planes(int L, int E) {
-    static const bool on = []() { const char* e = getenv("MCR_ENC_PLANES"); return !(e && e[0] == '0'); }();
-    return on && fp16_planes_variant() && L >= 512 && E % 32 == 0;
-}
-
-// The layers either side of the encoders (the embeddings' second layer, the final LayerNorm and the fc / lin0 layers behind it) on the
-// same planes path; MCR_ENDS_PLANES=0: the fp32 / bf16 x 6 kernels as before (A/B)
-static inline bool ends_planes(int L, int E) {
-    static const bool on = []() { const char* e = getenv("MCR_ENDS_PLANES"); return !(e && e[0] == '0'); }();
-    return on && enc_planes(L, E);
-}
+// occupancy / harmonics that come out non-finite otherwise are what the range guards look at.  The layers either side of the encoders
+// (the embeddings' second layer, the final LayerNorm and the fc / lin0 layers behind it) are on the same path under the same condition.
+static inline bool enc_planes(int L, int E) { return fp16_planes_variant() && L >= 512 && E % 32 == 0; }
 
 // The planes live in the encoder's own scratch (an fp32 row = two fp16 rows): h <- planes of LayerNorm(x) / fp32 attention output,
 // ff <- planes of the attention output, then of the FF's hidden layer; the weights' planes (split per call, 2^8 scale: linear3h.hip)
@@ -123,27 +101,23 @@ static void run_encoder_planes(hipStream_t s, const EncW& w, float* x, float* h,
     launch_layernorm_planes(s, x, E, w.n1g, w.n1b, hh, hl, E, T, E);                         // Attention.py:287
     const _Float16* Wq = wsplit(w.qkv.w, W3, E, ff, w.p_qkv);
     _Float16* ah = reinterpret_cast<_Float16*>(qkv);                                         // the attention's result as planes [2][T][E]
-    static const bool att_planes = []() { const char* e = getenv("MCR_ENC_ATT_PLANES"); return !(e && e[0] == '0'); }();   // (A/B)
-    if ((att_planes || np == 1) && attention_planes_applicable(H, dqk, E, W3)) {
+    if (attention_planes_applicable(H, dqk, E, W3)) {
         // q | k | v leave the projection as planes [2][T][W3] over qkv (:186-188); the attention stages K / V tiles by DMA (:191-198) and
         // writes its result as planes over h (the LayerNorm's, consumed by then).  One block per (query tile, head, sequence) whatever S is
         // (a cloud's result must not depend on how many clouds share the launch): a batch of clouds saves the combine pass and the fp32
         // parts of the key-split form (0.23 ms of a MACARONS decision); one cloud alone pays 13 us per attention for it (41 instead of
-        // 23 + 5 us, hidden beside the local transformers in an NBV step).  MCR_ENC_ATT_SPLIT=1: keys over two blocks + combine (A/B)
+        // 23 + 5 us, hidden beside the local transformers in an NBV step).
         _Float16 *qh_ = reinterpret_cast<_Float16*>(qkv), *ql_ = qh_ + (size_t)T * W3;
         launch_linear3p(s, hh, hl, E, Wq, Wq + (size_t)W3 * E, E, w.qkv.b, nullptr, qh_, ql_, W3, T, W3, E, ACT_NONE, inv, nullptr, 0, nullptr,
                         nullptr, 0, np);
-        static const int split_mode_env = []() { const char* e = getenv("MCR_ENC_ATT_SPLIT"); return e ? atoi(e) : 0; }();
-        const int split_mode = np == 1 ? 0 : split_mode_env;                                   // (the single-plane form never splits its keys)
-        if (split_mode == 0) ah = hh;                                                          // (split: the combine pass writes the planes over qkv, dead by then)
-        launch_attention_planes(s, qh_, ql_, W3, h, E, ah, ah + (size_t)T * E, E, S, L, H, dqk, E, lens, ff, (size_t)T * 2 * E, split_mode, np);
+        ah = hh;
+        launch_attention_planes(s, qh_, ql_, W3, h, E, ah, ah + (size_t)T * E, E, S, L, H, dqk, E, lens, ff, (size_t)T * 2 * E, /*split_mode=*/0, np);
     } else {
         launch_linear3p(s, hh, hl, E, Wq, Wq + (size_t)W3 * E, E, w.qkv.b, qkv, nullptr, nullptr, W3, T, W3, E, ACT_NONE, inv, nullptr, 0, nullptr);   // :186-188
         // attention: fp32 parts in h / ff (key-split scratch); its combine pass writes the result straight as planes into qkv (free by then)
         bool planes_done = false;
-        static const bool fuse = []() { const char* e = getenv("MCR_ENC_COMBINE_PLANES"); return !(e && e[0] == '0'); }();   // (A/B)
         launch_attention(s, qkv, W3, h, E, S, L, H, dqk, E, lens, ff, (size_t)T * 2 * E, /*split_by_length=*/true, attn_pv_half(), nullptr, 0, 0, 0,
-                         fuse ? ah : nullptr, ah + (size_t)T * E, E, &planes_done);              // :191-198
+                         ah, ah + (size_t)T * E, E, &planes_done);              // :191-198
         if (!planes_done) launch_split_to_planes(s, h, E, ah, ah + (size_t)T * E, E, T, E);
     }
     const _Float16* Wo = wsplit(w.out.w, E, E, ff, w.p_out);
@@ -198,7 +172,7 @@ static void run_pct(hipStream_t s, const PctW& w, const float* pc, float* feat, 
                     const EncScratch& ws, const int* lens = nullptr) {
     const int64_t T = S * L;
     float *x = ws.x, *h = ws.h, *qkv = ws.qkv, *ff = ws.ff;
-    const bool planes = ends_planes(L, PCT_E) && half % 4 == 0;
+    const bool planes = enc_planes(L, PCT_E) && half % 4 == 0;
     const float inv = 1.0f / 256.0f;
     const int np = matrix_planes();                       // 1 on variant 7: the GEMMs below read / write the high planes alone
     _Float16 *hh = reinterpret_cast<_Float16*>(h), *hl = hh + (size_t)T * PCT_E;            // planes [2][T][128] over h
@@ -230,7 +204,7 @@ static void run_pct(hipStream_t s, const PctW& w, const float* pc, float* feat, 
                         nullptr, 0, nullptr, nullptr, 0, np);
     } else {
         launch_layernorm(s, x, PCT_E, w.ng, w.nb, h, PCT_E, T, PCT_E);                      // SconeOcc.py:119
-        launch_linear(s, h, PCT_E, w.lin0.w, w.lin0.b, nullptr, 0, ff, half, T, half, PCT_E, ACT_NONE, nullptr, 0, 0, head_route(L));   // :122
+        launch_linear(s, h, PCT_E, w.lin0.w, w.lin0.b, nullptr, 0, ff, half, T, half, PCT_E, ACT_NONE, nullptr, 0, 0, seq_route(L));   // :122
     }
     launch_pool_max_avg(s, ff, half, feat, ld_feat, S, L, half, lens);                       // :124-126
 }
@@ -302,15 +276,8 @@ static void run_head_planes(hipStream_t s, const float* x, const float* view_har
     launch_linear3p(s, fh, fl, 1344, Wh, Wl, 1344, lin1.b, nullptr, hh, hh + (size_t)T * 512, 512, T, 512, 1344, ACT_GELU, inv, gbias,
                     rows_per_group, row_group, nullptr, 0, np);
     head_planes_weights(s, 3, lin2.w, 512, 256, 512, head_planes, head_inv_scales, w.wplanes, Wh, Wl, inv);
-    static const bool fuse_tail = []() { const char* e = getenv("MCR_HEAD_FUSE_TAIL"); return !(e && e[0] == '0'); }();     // dev A/B knob
-    if (fuse_tail && linear3p_dot_applicable(256, 512, 512, 512)) {
-        // 512 -> 256 (GELU) -> 1 (GELU) in one launch: the block owns all 256 features of its rows and dots them with linear3.weight
-        launch_linear3p_dot(s, hh, hh + (size_t)T * 512, 512, Wh, Wl, 512, lin2.b, T, 512, ACT_GELU, inv, lin3.w, lin3.b, ACT_GELU, out, np);
-        return;
-    }
-    launch_linear3p(s, hh, hh + (size_t)T * 512, 512, Wh, Wl, 512, lin2.b, w.h2, nullptr, nullptr, 256, T, 256, 512, ACT_GELU, inv, nullptr, 0,
-                    nullptr, nullptr, 0, np);
-    launch_linear(s, w.h2, 256, lin3.w, lin3.b, nullptr, 0, out, 1, T, 1, 256, ACT_GELU, nullptr, 0, 0, 1);
+    // 512 -> 256 (GELU) -> 1 (GELU) in one launch: the block owns all 256 features of its rows and dots them with linear3.weight
+    launch_linear3p_dot(s, hh, hh + (size_t)T * 512, 512, Wh, Wl, 512, lin2.b, T, 512, ACT_GELU, inv, lin3.w, lin3.b, ACT_GELU, out, np);
 }
 
 }  // namespace mcr
@@ -545,7 +512,7 @@ int mcr_scone_vis_forward(const float* pts, const float* view_harmonics, float* 
     const EncScratch ws = carve_enc(a, T, VIS_E);
     MCR_REQUIRE(a.ok(), "mcr_scone_vis_forward: workspace too small");
     float *x = ws.x, *h = ws.h, *qkv = ws.qkv, *ff = ws.ff;
-    const bool planes = ends_planes((int)N, VIS_E);
+    const bool planes = enc_planes((int)N, VIS_E);
     const float inv = 1.0f / 256.0f;
     const int np = matrix_planes();                       // 1 on variant 7: the GEMMs below read / write the high planes alone
     _Float16 *hh = reinterpret_cast<_Float16*>(h), *hl = hh + (size_t)T * VIS_E;               // planes [2][T][<= 256] over h
@@ -596,9 +563,9 @@ int mcr_scone_vis_forward(const float* pts, const float* view_harmonics, float* 
     } else {
         launch_layernorm(s, x, VIS_E, w.ng, w.nb, h, VIS_E, T, VIS_E);                                   // :143
         // fc1 256->192 GELU, || view_harmonics (64), fc2 256->128 GELU, fc3 128->64                  (:146-152)
-        launch_linear(s, h, VIS_E, fc1.w, fc1.b, nullptr, 0, ff, VIS_E, T, 192, VIS_E, ACT_GELU, nullptr, 0, 0, head_route(N));
+        launch_linear(s, h, VIS_E, fc1.w, fc1.b, nullptr, 0, ff, VIS_E, T, 192, VIS_E, ACT_GELU, nullptr, 0, 0, seq_route(N));
         launch_copy2d(s, view_harmonics, 64, ff + 192, VIS_E, T, 64);
-        launch_linear(s, ff, VIS_E, fc2.w, fc2.b, nullptr, 0, h, 128, T, 128, VIS_E, ACT_GELU, nullptr, 0, 0, head_route(N));
+        launch_linear(s, ff, VIS_E, fc2.w, fc2.b, nullptr, 0, h, 128, T, 128, VIS_E, ACT_GELU, nullptr, 0, 0, seq_route(N));
         launch_linear(s, h, 128, fc3.w, fc3.b, nullptr, 0, out, 64, T, 64, 128, ACT_NONE, nullptr, 0, 0, N);
     }
     MCR_LAUNCH_CHECK("mcr_scone_vis_forward");
@@ -830,24 +797,16 @@ int mcr_scone_occ_forward_phase(const float* pc_global, int64_t Lg, const float*
     // the [Q,16,3] offsets is materialised); layer-by-layer path: chunked over queries to bound its workspace.
     const bool fused_all = local_blobs && local_blobs[0] && local_blobs[1] && local_blobs[2];
     const int64_t qc = fused_all ? Q : std::min<int64_t>(Q, OCC_CHUNK);
-    // the planes head (OccHead::planes; MCR_HEAD_PLANES=0: the fp32-input linear3h path)
-    static const bool planes_on = []() { const char* e = getenv("MCR_HEAD_PLANES"); return !(e && e[0] == '0'); }();
-    const bool planes = planes_on && fused_all && fp16_planes_variant();
+    // the planes head (OccHead::planes); without all three fused blobs, or on variants 1 and 5: the fp32-input head (head_linear)
+    const bool planes = fused_all && fp16_planes_variant();
     _Float16* featP = hd.featP();
     const int64_t Tall = B * Q;
-    // the x embedding of the planes head (0.3 ms of GEMMs that need only the queries) rides on the side stream behind the global
-    // transformer: its workgroups fill the machine in the holes of the local path (kNN preparation, the parked kNN groups, kernel
-    // tails) instead of extending the serial tail of the step.  MCR_OCC_X_SIDE=0: on the caller's stream, after the local path.
-    static const bool x_side_on = []() { const char* e = getenv("MCR_OCC_X_SIDE"); return !(e && e[0] == '0'); }();
-    const HeadScratch head_scratch = hd.planes();
-    // ... and it needs nothing but the queries, so it is queued with the EARLY part (phase 1 / the start of the single call), where the
-    // GPU is nearly idle for ~0.4 ms (query order, cloud build, the scale-0 search): behind the global transformer it only found the
-    // holes between the local-transformer launches and finished 0.15 ms AFTER the last of them -- the head waited for it
-    // (profiles/r04_nbv_step_breakdown.txt).  The view harmonics (known in phase 2 only) are split there.  MCR_OCC_X_EARLY=0: as before.
-    static const bool x_early_on = []() { const char* e = getenv("MCR_OCC_X_EARLY"); return !(e && e[0] == '0'); }();
-    OccSide* xside = planes && x_side_on && x_early_on && occ_side(s) ? occ_side(s, 1) : nullptr;
-    const bool x_early = xside != nullptr;               // (the same answer in phase 1 and in phase 2 of one forward)
-    const bool x_on_side = planes && side && x_side_on;
+    // The x embedding of the planes head (0.3 ms of GEMMs that need nothing but the queries) has two placements.  Where its own side
+    // stream (slot 1) exists it is queued there with the EARLY part (phase 1 / the start of the single call), where the GPU is nearly
+    // idle for ~0.4 ms (query order, cloud build, the scale-0 search; profiles/r04_nbv_step_breakdown.txt), and the view harmonics
+    // (known in phase 2 only) are split into their columns beside the global transformer.  Otherwise (no stream: creation failed,
+    // MCR_OCC_OVERLAP=0) the whole of it runs inside run_head_planes on the caller's stream.
+    OccSide* xside = planes ? occ_side(s, 1) : nullptr;   // (the same answer in phase 1 and in phase 2 of one forward)
     // the caller's stream waits for the early x embedding BEHIND the early part's own kernels (end of phase 1 / before the head); every
     // way out of the function in between queues that wait too (a dangling fork would poison a capture)
     struct XJoin {
@@ -855,18 +814,17 @@ int mcr_scone_occ_forward_phase(const float* pc_global, int64_t Lg, const float*
         bool wait() { if (!armed) return true; armed = false; return hipStreamWaitEvent(s, side->join, 0) == hipSuccess; }
         ~XJoin() { (void)wait(); }
     } x_join{xside, s, false};
-    if (x_early && early) {
+    if (xside && early) {
         MCR_REQUIRE(hipEventRecord(xside->fork, s) == hipSuccess && hipStreamWaitEvent(xside->s, xside->fork, 0) == hipSuccess,
                     "mcr_scone_occ_forward: side stream (x embedding fork)");
-        run_x_embedding_planes(xside->s, x, nullptr, B * Q, w.xe1, w.xe2, w.xe3, head_planes, head_inv_scales, head_scratch);
+        run_x_embedding_planes(xside->s, x, nullptr, B * Q, w.xe1, w.xe2, w.xe3, head_planes, head_inv_scales, hd.planes());
         MCR_REQUIRE(hipEventRecord(xside->join, xside->s) == hipSuccess, "mcr_scone_occ_forward: side stream (x embedding record)");
         x_join.armed = true;
     }
     if (late) {
         run_global(gs, w, pc_global, B, Lg, nullptr, ws.glob, hd);
-        if (x_on_side && x_early)
+        if (xside)
             launch_split_to_planes(gs, view_harmonics, 64, featP + 1280, matrix_planes() == 1 ? nullptr : featP + Tall * FEAT + 1280, 1344, B * Q, 64);
-        else if (x_on_side) run_x_embedding_planes(gs, x, view_harmonics, B * Q, w.xe1, w.xe2, w.xe3, head_planes, head_inv_scales, head_scratch);
     }
     if (side) {
         MCR_REQUIRE(hipEventRecord(side->join, side->s) == hipSuccess, "mcr_scone_occ_forward: side stream (record)");
@@ -913,21 +871,19 @@ int mcr_scone_occ_forward_phase(const float* pc_global, int64_t Lg, const float*
         const bool fused = planes || (local_blobs && local_blobs[sc]);      // the fused LDS-resident kernel (local_pct*.hip)
         // a batch of clouds on the fused path (config 3's scene batch): ONE search and ONE transformer launch per scale over all B x Q
         // rows instead of one per cloud -- eight brute-force searches of 256 workgroups each (one wave per SIMD: every wave waits out
-        // its own latencies) become one of 2048.  The rows are the same rows: same bits.  MCR_OCC_BATCH_LOCAL=0: per cloud (A/B)
-        static const bool batch_local_on = []() { const char* e = getenv("MCR_OCC_BATCH_LOCAL"); return !(e && e[0] == '0'); }();
-        if (batch_local_on && B > 1 && qc == Q && fused) {
+        // its own latencies) become one of 2048.  The rows are the same rows: same bits.
+        if (B > 1 && qc == Q && fused) {
             Arena a = ws.scratch;
             float* offs = carve_occ_local(a, Tall, false).offs;
-            if (a.ok()) {
-                if (grid_knn) {
-                    launch_knn16_grid(s, x, pc_scale[sc], M_scale[sc], knn_qperm, knn_cloud, 0, B, Q, nullptr, nullptr, offs, true, ws.knn_park, sc);
-                    MCR_LAUNCH_CHECK("knn_grid_kernel");
-                } else if (int e = mcr_knn_points(x, pc_scale[sc], nullptr, nullptr, offs, B, Q, M_scale[sc], 16, 1, stream))
-                    return e;
-                if (planes) run_local_pct(s, offs, nullptr, FEAT, Tall, local_blobs[sc], featP + sc * 256, featP + Tall * FEAT + sc * 256);
-                else run_local_pct(s, offs, feat + sc * 256, FEAT, Tall, local_blobs[sc]);
-                continue;
-            }                                              // (workspace sized by an older caller: the per-cloud form below)
+            MCR_REQUIRE(a.ok(), "mcr_scone_occ_forward: workspace overflow (kNN)");
+            if (grid_knn) {
+                launch_knn16_grid(s, x, pc_scale[sc], M_scale[sc], knn_qperm, knn_cloud, 0, B, Q, nullptr, nullptr, offs, true, ws.knn_park, sc);
+                MCR_LAUNCH_CHECK("knn_grid_kernel");
+            } else if (int e = mcr_knn_points(x, pc_scale[sc], nullptr, nullptr, offs, B, Q, M_scale[sc], 16, 1, stream))
+                return e;
+            if (planes) run_local_pct(s, offs, nullptr, FEAT, Tall, local_blobs[sc], featP + sc * 256, featP + Tall * FEAT + sc * 256);
+            else run_local_pct(s, offs, feat + sc * 256, FEAT, Tall, local_blobs[sc]);
+            continue;
         }
         for (int64_t q0 = 0; q0 < Q; q0 += qc) {
             const int64_t nq = std::min<int64_t>(qc, Q - q0);
@@ -958,7 +914,7 @@ int mcr_scone_occ_forward_phase(const float* pc_global, int64_t Lg, const float*
         MCR_LAUNCH_CHECK("mcr_scone_occ_forward (phase 1)");
         return 0;
     }
-    return run_occ_head(who, s, w, x, view_harmonics, Tall, hd, Q, nullptr, head_planes, head_inv_scales, planes, /*x_done=*/x_on_side, side,
+    return run_occ_head(who, s, w, x, view_harmonics, Tall, hd, Q, nullptr, head_planes, head_inv_scales, planes, /*x_done=*/xside != nullptr, side,
                         side_join, range_flag, out);
 }
 
@@ -1019,8 +975,7 @@ int mcr_scone_occ_forward_ragged_phase(const float* pc_global, const int* global
     const OccRaggedScratch ws = carve_occ_ragged(arena, J, T, Lg);
     MCR_REQUIRE(arena.ok(), "mcr_scone_occ_forward_ragged: workspace overflow (kNN)");
     const OccHead& hd = ws.head;
-    static const bool planes_on = []() { const char* e = getenv("MCR_HEAD_PLANES"); return !(e && e[0] == '0'); }();
-    const bool planes = planes_on && fp16_planes_variant();
+    const bool planes = fp16_planes_variant();
     _Float16* featP = hd.featP();
     auto local_scale = [&](int sc) {                      // one segmented kNN + one fused transformer launch over ALL rows
         // (the whole clouds of scale 0 are the large ones: a launch with few query blocks cuts every job's candidates into slices of

@@ -150,8 +150,8 @@ static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t
 // K <= 4 (the xyz embeddings 3 -> 128 over all queries): a thread owns 4 consecutive outputs of one row.  The fmaf chain in
 // ascending k from 0, then + bias, is bit for bit what the zero-padded fp32 MFMA path returns (the fp32 MFMA is an exact fmaf
 // chain); that path spent 69 us on 100k x 128 outputs, this one is bound by its 51 MB of stores.
-// PLANES: the result leaves as fp16 hi/lo planes Yh / Yl [M][ldy] (the operand format of the planes GEMM that consumes it: the
-// SconeOcc head's x-embedding) instead of fp32 rows -- the same values split2h would make of them, without the 2 x 51 MB round trip.
+// PLANES: the result leaves as fp16 hi/lo planes Yh / Yl [M][ldy] instead of fp32 rows.  Nothing instantiates it any more (every
+// planes launch takes linear_smallk_rows_kernel below); the parameter stays so that the fp32 form keeps its symbol and its code.
 template <bool PLANES>
 __global__ __launch_bounds__(256) void linear_smallk_kernel(const float* __restrict__ X, long long ldx, const float* __restrict__ W,
                                                             long long ldw, const float* __restrict__ bias,
@@ -190,9 +190,10 @@ __global__ __launch_bounds__(256) void linear_smallk_kernel(const float* __restr
     }
 }
 
-// The planes form at many rows (the xyz / xyz+occupancy embeddings of a batch of clouds, the query embedding of the SconeOcc head:
-// 60k ... 100k rows x 128 outputs).  The kernel above re-reads 16 weights per thread through the vector memory path and calls libm's
-// branchy erff: 79 us for 61 440 x 128 outputs.  Here a thread keeps the weights and the bias of its 4 outputs in registers and walks
+// The planes form (the xyz / xyz+occupancy embeddings of a batch of clouds, the query embedding of the SconeOcc head: up to
+// 60k ... 100k rows x 128 outputs): the result leaves as fp16 hi/lo planes Yh / Yl [M][ldy], the operand format of the planes GEMM
+// that consumes it -- the same values split2h would make of fp32 rows, without the 2 x 51 MB round trip.  The kernel above re-reads
+// 16 weights per thread through the vector memory path and calls libm's branchy erff: 79 us for 61 440 x 128 outputs.  Here a thread keeps the weights and the bias of its 4 outputs in registers and walks
 // the rows of its block (up to LSK_ROWS per block -- fewer when that leaves the chip short of blocks; a row's result does not depend on
 // it --, 256 / (N / 4) at a time); the fmaf chain (ascending k from 0, then + bias) is the one above,
 // the GELU is l3_gelu -- the exact-erf GELU of every other epilogue of the planes path (|erf error| <= 1.5e-7).
@@ -238,18 +239,16 @@ void launch_linear_smallk_planes(hipStream_t s, const float* X, int64_t ldx, con
                                  int64_t ldy, int64_t M, int N, int K, int act, int Np) {
     if (M <= 0 || N <= 0) return;
     const int Nw = Np > N ? Np : N;                        // outputs written per row
-    static const bool rows_on = []() { const char* e = getenv("MCR_SMALLK_ROWS"); return !(e && e[0] == '0'); }();
-    if (rows_on && Nw % 4 == 0 && Nw / 4 <= 256 && 256 % (Nw / 4) == 0 && K <= 4) {   // (the GELU differs from the form below by <= 2e-7: every size takes this one)
-        const int rpp = 256 / (Nw / 4);
-        int rows = LSK_ROWS;
-        while (rows > rpp && cdiv(M, rows) < 1024) rows >>= 1;
-        rows = std::max(rows, rpp);
-        hipLaunchKernelGGL(linear_smallk_rows_kernel, dim3((unsigned)cdiv(M, rows)), dim3(256), 0, s, X, (long long)ldx, W, (long long)K, bias,
-                           (long long)ldy, (long long)M, Nw, K, act, (_Float16*)Yh, (_Float16*)Yl, N, rows);
+    if (!(Nw % 4 == 0 && Nw / 4 <= 256 && 256 % (Nw / 4) == 0 && K <= 4)) {   // (every caller writes 128 columns from K = 3 or 4)
+        refuse("linear_smallk_planes: needs K <= 4 and a written width whose quarter divides 256 (got K = %d, width %d)", K, Nw);
         return;
     }
-    hipLaunchKernelGGL(linear_smallk_kernel<true>, dim3((unsigned)cdiv(M * (Nw / 4), 256)), dim3(256), 0, s, X, (long long)ldx, W, (long long)K,
-                       bias, (const float*)nullptr, 0ll, (float*)nullptr, (long long)ldy, (long long)M, Nw, K, act, (_Float16*)Yh, (_Float16*)Yl, N);
+    const int rpp = 256 / (Nw / 4);
+    int rows = LSK_ROWS;
+    while (rows > rpp && cdiv(M, rows) < 1024) rows >>= 1;
+    rows = std::max(rows, rpp);
+    hipLaunchKernelGGL(linear_smallk_rows_kernel, dim3((unsigned)cdiv(M, rows)), dim3(256), 0, s, X, (long long)ldx, W, (long long)K, bias,
+                       (long long)ldy, (long long)M, Nw, K, act, (_Float16*)Yh, (_Float16*)Yl, N, rows);
 }
 
 void launch_linear(hipStream_t s, const float* X, int64_t ldx, const float* W, const float* bias, const float* R,
@@ -257,13 +256,12 @@ void launch_linear(hipStream_t s, const float* X, int64_t ldx, const float* W, c
                    int64_t rows_per_group, int64_t ldw, int64_t route_rows, const int* row_group) {
     if (M <= 0 || N <= 0) return;
     if (ldw == 0) ldw = K;
-    static const bool use_split = []() { const char* e = getenv("MCR_LINEAR3"); return !(e && e[0] == '0'); }();   // dev A/B knob
     // route_rows < 0: "one sequence of -route_rows rows, matrix path chosen on the layer's SHAPE alone" (the 2048-token encoders
     // on the split-precision variants: a batch of 30 sequences and a single one take the same kernel family, whose column-tile
     // width -- performance only -- follows M)
     const bool by_shape = route_rows < 0;
     if (by_shape) route_rows = -route_rows;
-    if (use_split && (by_shape ? linear3_shape_ok(X, ldx, W, ldw, N, K) : linear3_applicable(X, ldx, W, ldw, route_rows > 0 ? route_rows : M, N, K))) {
+    if (by_shape ? linear3_shape_ok(X, ldx, W, ldw, N, K) : linear3_applicable(X, ldx, W, ldw, route_rows > 0 ? route_rows : M, N, K)) {
         launch_linear3(s, X, ldx, W, bias, R, ldr, Y, ldy, M, N, K, act, row_bias, rows_per_group, ldw, row_group);
         return;
     }
@@ -577,7 +575,7 @@ __global__ __launch_bounds__(64 * KS) void attention_flash_kernel(const float* _
 
 // =====================================================================================================
 // attention, long sequences, on the fp32 matrix pipe (v_mfma_f32_16x16x4_f32 = exact fp32 fma chains; same math as
-// attention_flash_kernel, which stays as the VALU reference path, env MCR_ATTN_MFMA=0).
+// attention_flash_kernel, which stays for qkv rows that are not 16-byte aligned).
 //   block = 4 waves x 16 queries of one (sequence, head); keys/values stream through LDS in tiles of 64.
 //   Per 16-key sub-tile a wave computes S^T = K Q^T (A = K rows from LDS, B = Q^T held in registers, pre-scaled by
 //   1/sqrt(d)): lane (qi = l & 15, g = l >> 4) then owns S[qi][j0 + 4g + r], r = 0..3.  Online softmax per query over the
@@ -1007,12 +1005,11 @@ void launch_attention(hipStream_t s, const float* qkv, int64_t ldq, float* out, 
     }
     constexpr int KS = 4;
     dim3 grid((unsigned)cdiv(L, 64), (unsigned)H, (unsigned)S);
-    static const bool use_mfma = []() { const char* e = getenv("MCR_ATTN_MFMA"); return !(e && e[0] == '0'); }();   // dev A/B knob
     const bool al16 = aligned16(qkv) && ldq % 4 == 0 && (H * dq) % 4 == 0;
     // one or two long sequences leave half the chip idle (L = 2048, 4 heads: 128 blocks): split the keys over two blocks
     const bool split = split_ws && split_ws_floats >= attention_split_floats(S, L, H, DV) && L >= 512 &&
                        2 * S <= 65535 && (split_by_length || (int64_t)grid.x * H * S <= 256);
-    if (use_mfma && al16 && ((dq == 8 && dv == 32) || (dq == 16 && dv == 64))) {
+    if (al16 && ((dq == 8 && dv == 32) || (dq == 16 && dv == 64))) {
 #define MCR_ATT(DQ_, DV_, SPLIT_, GRID_, P1_, ML_)                                                                                    \
     do {                                                                                                                               \
         if (mask)                                                                                                                      \
@@ -1035,10 +1032,9 @@ void launch_attention(hipStream_t s, const float* qkv, int64_t ldq, float* out, 
                                out, (long long)ldo, L, H, lens, P1_, ML_);                                                             \
     } while (0)
         // a batch of sequences fills the chip with 128-query blocks (two 16-query groups per wave: half the staging and fragment
-        // reads per query; same bits): >= 2 blocks per CU; MCR_ATTN_QG2=0: always 64-query blocks (A/B)
-        static const bool qg2_on = []() { const char* e = getenv("MCR_ATTN_QG2"); return !(e && e[0] == '0'); }();
+        // reads per query; same bits): >= 2 blocks per CU; fewer, or a mask: 64-query blocks
         const dim3 grid2((unsigned)cdiv(L, 128), (unsigned)H, (unsigned)(split ? 2 * S : S));
-        const bool qg2 = qg2_on && !mask && (int64_t)grid2.x * grid2.y * grid2.z >= 512;
+        const bool qg2 = !mask && (int64_t)grid2.x * grid2.y * grid2.z >= 512;
         if (split) {
             float* part1 = split_ws;
             float* ml = split_ws + (size_t)S * L * DV;

@@ -9,7 +9,6 @@ all-gathers the occupancies; sampling and SconeVis (cheap, N <= 2048) run redund
 C candidate cameras are block-partitioned and the only other exchange is the all-gather of each rank's
 (best gain, global camera index).
 """
-import os
 
 import torch
 
@@ -38,7 +37,7 @@ def _harmonics_beside(scone_occ, pc, Xl, harmonics_of):
     fork = torch.cuda.Event()
     fork.record(main)                                   # the inputs are ready here; what is queued next need not be waited for
     begun = scone_occ.forward_begin(pc, Xl)
-    if begun is None or os.environ.get("MCR_NBV_SIDE") == "0":      # (A/B only: harmonics on the caller's stream after phase 1)
+    if begun is None:
         return begun, harmonics_of(Xl)
     side = _side_streams.get((dev.index, main.cuda_stream))
     if side is None:

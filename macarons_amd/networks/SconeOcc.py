@@ -403,7 +403,7 @@ class SconeOcc(RangeGuard, nn.Module):
         forward(..., begun=handle), which then runs the rest.  A caller that still has host work to do before it can call forward --
         view state, harmonics, down-sampled clouds (nbv_step) -- hides that work behind this first long kernel.  None (and nothing
         queued) when the split does not apply (gradients wanted, non-default architecture, layer-by-layer path)."""
-        if not self._is_default_arch() or not self.fused_local or A.needs_grad(self, pc, x) or os.environ.get("MCR_OCC_BEGIN") == "0":
+        if not self._is_default_arch() or not self.fused_local or A.needs_grad(self, pc, x):
             return None
         variant = ops.current_variant()
         pc0, x_ = pc.contiguous(), x.contiguous()

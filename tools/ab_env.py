@@ -1,5 +1,5 @@
 """A/B of one environment knob on ONE box (the boxes of the pool differ by more than most effects): alternates KNOB=0 / unset N times.
-    python tools/ab_env.py MCR_OCC_X_EARLY nbv        (legs: nbv = headline NBV step p50, batch = config 3, mac = config 5)"""
+    python tools/ab_env.py MCR_OCC_OVERLAP nbv        (legs: nbv = headline NBV step p50, batch = config 3, mac = config 5)"""
 import json, os, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 knob, leg = sys.argv[1], (sys.argv[2] if len(sys.argv) > 2 else "nbv")

@@ -1,6 +1,7 @@
 """Dev fuzz: the long-sequence attention on random batches (sequence count, length, head shape, a V tile outside the fp16 range now and
-then) == every sequence alone, bit for bit without the key split and within rounding with it; MCR_ATTN_QG2=0 must give the same bits."""
-import os, sys, subprocess
+then) == every sequence alone, bit for bit without the key split and within rounding with it (a sequence alone runs in 64-query blocks,
+a batch that fills the chip in 128-query blocks: the same bits)."""
+import os, sys
 import numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from macarons_amd import ops

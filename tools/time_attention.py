@@ -1,7 +1,10 @@
-"""Dev: long-sequence attention kernel timing, one block per (query tile, head) vs keys split over two blocks
-(MCR_ATTN_MFMA=0 selects the VALU reference kernel)."""
+"""Dev: long-sequence attention kernel timing, one block per (query tile, head) vs keys split over two blocks.  MCR_DEV_LIB=NAME times
+tools/_libs/libmacarons_hip_NAME.so (tools/build_variant.py) instead of the product library."""
 import sys, os, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from macarons_amd import _lib
+if os.environ.get("MCR_DEV_LIB"):
+    _lib.LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "_libs", f"libmacarons_hip_{os.environ['MCR_DEV_LIB']}.so")
 from macarons_amd import ops
 dev = torch.device("cuda:0")
 for (S, L, H, qk, v) in [(1, 2048, 4, 64, 256), (1, 2048, 4, 32, 128), (1, 1777, 4, 64, 256), (3, 333, 4, 32, 128)]:
@@ -15,5 +18,5 @@ for (S, L, H, qk, v) in [(1, 2048, 4, 64, 256), (1, 2048, 4, 32, 128), (1, 1777,
         e0.record()
         for _ in range(50): y = ops.attention_packed(qkv, H, qk, v, split=split)
         e1.record(); torch.cuda.synchronize()
-        print(f"[MCR_ATTN_MFMA={os.environ.get('MCR_ATTN_MFMA','1')} key-split scratch={split}] S={S} L={L} dq={qk//H} dv={v//H}: "
+        print(f"[{os.environ.get('MCR_DEV_LIB','main')} key-split scratch={split}] S={S} L={L} dq={qk//H} dv={v//H}: "
               f"{e0.elapsed_time(e1)/50*1e3:.1f} us  err {float((y.double()-ref).abs().max()):.1e}")

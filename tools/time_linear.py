@@ -1,4 +1,5 @@
-"""Per-shape timing of ops.linear (run on the GPU box)."""
+"""Per-shape timing of ops.linear (run on the GPU box).  MCR_DEV_LIB=NAME times tools/_libs/libmacarons_hip_NAME.so (tools/build_variant.py:
+a parent commit's library, or one with other -D switches) instead of the product library: run once per library on the same box."""
 import sys, time, os
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -24,4 +25,4 @@ for (M, N, K, gelu, res) in shapes:
     if res: ref = ref + r[:4096].double()
     y = ops.linear(x, w, b, gelu=bool(gelu), residual=r)[:4096].double()
     err = float((y - ref).abs().max() / ref.abs().max())
-    print(f"[MCR_LINEAR3={os.environ.get('MCR_LINEAR3','1')}] err {err:.1e} M={M:7d} N={N:4d} K={K:5d} gelu={gelu} res={res}: {dt*1e6:9.1f} us  {fl/dt/1e12:6.1f} TFLOP/s  {by/dt/1e9:7.0f} GB/s")
+    print(f"[{os.environ.get('MCR_DEV_LIB','main')}] err {err:.1e} M={M:7d} N={N:4d} K={K:5d} gelu={gelu} res={res}: {dt*1e6:9.1f} us  {fl/dt/1e12:6.1f} TFLOP/s  {by/dt/1e9:7.0f} GB/s")

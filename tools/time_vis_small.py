@@ -1,8 +1,11 @@
-"""SconeVis.forward / global PCTransformer at one cloud of 2048 tokens, with and without the small-problem GEMM (env MCR_LINEAR3S=0/1
-is read once per process: run twice)."""
-import os, sys, time
+"""SconeVis.forward / global PCTransformer at one cloud of 2048 tokens.  MCR_DEV_LIB=NAME times tools/_libs/libmacarons_hip_NAME.so
+(tools/build_variant.py) instead of the product library: run once per library on the same box."""
+import os, sys
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from macarons_amd import _lib
+if os.environ.get("MCR_DEV_LIB"):
+    _lib.LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "_libs", f"libmacarons_hip_{os.environ['MCR_DEV_LIB']}.so")
 from macarons_amd.networks import SconeVis, SconeOcc
 dev = torch.device("cuda:0")
 torch.manual_seed(0)
@@ -26,5 +29,5 @@ def bench(f, n=200, warm=20):
 
 
 with torch.no_grad():
-    print(f"MCR_LINEAR3S={os.environ.get('MCR_LINEAR3S', '1')}: SconeVis.forward 2048 tokens {bench(lambda: vis(pts, view_harmonics=vh)):.1f} us; "
+    print(f"[{os.environ.get('MCR_DEV_LIB', 'main')}] SconeVis.forward 2048 tokens {bench(lambda: vis(pts, view_harmonics=vh)):.1f} us; "
           f"global PCTransformer 2048 tokens {bench(lambda: occ.global_transformer(pc)):.1f} us")
