@@ -153,6 +153,39 @@ int mcr_attention_planes(const float* qkv, int64_t ldq, float* out, int64_t ldo,
 int mcr_colmax_broadcast(const float* X, int64_t ldx, float* Y, int64_t ldy, int64_t S, int64_t L, int E, void* stream);
 int mcr_pool_max_avg(const float* X, int64_t ldx, float* Y, int64_t ldy, int64_t S, int64_t L, int E, void* stream);
 
+/* ---- the planes GEMMs of variants 6 / 7 as blocks (linear3p.hip): BRING-UP / TEST entries -----------------------------------------
+ * The matrix path of the default numerics: both operands stored as fp16 planes, hi = fp16(x) (round to nearest even) and
+ * lo = fp16(x - hi), and multiplied as W_lo X_hi + W_hi X_lo + W_hi X_hi in fp32 (n_planes = 2), or the high planes alone
+ * (n_planes = 1, variant 7; Xl / Wl / Yl / Pl are then neither read nor written and may be NULL).  The networks call the same
+ * launchers directly; these entries add no kernel.  hi and lo are independent operands: nothing assumes that lo came from a split.
+ * mcr_split_to_planes: X [M, ldx] fp32 -> Ph, Pl [M, ldp] fp16, the first E columns of every row; Pl may be NULL.  Needs |x| < 65504
+ *   (beyond it, and for inf / NaN, hi is non-finite -- what the range guard looks for).
+ * mcr_linear_planes: y[m][n] = act(wscale_inv * sum_k W[n][k] X[m][k] + bias[n] + row_bias[g(m)][n]) (+ R[m][n], fp32 output only),
+ *   X planes [M, ldx], W planes [N, ldw] (the weights times a power of two whose inverse is wscale_inv), bias [N] or NULL, row_bias
+ *   [groups, N] or NULL with g(m) = row_group[m] (device int [M]) if row_group, else m / rows_per_group; act = the exact-erf GELU
+ *   (gelu != 0; erf by Abramowitz-Stegun 7.1.26) or identity.  Exactly one of Y (fp32 [M, ldy]) and Yh (with Yl: y split into planes
+ *   [M, ldy] again; n_planes = 1: Yh = fp16(y) alone) is given.  R may be Y (in place x += ...).  Which of the three tile forms runs
+ *   follows from the shape alone (M <= 4096, no row bias, K = 128 or a multiple of 256: one shot; else K <= 512: two stages; else
+ *   three); every form adds the same products in the same order, so the bits do not depend on it.
+ * mcr_linear_planes_dot: out[m] = act2(sum_n act(y[m][n]) v[n] + c[0]) for a 256-feature layer (N = 256; y as above without row
+ *   bias; c may be NULL), one launch for two layers; the 256 terms are added in one fixed order whatever M is.
+ * Leading dimensions and alignment (checked on the host: a call outside them returns 1 and launches nothing).  Leading dimensions of
+ *   planes are in halves, of fp32 operands in floats; every one must cover its row.
+ *   mcr_split_to_planes: E % 4 == 0; ldx % 4 == 0 and X 16-byte aligned (16-byte loads); ldp % 4 == 0 and Ph, Pl 8-byte aligned.
+ *   mcr_linear_planes, mcr_linear_planes_dot: K % 32 == 0; N % 4 == 0; ldx % 8 == 0, ldw % 8 == 0 and Xh, Xl, Wh, Wl 16-byte aligned
+ *     (rows reach LDS by 16-byte DMA); bias, row_bias and v 16-byte aligned (read four columns at a time; row_bias rows have stride N);
+ *     ldy % 4 == 0; Yh, Yl 8-byte aligned; Y, R, out, c 4-byte aligned, any ldr >= N.  Whole-row 16-byte stores are taken where N % 8
+ *     == 0, ldy % 8 == 0 and 16-byte aligned planes (fp32: ldr % 4 == 0 and 16-byte aligned Y, R, no row bias) allow them, else a lane
+ *     stores its own four columns; same values either way.  n_planes in {1, 2}; a residual needs fp32 output; row_bias needs
+ *     rows_per_group > 0 or row_group. */
+int mcr_split_to_planes(const float* X, int64_t ldx, void* Ph, void* Pl, int64_t ldp, int64_t M, int E, void* stream);
+int mcr_linear_planes(const void* Xh, const void* Xl, int64_t ldx, const void* Wh, const void* Wl, int64_t ldw, const float* bias, float* Y,
+                      void* Yh, void* Yl, int64_t ldy, int64_t M, int N, int K, int gelu, float wscale_inv, const float* row_bias,
+                      int64_t rows_per_group, const int* row_group, const float* R, int64_t ldr, int n_planes, void* stream);
+int mcr_linear_planes_dot(const void* Xh, const void* Xl, int64_t ldx, const void* Wh, const void* Wl, int64_t ldw, const float* bias,
+                          int64_t M, int K, int gelu, float wscale_inv, const float* v, const float* c, int gelu2, float* out,
+                          int n_planes, void* stream);
+
 /* ---- backward building blocks (scone_vis_bwd.hip): fp32, deterministic (no float atomics; fixed-order sums) ----------------------
  * mcr_attention_backward: gradient of mcr_attention's output (with lens as mcr_attention_planes: keys of sequence s = its first
  *   min(L, max(1, lens[s])) rows; lens may be NULL) with respect to the packed rows: d_qkv [S*L, ld_dqkv] <- [dq | dk | dv] given

@@ -27,7 +27,8 @@ namespace mcr {
 // GELU in the epilogues: l3_gelu (lp_split.h) -- the exact-erf GELU with erf by Abramowitz-Stegun 7.1.26 (|error| <= 1.5e-7, one rcp,
 // one exp2, seven fma: 14 instructions), the function the fused local transformer of this numerics variant already applies.  libm's
 // branchy erff was ~45 vector instructions per value with both branches executed: 43 of the 100 us of an encoder's FF1 at 30 x 2048
-// tokens were its epilogue.
+// tokens were its epilogue.  The fp32-out epilogues take l3_gelu_fma, the same function with its last line as one spelled-out fma:
+// contracted by the compiler, the transposed fp32 epilogue of the two-plane kernels was an ulp off every other form.
 constexpr int LP_BK = 32;                                 // k per chunk
 // output modes: fp32 rows, fp16 hi/lo planes (128 features x 256 rows per block), or LP_DOT: 256 features x 128 rows per block --
 // the block then owns ALL 256 outputs of its rows and the epilogue reduces them against a vector: out[m] = act2(act(y[m][:]) . v +
@@ -319,7 +320,7 @@ __global__ __launch_bounds__(SMALL ? 256 : 512, SMALL ? 2 : 1) void linear3p_ker
                               fmaf(acc[t][4 * g + 2], wscale_inv, b4.z), fmaf(acc[t][4 * g + 3], wscale_inv, b4.w)};
                 if (act == ACT_GELU) {
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) y[e] = l3_gelu(y[e]);
+                    for (int e = 0; e < 4; ++e) y[e] = l3_gelu_fma(y[e]);
                 }
                 const int u = 8 * wn + 2 * g + h;
                 *reinterpret_cast<float4*>(tb + row * 512 + ((u ^ (row & 31)) << 4)) = make_float4(y[0], y[1], y[2], y[3]);
@@ -363,7 +364,7 @@ __global__ __launch_bounds__(SMALL ? 256 : 512, SMALL ? 2 : 1) void linear3p_ker
                           fmaf(acc[t][4 * g + 2], wscale_inv, b4.z), fmaf(acc[t][4 * g + 3], wscale_inv, b4.w)};
             if (act == ACT_GELU) {
 #pragma unroll
-                for (int e = 0; e < 4; ++e) y[e] = l3_gelu(y[e]);
+                for (int e = 0; e < 4; ++e) y[e] = MODE == LP_F32 ? l3_gelu_fma(y[e]) : l3_gelu(y[e]);
             }
             if (PLANES_OUT && NP == 1) {
                 *reinterpret_cast<uint2*>(Yh + m * ldy + n) = make_uint2(pack2h(y[0], y[1]), pack2h(y[2], y[3]));
@@ -475,7 +476,7 @@ __global__ __launch_bounds__(256, 1) void linear3p_once_kernel(const _Float16* _
                       fmaf(acc[4 * g + 3], wscale_inv, b4.w)};
         if (act == ACT_GELU) {
 #pragma unroll
-            for (int e = 0; e < 4; ++e) y[e] = l3_gelu(y[e]);
+            for (int e = 0; e < 4; ++e) y[e] = MODE == LP_F32 ? l3_gelu_fma(y[e]) : l3_gelu(y[e]);
         }
         if (MODE == LP_PLANES && NP == 1) {
             *reinterpret_cast<uint2*>(Yh + m * ldy + n) = make_uint2(pack2h(y[0], y[1]), pack2h(y[2], y[3]));

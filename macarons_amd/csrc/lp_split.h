@@ -76,6 +76,21 @@ __device__ __forceinline__ float l3_gelu(float x) {           // exact-erf GELU,
     const float erfa = fmaf(-p * t, e, 1.0f);
     return 0.5f * x + 0.5f * fabsf(x) * erfa;
 }
+// The same with the last line as ONE spelled-out fma.  Left to -ffp-contract, the sum of two products above is contracted on either
+// product depending on the code around it: every planes epilogue takes fma(0.5 |x|, erfa, 0.5 x), but the transposed fp32 epilogue of
+// linear3p_kernel<LP_F32, *, 2> took fma(0.5, x, 0.5 |x| erfa) and came out an ulp off the direct and the one-shot form of the same
+// call.  The fp32-out epilogues (no network runs a GELU there) use this one; the others keep the text their bits were pinned with.
+__device__ __forceinline__ float l3_gelu_fma(float x) {
+    const float z = fabsf(x) * 0.70710678118654752440f;
+    const float t = __builtin_amdgcn_rcpf(fmaf(0.3275911f, z, 1.0f));
+    float p = fmaf(1.061405429f, t, -1.453152027f);
+    p = fmaf(p, t, 1.421413741f);
+    p = fmaf(p, t, -0.284496736f);
+    p = fmaf(p, t, 0.254829592f);
+    const float e = __builtin_amdgcn_exp2f(-1.4426950408889634f * z * z);
+    const float erfa = fmaf(-p * t, e, 1.0f);
+    return fmaf(0.5f * fabsf(x), erfa, 0.5f * x);
+}
 
 // ---- exact three-way split of 8 consecutive fp32 values into packed bf16x8 planes (variant 5) ----
 struct Split3 { uint4 hi, mid, lo; };

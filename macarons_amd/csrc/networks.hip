@@ -423,6 +423,63 @@ int mcr_nonfinite_flag(const float* x, int64_t n, int* flag, void* stream) {
     return 0;
 }
 
+// ---- the planes GEMMs of variants 6 / 7 (linear3p.hip) as blocks of their own: bring-up / test entries.  The networks call the
+// launchers directly; these forward to the same launchers after checking on the host what the kernels assume.
+static inline bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+static inline bool al8(const void* p) { return ((uintptr_t)p & 7) == 0; }
+
+int mcr_split_to_planes(const float* X, int64_t ldx, void* Ph, void* Pl, int64_t ldp, int64_t M, int E, void* stream) {
+    MCR_REQUIRE(X && Ph, "mcr_split_to_planes: null pointer");
+    MCR_REQUIRE(M > 0 && E > 0 && E % 4 == 0, "mcr_split_to_planes: need M > 0 and E a positive multiple of 4 (got %d)", E);
+    MCR_REQUIRE(ldx >= E && ldp >= E, "mcr_split_to_planes: leading dimension too small");
+    // one thread moves four values: a 16-byte load of X, an 8-byte store per plane
+    MCR_REQUIRE(ldx % 4 == 0 && al16(X), "mcr_split_to_planes: ldx must be a multiple of 4 and X 16-byte aligned");
+    MCR_REQUIRE(ldp % 4 == 0 && al8(Ph) && al8(Pl), "mcr_split_to_planes: ldp must be a multiple of 4 and the planes 8-byte aligned");
+    launch_split_to_planes((hipStream_t)stream, X, ldx, Ph, Pl, ldp, M, E);
+    MCR_LAUNCH_CHECK("mcr_split_to_planes");
+    return 0;
+}
+
+int mcr_linear_planes(const void* Xh, const void* Xl, int64_t ldx, const void* Wh, const void* Wl, int64_t ldw, const float* bias, float* Y,
+                      void* Yh, void* Yl, int64_t ldy, int64_t M, int N, int K, int gelu, float wscale_inv, const float* row_bias,
+                      int64_t rows_per_group, const int* row_group, const float* R, int64_t ldr, int n_planes, void* stream) {
+    MCR_REQUIRE(n_planes == 1 || n_planes == 2, "mcr_linear_planes: n_planes must be 1 or 2 (got %d)", n_planes);
+    MCR_REQUIRE(Xh && Wh && (n_planes == 1 || (Xl && Wl)), "mcr_linear_planes: null operand plane");
+    MCR_REQUIRE((Y != nullptr) != (Yh != nullptr), "mcr_linear_planes: exactly one of Y and Yh must be given");
+    MCR_REQUIRE(!Yh || n_planes == 1 || Yl, "mcr_linear_planes: null low output plane");
+    MCR_REQUIRE(M > 0 && N > 0 && K > 0, "mcr_linear_planes: empty problem");
+    MCR_REQUIRE(linear3p_applicable(N, K, ldx, ldw, ldy),
+                "mcr_linear_planes: need K a multiple of 32, N a multiple of 4, ldx and ldw multiples of 8, ldy a multiple of 4");
+    MCR_REQUIRE(ldx >= K && ldw >= K && ldy >= N && (!R || ldr >= N), "mcr_linear_planes: leading dimension too small");
+    // the operand planes are the sources of 16-byte DMA; bias rows are read by 16-byte loads at columns that are multiples of 4
+    MCR_REQUIRE(al16(Xh) && al16(Wh) && (n_planes == 1 || (al16(Xl) && al16(Wl))), "mcr_linear_planes: operand planes must be 16-byte aligned");
+    MCR_REQUIRE(al16(bias) && al16(row_bias), "mcr_linear_planes: bias and row_bias must be 16-byte aligned");
+    MCR_REQUIRE(!Yh || (al8(Yh) && (n_planes == 1 || al8(Yl))), "mcr_linear_planes: output planes must be 8-byte aligned");
+    MCR_REQUIRE(((uintptr_t)Y | (uintptr_t)R) % 4 == 0, "mcr_linear_planes: Y and R must be 4-byte aligned");
+    MCR_REQUIRE(!R || Y, "mcr_linear_planes: a residual needs fp32 output");
+    MCR_REQUIRE(!row_bias || rows_per_group > 0 || row_group, "mcr_linear_planes: row_bias needs rows_per_group > 0 or row_group");
+    launch_linear3p((hipStream_t)stream, Xh, Xl, ldx, Wh, Wl, ldw, bias, Y, Yh, Yl, ldy, M, N, K, gelu ? ACT_GELU : ACT_NONE, wscale_inv, row_bias,
+                    rows_per_group, row_group, R, ldr, n_planes);
+    MCR_LAUNCH_CHECK("mcr_linear_planes");
+    return 0;
+}
+
+int mcr_linear_planes_dot(const void* Xh, const void* Xl, int64_t ldx, const void* Wh, const void* Wl, int64_t ldw, const float* bias, int64_t M,
+                          int K, int gelu, float wscale_inv, const float* v, const float* c, int gelu2, float* out, int n_planes, void* stream) {
+    MCR_REQUIRE(n_planes == 1 || n_planes == 2, "mcr_linear_planes_dot: n_planes must be 1 or 2 (got %d)", n_planes);
+    MCR_REQUIRE(Xh && Wh && (n_planes == 1 || (Xl && Wl)) && v && out, "mcr_linear_planes_dot: null pointer");
+    MCR_REQUIRE(M > 0 && K > 0, "mcr_linear_planes_dot: empty problem");
+    MCR_REQUIRE(linear3p_applicable(256, K, ldx, ldw, 4), "mcr_linear_planes_dot: need K a multiple of 32, ldx and ldw multiples of 8");
+    MCR_REQUIRE(ldx >= K && ldw >= K, "mcr_linear_planes_dot: leading dimension too small");
+    MCR_REQUIRE(al16(Xh) && al16(Wh) && (n_planes == 1 || (al16(Xl) && al16(Wl))), "mcr_linear_planes_dot: operand planes must be 16-byte aligned");
+    MCR_REQUIRE(al16(bias) && al16(v), "mcr_linear_planes_dot: bias and v must be 16-byte aligned");
+    MCR_REQUIRE(((uintptr_t)out | (uintptr_t)c) % 4 == 0, "mcr_linear_planes_dot: out and c must be 4-byte aligned");
+    launch_linear3p_dot((hipStream_t)stream, Xh, Xl, ldx, Wh, Wl, ldw, bias, M, K, gelu ? ACT_GELU : ACT_NONE, wscale_inv, v, c,
+                        gelu2 ? ACT_GELU : ACT_NONE, out, n_planes);
+    MCR_LAUNCH_CHECK("mcr_linear_planes_dot");
+    return 0;
+}
+
 int mcr_get_local_pct_variant(void);
 int mcr_local_pct_blob_floats(void) { return local_pct_blob_floats(); }
 int mcr_local_pct3_blob_floats(void) { return local_pct3_blob_floats(); }

@@ -11,6 +11,10 @@ compared as int32: check_guard() names every element outside the window whose bi
 padding columns cols .. ld-1 of every row, the GUARD floats behind the last row).  The guard is inside the same allocation on
 purpose: an overrun of a few rows lands in our own memory and is reported, it does not leave the allocation.  check_unchanged()
 compares the whole buffer with its state at creation: inputs, and outputs of calls that were refused.
+
+HalfArena is the same layout for fp16 operands (the hi / lo planes of the planes GEMMs), every quantity counted in halves.  Its fill
+is a half-precision NaN with a fixed payload in EVERY half (FILL_BITS seen as two halves is a NaN and -1.73): a guard half that
+reaches an accumulator poisons the output.
 """
 import numpy as np
 import torch
@@ -18,35 +22,43 @@ import torch
 FILL_BITS = 0x7FC0BEEF           # quiet NaN, payload 0xBEEF
 GUARD = 4096                     # floats behind the last row
 LEAD = 64                        # floats (256 bytes) before the operand
+HALF_FILL_BITS = 0x7EEF          # fp16 quiet NaN, payload 0xEF
+HALF_GUARD = 2 * GUARD           # halves behind the last row (the same bytes)
+HALF_LEAD = 2 * LEAD             # halves (256 bytes) before the operand
 
 
 class Arena:
-    def __init__(self, rows, cols, ld=None, offset=0, data=None, device="cpu", guard=GUARD):
+    # element type of the operand, the integer type its bits are compared as, and the layout constants in elements
+    T_VAL, T_BITS, NP_VAL, NP_BITS, ITEM = torch.float32, torch.int32, np.float32, np.int32, 4
+    FILL, LEAD_N, GUARD_N = FILL_BITS, LEAD, GUARD
+
+    def __init__(self, rows, cols, ld=None, offset=0, data=None, device="cpu", guard=None):
         ld = cols if ld is None else ld
-        assert rows > 0 and cols > 0 and ld >= cols and 0 <= offset < LEAD and guard >= GUARD
+        guard = self.GUARD_N if guard is None else guard
+        assert rows > 0 and cols > 0 and ld >= cols and 0 <= offset < self.LEAD_N and guard >= self.GUARD_N
         self.rows, self.cols, self.ld, self.offset, self.guard = rows, cols, ld, offset, guard
-        self.start = LEAD + offset
+        self.start = self.LEAD_N + offset
         self.n = self.start + rows * ld + guard
-        self.bits = torch.full((self.n,), FILL_BITS, dtype=torch.int32, device=device)
+        self.bits = torch.full((self.n,), self.FILL, dtype=self.T_BITS, device=device)
         assert not self.bits.is_cuda or self.bits.data_ptr() % 256 == 0
-        self.floats = self.bits.view(torch.float32)
+        self.floats = self.bits.view(self.T_VAL)
         if data is not None:
-            d = torch.as_tensor(np.ascontiguousarray(data, dtype=np.float32) if isinstance(data, np.ndarray) else data)
-            assert tuple(d.shape) == (rows, cols) and d.dtype == torch.float32, (d.shape, d.dtype)
+            d = torch.as_tensor(np.ascontiguousarray(data, dtype=self.NP_VAL) if isinstance(data, np.ndarray) else data)
+            assert tuple(d.shape) == (rows, cols) and d.dtype == self.T_VAL, (d.shape, d.dtype)
             self.window().copy_(d)
         self.initial = self.bits.clone()
 
     @property
     def ptr(self):
         """Device address of element (0, 0) of the operand."""
-        return self.bits.data_ptr() + 4 * self.start
+        return self.bits.data_ptr() + self.ITEM * self.start
 
     def window(self):
         """The logical [rows, cols] matrix as a strided view of the arena."""
         return self.floats.as_strided((self.rows, self.cols), (self.ld, 1), self.start)
 
     def packed(self):
-        """A packed host copy of the logical matrix (fp32 numpy)."""
+        """A packed host copy of the logical matrix (numpy, the arena's element type)."""
         return self.window().cpu().contiguous().numpy()
 
     def outside_mask(self):
@@ -65,7 +77,7 @@ class Arena:
 
     def guard_violations(self):
         bits = self.bits.cpu().numpy()
-        bad = np.flatnonzero(self.outside_mask() & (bits != np.int32(FILL_BITS)))
+        bad = np.flatnonzero(self.outside_mask() & (bits != self.NP_BITS(self.FILL)))
         return [(int(i), self.region(int(i))) for i in bad]
 
     def check_guard(self, what=""):
@@ -75,6 +87,16 @@ class Arena:
     def check_unchanged(self, what=""):
         diff = torch.nonzero(self.bits != self.initial).flatten().cpu().numpy()
         assert diff.size == 0, f"{what}: {diff.size} element(s) changed, first at {[(int(i), self.region(int(i))) for i in diff[:8]]}"
+
+
+class HalfArena(Arena):
+    """An arena of fp16 values: rows, cols, ld, offset and the guard are counted in halves (offset 0..7 moves the operand off the
+    16-byte grid); `floats` holds halves, packed() returns float16, packed_bits() the same as uint16."""
+    T_VAL, T_BITS, NP_VAL, NP_BITS, ITEM = torch.float16, torch.int16, np.float16, np.int16, 2
+    FILL, LEAD_N, GUARD_N = HALF_FILL_BITS, HALF_LEAD, HALF_GUARD
+
+    def packed_bits(self):
+        return self.packed().view(np.uint16)
 
 
 class Workspace(Arena):
