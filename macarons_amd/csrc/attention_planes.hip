@@ -412,27 +412,27 @@ bool attention_planes_applicable(int H, int DQK, int DV, int64_t ldp) {
 
 // See nn_kernels.h.  split_ws: attention_split_floats(S, L, H, DV) floats, used when the keys of a sequence are split over two blocks
 // (out then receives fp32 parts and the combine pass writes the planes Oh / Ol, or fp32 rows of `out` when Oh is null).
-void launch_attention_planes(hipStream_t s, const void* Ph_, const void* Pl_, int64_t ldp, float* out, int64_t ldo, void* Oh_, void* Ol_,
-                             int64_t ldoh, int64_t S, int L, int H, int DQK, int DV, const int* lens, float* split_ws, size_t split_ws_floats,
-                             int split_mode, int n_planes) {
+void launch_attention_planes(hipStream_t s, Planes P, RowsOut out_, Planes O, int64_t S, int L, int H, int DQK, int DV, const int* lens,
+                             AttnSplit sp, int n_planes) {
     if (S <= 0 || L <= 0) return;
     const int dq = DQK / H, dv = DV / H;
+    const int64_t ldp = P.ld, ldo = out_.ld, ldoh = O.ld;
+    float* out = out_.p;
     if ((int64_t)L * ldp >= ((int64_t)1 << 31)) { refuse("launch_attention_planes: sequence too long for 32-bit row offsets"); return; }
-    if (!attention_planes_applicable(H, DQK, DV, ldp) || (reinterpret_cast<uintptr_t>(Ph_) & 15) || (n_planes != 1 && (reinterpret_cast<uintptr_t>(Pl_) & 15))) {
+    if (!attention_planes_applicable(H, DQK, DV, ldp) || (reinterpret_cast<uintptr_t>(P.h) & 15) || (n_planes != 1 && (reinterpret_cast<uintptr_t>(P.l) & 15))) {
         refuse("launch_attention_planes: unsupported head dims / alignment (dq=%d dv=%d ldp=%lld)", dq, dv, (long long)ldp);
         return;
     }
-    const _Float16 *Ph = (const _Float16*)Ph_, *Pl = (const _Float16*)Pl_;
-    _Float16 *Oh = (_Float16*)Oh_, *Ol = (_Float16*)Ol_;
-    // split_mode: 1 = always (when L >= 512 and the scratch is there), 0 = never, -1 = when the unsplit grid leaves CUs idle
+    const _Float16 *Ph = P.h, *Pl = P.l;
+    _Float16 *Oh = O.h, *Ol = O.l;
     const int64_t blocks64 = (int64_t)cdiv(L, 64) * H * S;
-    const bool can_split = n_planes != 1 && split_ws && split_ws_floats >= attention_split_floats(S, L, H, DV) && L >= 512 && 2 * S <= 65535;   // (single-plane form: never split)
-    const bool split = can_split && (split_mode == 1 || (split_mode < 0 && blocks64 <= 256));
+    const bool can_split = n_planes != 1 && sp.ws && sp.floats >= attention_split_floats(S, L, H, DV) && L >= 512 && 2 * S <= 65535;   // (single-plane form: never split)
+    const bool split = can_split && (sp.mode == 1 || (sp.mode < 0 && blocks64 <= 256));
     const unsigned gz = (unsigned)(split ? 2 * S : S);
     const bool qg2 = (int64_t)cdiv(L, 128) * H * gz >= 512;
     const dim3 grid((unsigned)cdiv(L, qg2 ? 128 : 64), (unsigned)H, gz);
-    float* part1 = split ? split_ws : nullptr;
-    float* ml = split ? split_ws + (size_t)S * L * DV : nullptr;
+    float* part1 = split ? sp.ws : nullptr;
+    float* ml = split ? sp.ws + (size_t)S * L * DV : nullptr;
 #define MCR_AP(DQ_, DV_, SPLIT_, QG_)                                                                                                  \
     hipLaunchKernelGGL((attention_planes_kernel<DQ_, DV_, SPLIT_, QG_>), grid, dim3(256), 0, s, Ph, Pl, (long long)ldp, out,            \
                        SPLIT_ ? (_Float16*)nullptr : Oh, SPLIT_ ? (_Float16*)nullptr : Ol, (long long)(SPLIT_ || !Oh ? ldo : ldoh), L, H, \
@@ -452,7 +452,7 @@ void launch_attention_planes(hipStream_t s, const void* Ph_, const void* Pl_, in
         else { if (qg2) MCR_AP(8, 32, false, 2); else MCR_AP(8, 32, false, 1); }
     }
 #undef MCR_AP
-    if (split) launch_attention_combine(s, out, ldo, part1, ml, S * L, H, dv, Oh_, Ol_, ldoh);
+    if (split) launch_attention_combine(s, out_, part1, ml, S * L, H, dv, O);
 }
 
 }  // namespace mcr

@@ -153,11 +153,9 @@ bool linear3_applicable(const float* X, int64_t ldx, const float* W, int64_t ldw
 }
 
 constexpr int64_t L3_XCD_MIN_ROW_BLOCKS = 64;             // row blocks from which a launch takes the XCD-aware block order
-void launch_linear3(hipStream_t s, const float* X, int64_t ldx, const float* W, const float* bias, const float* R, int64_t ldr,
-                    float* Y, int64_t ldy, int64_t M, int N, int K, int act, const float* row_bias, int64_t rows_per_group,
-                    int64_t ldw, const int* row_group) {
+void launch_linear3(hipStream_t s, Rows X, Rows W, const Epilogue& e, RowsOut Y, int64_t M, int N, int K) {
     const int64_t mb = cdiv(M, L3G_BM);
-    const long long rpg = rows_per_group > 0 ? rows_per_group : 1;
+    const long long rpg = e.row_bias.rows_per_group > 0 ? e.row_bias.rows_per_group : 1;
     // widest column tile that still gives the chip ~2 blocks per CU (performance only: see the note on L3G_NT above); the short-K
     // GEMMs of the encoders (K = 256 / 512: eight or sixteen chunks between an exposed first load and the epilogue) run better on
     // 64-column blocks, four per CU, than on 128-column ones, three per CU (SconeVis on 30 x 2048 tokens: 3.80 vs 4.11 ms); the
@@ -167,9 +165,9 @@ void launch_linear3(hipStream_t s, const float* X, int64_t ldx, const float* W, 
     // XCD-aware block order for the batch-sized launches (SconeVis on 30 x 2048 tokens: 3.77 -> 3.53 ms)
     const int xo = mb >= L3_XCD_MIN_ROW_BLOCKS;
 #define MCR_L3(NT)                                                                                                              \
-    hipLaunchKernelGGL((linear3_kernel<NT>), dim3((unsigned)((xo ? cdiv(mb, 8) * 8 : mb) * cdiv(N, NT * 32))), dim3(256), 0, s, X, \
-                       (long long)ldx, W, (long long)ldw, bias, row_bias, rpg, R, (long long)ldr, Y, (long long)ldy,            \
-                       (long long)M, N, K, act, row_group, xo)
+    hipLaunchKernelGGL((linear3_kernel<NT>), dim3((unsigned)((xo ? cdiv(mb, 8) * 8 : mb) * cdiv(N, NT * 32))), dim3(256), 0, s, X.p, \
+                       (long long)X.ld, W.p, (long long)W.ld, e.bias, e.row_bias.p, rpg, e.residual.p, (long long)e.residual.ld, Y.p,  \
+                       (long long)Y.ld, (long long)M, N, K, e.act, e.row_bias.row_group, xo)
     if (nt == 4) MCR_L3(4);
     else if (nt == 2) MCR_L3(2);
     else MCR_L3(1);

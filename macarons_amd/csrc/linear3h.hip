@@ -15,7 +15,7 @@
 namespace mcr {
 
 constexpr int LH_BM = 128, LH_BK = 32, LH_NT = 4, LH_BN = 32 * LH_NT;
-constexpr float LH_WSCALE = 256.0f, LH_WSCALE_INV = 1.0f / 256.0f;
+constexpr float LH_WSCALE = 256.0f;             // (its inverse travels with the planes: WSPLIT_INV)
 
 __device__ __forceinline__ int lh_chunk(int row, int c) { return row * 4 + (c ^ ((row >> 2) & 3)); }
 
@@ -156,21 +156,14 @@ void launch_split_weights(hipStream_t s, const float* W, int64_t ldw, void* plan
                        reinterpret_cast<uint4*>(planes), N, K8);
 }
 
-// planes: scratch of linear3h_planes_bytes(N, K) bytes (16-byte aligned) that receives the split weights -- or, with
-// presplit_inv_scale > 0, planes the HOST already built (networks/packing.py: pack_head_planes, cached per parameter version;
-// fp16 hi/lo of W * 2^e with e chosen per matrix like the local-transformer blobs): no split launch, the epilogue multiplies by
-// presplit_inv_scale = 2^-e.
-void launch_linear3h(hipStream_t s, const float* X, int64_t ldx, const float* W, int64_t ldw, void* planes, const float* bias,
-                     const float* R, int64_t ldr, float* Y, int64_t ldy, int64_t M, int N, int K, int act, const float* row_bias,
-                     int64_t rows_per_group, float presplit_inv_scale, const int* row_group) {
-    const int K8 = K / 8;
-    uint4* Wp = reinterpret_cast<uint4*>(planes);
-    if (!(presplit_inv_scale > 0.f))
-        hipLaunchKernelGGL(split_weights_kernel, dim3((unsigned)cdiv((int64_t)N * K8, 256)), dim3(256), 0, s, W, (long long)ldw, Wp, N, K8);
+// W: dense planes [2][N][K] (16-byte aligned) -- launch_split_weights' (2^8 scale) or the ones the HOST built (networks/packing.py:
+// pack_head_planes, cached per parameter version; fp16 hi/lo of W * 2^e with e chosen per matrix like the local-transformer blobs);
+// the epilogue multiplies by W.inv_scale = 2^-e.
+void launch_linear3h(hipStream_t s, Rows X, WPlanes W, const Epilogue& e, RowsOut Y, int64_t M, int N, int K) {
     dim3 grid((unsigned)cdiv(M, LH_BM), (unsigned)cdiv(N, LH_BN));
-    hipLaunchKernelGGL(linear3h_kernel, grid, dim3(256), 0, s, X, (long long)ldx, Wp, bias, row_bias,
-                       (long long)(rows_per_group > 0 ? rows_per_group : 1), R, (long long)ldr, Y, (long long)ldy, (long long)M, N,
-                       K, act, presplit_inv_scale > 0.f ? presplit_inv_scale : LH_WSCALE_INV, row_group);
+    hipLaunchKernelGGL(linear3h_kernel, grid, dim3(256), 0, s, X.p, (long long)X.ld, reinterpret_cast<const uint4*>(W.h), e.bias, e.row_bias.p,
+                       (long long)(e.row_bias.rows_per_group > 0 ? e.row_bias.rows_per_group : 1), e.residual.p, (long long)e.residual.ld, Y.p,
+                       (long long)Y.ld, (long long)M, N, K, e.act, W.inv_scale, e.row_bias.row_group);
 }
 
 }  // namespace mcr

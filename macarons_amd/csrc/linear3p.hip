@@ -513,15 +513,19 @@ bool linear3p_applicable(int N, int K, int64_t ldx, int64_t ldw, int64_t ldy) {
     return K % LP_BK == 0 && K >= LP_BK && N % 4 == 0 && ldx % 8 == 0 && ldw % 8 == 0 && ldy % 4 == 0;
 }
 
+// exactly one of Yr.p (fp32 rows, ld in floats) and Yp.h (planes, ld in halves) is set
 template <int NP>
-static void launch_linear3p_np(hipStream_t s, const void* Xh, const void* Xl, int64_t ldx, const void* Wh, const void* Wl, int64_t ldw,
-                               const float* bias, float* Y, void* Yh, void* Yl, int64_t ldy, int64_t M, int N, int K, int act, float wscale_inv,
-                               const float* row_bias, int64_t rows_per_group, const int* row_group, const float* R, int64_t ldr) {
-    const long long rpg = rows_per_group > 0 ? rows_per_group : 1;
+static void launch_linear3p_np(hipStream_t s, Planes X, WPlanes W, const Epilogue& e, RowsOut Yr, Planes Yp, int64_t M, int N, int K) {
+    const long long rpg = e.row_bias.rows_per_group > 0 ? e.row_bias.rows_per_group : 1;
     // three forms, the same bits: a few thousand rows take the one-shot form, short K the two-blocks-per-CU form, the rest the large tile
-    const _Float16 *xh = (const _Float16*)Xh, *xl = (const _Float16*)Xl, *wh = (const _Float16*)Wh, *wl = (const _Float16*)Wl;
-    _Float16 *yh = (_Float16*)Yh, *yl = (_Float16*)Yl;
-    const float* nf = nullptr;
+    const _Float16 *xh = X.h, *xl = X.l, *wh = W.h, *wl = W.l;
+    _Float16 *Yh = Yp.h, *yh = Yp.h, *yl = Yp.l;
+    float* Y = Yr.p;
+    const int64_t ldx = X.ld, ldw = W.ld, ldy = Yh ? Yp.ld : Yr.ld, ldr = e.residual.ld;
+    const float *bias = e.bias, *row_bias = e.row_bias.p, *R = e.residual.p, *nf = nullptr;
+    const int* row_group = e.row_bias.row_group;
+    const int act = e.act;
+    const float wscale_inv = W.inv_scale;
     if (M <= 4096 && !row_bias && (K == 128 || K % LPO_KS == 0)) {
         if (!(Yh ? lpo_reserve<LP_PLANES, NP>() : lpo_reserve<LP_F32, NP>())) { refuse("launch_linear3p: cannot reserve %d bytes of LDS", LPO_LDS_BYTES); return; }
         dim3 g((unsigned)(cdiv(M, LPO_T) * cdiv(N, LPO_T)));
@@ -556,42 +560,43 @@ static void launch_linear3p_np(hipStream_t s, const void* Xh, const void* Xl, in
                            nf, 0, R, (long long)ldr);
 }
 
-// Y (fp32, ldy floats) or Yh / Yl (fp16 planes, ldy halves) = act(X W^T * wscale_inv + bias (+ row bias)); exactly one of Y, Yh is set.
-// n_planes = 1: the high planes alone (variant 7): Xl / Wl / Yl are ignored
-void launch_linear3p(hipStream_t s, const void* Xh, const void* Xl, int64_t ldx, const void* Wh, const void* Wl, int64_t ldw,
-                     const float* bias, float* Y, void* Yh, void* Yl, int64_t ldy, int64_t M, int N, int K, int act, float wscale_inv,
-                     const float* row_bias, int64_t rows_per_group, const int* row_group, const float* R, int64_t ldr, int n_planes) {
+// Y (fp32 rows, or fp16 planes) = act(X W^T * W.inv_scale + bias (+ row bias)) (+ residual: fp32 rows only)
+// n_planes = 1: the high planes alone (variant 7): X.l / W.l / Y.l are ignored
+static void linear3p(hipStream_t s, Planes X, WPlanes W, const Epilogue& e, RowsOut Yr, Planes Yp, int64_t M, int N, int K, int n_planes) {
     if (M <= 0 || N <= 0) return;
-    if (n_planes == 1)
-        launch_linear3p_np<1>(s, Xh, Xl, ldx, Wh, Wl, ldw, bias, Y, Yh, Yl, ldy, M, N, K, act, wscale_inv, row_bias, rows_per_group, row_group, R, ldr);
-    else
-        launch_linear3p_np<2>(s, Xh, Xl, ldx, Wh, Wl, ldw, bias, Y, Yh, Yl, ldy, M, N, K, act, wscale_inv, row_bias, rows_per_group, row_group, R, ldr);
+    if (n_planes == 1) launch_linear3p_np<1>(s, X, W, e, Yr, Yp, M, N, K);
+    else launch_linear3p_np<2>(s, X, W, e, Yr, Yp, M, N, K);
+}
+void launch_linear3p(hipStream_t s, Planes X, WPlanes W, const Epilogue& e, RowsOut Y, int64_t M, int N, int K, int n_planes) {
+    linear3p(s, X, W, e, Y, Planes{}, M, N, K, n_planes);
+}
+void launch_linear3p(hipStream_t s, Planes X, WPlanes W, const Epilogue& e, Planes Y, int64_t M, int N, int K, int n_planes) {
+    linear3p(s, X, W, e, RowsOut{}, Y, M, N, K, n_planes);
 }
 
 // out[m] = act2( act(X W^T * wscale_inv + bias)[m][:] . v + c ) for a 256-feature layer (N == 256): two layers, one launch
 // (K a multiple of LP_BK, ldx and ldw multiples of 8: the SconeOcc head's 512 -> 256 -> 1 tail is the caller)
 template <int NP>
-static void launch_linear3p_dot_np(hipStream_t s, const void* Xh, const void* Xl, int64_t ldx, const void* Wh, const void* Wl, int64_t ldw,
-                                   const float* bias, int64_t M, int K, int act, float wscale_inv, const float* v, const float* c, int act2, float* out) {
+static void launch_linear3p_dot_np(hipStream_t s, Planes X, WPlanes W, const Epilogue& e, int64_t M, int K, const float* v, const float* c, int act2,
+                                   float* out) {
     if (!lp_reserve<LP_DOT, false, NP>()) { refuse("launch_linear3p_dot: cannot reserve %d bytes of LDS", LP_LDS_BYTES); return; }
     dim3 grid((unsigned)(cdiv(cdiv(M, 128), 8) * 8));
-    hipLaunchKernelGGL((linear3p_kernel<LP_DOT, false, NP>), grid, dim3(512), LP_LDS_BYTES, s, (const _Float16*)Xh, (const _Float16*)Xl, (long long)ldx,
-                       (const _Float16*)Wh, (const _Float16*)Wl, (long long)ldw, bias, (const float*)nullptr, 1ll, (const int*)nullptr, out,
-                       (_Float16*)nullptr, (_Float16*)nullptr, 1ll, (long long)M, 256, K, act, wscale_inv, v, c, act2, (const float*)nullptr, 0ll);
+    hipLaunchKernelGGL((linear3p_kernel<LP_DOT, false, NP>), grid, dim3(512), LP_LDS_BYTES, s, (const _Float16*)X.h, (const _Float16*)X.l, (long long)X.ld,
+                       W.h, W.l, (long long)W.ld, e.bias, (const float*)nullptr, 1ll, (const int*)nullptr, out,
+                       (_Float16*)nullptr, (_Float16*)nullptr, 1ll, (long long)M, 256, K, e.act, W.inv_scale, v, c, act2, (const float*)nullptr, 0ll);
 }
-void launch_linear3p_dot(hipStream_t s, const void* Xh, const void* Xl, int64_t ldx, const void* Wh, const void* Wl, int64_t ldw,
-                         const float* bias, int64_t M, int K, int act, float wscale_inv, const float* v, const float* c, int act2, float* out,
-                         int n_planes) {
+void launch_linear3p_dot(hipStream_t s, Planes X, WPlanes W, const Epilogue& e, int64_t M, int K, const float* v, const float* c, int act2,
+                         float* out, int n_planes) {
     if (M <= 0) return;
-    if (n_planes == 1) launch_linear3p_dot_np<1>(s, Xh, Xl, ldx, Wh, Wl, ldw, bias, M, K, act, wscale_inv, v, c, act2, out);
-    else launch_linear3p_dot_np<2>(s, Xh, Xl, ldx, Wh, Wl, ldw, bias, M, K, act, wscale_inv, v, c, act2, out);
+    if (n_planes == 1) launch_linear3p_dot_np<1>(s, X, W, e, M, K, v, c, act2, out);
+    else launch_linear3p_dot_np<2>(s, X, W, e, M, K, v, c, act2, out);
 }
 
-void launch_split_to_planes(hipStream_t s, const float* X, int64_t ldx, void* Ph, void* Pl, int64_t ldp, int64_t M, int E) {
+void launch_split_to_planes(hipStream_t s, Rows X, Planes P, int64_t M, int E) {
     if (M <= 0 || E <= 0) return;
     const int E4 = E / 4;
-    hipLaunchKernelGGL(split_to_planes_kernel, dim3((unsigned)cdiv(M * E4, 256)), dim3(256), 0, s, X, (long long)ldx, (_Float16*)Ph,
-                       (_Float16*)Pl, (long long)ldp, (long long)M, E4);
+    hipLaunchKernelGGL(split_to_planes_kernel, dim3((unsigned)cdiv(M * E4, 256)), dim3(256), 0, s, X.p, (long long)X.ld, P.h, P.l, (long long)P.ld,
+                       (long long)M, E4);
 }
 
 }  // namespace mcr

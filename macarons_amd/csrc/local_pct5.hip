@@ -471,6 +471,6 @@ void launch_local_pct5(hipStream_t s, const float* offs, float* feat, int64_t ld
                        (long long)S, blob);
 }
 
-int local_pct3_blob_floats() { return L3_BLOB_FLOATS; }
+int local_pct5_blob_floats() { return L3_BLOB_FLOATS; }
 
 }  // namespace mcr

@@ -81,55 +81,66 @@ static inline bool attn_pv_half() { return fp16_planes_variant(); }
 // (the embeddings' second layer, the final LayerNorm and the fc / lin0 layers behind it) are on the same path under the same condition.
 static inline bool enc_planes(int L, int E) { return fp16_planes_variant() && L >= 512 && E % 32 == 0; }
 
-// The planes live in the encoder's own scratch (an fp32 row = two fp16 rows): h <- planes of LayerNorm(x) / fp32 attention output,
-// ff <- planes of the attention output, then of the FF's hidden layer; the weights' planes (split per call, 2^8 scale: linear3h.hip)
-// go to whichever of ff / qkv is idle.  L >= 512 makes every region large enough for them.
+// The weight planes of one layer: the host-built ones (`given`, scale 1 / given_inv; one split per parameter version instead of per call)
+// when the table has them, else planes split here into `scratch` with the fixed 2^8 scale (|w| < 255).  Np, Kp (optional): the layer
+// zero-padded to [2][Np][Kp]; its padded bias then goes behind the planes and replaces *bias_p -- on entry the host-built one.
+static WPlanes weight_planes(hipStream_t s, const void* given, float given_inv, const LinW& lin, int64_t ldw, int N, int K, void* scratch,
+                             int Np = 0, int Kp = 0, const float** bias_p = nullptr) {
+    const bool pad = Np > 0;
+    if (!pad) { Np = N; Kp = K; }
+    if (!given) {
+        if (pad) {
+            float* bp = reinterpret_cast<float*>(scratch) + (size_t)Np * Kp;               // behind the [2][Np][Kp] halves
+            launch_pad_weights(s, lin.w, ldw, lin.b, scratch, bp, N, K, Np, Kp);
+            *bias_p = bp;
+        } else
+            launch_split_weights(s, lin.w, ldw, scratch, N, K);
+        given = scratch;
+        given_inv = WSPLIT_INV;
+    }
+    const _Float16* h = (const _Float16*)given;
+    return {h, h + (size_t)Np * Kp, Kp, given_inv};
+}
+
+// The planes live in the encoder's own scratch (planes_over: an fp32 row = two fp16 rows): h <- planes of LayerNorm(x) / of the planes
+// attention's output, ff <- planes of the FF's hidden layer; the weights' planes (split per call unless the host built them) go to
+// whichever of ff / qkv is idle.  L >= 512 makes every region large enough for them.
 static void run_encoder_planes(hipStream_t s, const EncW& w, float* x, float* h, float* qkv, float* ff, int64_t S, int L, int E, int H,
                                const int* lens) {
     const int64_t T = S * L;
     const int dqk = E / 4, W3 = 2 * dqk + E;
-    const float inv = 1.0f / 256.0f;
-    // 1 on variant 7 (with head dims the planes attention covers: the default architectures): the low planes below are neither written nor read
-    const int np = attention_planes_applicable(H, dqk, E, W3) ? matrix_planes() : 2;
-    _Float16 *hh = reinterpret_cast<_Float16*>(h), *hl = np == 1 ? nullptr : hh + (size_t)T * E;   // planes [2][T][E] over h
-    _Float16 *fh = reinterpret_cast<_Float16*>(ff);                                          // planes over ff: [2][T][E] or [2][T][2E]
-    auto wsplit = [&](const float* W, int N, int K, void* dst, const void* given = nullptr) {
-        if (given) return (const _Float16*)given;            // host-built planes (one split per parameter version instead of per call)
-        launch_split_weights(s, W, K, dst, N, K);
-        return (const _Float16*)dst;
-    };
-    launch_layernorm_planes(s, x, E, w.n1g, w.n1b, hh, hl, E, T, E);                         // Attention.py:287
-    const _Float16* Wq = wsplit(w.qkv.w, W3, E, ff, w.p_qkv);
-    _Float16* ah = reinterpret_cast<_Float16*>(qkv);                                         // the attention's result as planes [2][T][E]
-    if (attention_planes_applicable(H, dqk, E, W3)) {
+    const bool attn_planes = attention_planes_applicable(H, dqk, E, W3);
+    // 1 on variant 7 (with head dims the planes attention covers: the default architectures): the LayerNorms' low plane is neither written nor read
+    const int np = attn_planes ? matrix_planes() : 2;
+    const Planes hP = planes_over(h, T, E), nP = hP.keep(np);                                // nP: what the LayerNorms write
+    const Planes fP = planes_over(ff, T, 2 * E);
+    const size_t ff_floats = (size_t)T * 2 * E;                                              // (ff is free during the attention: key-split scratch)
+    launch_layernorm_planes(s, {x, E}, w.n1g, w.n1b, nP, T, E);                              // Attention.py:287
+    const WPlanes Wq = weight_planes(s, w.p_qkv, WSPLIT_INV, w.qkv, E, W3, E, ff);
+    Planes aP = planes_over(qkv, T, E);                                                      // the attention's result
+    if (attn_planes) {
         // q | k | v leave the projection as planes [2][T][W3] over qkv (:186-188); the attention stages K / V tiles by DMA (:191-198) and
         // writes its result as planes over h (the LayerNorm's, consumed by then).  One block per (query tile, head, sequence) whatever S is
         // (a cloud's result must not depend on how many clouds share the launch): a batch of clouds saves the combine pass and the fp32
         // parts of the key-split form (0.23 ms of a MACARONS decision); one cloud alone pays 13 us per attention for it (41 instead of
         // 23 + 5 us, hidden beside the local transformers in an NBV step).
-        _Float16 *qh_ = reinterpret_cast<_Float16*>(qkv), *ql_ = qh_ + (size_t)T * W3;
-        launch_linear3p(s, hh, hl, E, Wq, Wq + (size_t)W3 * E, E, w.qkv.b, nullptr, qh_, ql_, W3, T, W3, E, ACT_NONE, inv, nullptr, 0, nullptr,
-                        nullptr, 0, np);
-        ah = hh;
-        launch_attention_planes(s, qh_, ql_, W3, h, E, ah, ah + (size_t)T * E, E, S, L, H, dqk, E, lens, ff, (size_t)T * 2 * E, /*split_mode=*/0, np);
+        const Planes qP = planes_over(qkv, T, W3);
+        launch_linear3p(s, nP, Wq, {w.qkv.b, ACT_NONE}, qP, T, W3, E, np);
+        aP = hP;
+        launch_attention_planes(s, qP, {h, E}, aP, S, L, H, dqk, E, lens, {ff, ff_floats, /*mode=*/0}, np);
     } else {
-        launch_linear3p(s, hh, hl, E, Wq, Wq + (size_t)W3 * E, E, w.qkv.b, qkv, nullptr, nullptr, W3, T, W3, E, ACT_NONE, inv, nullptr, 0, nullptr);   // :186-188
+        launch_linear3p(s, nP, Wq, {w.qkv.b, ACT_NONE}, {qkv, W3}, T, W3, E, np);            // :186-188
         // attention: fp32 parts in h / ff (key-split scratch); its combine pass writes the result straight as planes into qkv (free by then)
-        bool planes_done = false;
-        launch_attention(s, qkv, W3, h, E, S, L, H, dqk, E, lens, ff, (size_t)T * 2 * E, /*split_by_length=*/true, attn_pv_half(), nullptr, 0, 0, 0,
-                         ah, ah + (size_t)T * E, E, &planes_done);              // :191-198
-        if (!planes_done) launch_split_to_planes(s, h, E, ah, ah + (size_t)T * E, E, T, E);
+        if (!launch_attention(s, {qkv, W3}, {h, E}, S, L, H, dqk, E, lens, {ff, ff_floats, 1}, attn_pv_half(), aP))   // :191-198
+            launch_split_to_planes(s, {h, E}, aP, T, E);
     }
-    const _Float16* Wo = wsplit(w.out.w, E, E, ff, w.p_out);
-    launch_linear3p(s, ah, ah + (size_t)T * E, E, Wo, Wo + (size_t)E * E, E, w.out.b, x, nullptr, nullptr, E, T, E, E, ACT_NONE, inv, nullptr, 0,
-                    nullptr, x, E, np);                                                        // :201-202 + residual :290
-    launch_layernorm_planes(s, x, E, w.n2g, w.n2b, hh, hl, E, T, E);                         // :293
-    const _Float16* W1 = wsplit(w.ff1.w, 2 * E, E, qkv, w.p_ff1);
-    launch_linear3p(s, hh, hl, E, W1, W1 + (size_t)2 * E * E, E, w.ff1.b, nullptr, fh, fh + (size_t)T * 2 * E, 2 * E, T, 2 * E, E, ACT_GELU, inv,
-                    nullptr, 0, nullptr, nullptr, 0, np);                                      // :232 (planes out)
-    const _Float16* W2 = wsplit(w.ff2.w, E, 2 * E, qkv, w.p_ff2);
-    launch_linear3p(s, fh, fh + (size_t)T * 2 * E, 2 * E, W2, W2 + (size_t)E * 2 * E, 2 * E, w.ff2.b, x, nullptr, nullptr, E, T, E, 2 * E, ACT_NONE,
-                    inv, nullptr, 0, nullptr, x, E, np);                                       // :235 + residual :298
+    const WPlanes Wo = weight_planes(s, w.p_out, WSPLIT_INV, w.out, E, E, E, ff);
+    launch_linear3p(s, aP, Wo, {w.out.b, ACT_NONE, {x, E}}, {x, E}, T, E, E, np);            // :201-202 + residual :290
+    launch_layernorm_planes(s, {x, E}, w.n2g, w.n2b, nP, T, E);                              // :293
+    const WPlanes W1 = weight_planes(s, w.p_ff1, WSPLIT_INV, w.ff1, E, 2 * E, E, qkv);
+    launch_linear3p(s, nP, W1, {w.ff1.b, ACT_GELU}, fP, T, 2 * E, E, np);                    // :232 (planes out)
+    const WPlanes W2 = weight_planes(s, w.p_ff2, WSPLIT_INV, w.ff2, 2 * E, E, 2 * E, qkv);
+    launch_linear3p(s, fP, W2, {w.ff2.b, ACT_NONE, {x, E}}, {x, E}, T, E, 2 * E, np);        // :235 + residual :298
 }
 
 // x <- Encoder(x)  in place.  x [T, E]; scratch h [T, E], qkv [T, 2*dqk + E], ff [T, 2E]
@@ -141,15 +152,15 @@ static void run_encoder(hipStream_t s, const EncW& w, float* x, float* h, float*
         run_encoder_planes(s, w, x, h, qkv, ff, S, L, E, H, lens);
         return;
     }
-    launch_layernorm(s, x, E, w.n1g, w.n1b, h, E, T, E);                                   // Attention.py:287
-    // every GEMM of the networks routes (fp32 vs split precision) on the rows of ONE sequence, not on T: see launch_linear
-    launch_linear(s, h, E, w.qkv.w, w.qkv.b, nullptr, 0, qkv, W3, T, W3, E, ACT_NONE, nullptr, 0, 0, seq_route(L));       // :186-188
-    launch_attention(s, qkv, W3, h, E, S, L, H, dqk, E, lens, ff, (size_t)T * 2 * E, /*split_by_length=*/true,     // :191-198 (ff is free here: key-split scratch)
-                     attn_pv_half());
-    launch_linear(s, h, E, w.out.w, w.out.b, x, E, x, E, T, E, E, ACT_NONE, nullptr, 0, 0, seq_route(L));                 // :201-202 + residual :290
-    launch_layernorm(s, x, E, w.n2g, w.n2b, h, E, T, E);                                   // :293
-    launch_linear(s, h, E, w.ff1.w, w.ff1.b, nullptr, 0, ff, 2 * E, T, 2 * E, E, ACT_GELU, nullptr, 0, 0, seq_route(L));  // :232
-    launch_linear(s, ff, 2 * E, w.ff2.w, w.ff2.b, x, E, x, E, T, E, 2 * E, ACT_NONE, nullptr, 0, 0, seq_route(L));        // :235 + residual :298
+    const int64_t route = seq_route(L);      // every GEMM of the networks routes (fp32 vs split precision) on the rows of ONE sequence, not on T: see launch_linear
+    const size_t ff_floats = (size_t)T * 2 * E;
+    launch_layernorm(s, x, E, w.n1g, w.n1b, h, E, T, E);                                                   // Attention.py:287
+    launch_linear(s, {h, E}, {w.qkv.w, E}, {w.qkv.b, ACT_NONE}, {qkv, W3}, T, W3, E, route);               // :186-188
+    launch_attention(s, {qkv, W3}, {h, E}, S, L, H, dqk, E, lens, {ff, ff_floats, 1}, attn_pv_half());     // :191-198 (ff is free here: key-split scratch)
+    launch_linear(s, {h, E}, {w.out.w, E}, {w.out.b, ACT_NONE, {x, E}}, {x, E}, T, E, E, route);           // :201-202 + residual :290
+    launch_layernorm(s, x, E, w.n2g, w.n2b, h, E, T, E);                                                   // :293
+    launch_linear(s, {h, E}, {w.ff1.w, E}, {w.ff1.b, ACT_GELU}, {ff, 2 * E}, T, 2 * E, E, route);          // :232
+    launch_linear(s, {ff, 2 * E}, {w.ff2.w, 2 * E}, {w.ff2.b, ACT_NONE, {x, E}}, {x, E}, T, E, 2 * E, route);   // :235 + residual :298
 }
 
 // ---- PCTransformer (SconeOcc.py:45-130): S sequences of L points (pts_dim 3), E = 128, 2 encoders, 4 heads ----
@@ -173,38 +184,29 @@ static void run_pct(hipStream_t s, const PctW& w, const float* pc, float* feat, 
     const int64_t T = S * L;
     float *x = ws.x, *h = ws.h, *qkv = ws.qkv, *ff = ws.ff;
     const bool planes = enc_planes(L, PCT_E) && half % 4 == 0;
-    const float inv = 1.0f / 256.0f;
-    const int np = matrix_planes();                       // 1 on variant 7: the GEMMs below read / write the high planes alone
-    _Float16 *hh = reinterpret_cast<_Float16*>(h), *hl = hh + (size_t)T * PCT_E;            // planes [2][T][128] over h
+    const int np = matrix_planes();                       // 1 on variant 7: the GEMMs below multiply the high planes alone
+    const Planes hP = planes_over(h, T, PCT_E);
     // Embedding (Attention.py:98-128): linear1 3->125, GELU, linear2 125->125, concat raw input -> 128
     if (planes) {
         // the 125-wide inner layer padded with exact zeros to the planes GEMM's K = 128: linear1 writes planes, linear2 multiplies them
         // (output columns 125..127 = 0 + 0, then overwritten by the raw input)
-        launch_linear_smallk_planes(s, pc, 3, w.l1.w, w.l1.b, hh, hl, PCT_E, T, PCT_INNER, 3, ACT_GELU, PCT_E);
-        const _Float16* wp = (const _Float16*)w.p_l2;                                        // host-built (once per parameter version) ...
-        const float* bp = w.b_l2p;
-        if (!wp) {                                                                           // ... or padded here, per call
-            float* bq = ff + (size_t)PCT_E * PCT_E;                                          // behind the [2][128][128] halves
-            launch_pad_weights(s, w.l2.w, PCT_INNER, w.l2.b, ff, bq, PCT_INNER, PCT_INNER, PCT_E, PCT_E);
-            wp = reinterpret_cast<const _Float16*>(ff); bp = bq;
-        }
-        launch_linear3p(s, hh, hl, PCT_E, wp, wp + (size_t)PCT_E * PCT_E, PCT_E, bp, x, nullptr, nullptr, PCT_E, T, PCT_E, PCT_E, ACT_NONE, inv,
-                        nullptr, 0, nullptr, nullptr, 0, np);
+        launch_linear_smallk_planes(s, {pc, 3}, w.l1.w, w.l1.b, ACT_GELU, hP, T, PCT_INNER, 3, PCT_E);
+        const float* b2 = w.b_l2p;
+        const WPlanes W2 = weight_planes(s, w.p_l2, WSPLIT_INV, w.l2, PCT_INNER, PCT_INNER, PCT_INNER, ff, PCT_E, PCT_E, &b2);
+        launch_linear3p(s, hP, W2, {b2, ACT_NONE}, {x, PCT_E}, T, PCT_E, PCT_E, np);
     } else {
-        launch_linear(s, pc, 3, w.l1.w, w.l1.b, nullptr, 0, h, PCT_INNER, T, PCT_INNER, 3, ACT_GELU, nullptr, 0, 0, L);
-        launch_linear(s, h, PCT_INNER, w.l2.w, w.l2.b, nullptr, 0, x, PCT_E, T, PCT_INNER, PCT_INNER, ACT_NONE, nullptr, 0, 0, L);
+        launch_linear(s, {pc, 3}, {w.l1.w, 3}, {w.l1.b, ACT_GELU}, {h, PCT_INNER}, T, PCT_INNER, 3, L);
+        launch_linear(s, {h, PCT_INNER}, {w.l2.w, PCT_INNER}, {w.l2.b, ACT_NONE}, {x, PCT_E}, T, PCT_INNER, PCT_INNER, L);
     }
     launch_copy2d(s, pc, 3, x + PCT_INNER, PCT_E, T, 3);
     for (int e = 0; e < 2; ++e) run_encoder(s, w.enc[e], x, h, qkv, ff, S, L, PCT_E, 4, lens);
     if (planes) {                                                                            // SconeOcc.py:119-122 on planes
-        launch_layernorm_planes(s, x, PCT_E, w.ng, w.nb, hh, np == 1 ? nullptr : hl, PCT_E, T, PCT_E);
-        const _Float16* wp = (const _Float16*)w.p_lin0;
-        if (!wp) { launch_split_weights(s, w.lin0.w, PCT_E, qkv, half, PCT_E); wp = reinterpret_cast<const _Float16*>(qkv); }
-        launch_linear3p(s, hh, hl, PCT_E, wp, wp + (size_t)half * PCT_E, PCT_E, w.lin0.b, ff, nullptr, nullptr, half, T, half, PCT_E, ACT_NONE, inv,
-                        nullptr, 0, nullptr, nullptr, 0, np);
+        launch_layernorm_planes(s, {x, PCT_E}, w.ng, w.nb, hP.keep(np), T, PCT_E);
+        const WPlanes W0 = weight_planes(s, w.p_lin0, WSPLIT_INV, w.lin0, PCT_E, half, PCT_E, qkv);
+        launch_linear3p(s, hP, W0, {w.lin0.b, ACT_NONE}, {ff, half}, T, half, PCT_E, np);
     } else {
         launch_layernorm(s, x, PCT_E, w.ng, w.nb, h, PCT_E, T, PCT_E);                      // SconeOcc.py:119
-        launch_linear(s, h, PCT_E, w.lin0.w, w.lin0.b, nullptr, 0, ff, half, T, half, PCT_E, ACT_NONE, nullptr, 0, 0, seq_route(L));   // :122
+        launch_linear(s, {h, PCT_E}, {w.lin0.w, PCT_E}, {w.lin0.b, ACT_NONE}, {ff, half}, T, half, PCT_E, seq_route(L));   // :122
     }
     launch_pool_max_avg(s, ff, half, feat, ld_feat, S, L, half, lens);                       // :124-126
 }
@@ -225,37 +227,25 @@ static void launch_nonfinite_flag(hipStream_t s, const float* x, int64_t n, int*
 // bytes as the fp32 layout): featP = planes [2][T][1344] fp16, h1P = [2][T][512] fp16 (first used as [2][T][256] for the
 // x-embedding), h2 = fp32 [T][256] (first half first used for xe1's fp32 output, second half for its planes).
 struct HeadScratch { _Float16* featP; _Float16* h1P; float* h2; void* wplanes; };
-static void head_planes_weights(hipStream_t s, int which, const float* W, int64_t ldw, int N, int K, const void* const* head_planes,
-                                const float* head_inv_scales, void* wplanes, const _Float16*& Wh, const _Float16*& Wl, float& inv) {
-    if (head_planes && head_planes[which] && head_inv_scales[which] > 0.f) {
-        Wh = (const _Float16*)head_planes[which];
-        inv = head_inv_scales[which];
-    } else {                                              // no host planes: split here (fixed 2^8 scale, |w| < 255)
-        launch_split_weights(s, W, ldw, wplanes, N, K);
-        Wh = (const _Float16*)wplanes;
-        inv = 1.0f / 256.0f;
-    }
-    Wl = Wh + (size_t)N * K;
+// weight planes of head layer `which` (0 xe2, 1 xe3, 2 lin1's columns 512..1855, 3 lin2: the order of the host's pre-split planes)
+static WPlanes head_weight_planes(hipStream_t s, int which, const LinW& lin, int64_t ldw, int N, int K, const void* const* head_planes,
+                                  const float* head_inv_scales, void* wplanes) {
+    const bool pre = head_planes && head_planes[which] && head_inv_scales[which] > 0.f;
+    return weight_planes(s, pre ? head_planes[which] : nullptr, pre ? head_inv_scales[which] : 0.f, lin, ldw, N, K, wplanes);
 }
 // the part of the planes head that needs nothing but the queries: x embedding 3 -> 128 -> 256 -> 512 (GELU each, SconeOcc.py:35-42)
 // into columns 768.. of the feature planes, the view harmonics into columns 1280..
 static void run_x_embedding_planes(hipStream_t s, const float* x, const float* view_harmonics, int64_t T, const LinW& xe1, const LinW& xe2,
                                    const LinW& xe3, const void* const* head_planes, const float* head_inv_scales, const HeadScratch& w) {
-    _Float16 *fh = w.featP, *fl = w.featP + (size_t)T * 1344;
-    _Float16 *hh = w.h1P;
-    _Float16* x1h = reinterpret_cast<_Float16*>(w.h2 + (size_t)T * 128);     // planes [2][T][128]
-    _Float16* x1l = x1h + (size_t)T * 128;
-    const _Float16 *Wh, *Wl;
-    float inv;
+    const Planes fP = planes_over(w.featP, T, 1344), hP = planes_over(w.h1P, T, 256);
+    const Planes x1 = planes_over(w.h2 + T * 128, T, 128);
     const int np = matrix_planes();                      // 1 on variant 7: the low planes below are neither written (GEMM epilogues) nor read
-    launch_linear_smallk_planes(s, x, 3, xe1.w, xe1.b, x1h, x1l, 128, T, 128, 3, ACT_GELU);       // (planes directly: no fp32 rows, no split pass)
-    head_planes_weights(s, 0, xe2.w, 128, 256, 128, head_planes, head_inv_scales, w.wplanes, Wh, Wl, inv);
-    launch_linear3p(s, x1h, x1l, 128, Wh, Wl, 128, xe2.b, nullptr, hh, hh + (size_t)T * 256, 256, T, 256, 128, ACT_GELU, inv, nullptr, 0, nullptr,
-                    nullptr, 0, np);
-    head_planes_weights(s, 1, xe3.w, 256, 512, 256, head_planes, head_inv_scales, w.wplanes, Wh, Wl, inv);
-    launch_linear3p(s, hh, hh + (size_t)T * 256, 256, Wh, Wl, 256, xe3.b, nullptr, fh + 768, fl + 768, 1344, T, 512, 256, ACT_GELU, inv, nullptr, 0,
-                    nullptr, nullptr, 0, np);
-    if (view_harmonics) launch_split_to_planes(s, view_harmonics, 64, fh + 1280, np == 1 ? nullptr : fl + 1280, 1344, T, 64);   // (NULL: the caller splits them later)
+    launch_linear_smallk_planes(s, {x, 3}, xe1.w, xe1.b, ACT_GELU, x1, T, 128, 3, /*Np=*/0);   // (planes directly: no fp32 rows, no split pass)
+    const WPlanes W2 = head_weight_planes(s, 0, xe2, 128, 256, 128, head_planes, head_inv_scales, w.wplanes);
+    launch_linear3p(s, x1, W2, {xe2.b, ACT_GELU}, hP, T, 256, 128, np);
+    const WPlanes W3 = head_weight_planes(s, 1, xe3, 256, 512, 256, head_planes, head_inv_scales, w.wplanes);
+    launch_linear3p(s, hP, W3, {xe3.b, ACT_GELU}, fP.cols(768), T, 512, 256, np);
+    if (view_harmonics) launch_split_to_planes(s, {view_harmonics, 64}, fP.cols(1280).keep(np), T, 64);   // (NULL: the caller splits them later)
 }
 
 // x_done: the x-embedding part has been queued elsewhere (the side stream: the join covers it)
@@ -264,20 +254,16 @@ static void run_head_planes(hipStream_t s, const float* x, const float* view_har
                             const LinW& xe3, const LinW& lin1, const LinW& lin2, const LinW& lin3, const float* gbias,
                             int64_t rows_per_group, const int* row_group, const void* const* head_planes, const float* head_inv_scales,
                             const HeadScratch& w, float* out, Join join, bool x_done = false) {
-    _Float16 *fh = w.featP, *fl = w.featP + (size_t)T * 1344;
-    _Float16 *hh = w.h1P;
-    const _Float16 *Wh, *Wl;
-    float inv;
+    const Planes fP = planes_over(w.featP, T, 1344), hP = planes_over(w.h1P, T, 512);
     const int np = matrix_planes();
     if (!x_done) run_x_embedding_planes(s, x, view_harmonics, T, xe1, xe2, xe3, head_planes, head_inv_scales, w);
     join();                                               // the global feature (side stream) is needed from here on
     // head MLP 1856 -> 512 -> 256 -> 1, GELU after every layer incl. the last (SconeOcc.py:334-345); the global 512 columns are gbias
-    head_planes_weights(s, 2, lin1.w + 512, 1856, 512, 1344, head_planes, head_inv_scales, w.wplanes, Wh, Wl, inv);
-    launch_linear3p(s, fh, fl, 1344, Wh, Wl, 1344, lin1.b, nullptr, hh, hh + (size_t)T * 512, 512, T, 512, 1344, ACT_GELU, inv, gbias,
-                    rows_per_group, row_group, nullptr, 0, np);
-    head_planes_weights(s, 3, lin2.w, 512, 256, 512, head_planes, head_inv_scales, w.wplanes, Wh, Wl, inv);
+    const WPlanes W1 = head_weight_planes(s, 2, {lin1.w + 512, lin1.b}, 1856, 512, 1344, head_planes, head_inv_scales, w.wplanes);
+    launch_linear3p(s, fP, W1, {lin1.b, ACT_GELU, {}, {gbias, rows_per_group, row_group}}, hP, T, 512, 1344, np);
+    const WPlanes W2 = head_weight_planes(s, 3, lin2, 512, 256, 512, head_planes, head_inv_scales, w.wplanes);
     // 512 -> 256 (GELU) -> 1 (GELU) in one launch: the block owns all 256 features of its rows and dots them with linear3.weight
-    launch_linear3p_dot(s, hh, hh + (size_t)T * 512, 512, Wh, Wl, 512, lin2.b, T, 512, ACT_GELU, inv, lin3.w, lin3.b, ACT_GELU, out, np);
+    launch_linear3p_dot(s, hP, W2, {lin2.b, ACT_GELU}, T, 512, lin3.w, lin3.b, ACT_GELU, out, np);
 }
 
 }  // namespace mcr
@@ -293,7 +279,7 @@ int mcr_linear(const float* X, int64_t ldx, const float* W, const float* bias, c
     MCR_REQUIRE(X && W && Y, "mcr_linear: null pointer");
     MCR_REQUIRE(M > 0 && N > 0 && K > 0, "mcr_linear: empty problem");
     MCR_REQUIRE(ldx >= K && ldy >= N && (!residual || ldr >= N), "mcr_linear: leading dimension too small");
-    launch_linear((hipStream_t)stream, X, ldx, W, bias, residual, ldr, Y, ldy, M, N, K, gelu ? ACT_GELU : ACT_NONE);
+    launch_linear((hipStream_t)stream, {X, ldx}, {W, K}, {bias, gelu ? ACT_GELU : ACT_NONE, {residual, ldr}}, {Y, ldy}, M, N, K, /*route_rows=*/0);
     MCR_LAUNCH_CHECK("mcr_linear");
     return 0;
 }
@@ -318,7 +304,7 @@ int mcr_attention(const float* qkv, int64_t ldq, float* out, int64_t ldo, int64_
                 n_heads, qk_dim, v_dim);
     MCR_REQUIRE(L == 16 || S <= 65535, "mcr_attention: too many long sequences");
     MCR_REQUIRE(ldq >= 2 * qk_dim + v_dim && ldo >= v_dim, "mcr_attention: leading dimension too small");
-    launch_attention((hipStream_t)stream, qkv, ldq, out, ldo, S, (int)L, n_heads, qk_dim, v_dim, nullptr, nullptr, 0, false, attn_pv_half());
+    launch_attention((hipStream_t)stream, {qkv, ldq}, {out, ldo}, S, (int)L, n_heads, qk_dim, v_dim, nullptr, AttnSplit{}, attn_pv_half());
     MCR_LAUNCH_CHECK("mcr_attention");
     return 0;
 }
@@ -335,8 +321,9 @@ int mcr_attention_masked(const float* qkv, int64_t ldq, float* out, int64_t ldo,
     MCR_REQUIRE(mask_seq_stride >= 0 && mask_head_stride >= 0 && mask_query_stride >= 0, "mcr_attention_masked: negative mask stride");
     MCR_REQUIRE(L == 16 || S <= 32767, "mcr_attention_masked: too many long sequences");
     MCR_REQUIRE(ldq >= 2 * qk_dim + v_dim && ldo >= v_dim, "mcr_attention_masked: leading dimension too small");
-    launch_attention((hipStream_t)stream, qkv, ldq, out, ldo, S, (int)L, n_heads, qk_dim, v_dim, nullptr, (float*)workspace,
-                     workspace ? workspace_bytes / sizeof(float) : 0, false, false, mask, mask_seq_stride, mask_head_stride, mask_query_stride);
+    const AttnSplit split{(float*)workspace, workspace ? workspace_bytes / sizeof(float) : 0, /*mode=*/-1};
+    launch_attention((hipStream_t)stream, {qkv, ldq}, {out, ldo}, S, (int)L, n_heads, qk_dim, v_dim, nullptr, split,
+                     AttnMask{mask, mask_seq_stride, mask_head_stride, mask_query_stride});
     MCR_LAUNCH_CHECK("mcr_attention_masked");
     return 0;
 }
@@ -355,8 +342,8 @@ int mcr_attention_ws(const float* qkv, int64_t ldq, float* out, int64_t ldo, int
                 n_heads, qk_dim, v_dim);
     MCR_REQUIRE(L == 16 || S <= 32767, "mcr_attention_ws: too many long sequences");
     MCR_REQUIRE(ldq >= 2 * qk_dim + v_dim && ldo >= v_dim, "mcr_attention_ws: leading dimension too small");
-    launch_attention((hipStream_t)stream, qkv, ldq, out, ldo, S, (int)L, n_heads, qk_dim, v_dim, nullptr, (float*)workspace,
-                     workspace ? workspace_bytes / sizeof(float) : 0, false, attn_pv_half());
+    const AttnSplit split{(float*)workspace, workspace ? workspace_bytes / sizeof(float) : 0, /*mode=*/-1};
+    launch_attention((hipStream_t)stream, {qkv, ldq}, {out, ldo}, S, (int)L, n_heads, qk_dim, v_dim, nullptr, split, attn_pv_half());
     MCR_LAUNCH_CHECK("mcr_attention_ws");
     return 0;
 }
@@ -390,10 +377,10 @@ int mcr_attention_planes(const float* qkv, int64_t ldq, float* out, int64_t ldo,
     Arena a{(char*)workspace, workspace_bytes};
     const AttnPlanesScratch ws = carve_attention_planes(a, S, L, n_heads, qk_dim, v_dim);
     MCR_REQUIRE(a.ok(), "mcr_attention_planes: workspace too small");
-    _Float16 *ph = ws.planes, *pl = ph + (size_t)T * W3;
-    launch_split_to_planes((hipStream_t)stream, qkv, ldq, ph, pl, W3, T, W3);
-    launch_attention_planes((hipStream_t)stream, ph, pl, W3, out, ldo, nullptr, nullptr, 0, S, (int)L, n_heads, qk_dim, v_dim, lens, ws.split,
-                            attention_split_floats(S, (int)L, n_heads, v_dim), split_mode);
+    const Planes P = planes_over(ws.planes, T, W3);
+    launch_split_to_planes((hipStream_t)stream, {qkv, ldq}, P, T, W3);
+    launch_attention_planes((hipStream_t)stream, P, {out, ldo}, Planes{}, S, (int)L, n_heads, qk_dim, v_dim, lens,
+                            {ws.split, attention_split_floats(S, (int)L, n_heads, v_dim), split_mode}, /*n_planes=*/2);
     MCR_LAUNCH_CHECK("mcr_attention_planes");
     return 0;
 }
@@ -435,7 +422,7 @@ int mcr_split_to_planes(const float* X, int64_t ldx, void* Ph, void* Pl, int64_t
     // one thread moves four values: a 16-byte load of X, an 8-byte store per plane
     MCR_REQUIRE(ldx % 4 == 0 && al16(X), "mcr_split_to_planes: ldx must be a multiple of 4 and X 16-byte aligned");
     MCR_REQUIRE(ldp % 4 == 0 && al8(Ph) && al8(Pl), "mcr_split_to_planes: ldp must be a multiple of 4 and the planes 8-byte aligned");
-    launch_split_to_planes((hipStream_t)stream, X, ldx, Ph, Pl, ldp, M, E);
+    launch_split_to_planes((hipStream_t)stream, {X, ldx}, {(_Float16*)Ph, (_Float16*)Pl, ldp}, M, E);
     MCR_LAUNCH_CHECK("mcr_split_to_planes");
     return 0;
 }
@@ -458,8 +445,11 @@ int mcr_linear_planes(const void* Xh, const void* Xl, int64_t ldx, const void* W
     MCR_REQUIRE(((uintptr_t)Y | (uintptr_t)R) % 4 == 0, "mcr_linear_planes: Y and R must be 4-byte aligned");
     MCR_REQUIRE(!R || Y, "mcr_linear_planes: a residual needs fp32 output");
     MCR_REQUIRE(!row_bias || rows_per_group > 0 || row_group, "mcr_linear_planes: row_bias needs rows_per_group > 0 or row_group");
-    launch_linear3p((hipStream_t)stream, Xh, Xl, ldx, Wh, Wl, ldw, bias, Y, Yh, Yl, ldy, M, N, K, gelu ? ACT_GELU : ACT_NONE, wscale_inv, row_bias,
-                    rows_per_group, row_group, R, ldr, n_planes);
+    const Planes X{(_Float16*)Xh, (_Float16*)Xl, ldx};                  // (read only: the launchers never write their X operand)
+    const WPlanes W{(const _Float16*)Wh, (const _Float16*)Wl, ldw, wscale_inv};
+    const Epilogue e{bias, gelu ? ACT_GELU : ACT_NONE, {R, ldr}, {row_bias, rows_per_group, row_group}};
+    if (Yh) launch_linear3p((hipStream_t)stream, X, W, e, Planes{(_Float16*)Yh, (_Float16*)Yl, ldy}, M, N, K, n_planes);
+    else launch_linear3p((hipStream_t)stream, X, W, e, RowsOut{Y, ldy}, M, N, K, n_planes);
     MCR_LAUNCH_CHECK("mcr_linear_planes");
     return 0;
 }
@@ -474,15 +464,16 @@ int mcr_linear_planes_dot(const void* Xh, const void* Xl, int64_t ldx, const voi
     MCR_REQUIRE(al16(Xh) && al16(Wh) && (n_planes == 1 || (al16(Xl) && al16(Wl))), "mcr_linear_planes_dot: operand planes must be 16-byte aligned");
     MCR_REQUIRE(al16(bias) && al16(v), "mcr_linear_planes_dot: bias and v must be 16-byte aligned");
     MCR_REQUIRE(((uintptr_t)out | (uintptr_t)c) % 4 == 0, "mcr_linear_planes_dot: out and c must be 4-byte aligned");
-    launch_linear3p_dot((hipStream_t)stream, Xh, Xl, ldx, Wh, Wl, ldw, bias, M, K, gelu ? ACT_GELU : ACT_NONE, wscale_inv, v, c,
-                        gelu2 ? ACT_GELU : ACT_NONE, out, n_planes);
+    const Planes X{(_Float16*)Xh, (_Float16*)Xl, ldx};                  // (read only)
+    const WPlanes W{(const _Float16*)Wh, (const _Float16*)Wl, ldw, wscale_inv};
+    launch_linear3p_dot((hipStream_t)stream, X, W, {bias, gelu ? ACT_GELU : ACT_NONE}, M, K, v, c, gelu2 ? ACT_GELU : ACT_NONE, out, n_planes);
     MCR_LAUNCH_CHECK("mcr_linear_planes_dot");
     return 0;
 }
 
 int mcr_get_local_pct_variant(void);
 int mcr_local_pct_blob_floats(void) { return local_pct_blob_floats(); }
-int mcr_local_pct3_blob_floats(void) { return local_pct3_blob_floats(); }
+int mcr_local_pct3_blob_floats(void) { return local_pct5_blob_floats(); }
 int mcr_local_pct6_blob_floats(void) { return local_pct6_blob_floats(); }
 int mcr_local_pct7_blob_floats(void) { return local_pct7_blob_floats(); }
 
@@ -498,15 +489,15 @@ int mcr_call_variant(int v) {
     t_next_variant = v;
     return 0;
 }
-static void run_local_pct(hipStream_t s, const float* offs, float* feat, int64_t ld, int64_t S, const float* blob,
-                          void* feat_h = nullptr, void* feat_l = nullptr) {
+// P (optional): the features as fp16 planes (row stride ld halves) instead of fp32 rows of feat
+static void run_local_pct(hipStream_t s, const float* offs, float* feat, int64_t ld, int64_t S, const float* blob, Planes P = Planes{}) {
     if (g_local_pct_variant == 1) launch_local_pct(s, offs, feat, ld, S, blob);
     else if (g_local_pct_variant == 5) launch_local_pct5(s, offs, feat, ld, S, blob);
 #ifdef MCR_DEV_LOCAL_PCT8
     else if (g_local_pct_variant == 8) launch_local_pct8(s, offs, feat, ld, S, blob);
 #endif
-    else if (g_local_pct_variant == 7) launch_local_pct7(s, offs, feat, ld, S, blob, feat_h);   // ONE plane out when feat_h is set
-    else launch_local_pct6(s, offs, feat, ld, S, blob, feat_h, feat_l);       // planes out (variant 6 only) when feat_h is set
+    else if (g_local_pct_variant == 7) launch_local_pct7(s, offs, feat, ld, S, blob, P.h);   // ONE plane out when P.h is set
+    else launch_local_pct6(s, offs, feat, ld, S, blob, P.h, P.l);       // planes out (variant 6 only) when P.h is set
 }
 
 int mcr_local_pct_forward(const float* offsets, float* features, int64_t ld_features, int64_t S, const float* blob,
@@ -570,60 +561,43 @@ int mcr_scone_vis_forward(const float* pts, const float* view_harmonics, float* 
     MCR_REQUIRE(a.ok(), "mcr_scone_vis_forward: workspace too small");
     float *x = ws.x, *h = ws.h, *qkv = ws.qkv, *ff = ws.ff;
     const bool planes = enc_planes((int)N, VIS_E);
-    const float inv = 1.0f / 256.0f;
-    const int np = matrix_planes();                       // 1 on variant 7: the GEMMs below read / write the high planes alone
-    _Float16 *hh = reinterpret_cast<_Float16*>(h), *hl = hh + (size_t)T * VIS_E;               // planes [2][T][<= 256] over h
+    const int np = matrix_planes();                       // 1 on variant 7: the GEMMs below multiply the high planes alone
+    const Planes hP = planes_over(h, T, VIS_E), h128 = planes_over(h, T, 128);                  // planes [2][T][256] / [2][T][128] over h
     // Embedding: 4 -> 126 GELU -> 126, || cloud-wide max (126) || raw input (4)  = 256   (Attention.py:98-128)
     if (planes) {
         // the 126-wide inner layer padded with exact zeros to K = 128: linear1 writes planes, linear2 multiplies them (its output
         // columns 126, 127 = 0 + 0 are overwritten by the cloud-wide max below)
-        _Float16* x1l = hh + (size_t)T * 128;
-        launch_linear_smallk_planes(s, pts, 4, l1.w, l1.b, hh, x1l, 128, T, VIS_F, 4, ACT_GELU, 128);
-        const _Float16* wp = (const _Float16*)w.p_l2;                                            // host-built (once per parameter version) ...
-        const float* bp = w.b_l2p;
-        if (!wp) {                                                                              // ... or padded here, per call
-            float* bq = ff + (size_t)128 * 128;
-            launch_pad_weights(s, l2.w, VIS_F, l2.b, ff, bq, VIS_F, VIS_F, 128, 128);
-            wp = reinterpret_cast<const _Float16*>(ff); bp = bq;
-        }
-        launch_linear3p(s, hh, x1l, 128, wp, wp + (size_t)128 * 128, 128, bp, x, nullptr, nullptr, VIS_E, T, 128, 128, ACT_NONE, inv, nullptr, 0, nullptr,
-                        nullptr, 0, np);
+        launch_linear_smallk_planes(s, {pts, 4}, l1.w, l1.b, ACT_GELU, h128, T, VIS_F, 4, 128);
+        const float* b2 = w.b_l2p;
+        const WPlanes W2 = weight_planes(s, w.p_l2, WSPLIT_INV, l2, VIS_F, VIS_F, VIS_F, ff, 128, 128, &b2);
+        launch_linear3p(s, h128, W2, {b2, ACT_NONE}, {x, VIS_E}, T, 128, 128, np);
     } else {
-        launch_linear(s, pts, 4, l1.w, l1.b, nullptr, 0, h, VIS_F, T, VIS_F, 4, ACT_GELU, nullptr, 0, 0, N);
-        launch_linear(s, h, VIS_F, l2.w, l2.b, nullptr, 0, x, VIS_E, T, VIS_F, VIS_F, ACT_NONE, nullptr, 0, 0, N);
+        launch_linear(s, {pts, 4}, {l1.w, 4}, {l1.b, ACT_GELU}, {h, VIS_F}, T, VIS_F, 4, N);
+        launch_linear(s, {h, VIS_F}, {l2.w, VIS_F}, {l2.b, ACT_NONE}, {x, VIS_E}, T, VIS_F, VIS_F, N);
     }
     launch_colmax_broadcast(s, x, VIS_E, x + VIS_F, VIS_E, B, (int)N, VIS_F, lengths, pts, 4, 4, x + 2 * VIS_F);   // (+ the raw input columns)
     for (int e = 0; e < 3; ++e) run_encoder(s, w.enc[e], x, h, qkv, ff, B, (int)N, VIS_E, 4, lengths);   // SconeVis.py:139-140
     if (planes) {
         // :143-152 on planes: LayerNorm -> planes; fc1 (GELU) writes columns 0..191 of the next operand's planes, the view harmonics are
-        // split into columns 192..255; fc2 (GELU) writes planes; fc3 leaves fp32.  Weight planes: split per call into the idle qkv region
-        launch_layernorm_planes(s, x, VIS_E, w.ng, w.nb, hh, np == 1 ? nullptr : hl, VIS_E, T, VIS_E);
-        const _Float16 *w1 = (const _Float16*)w.p_fc1, *w2 = (const _Float16*)w.p_fc2, *w3 = (const _Float16*)w.p_fc3;
-        if (!w1) {
-            _Float16* q1 = reinterpret_cast<_Float16*>(qkv);
-            _Float16* q2 = q1 + (size_t)2 * 192 * VIS_E;
-            _Float16* q3 = q2 + (size_t)2 * 128 * VIS_E;
-            launch_split_weights(s, fc1.w, VIS_E, q1, 192, VIS_E);
-            launch_split_weights(s, fc2.w, VIS_E, q2, 128, VIS_E);
-            launch_split_weights(s, fc3.w, 128, q3, 64, 128);
-            w1 = q1; w2 = q2; w3 = q3;
-        }
-        _Float16 *fh = reinterpret_cast<_Float16*>(ff), *fl = fh + (size_t)T * VIS_E;            // planes [2][T][256] over ff
-        launch_linear3p(s, hh, hl, VIS_E, w1, w1 + (size_t)192 * VIS_E, VIS_E, fc1.b, nullptr, fh, fl, VIS_E, T, 192, VIS_E, ACT_GELU, inv, nullptr, 0, nullptr,
-                        nullptr, 0, np);
-        launch_split_to_planes(s, view_harmonics, 64, fh + 192, np == 1 ? nullptr : fl + 192, VIS_E, T, 64);
-        _Float16* gl = hh + (size_t)T * 128;                                                       // planes [2][T][128] over h (the LayerNorm's are consumed)
-        launch_linear3p(s, fh, fl, VIS_E, w2, w2 + (size_t)128 * VIS_E, VIS_E, fc2.b, nullptr, hh, gl, 128, T, 128, VIS_E, ACT_GELU, inv, nullptr, 0, nullptr,
-                        nullptr, 0, np);
-        launch_linear3p(s, hh, gl, 128, w3, w3 + (size_t)64 * 128, 128, fc3.b, out, nullptr, nullptr, 64, T, 64, 128, ACT_NONE, inv, nullptr, 0, nullptr,
-                        nullptr, 0, np);
+        // split into columns 192..255; fc2 (GELU) writes planes over h (the LayerNorm's are consumed); fc3 leaves fp32.  Weight planes:
+        // split per call into the idle qkv region, one behind the other
+        launch_layernorm_planes(s, {x, VIS_E}, w.ng, w.nb, hP.keep(np), T, VIS_E);
+        _Float16* q = reinterpret_cast<_Float16*>(qkv);
+        const WPlanes W1 = weight_planes(s, w.p_fc1, WSPLIT_INV, fc1, VIS_E, 192, VIS_E, q);
+        const WPlanes W2 = weight_planes(s, w.p_fc2, WSPLIT_INV, fc2, VIS_E, 128, VIS_E, q + 2 * 192 * VIS_E);
+        const WPlanes W3 = weight_planes(s, w.p_fc3, WSPLIT_INV, fc3, 128, 64, 128, q + 2 * (192 + 128) * VIS_E);
+        const Planes fP = planes_over(ff, T, VIS_E);
+        launch_linear3p(s, hP, W1, {fc1.b, ACT_GELU}, fP, T, 192, VIS_E, np);
+        launch_split_to_planes(s, {view_harmonics, 64}, fP.cols(192).keep(np), T, 64);
+        launch_linear3p(s, fP, W2, {fc2.b, ACT_GELU}, h128, T, 128, VIS_E, np);
+        launch_linear3p(s, h128, W3, {fc3.b, ACT_NONE}, {out, 64}, T, 64, 128, np);
     } else {
         launch_layernorm(s, x, VIS_E, w.ng, w.nb, h, VIS_E, T, VIS_E);                                   // :143
         // fc1 256->192 GELU, || view_harmonics (64), fc2 256->128 GELU, fc3 128->64                  (:146-152)
-        launch_linear(s, h, VIS_E, fc1.w, fc1.b, nullptr, 0, ff, VIS_E, T, 192, VIS_E, ACT_GELU, nullptr, 0, 0, seq_route(N));
+        launch_linear(s, {h, VIS_E}, {fc1.w, VIS_E}, {fc1.b, ACT_GELU}, {ff, VIS_E}, T, 192, VIS_E, seq_route(N));
         launch_copy2d(s, view_harmonics, 64, ff + 192, VIS_E, T, 64);
-        launch_linear(s, ff, VIS_E, fc2.w, fc2.b, nullptr, 0, h, 128, T, 128, VIS_E, ACT_GELU, nullptr, 0, 0, seq_route(N));
-        launch_linear(s, h, 128, fc3.w, fc3.b, nullptr, 0, out, 64, T, 64, 128, ACT_NONE, nullptr, 0, 0, N);
+        launch_linear(s, {ff, VIS_E}, {fc2.w, VIS_E}, {fc2.b, ACT_GELU}, {h, 128}, T, 128, VIS_E, seq_route(N));
+        launch_linear(s, {h, 128}, {fc3.w, 128}, {fc3.b, ACT_NONE}, {out, 64}, T, 64, 128, N);
     }
     MCR_LAUNCH_CHECK("mcr_scone_vis_forward");
     return 0;
@@ -648,8 +622,7 @@ struct OccHead {
     void* wplanes;                                        // split weight planes of the largest head layer (reused layer after layer)
     // variant 6 with all three fused transformers: the head runs on fp16 hi/lo planes end to end (run_head_planes); the feature
     // buffer then holds planes [2][T][1344] fp16 instead of fp32 [T][1344]
-    _Float16* featP() const { return reinterpret_cast<_Float16*>(feat); }
-    HeadScratch planes() const { return HeadScratch{featP(), reinterpret_cast<_Float16*>(h1), h2, wplanes}; }
+    HeadScratch planes() const { return HeadScratch{reinterpret_cast<_Float16*>(feat), reinterpret_cast<_Float16*>(h1), h2, wplanes}; }
 };
 static OccHead carve_occ_head(Arena& a, int64_t T, int64_t G) {
     OccHead w;
@@ -711,28 +684,27 @@ struct SideJoin {
 static void run_global(hipStream_t gs, const OccW& w, const float* pc_global, int64_t G, int64_t Lg, const int* lens, const EncScratch& glob,
                        const OccHead& hd) {
     run_pct(gs, w.global, pc_global, hd.gfeat, 512, G, (int)Lg, 256, glob, lens);
-    launch_linear(gs, hd.gfeat, 512, w.lin1.w, nullptr, nullptr, 0, hd.gbias, 512, G, 512, 512, ACT_NONE, nullptr, 0, 1856, 1);
+    launch_linear(gs, {hd.gfeat, 512}, {w.lin1.w, 1856}, {nullptr, ACT_NONE}, {hd.gbias, 512}, G, 512, 512, /*route_rows=*/1);
 }
 
 // The large layers of the fp32-input head run on the matrix path of the selected variant -- 6: fp16 x 3 with the weights split once
 // per call into `wplanes`; 5: bf16 x 6 (exact hi/mid/lo); 1: exact fp32 MFMA -- chosen by the variant and the layer alone, never by
 // the number of rows: a query's occupancy must not depend on how many other queries share the launch (query shards of the
 // multi-GPU step, chunks, scene batches and the single call agree bit for bit).
-// which: 0 xe2, 1 xe3, 2 lin1 (columns 512..1855), 3 lin2 -- the order of the host's pre-split planes (variant 6)
+// which: as for head_weight_planes (variants 6 / 7).  lin: the layer, its weight rows ldw floats apart
 // rb (optional): the row bias, grouped by rows_per_group (dense: rows of one cloud) or by row_group (ragged: the job of each row)
-static void head_linear(hipStream_t s, int which, const float* X, int64_t ldx, const float* W, int64_t ldw, const float* b, float* Y, int64_t ldy,
-                        int64_t M, int N, int K, const float* rb, int64_t rows_per_group, const int* row_group, const void* const* head_planes,
-                        const float* head_inv_scales, void* wplanes) {
+static void head_linear(hipStream_t s, int which, Rows X, const LinW& lin, int64_t ldw, RowsOut Y, int64_t M, int N, int K, RowBias rb,
+                        const void* const* head_planes, const float* head_inv_scales, void* wplanes) {
     const int variant = g_local_pct_variant;
     const int64_t ANY_M = (int64_t)1 << 40;
-    if ((variant == 6 || variant == 7) && linear3h_applicable(X, ldx, W, ldw, ANY_M, N, K)) {
-        const bool pre = head_planes && head_planes[which] && head_inv_scales[which] > 0.f;
-        launch_linear3h(s, X, ldx, W, ldw, pre ? const_cast<void*>(head_planes[which]) : wplanes, b, nullptr, 0, Y, ldy, M, N, K, ACT_GELU, rb,
-                        rows_per_group, pre ? head_inv_scales[which] : 0.f, row_group);
-    } else if (variant == 5 && linear3_applicable(X, ldx, W, ldw, ANY_M, N, K))
-        launch_linear3(s, X, ldx, W, b, nullptr, 0, Y, ldy, M, N, K, ACT_GELU, rb, rows_per_group, ldw, row_group);
+    const Rows W{lin.w, ldw};
+    const Epilogue e{lin.b, ACT_GELU, {}, rb};
+    if ((variant == 6 || variant == 7) && linear3h_applicable(X.p, X.ld, W.p, W.ld, ANY_M, N, K))
+        launch_linear3h(s, X, head_weight_planes(s, which, lin, ldw, N, K, head_planes, head_inv_scales, wplanes), e, Y, M, N, K);
+    else if (variant == 5 && linear3_applicable(X.p, X.ld, W.p, W.ld, ANY_M, N, K))
+        launch_linear3(s, X, W, e, Y, M, N, K);
     else
-        launch_linear(s, X, ldx, W, b, nullptr, 0, Y, ldy, M, N, K, ACT_GELU, rb, rows_per_group, ldw, /*route_rows=*/1, row_group);
+        launch_linear(s, X, W, e, Y, M, N, K, /*route_rows=*/1);
 }
 
 // Everything behind the local features: x embedding, the join with the side stream (the global feature is needed from the first
@@ -752,17 +724,17 @@ static int run_occ_head(const char* who, hipStream_t s, const OccW& w, const flo
                         head_inv_scales, hd.planes(), out, join, x_done);
     else {
         // ---- x embedding 3 -> 128 -> 256 -> 512, GELU each (SconeOcc.py:35-42) ----
-        launch_linear(s, x, 3, w.xe1.w, w.xe1.b, nullptr, 0, hd.h2, 128, T, 128, 3, ACT_GELU, nullptr, 0, 0, 1);
-        head_linear(s, 0, hd.h2, 128, w.xe2.w, 128, w.xe2.b, hd.h1, 256, T, 256, 128, nullptr, 0, nullptr, head_planes, head_inv_scales, hd.wplanes);
-        head_linear(s, 1, hd.h1, 256, w.xe3.w, 256, w.xe3.b, hd.feat + 768, FEAT, T, 512, 256, nullptr, 0, nullptr, head_planes, head_inv_scales, hd.wplanes);
+        launch_linear(s, {x, 3}, {w.xe1.w, 3}, {w.xe1.b, ACT_GELU}, {hd.h2, 128}, T, 128, 3, /*route_rows=*/1);
+        head_linear(s, 0, {hd.h2, 128}, w.xe2, 128, {hd.h1, 256}, T, 256, 128, {}, head_planes, head_inv_scales, hd.wplanes);
+        head_linear(s, 1, {hd.h1, 256}, w.xe3, 256, {hd.feat + 768, FEAT}, T, 512, 256, {}, head_planes, head_inv_scales, hd.wplanes);
         launch_copy2d(s, view_harmonics, 64, hd.feat + 1280, FEAT, T, 64);
         // ---- head MLP 1856 -> 512 -> 256 -> 1, GELU after every layer incl. the last (SconeOcc.py:334-345) ----
         join();
         MCR_REQUIRE(!join_failed, "%s: side stream (join)", who);
-        head_linear(s, 2, hd.feat, FEAT, w.lin1.w + 512, 1856, w.lin1.b, hd.h1, 512, T, 512, FEAT, hd.gbias, rows_per_group, row_group, head_planes,
-                    head_inv_scales, hd.wplanes);
-        head_linear(s, 3, hd.h1, 512, w.lin2.w, 512, w.lin2.b, hd.h2, 256, T, 256, 512, nullptr, 0, nullptr, head_planes, head_inv_scales, hd.wplanes);
-        launch_linear(s, hd.h2, 256, w.lin3.w, w.lin3.b, nullptr, 0, out, 1, T, 1, 256, ACT_GELU, nullptr, 0, 0, 1);
+        head_linear(s, 2, {hd.feat, FEAT}, {w.lin1.w + 512, w.lin1.b}, 1856, {hd.h1, 512}, T, 512, FEAT, {hd.gbias, rows_per_group, row_group},
+                    head_planes, head_inv_scales, hd.wplanes);
+        head_linear(s, 3, {hd.h1, 512}, w.lin2, 512, {hd.h2, 256}, T, 256, 512, {}, head_planes, head_inv_scales, hd.wplanes);
+        launch_linear(s, {hd.h2, 256}, {w.lin3.w, 256}, {w.lin3.b, ACT_GELU}, {out, 1}, T, 1, 256, /*route_rows=*/1);
     }
     MCR_REQUIRE(!join_failed, "%s: side stream (join)", who);
     // range guard of the fp16 split path: an activation beyond the fp16 range (|x| >= 65520) becomes inf in its high plane and
@@ -856,8 +828,8 @@ int mcr_scone_occ_forward_phase(const float* pc_global, int64_t Lg, const float*
     const int64_t qc = fused_all ? Q : std::min<int64_t>(Q, OCC_CHUNK);
     // the planes head (OccHead::planes); without all three fused blobs, or on variants 1 and 5: the fp32-input head (head_linear)
     const bool planes = fused_all && fp16_planes_variant();
-    _Float16* featP = hd.featP();
     const int64_t Tall = B * Q;
+    const Planes featP = planes_over(hd.feat, Tall, FEAT);
     // The x embedding of the planes head (0.3 ms of GEMMs that need nothing but the queries) has two placements.  Where its own side
     // stream (slot 1) exists it is queued there with the EARLY part (phase 1 / the start of the single call), where the GPU is nearly
     // idle for ~0.4 ms (query order, cloud build, the scale-0 search; profiles/r04_nbv_step_breakdown.txt), and the view harmonics
@@ -881,7 +853,7 @@ int mcr_scone_occ_forward_phase(const float* pc_global, int64_t Lg, const float*
     if (late) {
         run_global(gs, w, pc_global, B, Lg, nullptr, ws.glob, hd);
         if (xside)
-            launch_split_to_planes(gs, view_harmonics, 64, featP + 1280, matrix_planes() == 1 ? nullptr : featP + Tall * FEAT + 1280, 1344, B * Q, 64);
+            launch_split_to_planes(gs, {view_harmonics, 64}, featP.cols(1280).keep(matrix_planes()), B * Q, 64);
     }
     if (side) {
         MCR_REQUIRE(hipEventRecord(side->join, side->s) == hipSuccess, "mcr_scone_occ_forward: side stream (record)");
@@ -938,7 +910,7 @@ int mcr_scone_occ_forward_phase(const float* pc_global, int64_t Lg, const float*
                 MCR_LAUNCH_CHECK("knn_grid_kernel");
             } else if (int e = mcr_knn_points(x, pc_scale[sc], nullptr, nullptr, offs, B, Q, M_scale[sc], 16, 1, stream))
                 return e;
-            if (planes) run_local_pct(s, offs, nullptr, FEAT, Tall, local_blobs[sc], featP + sc * 256, featP + Tall * FEAT + sc * 256);
+            if (planes) run_local_pct(s, offs, nullptr, FEAT, Tall, local_blobs[sc], featP.cols(sc * 256));
             else run_local_pct(s, offs, feat + sc * 256, FEAT, Tall, local_blobs[sc]);
             continue;
         }
@@ -956,9 +928,8 @@ int mcr_scone_occ_forward_phase(const float* pc_global, int64_t Lg, const float*
                 } else if (int e = mcr_knn_points(x + (b * Q + q0) * 3, pc_scale[sc] + b * M_scale[sc] * 3, nullptr, nullptr, offs, 1, nq,
                                                   M_scale[sc], 16, 1, stream))
                     return e;
-                if (planes)
-                    run_local_pct(s, offs, nullptr, FEAT, nq, local_blobs[sc], featP + (b * Q + q0) * FEAT + sc * 256,
-                                  featP + Tall * FEAT + (b * Q + q0) * FEAT + sc * 256);
+                if (planes)                              // (row b * Q + q0, column sc * 256 of both planes)
+                    run_local_pct(s, offs, nullptr, FEAT, nq, local_blobs[sc], featP.cols((b * Q + q0) * FEAT + sc * 256));
                 else if (fused)
                     run_local_pct(s, offs, feat + (b * Q + q0) * FEAT + sc * 256, FEAT, nq, local_blobs[sc]);
                 else                                      // layer-by-layer path through HBM
@@ -1033,12 +1004,12 @@ int mcr_scone_occ_forward_ragged_phase(const float* pc_global, const int* global
     MCR_REQUIRE(arena.ok(), "mcr_scone_occ_forward_ragged: workspace overflow (kNN)");
     const OccHead& hd = ws.head;
     const bool planes = fp16_planes_variant();
-    _Float16* featP = hd.featP();
+    const Planes featP = planes_over(hd.feat, T, FEAT);
     auto local_scale = [&](int sc) {                      // one segmented kNN + one fused transformer launch over ALL rows
         // (the whole clouds of scale 0 are the large ones: a launch with few query blocks cuts every job's candidates into slices of
         // ~2048 for more workgroups; slicing the down-sampled clouds of the coarser scales too -- 512 per slice -- measured no better)
         launch_knn16_segmented(s, x, pc_scale[sc], (const long long*)scale_off[sc], knn_blocks, n_blocks, T, ws.offs, ws.knn_split, sc == 0 ? 2048 : 0);
-        if (planes) run_local_pct(s, ws.offs, nullptr, FEAT, T, local_blobs[sc], featP + sc * 256, featP + T * FEAT + sc * 256);
+        if (planes) run_local_pct(s, ws.offs, nullptr, FEAT, T, local_blobs[sc], featP.cols(sc * 256));
         else run_local_pct(s, ws.offs, hd.feat + sc * 256, FEAT, T, local_blobs[sc]);
     };
     if (early) {

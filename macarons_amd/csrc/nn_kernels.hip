@@ -235,8 +235,7 @@ __global__ __launch_bounds__(256) void linear_smallk_rows_kernel(const float* __
 }
 
 // act(X W^T + bias) for K <= 4, written as fp16 hi/lo planes (N % 4 == 0, ldy % 4 == 0)
-void launch_linear_smallk_planes(hipStream_t s, const float* X, int64_t ldx, const float* W, const float* bias, void* Yh, void* Yl,
-                                 int64_t ldy, int64_t M, int N, int K, int act, int Np) {
+void launch_linear_smallk_planes(hipStream_t s, Rows X, const float* W, const float* bias, int act, Planes Y, int64_t M, int N, int K, int Np) {
     if (M <= 0 || N <= 0) return;
     const int Nw = Np > N ? Np : N;                        // outputs written per row
     if (!(Nw % 4 == 0 && Nw / 4 <= 256 && 256 % (Nw / 4) == 0 && K <= 4)) {   // (every caller writes 128 columns from K = 3 or 4)
@@ -247,22 +246,24 @@ void launch_linear_smallk_planes(hipStream_t s, const float* X, int64_t ldx, con
     int rows = LSK_ROWS;
     while (rows > rpp && cdiv(M, rows) < 1024) rows >>= 1;
     rows = std::max(rows, rpp);
-    hipLaunchKernelGGL(linear_smallk_rows_kernel, dim3((unsigned)cdiv(M, rows)), dim3(256), 0, s, X, (long long)ldx, W, (long long)K, bias,
-                       (long long)ldy, (long long)M, Nw, K, act, (_Float16*)Yh, (_Float16*)Yl, N, rows);
+    hipLaunchKernelGGL(linear_smallk_rows_kernel, dim3((unsigned)cdiv(M, rows)), dim3(256), 0, s, X.p, (long long)X.ld, W, (long long)K, bias,
+                       (long long)Y.ld, (long long)M, Nw, K, act, Y.h, Y.l, N, rows);
 }
 
-void launch_linear(hipStream_t s, const float* X, int64_t ldx, const float* W, const float* bias, const float* R,
-                   int64_t ldr, float* Y, int64_t ldy, int64_t M, int N, int K, int act, const float* row_bias,
-                   int64_t rows_per_group, int64_t ldw, int64_t route_rows, const int* row_group) {
+void launch_linear(hipStream_t s, Rows Xr, Rows Wr, const Epilogue& e, RowsOut Yr, int64_t M, int N, int K, int64_t route_rows) {
     if (M <= 0 || N <= 0) return;
-    if (ldw == 0) ldw = K;
+    const float *X = Xr.p, *W = Wr.p, *bias = e.bias, *R = e.residual.p, *row_bias = e.row_bias.p;
+    float* Y = Yr.p;
+    const int64_t ldx = Xr.ld, ldw = Wr.ld, ldr = e.residual.ld, ldy = Yr.ld, rows_per_group = e.row_bias.rows_per_group;
+    const int* row_group = e.row_bias.row_group;
+    const int act = e.act;
     // route_rows < 0: "one sequence of -route_rows rows, matrix path chosen on the layer's SHAPE alone" (the 2048-token encoders
     // on the split-precision variants: a batch of 30 sequences and a single one take the same kernel family, whose column-tile
     // width -- performance only -- follows M)
     const bool by_shape = route_rows < 0;
     if (by_shape) route_rows = -route_rows;
     if (by_shape ? linear3_shape_ok(X, ldx, W, ldw, N, K) : linear3_applicable(X, ldx, W, ldw, route_rows > 0 ? route_rows : M, N, K)) {
-        launch_linear3(s, X, ldx, W, bias, R, ldr, Y, ldy, M, N, K, act, row_bias, rows_per_group, ldw, row_group);
+        launch_linear3(s, Xr, Wr, e, Yr, M, N, K);
         return;
     }
     if (K <= 4 && N % 4 == 0 && ldy % 4 == 0 && aligned16(Y) && !row_bias && M * (N / 4) >= 65536) {
@@ -382,14 +383,13 @@ __global__ __launch_bounds__(256) void layernorm_planes_kernel(const float* __re
     }
 }
 
-void launch_layernorm_planes(hipStream_t s, const float* X, int64_t ldx, const float* g, const float* b, void* Yh, void* Yl, int64_t ldp,
-                             int64_t M, int E) {
+void launch_layernorm_planes(hipStream_t s, Rows X, const float* g, const float* b, Planes Y, int64_t M, int E) {
     if (M <= 0) return;
     dim3 grid((unsigned)cdiv(M, 4));
     const int epl = (E + 63) / 64;
 #define MCR_LNP(EPL) \
-    hipLaunchKernelGGL((layernorm_planes_kernel<EPL>), grid, dim3(256), 0, s, X, (long long)ldx, g, b, (_Float16*)Yh, (_Float16*)Yl, \
-                       (long long)ldp, (long long)M, E)
+    hipLaunchKernelGGL((layernorm_planes_kernel<EPL>), grid, dim3(256), 0, s, X.p, (long long)X.ld, g, b, Y.h, Y.l, \
+                       (long long)Y.ld, (long long)M, E)
     if (epl <= 2) MCR_LNP(2);
     else if (epl <= 4) MCR_LNP(4);
     else MCR_LNP(8);
@@ -415,7 +415,6 @@ void launch_layernorm(hipStream_t s, const float* X, int64_t ldx, const float* g
 // =====================================================================================================
 // mask (optional; Attention.py:24-27): byte (sequence s, head h, query q, key k) at mask[s * ms + h * mh + q * mq + k]; where it is 0 the
 // score is REPLACED by -1e3 before the 1/sqrt(d) scale (not -inf: a fully masked row attends uniformly, as upstream).
-struct AttnMask { const unsigned char* p; long long ms, mh, mq; };
 template <int L, int H, int DQ, int DV, int SPB>
 __global__ __launch_bounds__(SPB* H* L) void attention_small_kernel(const float* __restrict__ qkv, long long ldq,
                                                                    float* __restrict__ out, long long ldo, long long S, AttnMask mk) {
@@ -981,34 +980,34 @@ __global__ void attention_combine_kernel(float* __restrict__ out, long long ldo,
     }
 }
 
-void launch_attention_combine(hipStream_t s, float* out, int64_t ldo, const float* part1, const float* ml, int64_t T, int H, int dv,
-                              void* planes_h, void* planes_l, int64_t ldp) {
-    hipLaunchKernelGGL(attention_combine_kernel, dim3((unsigned)cdiv(T * H * dv, 256)), dim3(256), 0, s, out, (long long)ldo, part1, ml,
-                       (long long)T, H, dv, (_Float16*)planes_h, (_Float16*)planes_l, (long long)ldp);
+void launch_attention_combine(hipStream_t s, RowsOut out, const float* part1, const float* ml, int64_t T, int H, int dv, Planes P) {
+    hipLaunchKernelGGL(attention_combine_kernel, dim3((unsigned)cdiv(T * H * dv, 256)), dim3(256), 0, s, out.p, (long long)out.ld, part1, ml,
+                       (long long)T, H, dv, P.h, P.l, (long long)P.ld);
 }
 
 size_t attention_split_floats(int64_t S, int L, int H, int DV) { return (size_t)S * L * DV + (size_t)4 * S * L * H; }
 
-void launch_attention(hipStream_t s, const float* qkv, int64_t ldq, float* out, int64_t ldo, int64_t S, int L, int H,
-                      int DQK, int DV, const int* lens, float* split_ws, size_t split_ws_floats, bool split_by_length, bool pv_half,
-                      const unsigned char* mask, int64_t mask_seq_stride, int64_t mask_head_stride, int64_t mask_query_stride,
-                      void* planes_h, void* planes_l, int64_t ldp, bool* planes_done) {
-    if (planes_done) *planes_done = false;
-    if (S <= 0 || L <= 0) return;
+// every form of launch_attention; returns whether the result left as `planes`
+static bool attention(hipStream_t s, Rows qkv_, RowsOut out_, int64_t S, int L, int H, int DQK, int DV, const int* lens, AttnSplit sp,
+                      bool pv_half, const AttnMask& mk, Planes planes) {
+    if (S <= 0 || L <= 0) return false;
+    const float* qkv = qkv_.p;
+    float* out = out_.p;
+    const int64_t ldq = qkv_.ld, ldo = out_.ld;
+    const unsigned char* mask = mk.p;
     const int dq = DQK / H, dv = DV / H;
-    const AttnMask mk{mask, (long long)mask_seq_stride, (long long)mask_head_stride, (long long)mask_query_stride};
     if (!lens && L == 16 && H == 4 && dq == 8 && dv == 32) {
         constexpr int SPB = 4;
         hipLaunchKernelGGL((attention_small_kernel<16, 4, 8, 32, SPB>), dim3((unsigned)cdiv(S, SPB)), dim3(SPB * 4 * 16), 0,
                            s, qkv, (long long)ldq, out, (long long)ldo, (long long)S, mk);
-        return;
+        return false;
     }
     constexpr int KS = 4;
     dim3 grid((unsigned)cdiv(L, 64), (unsigned)H, (unsigned)S);
     const bool al16 = aligned16(qkv) && ldq % 4 == 0 && (H * dq) % 4 == 0;
     // one or two long sequences leave half the chip idle (L = 2048, 4 heads: 128 blocks): split the keys over two blocks
-    const bool split = split_ws && split_ws_floats >= attention_split_floats(S, L, H, DV) && L >= 512 &&
-                       2 * S <= 65535 && (split_by_length || (int64_t)grid.x * H * S <= 256);
+    const bool split = sp.ws && sp.floats >= attention_split_floats(S, L, H, DV) && L >= 512 &&
+                       2 * S <= 65535 && (sp.mode == 1 || (sp.mode < 0 && (int64_t)grid.x * H * S <= 256));
     if (al16 && ((dq == 8 && dv == 32) || (dq == 16 && dv == 64))) {
 #define MCR_ATT(DQ_, DV_, SPLIT_, GRID_, P1_, ML_)                                                                                    \
     do {                                                                                                                               \
@@ -1036,8 +1035,8 @@ void launch_attention(hipStream_t s, const float* qkv, int64_t ldq, float* out, 
         const dim3 grid2((unsigned)cdiv(L, 128), (unsigned)H, (unsigned)(split ? 2 * S : S));
         const bool qg2 = !mask && (int64_t)grid2.x * grid2.y * grid2.z >= 512;
         if (split) {
-            float* part1 = split_ws;
-            float* ml = split_ws + (size_t)S * L * DV;
+            float* part1 = sp.ws;
+            float* ml = sp.ws + (size_t)S * L * DV;
             const dim3 g2(grid.x, grid.y, (unsigned)(2 * S));
             if (qg2) {
                 if (dq == 8) MCR_ATT2(8, 32, true, grid2, part1, ml);
@@ -1047,8 +1046,8 @@ void launch_attention(hipStream_t s, const float* qkv, int64_t ldq, float* out, 
             } else {
                 MCR_ATT(16, 64, true, g2, part1, ml);
             }
-            launch_attention_combine(s, out, ldo, part1, ml, S * L, H, dv, planes_h, planes_l, ldp);
-            if (planes_done) *planes_done = planes_h != nullptr;
+            launch_attention_combine(s, out_, part1, ml, S * L, H, dv, planes);
+            return planes.h != nullptr;
         } else if (qg2) {
             if (dq == 8) MCR_ATT2(8, 32, false, grid2, (float*)nullptr, (float*)nullptr);
             else MCR_ATT2(16, 64, false, grid2, (float*)nullptr, (float*)nullptr);
@@ -1059,11 +1058,11 @@ void launch_attention(hipStream_t s, const float* qkv, int64_t ldq, float* out, 
         }
 #undef MCR_ATT2
 #undef MCR_ATT
-        return;
+        return false;
     }
     if (lens || mask) {
         refuse("launch_attention: per-sequence lengths / masks need the MFMA kernel (16-byte aligned qkv, head dims (8,32) or (16,64))");
-        return;
+        return false;
     }
     if (dq == 8 && dv == 32)
         hipLaunchKernelGGL((attention_flash_kernel<8, 32, KS>), grid, dim3(64 * KS), 0, s, qkv, (long long)ldq, out,
@@ -1073,6 +1072,19 @@ void launch_attention(hipStream_t s, const float* qkv, int64_t ldq, float* out, 
                            (long long)ldo, L, H);
     else
         refuse("launch_attention: unsupported head dims dq=%d dv=%d", dq, dv);
+    return false;
+}
+void launch_attention(hipStream_t s, Rows qkv, RowsOut out, int64_t S, int L, int H, int DQK, int DV, const int* lens, AttnSplit split,
+                      bool pv_half) {
+    attention(s, qkv, out, S, L, H, DQK, DV, lens, split, pv_half, AttnMask{}, Planes{});
+}
+void launch_attention(hipStream_t s, Rows qkv, RowsOut out, int64_t S, int L, int H, int DQK, int DV, const int* lens, AttnSplit split,
+                      const AttnMask& mask) {
+    attention(s, qkv, out, S, L, H, DQK, DV, lens, split, false, mask, Planes{});
+}
+bool launch_attention(hipStream_t s, Rows qkv, RowsOut out, int64_t S, int L, int H, int DQK, int DV, const int* lens, AttnSplit split,
+                      bool pv_half, Planes planes) {
+    return attention(s, qkv, out, S, L, H, DQK, DV, lens, split, pv_half, AttnMask{}, planes);
 }
 
 // =====================================================================================================

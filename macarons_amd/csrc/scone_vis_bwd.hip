@@ -173,7 +173,7 @@ __global__ __launch_bounds__(256) void vb_transpose_kernel(const float* __restri
 void gemm_dx(hipStream_t s, const float* dZ, int64_t ldz, const float* W, int64_t ldw, float* dX, int64_t ldx, int64_t M, int N, int K,
              bool accumulate, float* wt) {
     hipLaunchKernelGGL(vb_transpose_kernel, dim3((unsigned)cdiv((int64_t)N * K, 256)), dim3(256), 0, s, W, (long long)ldw, wt, N, K);
-    launch_linear(s, dZ, ldz, wt, nullptr, accumulate ? dX : nullptr, ldx, dX, ldx, M, K, N, ACT_NONE, nullptr, 0, N, 1);
+    launch_linear(s, {dZ, ldz}, {wt, N}, {nullptr, ACT_NONE, {accumulate ? dX : nullptr, ldx}}, {dX, ldx}, M, K, N, /*route_rows=*/1);
 }
 
 // dW[N, K] = dZ^T X, db[N] = sum_rows dZ (either may be NULL); part: vb_gradw_floats(M, N, K) floats
@@ -761,9 +761,8 @@ size_t vb_part_floats(int64_t T) {
 }
 
 // the fp32 GEMMs of the forward (launch_linear routed on one row: never the split-precision kernels)
-void vb_linear(hipStream_t s, const float* X, int64_t ldx, const LinW& w, const float* R, int64_t ldr, float* Y, int64_t ldy, int64_t T,
-               int N, int K, int act) {
-    launch_linear(s, X, ldx, w.w, w.b, R, ldr, Y, ldy, T, N, K, act, nullptr, 0, 0, 1);
+void vb_linear(hipStream_t s, Rows X, const LinW& w, Rows R, RowsOut Y, int64_t T, int N, int K, int act) {
+    launch_linear(s, X, {w.w, K}, {w.b, act, R}, Y, T, N, K, /*route_rows=*/1);
 }
 
 // x_out = Encoder(x) (x_out NULL: the interior for the backward, LSE included).  The boundary pass (x_out given) needs no LSE: it takes
@@ -771,14 +770,14 @@ void vb_linear(hipStream_t s, const float* X, int64_t ldx, const LinW& w, const 
 void vb_encoder_fwd(hipStream_t s, const EncW& w, const float* x, float* x_out, const VbInterior& I, int64_t B, int N, const int* lens) {
     const int64_t T = B * N;
     launch_layernorm(s, x, VB_E, w.n1g, w.n1b, I.h1, VB_E, T, VB_E);
-    vb_linear(s, I.h1, VB_E, w.qkv, nullptr, 0, I.qkv, VB_W3, T, VB_W3, VB_E, ACT_NONE);
-    if (x_out) launch_attention(s, I.qkv, VB_W3, I.O, VB_E, B, N, VB_H, 64, VB_E, lens, nullptr, 0, false, /*pv_half=*/false);
+    vb_linear(s, {I.h1, VB_E}, w.qkv, {}, {I.qkv, VB_W3}, T, VB_W3, VB_E, ACT_NONE);
+    if (x_out) launch_attention(s, {I.qkv, VB_W3}, {I.O, VB_E}, B, N, VB_H, 64, VB_E, lens, AttnSplit{}, /*pv_half=*/false);
     else launch_attn_fwd(s, I.qkv, VB_W3, I.O, VB_E, I.lse, B, N, VB_H, lens, I.part);
-    vb_linear(s, I.O, VB_E, w.out, x, VB_E, I.xm, VB_E, T, VB_E, VB_E, ACT_NONE);
+    vb_linear(s, {I.O, VB_E}, w.out, {x, VB_E}, {I.xm, VB_E}, T, VB_E, VB_E, ACT_NONE);
     launch_layernorm(s, I.xm, VB_E, w.n2g, w.n2b, I.h2, VB_E, T, VB_E);
-    vb_linear(s, I.h2, VB_E, w.ff1, nullptr, 0, I.z, 2 * VB_E, T, 2 * VB_E, VB_E, ACT_NONE);
+    vb_linear(s, {I.h2, VB_E}, w.ff1, {}, {I.z, 2 * VB_E}, T, 2 * VB_E, VB_E, ACT_NONE);
     launch_gelu(s, I.z, 2 * VB_E, I.g, 2 * VB_E, T, 2 * VB_E, 0);
-    if (x_out) vb_linear(s, I.g, 2 * VB_E, w.ff2, I.xm, VB_E, x_out, VB_E, T, VB_E, 2 * VB_E, ACT_NONE);
+    if (x_out) vb_linear(s, {I.g, 2 * VB_E}, w.ff2, {I.xm, VB_E}, {x_out, VB_E}, T, VB_E, 2 * VB_E, ACT_NONE);
 }
 
 // The workspace of mcr_scone_vis_backward over T = B * N tokens
@@ -954,16 +953,16 @@ int mcr_scone_vis_backward(const float* pts, const float* view_harmonics, const 
     auto DW = [&](int slot) { return d_weights ? d_weights[slot] : nullptr; };
 
     // ---- forward of the fp32 network: boundaries X0..X3, the embedding's and the head's pre-activations
-    vb_linear(s, pts, 4, w.l1, nullptr, 0, z1, VB_F, T, VB_F, 4, ACT_NONE);
+    vb_linear(s, {pts, 4}, w.l1, {}, {z1, VB_F}, T, VB_F, 4, ACT_NONE);
     launch_gelu(s, z1, VB_F, g1, VB_F, T, VB_F, 0);
-    vb_linear(s, g1, VB_F, w.l2, nullptr, 0, X[0], VB_E, T, VB_F, VB_F, ACT_NONE);
+    vb_linear(s, {g1, VB_F}, w.l2, {}, {X[0], VB_E}, T, VB_F, VB_F, ACT_NONE);
     launch_colmax_broadcast(s, X[0], VB_E, X[0] + VB_F, VB_E, B, iN, VB_F, lengths, pts, 4, 4, X[0] + 2 * VB_F);
     for (int e = 0; e < 3; ++e) vb_encoder_fwd(s, w.enc[e], X[e], X[e + 1], I, B, iN, lengths);
     launch_layernorm(s, X[3], VB_E, w.ng, w.nb, hn, VB_E, T, VB_E);
-    vb_linear(s, hn, VB_E, w.fc1, nullptr, 0, zf1, 192, T, 192, VB_E, ACT_NONE);
+    vb_linear(s, {hn, VB_E}, w.fc1, {}, {zf1, 192}, T, 192, VB_E, ACT_NONE);
     launch_gelu(s, zf1, 192, c2, VB_E, T, 192, 0);
     launch_copy2d(s, view_harmonics, 64, c2 + 192, VB_E, T, 64);
-    vb_linear(s, c2, VB_E, w.fc2, nullptr, 0, zf2, 128, T, 128, VB_E, ACT_NONE);
+    vb_linear(s, {c2, VB_E}, w.fc2, {}, {zf2, 128}, T, 128, VB_E, ACT_NONE);
     launch_gelu(s, zf2, 128, gf2, 128, T, 128, 0);
 
     // ---- head (SconeVis.py:143-152), backwards
