@@ -204,7 +204,15 @@ int mcr_linear_planes_dot(const void* Xh, const void* Xl, int64_t ldx, const voi
  *   dimension must cover its row.  mcr_attention_backward: ldq, ld_dout, ld_dqkv multiples of 4; qkv, d_out, d_qkv and workspace
  *   16-byte aligned.  mcr_linear_backward, mcr_layernorm_backward, mcr_colmax_backward: any leading dimension >= the row, operands
  *   and workspace 4-byte aligned (scalar accesses throughout).  mcr_linear_backward reads X for db as well as for dW (db rides on
- *   the dW product): X may be NULL only when both are. */
+ *   the dW product): X may be NULL only when both are.
+ * mcr_attention_backward_pct: mcr_attention_backward for the PCTransformer's heads: 4 heads of per-head widths 8 (q, k) and 32 (v),
+ *   packed rows [q 32 | k 32 | v 128], scores / sqrt(8); same arguments, leading dimensions and alignment.  L == 16 (any S): one wave
+ *   per sequence rebuilds the soft-max in registers and writes d_qkv alone -- no workspace is touched (workspace may be NULL), and
+ *   lens must be NULL (refused otherwise).  Any other L: the recomputing three-pass scheme above, S <= 65535, lens honoured.
+ *   workspace: mcr_attention_backward_pct_workspace_bytes(S, L).
+ * mcr_pool_max_avg_backward: for mcr_pool_max_avg given dY [S, ldy] = [d_max (E) | d_avg (E)]: dX[(s, r), c] = d_avg[s, c] / L, plus
+ *   d_max[s, c] on the lowest row r holding the column's max (torch.max(dim)'s choice on ties).  Written, not accumulated.  Any S;
+ *   leading dimensions >= the row (ldy >= 2 E), operands 4-byte aligned. */
 size_t mcr_attention_backward_workspace_bytes(int64_t S, int64_t L, int n_heads, int v_dim);
 int mcr_attention_backward(const float* qkv, int64_t ldq, const float* d_out, int64_t ld_dout, float* d_qkv, int64_t ld_dqkv, int64_t S,
                            int64_t L, int n_heads, int qk_dim, int v_dim, const int* lens, void* workspace, size_t workspace_bytes,
@@ -219,6 +227,12 @@ int mcr_layernorm_backward(const float* X, int64_t ldx, const float* gamma, cons
                            void* stream);
 int mcr_colmax_backward(const float* X, int64_t ldx, const float* d_bcast, int64_t ldg, float* dX, int64_t ld_dx, int64_t S, int64_t L,
                         int E, const int* lens, void* stream);
+size_t mcr_attention_backward_pct_workspace_bytes(int64_t S, int64_t L);
+int mcr_attention_backward_pct(const float* qkv, int64_t ldq, const float* d_out, int64_t ld_dout, float* d_qkv, int64_t ld_dqkv, int64_t S,
+                               int64_t L, int n_heads, int qk_dim, int v_dim, const int* lens, void* workspace, size_t workspace_bytes,
+                               void* stream);
+int mcr_pool_max_avg_backward(const float* X, int64_t ldx, const float* dY, int64_t ldy, float* dX, int64_t ld_dx, int64_t S, int64_t L,
+                              int E, void* stream);
 
 /* ---- network forwards -----------------------------------------------------------------------------------
  * Weight tables are arrays of device pointers to contiguous fp32 tensors in nn.Module layout ([out,in] weights):
@@ -280,6 +294,22 @@ size_t mcr_scone_vis_backward_workspace_bytes(int64_t B, int64_t N);
 int mcr_scone_vis_backward(const float* pts, const float* view_harmonics, const float* d_out, int64_t B, int64_t N,
                            const float* const* weights, int n_weights, const int* lengths, float* const* d_weights, float* d_pts,
                            float* d_view_harmonics, void* workspace, size_t workspace_bytes, void* stream);
+/* mcr_pc_transformer_backward: gradient of mcr_pc_transformer_forward given d_features [S, feature_dim], computed on the fp32 network
+ *   whatever the call's variant (as mcr_scone_vis_backward).  The forward is recomputed: the residual stream at the three encoder
+ *   boundaries and the embedding's pre-activation are kept, each encoder's interior is rebuilt just before its backward.
+ *   weights: the PCT table (32 entries; a PLANES / END PLANES tail is accepted and ignored).
+ *   d_weights (may be NULL: no parameter gradients): 32 DEVICE pointers in the table's order and shapes (the packed qkv weight
+ *   [192,128] and bias [192] one entry each); written, not accumulated.  d_pc [S,L,3] may be NULL; both NULL: returns 0 at once.
+ *   L == 16 || S <= 65535, as the forward.  Sequences of 16 tokens are processed INSIDE the entry in chunks of
+ *   mcr_pc_transformer_backward_chunk(S, L) sequences -- a function of (S, L) alone -- whose weight gradients are summed in chunk
+ *   order, so the workspace does not grow with S beyond one chunk and two calls give identical bits; other lengths run as one chunk.
+ *   pc, d_features and the workspace 16-byte aligned.  workspace: mcr_pc_transformer_backward_workspace_bytes(S, L) bytes.
+ *   Deterministic (no float atomics), no host synchronisation. */
+int mcr_pc_transformer_backward_chunk(int64_t S, int64_t L);
+size_t mcr_pc_transformer_backward_workspace_bytes(int64_t S, int64_t L);
+int mcr_pc_transformer_backward(const float* pc, const float* d_features, int64_t S, int64_t L, int feature_dim,
+                                const float* const* weights, int n_weights, float* const* d_weights, float* d_pc, void* workspace,
+                                size_t workspace_bytes, void* stream);
 size_t mcr_scone_occ_workspace_bytes(int64_t B, int64_t Q, int64_t Lg);
 int mcr_scone_occ_forward(const float* pc_global, int64_t Lg, const float* const* pc_scale, const int64_t* M_scale,
                           const float* x, const float* view_harmonics, float* out, int64_t B, int64_t Q,

@@ -3,9 +3,12 @@ macarons/trainers/pretrain_scone_vis.py:224, through SconeOcc.forward at pretrai
 
 The forward passes stay on the hand-written HIP kernels.  SconeVis.forward's backward is HIP too (SconeVisFunction below:
 mcr_scone_vis_backward, scone_vis_bwd.hip), as is the scorer's (the Autograd kernels of torch.ops.macarons.sh_coverage_gain /
-sh_visibilities).  SconeOcc's entry point is still wrapped in a torch.autograd.Function whose backward RECOMPUTES the same
+sh_visibilities) and that of PCTransformer.forward called on its own (PCTransformerFunction below: mcr_pc_transformer_backward).
+SconeOcc's entry point is still wrapped in a torch.autograd.Function whose backward RECOMPUTES the same
 mathematics with plain torch ops on the same device (composite functions below, written against the modules' own parameters) under
-autograd and back-propagates through that; env MCR_SCONE_VIS_BWD=composite puts SconeVis back on that path (A/B).  The composites
+autograd and back-propagates through that; env MCR_SCONE_VIS_BWD=composite puts SconeVis back on that path (A/B).  Opt-in, env
+MCR_SCONE_OCC_BWD=pct: that recomputation evaluates SconeOcc's four PCTransformers -- almost all of its work -- through
+PCTransformerFunction (HIP forward and backward); the gather, the offsets, the x-embedding and the head stay torch.  The composites
 are ordinary differentiable torch code, so they are also what the parity tests differentiate numerically (tests/test_autograd.py:
 fp64 finite differences on CPU; on the GPU the composite forward must reproduce the HIP forward to 1e-4, which makes its gradient
 the gradient of the kernels' function) and the second reference of the HIP backward's tests.
@@ -130,8 +133,19 @@ def pc_transformer(pct, x):
     return torch.cat((x.max(dim=1)[0], x.mean(dim=1)), dim=-1)
 
 
+def scone_occ_backward_mode():
+    """'composite' (default) or 'pct' (env MCR_SCONE_OCC_BWD=pct: the four PCTransformers of the recomputation on the HIP backward)."""
+    return "pct" if os.environ.get("MCR_SCONE_OCC_BWD", "").lower() == "pct" else "composite"
+
+
 def scone_occ(model, pc_global, scales, x, view_harmonics, knn_idx):
     """SconeOcc.forward (SconeOcc.py:250-347) given the down-sampled clouds and, per scale, the neighbour indices [B,Q,16]."""
+    if scone_occ_backward_mode() == "pct":          # the module's own forward: PCTransformerFunction where a gradient is needed
+        return _scone_occ(lambda pct, pc: pct(pc), model, pc_global, scales, x, view_harmonics, knn_idx)
+    return _scone_occ(pc_transformer, model, pc_global, scales, x, view_harmonics, knn_idx)
+
+
+def _scone_occ(pc_transformer, model, pc_global, scales, x, view_harmonics, knn_idx):
     B, Q = x.shape[0], x.shape[1]
     feats = [pc_transformer(model.global_transformer, pc_global)[:, None, :].expand(-1, Q, -1)]
     for pc_s, idx, lt in zip(scales, knn_idx, model.local_transformers):
@@ -222,3 +236,36 @@ class SconeVisFunction(torch.autograd.Function):
             grads.append(g)
         return (None, None, None, None, d_pts.to(pts.dtype) if d_pts is not None else None,
                 d_vh.to(vh.dtype) if d_vh is not None else None, *grads)
+
+
+# ---- PCTransformer: HIP forward + HIP backward -----------------------------------------------------------------------------------
+class PCTransformerFunction(torch.autograd.Function):
+    """apply(hip_fn, table_fn, slots, feature_dim, pc, *params): forward = hip_fn(pc) without a graph; backward =
+    ops.pc_transformer_backward (mcr_pc_transformer_backward: the gradient of the fp32 network, HIP kernels only) on the weight table
+    table_fn() returns.  slots[j] = (table index, row slice or None) of params[j] -- the packed qkv entries hand rows 0:32, 32:64 and
+    64:192 to w_q, w_k and w_v.  Differentiable once."""
+
+    @staticmethod
+    def forward(ctx, hip_fn, table_fn, slots, feature_dim, pc, *params):
+        ctx.table_fn, ctx.slots, ctx.feature_dim = table_fn, slots, feature_dim
+        ctx.param_dtypes = tuple(p.dtype for p in params)
+        ctx.save_for_backward(pc)
+        with torch.no_grad():
+            return hip_fn(pc)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        if torch.is_grad_enabled():
+            raise RuntimeError("PCTransformer.forward is differentiable once: its HIP backward builds no graph (create_graph is not supported)")
+        from . import ops
+        pc, = ctx.saved_tensors
+        need_p, need_w = ctx.needs_input_grad[4], any(ctx.needs_input_grad[5:])
+        d_w, d_pc = ops.pc_transformer_backward(pc, grad_out, ctx.table_fn(), ctx.feature_dim, need=(need_w, need_p))
+        grads = []
+        for j, (idx, rows) in enumerate(ctx.slots):
+            if not ctx.needs_input_grad[5 + j]:
+                grads.append(None)
+                continue
+            g = d_w[idx] if rows is None else d_w[idx][rows[0]:rows[1]]
+            grads.append(g.to(ctx.param_dtypes[j]))
+        return (None, None, None, None, d_pc.to(pc.dtype) if d_pc is not None else None, *grads)

@@ -22,6 +22,13 @@
 // Numerics: fp32 throughout -- VALU FMA in the attention and weight-gradient kernels, the forward's exact-fp32 GEMM kernels
 // (launch_linear routed to the fp32 MFMA kernel) in the recompute and the dX products.  The fp16 planes path is never taken, whatever the caller's variant: the result is the gradient of
 // the fp32 network at the given inputs (on variants 6 and 7 too).  No float atomics: two calls give identical bits.
+//
+// PCTransformer backward (SconeOcc.py:45-130: SconeOcc's global transformer on one 2048-token sequence per cloud, its three local ones on
+// B * Q sequences of 16 tokens): mcr_pc_transformer_backward, same scheme on the same launchers at E = 128.  The encoder's forward and
+// backward (vb_encoder_fwd / vb_encoder_bwd) are shared with SconeVis and take the width; the attention kernels are compiled for the
+// per-head widths (16, 64) and (8, 32).  Sequences of 16 tokens have a fused attention backward of their own (a16_bwd_kernel: one wave per
+// sequence, nothing but d_qkv written) and are processed in chunks of PB_CHUNK16 sequences INSIDE the entry, their weight gradients
+// summed in chunk order: the workspace holds one chunk whatever S is.  The tail's pooling has its own backward (pb_pool_bwd_kernel).
 #include "nn_kernels.h"
 #include "net_layout.h"
 #include <algorithm>
@@ -34,9 +41,9 @@ namespace {
 typedef float f2 __attribute__((ext_vector_type(2)));
 
 constexpr int VB_E = 256, VB_F = 126, VB_H = 4;
-constexpr int AB_DQK = 16, AB_DV = 64;                 // per-head q / k and v widths of the attention kernels
+// The attention kernels are compiled for two pairs of per-head widths <DQ (q, k), DV (v)>: (16, 64) SconeVis, (8, 32) PCTransformer
 constexpr int AB_TILE = 32;                            // keys (queries) staged per wave and step
-constexpr float AB_SCALE = 0.25f;                      // 1 / sqrt(16)
+template <int DQ> constexpr float ab_scale() { return DQ == 16 ? 0.25f : 0.35355339059327379f; }   // 1 / sqrt(DQ), DQ = 16 or 8
 
 __device__ __forceinline__ float gelu_f(float z) { return 0.5f * z * (1.0f + erff(z * 0.70710678118654752f)); }
 __device__ __forceinline__ float gelu_d(float z) {
@@ -310,23 +317,25 @@ void launch_colmax_bwd(hipStream_t s, const float* X, int64_t ldx, const float* 
 }
 
 // ---- attention -----------------------------------------------------------------------------------------------------------------------
-// Packed rows qkv[m*ldq + ...] = [q (H*16) | k (H*16) | v (H*64)], head h owning q / k channels h*16.. and v channels h*64..;
+// Packed rows qkv[m*ldq + ...] = [q (H*DQ) | k (H*DQ) | v (H*DV)], head h owning q / k channels h*DQ.. and v channels h*DV..;
 // S sequences of L rows; keys of sequence s: its first kmax = min(L, max(1, lens[s])) rows.  Grid (row blocks of 64, H, S), 4 waves.
 __device__ __forceinline__ int ab_kmax(const int* lens, long long s, int L) { return lens ? min(L, max(1, lens[s])) : L; }
 
-__device__ __forceinline__ void ab_load16(const float* p, f2 (&d)[8], float scale) {
+template <int N2>
+__device__ __forceinline__ void ab_load(const float* p, f2 (&d)[N2], float scale) {
 #pragma unroll
-    for (int c = 0; c < 4; ++c) {
+    for (int c = 0; c < N2 / 2; ++c) {
         const float4 v = *reinterpret_cast<const float4*>(p + 4 * c);
         d[2 * c] = f2{v.x * scale, v.y * scale};
         d[2 * c + 1] = f2{v.z * scale, v.w * scale};
     }
 }
 
-__device__ __forceinline__ float ab_dot16(const f2 (&a)[8], const float* b) {
+template <int N2>
+__device__ __forceinline__ float ab_dotq(const f2 (&a)[N2], const float* b) {
     f2 acc{0.f, 0.f};
 #pragma unroll
-    for (int c = 0; c < 4; ++c) {
+    for (int c = 0; c < N2 / 2; ++c) {
         const float4 v = *reinterpret_cast<const float4*>(b + 4 * c);
         acc = __builtin_elementwise_fma(a[2 * c], f2{v.x, v.y}, acc);
         acc = __builtin_elementwise_fma(a[2 * c + 1], f2{v.z, v.w}, acc);
@@ -334,10 +343,11 @@ __device__ __forceinline__ float ab_dot16(const f2 (&a)[8], const float* b) {
     return acc.x + acc.y;
 }
 
-__device__ __forceinline__ float ab_dot64(const f2 (&a)[32], const float* b) {
+template <int N2>
+__device__ __forceinline__ float ab_dotv(const f2 (&a)[N2], const float* b) {
     f2 acc0{0.f, 0.f}, acc1{0.f, 0.f};
 #pragma unroll
-    for (int c = 0; c < 16; c += 2) {
+    for (int c = 0; c < N2 / 2; c += 2) {
         const float4 v = *reinterpret_cast<const float4*>(b + 4 * c);
         const float4 u = *reinterpret_cast<const float4*>(b + 4 * c + 4);
         acc0 = __builtin_elementwise_fma(a[2 * c], f2{v.x, v.y}, acc0);
@@ -382,9 +392,9 @@ inline int ab_nsplit(int64_t S, int L, int H) {
     const int64_t blocks = S * H * cdiv(L, 64);
     return blocks >= 512 ? 1 : blocks >= 256 ? 2 : 4;
 }
-inline size_t ab_part_floats(int64_t S, int L, int H) {
+inline size_t ab_part_floats(int64_t S, int L, int H, int dq = 16, int dv = 64) {
     const int ns = ab_nsplit(S, L, H);
-    return ns > 1 ? (size_t)ns * S * L * H * (AB_DQK + AB_DV) : 0;   // (>= the forward's H * 66 and the dq parts' H * 16 per row)
+    return ns > 1 ? (size_t)ns * S * L * H * (dq + dv) : 0;   // (>= the forward's H * (dv + 2) and the dq parts' H * dq per row)
 }
 __device__ __forceinline__ void ab_part_tiles(int n, int nsplit, int sp, int& t_lo, int& t_hi) {
     const int tiles = (n + AB_TILE - 1) / AB_TILE, per = (tiles + nsplit - 1) / nsplit;
@@ -393,29 +403,30 @@ __device__ __forceinline__ void ab_part_tiles(int n, int nsplit, int sp, int& t_
 }
 
 // O = (sum_p e^{m_p - m} o_p) / l, LSE = m + log l, l = sum_p e^{m_p - m} l_p over the key parts, in part order; one thread per (row, head)
+template <int DV>
 __global__ __launch_bounds__(256) void ab_fwd_merge_kernel(const float* __restrict__ part, int nsplit, long long TH, int H, float* __restrict__ O,
                                                            long long ldo, float* __restrict__ lse) {
     const long long e = blockIdx.x * 256ll + threadIdx.x;
     if (e >= TH) return;
     const long long row = e / H;
     const int h = (int)(e - row * H);
-    float m = -INFINITY, l = 0.f, o[AB_DV];
+    float m = -INFINITY, l = 0.f, o[DV];
 #pragma unroll
-    for (int c = 0; c < AB_DV; ++c) o[c] = 0.f;
+    for (int c = 0; c < DV; ++c) o[c] = 0.f;
     for (int p = 0; p < nsplit; ++p) {
-        const float* pp = part + (p * TH + e) * (AB_DV + 2);
+        const float* pp = part + (p * TH + e) * (DV + 2);
         const float m2 = pp[0];
         if (m2 == -INFINITY) continue;
         const float mn = fmaxf(m, m2), a1 = __expf(m - mn), a2 = __expf(m2 - mn);
         l = l * a1 + pp[1] * a2;
 #pragma unroll
-        for (int c = 0; c < AB_DV; ++c) o[c] = o[c] * a1 + pp[2 + c] * a2;
+        for (int c = 0; c < DV; ++c) o[c] = o[c] * a1 + pp[2 + c] * a2;
         m = mn;
     }
     const float inv = 1.0f / l;
-    float* op = O + row * ldo + h * AB_DV;
+    float* op = O + row * ldo + h * DV;
 #pragma unroll
-    for (int c = 0; c < AB_DV; ++c) op[c] = o[c] * inv;
+    for (int c = 0; c < DV; ++c) op[c] = o[c] * inv;
     lse[e] = m + logf(l);
 }
 
@@ -431,41 +442,42 @@ __global__ __launch_bounds__(256) void ab_sum_parts_kernel(const float* __restri
     out[r * ldo + c] = acc * scale;
 }
 
-constexpr int AB_KV_TILE = AB_TILE * (AB_DQK + AB_DV);            // floats of one wave's K | V tile
-constexpr int AB_FWD_LDS = 3 * 64 * (AB_DV + 2);                   // the combine buffer (> 4 staging tiles)
-static_assert(AB_FWD_LDS >= 4 * AB_KV_TILE, "LDS plan");
+template <int DQ, int DV> constexpr int AB_KV_TILE = AB_TILE * (DQ + DV);            // floats of one wave's K | V tile
+template <int DQ, int DV> constexpr int AB_FWD_LDS = 3 * 64 * (DV + 2);                   // the combine buffer (> 4 staging tiles)
+static_assert(AB_FWD_LDS<16, 64> >= 4 * AB_KV_TILE<16, 64> && AB_FWD_LDS<8, 32> >= 4 * AB_KV_TILE<8, 32>, "LDS plan");
 
-// O = softmax(q k^T / 4) v and LSE = m + log(l) per (row, head).  Each wave runs the key tiles w, w + 4, ... with an online soft-max.
+// O = softmax(q k^T / sqrt(DQ)) v and LSE = m + log(l) per (row, head).  Each wave runs the key tiles w, w + 4, ... with an online soft-max.
+template <int DQ, int DV>
 __global__ __launch_bounds__(256) void ab_fwd_kernel(const float* __restrict__ qkv, long long ldq, float* __restrict__ O, long long ldo,
                                                      float* __restrict__ lse, int L, int H, const int* __restrict__ lens,
                                                      float* __restrict__ part, int nsplit) {
-    __shared__ float4 smem4[AB_FWD_LDS / 4];
+    __shared__ float4 smem4[AB_FWD_LDS<DQ, DV> / 4];
     float* smem = reinterpret_cast<float*>(smem4);
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, h = blockIdx.y;
     const long long s = blockIdx.z / nsplit;
     const int sp = blockIdx.z - (int)s * nsplit;
     const int qi = blockIdx.x * 64 + lane;
     const int kmax = ab_kmax(lens, s, L);
-    const int QK = H * AB_DQK;
+    const int QK = H * DQ;
     const float* base = qkv + s * L * ldq;
-    f2 q[8];
-    if (qi < L) ab_load16(base + (long long)qi * ldq + h * AB_DQK, q, AB_SCALE);
+    f2 q[DQ / 2];
+    if (qi < L) ab_load(base + (long long)qi * ldq + h * DQ, q, ab_scale<DQ>());
     else
 #pragma unroll
-        for (int c = 0; c < 8; ++c) q[c] = f2{0.f, 0.f};
-    f2 o[32];
+        for (int c = 0; c < DQ / 2; ++c) q[c] = f2{0.f, 0.f};
+    f2 o[DV / 2];
 #pragma unroll
-    for (int c = 0; c < 32; ++c) o[c] = f2{0.f, 0.f};
+    for (int c = 0; c < DV / 2; ++c) o[c] = f2{0.f, 0.f};
     float m = -INFINITY, l = 0.f;
-    float* kt = smem + w * AB_KV_TILE;
-    float* vt = kt + AB_TILE * AB_DQK;
+    float* kt = smem + w * AB_KV_TILE<DQ, DV>;
+    float* vt = kt + AB_TILE * DQ;
     int t_lo, n_tiles;
     ab_part_tiles(kmax, nsplit, sp, t_lo, n_tiles);
     for (int t0 = t_lo; t0 < n_tiles; t0 += 4) {
         const int t = t0 + w;
         if (t < n_tiles) {
-            ab_stage<AB_DQK / 4>(kt, base + QK + h * AB_DQK, ldq, t * AB_TILE, kmax, lane, 1.f);
-            ab_stage<AB_DV / 4>(vt, base + 2 * QK + h * AB_DV, ldq, t * AB_TILE, kmax, lane, 1.f);
+            ab_stage<DQ / 4>(kt, base + QK + h * DQ, ldq, t * AB_TILE, kmax, lane, 1.f);
+            ab_stage<DV / 4>(vt, base + 2 * QK + h * DV, ldq, t * AB_TILE, kmax, lane, 1.f);
         }
         __syncthreads();
         if (t < n_tiles) {
@@ -474,31 +486,31 @@ __global__ __launch_bounds__(256) void ab_fwd_kernel(const float* __restrict__ q
             float mt = m;
 #pragma unroll
             for (int j = 0; j < AB_TILE; ++j) {
-                sc[j] = j < nk ? ab_dot16(q, kt + j * AB_DQK) : -INFINITY;
+                sc[j] = j < nk ? ab_dotq(q, kt + j * DQ) : -INFINITY;
                 mt = fmaxf(mt, sc[j]);
             }
             const float alpha = __expf(m - mt);
             l *= alpha;
             const f2 aa{alpha, alpha};
 #pragma unroll
-            for (int c = 0; c < 32; ++c) o[c] *= aa;
+            for (int c = 0; c < DV / 2; ++c) o[c] *= aa;
 #pragma unroll
             for (int j = 0; j < AB_TILE; ++j) {
                 const float p = __expf(sc[j] - mt);
                 l += p;
-                ab_axpy(o, p, vt + j * AB_DV);
+                ab_axpy(o, p, vt + j * DV);
             }
             m = mt;
         }
         __syncthreads();
     }
-    constexpr int F = AB_DV + 2;
+    constexpr int F = DV + 2;
     if (w > 0) {
         float* cb = smem + (w - 1) * F * 64;
         cb[lane] = m;
         cb[64 + lane] = l;
 #pragma unroll
-        for (int c = 0; c < 32; ++c) { cb[(2 + 2 * c) * 64 + lane] = o[c].x; cb[(3 + 2 * c) * 64 + lane] = o[c].y; }
+        for (int c = 0; c < DV / 2; ++c) { cb[(2 + 2 * c) * 64 + lane] = o[c].x; cb[(3 + 2 * c) * 64 + lane] = o[c].y; }
     }
     __syncthreads();
     if (w == 0 && qi < L) {
@@ -510,51 +522,52 @@ __global__ __launch_bounds__(256) void ab_fwd_kernel(const float* __restrict__ q
             const float mn = fmaxf(m, m2), a1 = __expf(m - mn), a2 = __expf(m2 - mn);
             l = l * a1 + l2 * a2;
 #pragma unroll
-            for (int c = 0; c < 32; ++c) o[c] = o[c] * f2{a1, a1} + f2{cb[(2 + 2 * c) * 64 + lane], cb[(3 + 2 * c) * 64 + lane]} * f2{a2, a2};
+            for (int c = 0; c < DV / 2; ++c) o[c] = o[c] * f2{a1, a1} + f2{cb[(2 + 2 * c) * 64 + lane], cb[(3 + 2 * c) * 64 + lane]} * f2{a2, a2};
             m = mn;
         }
         if (nsplit > 1) {                                              // this key part's (max, sum, unnormalised O): ab_fwd_merge_kernel
             const long long T = (long long)(gridDim.z / nsplit) * L;
-            float* pp = part + ((sp * T + s * L + qi) * H + h) * (AB_DV + 2);
+            float* pp = part + ((sp * T + s * L + qi) * H + h) * (DV + 2);
             pp[0] = m;
             pp[1] = l;
 #pragma unroll
-            for (int c = 0; c < 32; ++c) { pp[2 + 2 * c] = o[c].x; pp[3 + 2 * c] = o[c].y; }
+            for (int c = 0; c < DV / 2; ++c) { pp[2 + 2 * c] = o[c].x; pp[3 + 2 * c] = o[c].y; }
             return;
         }
         const float inv = 1.0f / l;
-        float* op = O + (s * L + qi) * ldo + h * AB_DV;
+        float* op = O + (s * L + qi) * ldo + h * DV;
 #pragma unroll
-        for (int c = 0; c < 16; ++c)
+        for (int c = 0; c < DV / 4; ++c)
             *reinterpret_cast<float4*>(op + 4 * c) = make_float4(o[2 * c].x * inv, o[2 * c].y * inv, o[2 * c + 1].x * inv, o[2 * c + 1].y * inv);
         lse[(s * L + qi) * H + h] = m + logf(l);
     }
 }
 
-// dQ pass (query-major): delta = rowsum(dO * O); for every key: p = exp(s - LSE), dp = dO . v, ds = p (dp - delta), dq += ds k / 4.
+// dQ pass (query-major): delta = rowsum(dO * O); for every key: p = exp(s - LSE), dp = dO . v, ds = p (dp - delta), dq += ds k / sqrt(DQ).
+template <int DQ, int DV>
 __global__ __launch_bounds__(256) void ab_dq_kernel(const float* __restrict__ qkv, long long ldq, const float* __restrict__ O, long long ldo,
                                                     const float* __restrict__ dO, long long lddo, const float* __restrict__ lse,
                                                     float* __restrict__ delta, float* __restrict__ dqkv, long long lddq, int L, int H,
                                                     const int* __restrict__ lens, float* __restrict__ part, int nsplit) {
-    __shared__ float4 smem4[4 * AB_KV_TILE / 4];
+    __shared__ float4 smem4[4 * AB_KV_TILE<DQ, DV> / 4];
     float* smem = reinterpret_cast<float*>(smem4);
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, h = blockIdx.y;
     const long long s = blockIdx.z / nsplit;
     const int sp = blockIdx.z - (int)s * nsplit;
     const int qi = blockIdx.x * 64 + lane;
     const int kmax = ab_kmax(lens, s, L);
-    const int QK = H * AB_DQK;
+    const int QK = H * DQ;
     const float* base = qkv + s * L * ldq;
-    f2 q[8], g[32];
+    f2 q[DQ / 2], g[DV / 2];
     float lq = 0.f, dl = 0.f;
     if (qi < L) {
         const long long row = s * L + qi;
-        ab_load16(base + (long long)qi * ldq + h * AB_DQK, q, AB_SCALE);
-        const float* gp = dO + row * lddo + h * AB_DV;
-        const float* op = O + row * ldo + h * AB_DV;
+        ab_load(base + (long long)qi * ldq + h * DQ, q, ab_scale<DQ>());
+        const float* gp = dO + row * lddo + h * DV;
+        const float* op = O + row * ldo + h * DV;
         f2 d2{0.f, 0.f};
 #pragma unroll
-        for (int c = 0; c < 16; ++c) {
+        for (int c = 0; c < DV / 4; ++c) {
             const float4 a = *reinterpret_cast<const float4*>(gp + 4 * c);
             const float4 b = *reinterpret_cast<const float4*>(op + 4 * c);
             g[2 * c] = f2{a.x, a.y};
@@ -566,106 +579,107 @@ __global__ __launch_bounds__(256) void ab_dq_kernel(const float* __restrict__ qk
         lq = lse[row * H + h];
     } else {
 #pragma unroll
-        for (int c = 0; c < 8; ++c) q[c] = f2{0.f, 0.f};
+        for (int c = 0; c < DQ / 2; ++c) q[c] = f2{0.f, 0.f};
 #pragma unroll
-        for (int c = 0; c < 32; ++c) g[c] = f2{0.f, 0.f};
+        for (int c = 0; c < DV / 2; ++c) g[c] = f2{0.f, 0.f};
     }
-    f2 dq[8];
+    f2 dq[DQ / 2];
 #pragma unroll
-    for (int c = 0; c < 8; ++c) dq[c] = f2{0.f, 0.f};
-    float* kt = smem + w * AB_KV_TILE;
-    float* vt = kt + AB_TILE * AB_DQK;
+    for (int c = 0; c < DQ / 2; ++c) dq[c] = f2{0.f, 0.f};
+    float* kt = smem + w * AB_KV_TILE<DQ, DV>;
+    float* vt = kt + AB_TILE * DQ;
     int t_lo, n_tiles;
     ab_part_tiles(kmax, nsplit, sp, t_lo, n_tiles);
     for (int t0 = t_lo; t0 < n_tiles; t0 += 4) {
         const int t = t0 + w;
         if (t < n_tiles) {
-            ab_stage<AB_DQK / 4>(kt, base + QK + h * AB_DQK, ldq, t * AB_TILE, kmax, lane, 1.f);
-            ab_stage<AB_DV / 4>(vt, base + 2 * QK + h * AB_DV, ldq, t * AB_TILE, kmax, lane, 1.f);
+            ab_stage<DQ / 4>(kt, base + QK + h * DQ, ldq, t * AB_TILE, kmax, lane, 1.f);
+            ab_stage<DV / 4>(vt, base + 2 * QK + h * DV, ldq, t * AB_TILE, kmax, lane, 1.f);
         }
         __syncthreads();
         if (t < n_tiles) {
             const int nk = min(AB_TILE, kmax - t * AB_TILE);
             for (int j = 0; j < nk; ++j) {
-                const float p = __expf(ab_dot16(q, kt + j * AB_DQK) - lq);
-                const float ds = p * (ab_dot64(g, vt + j * AB_DV) - dl);
-                ab_axpy(dq, ds, kt + j * AB_DQK);
+                const float p = __expf(ab_dotq(q, kt + j * DQ) - lq);
+                const float ds = p * (ab_dotv(g, vt + j * DV) - dl);
+                ab_axpy(dq, ds, kt + j * DQ);
             }
         }
         __syncthreads();
     }
     if (w > 0) {
-        float* cb = smem + (w - 1) * AB_DQK * 64;
+        float* cb = smem + (w - 1) * DQ * 64;
 #pragma unroll
-        for (int c = 0; c < 8; ++c) { cb[(2 * c) * 64 + lane] = dq[c].x; cb[(2 * c + 1) * 64 + lane] = dq[c].y; }
+        for (int c = 0; c < DQ / 2; ++c) { cb[(2 * c) * 64 + lane] = dq[c].x; cb[(2 * c + 1) * 64 + lane] = dq[c].y; }
     }
     __syncthreads();
     if (w == 0 && qi < L) {
         for (int k = 0; k < 3; ++k) {
-            const float* cb = smem + k * AB_DQK * 64;
+            const float* cb = smem + k * DQ * 64;
 #pragma unroll
-            for (int c = 0; c < 8; ++c) dq[c] += f2{cb[(2 * c) * 64 + lane], cb[(2 * c + 1) * 64 + lane]};
+            for (int c = 0; c < DQ / 2; ++c) dq[c] += f2{cb[(2 * c) * 64 + lane], cb[(2 * c + 1) * 64 + lane]};
         }
         const long long row = s * L + qi;
-        const float sc = nsplit > 1 ? 1.f : AB_SCALE;                  // (parts: scaled once summed, ab_sum_parts_kernel)
-        float* dp = nsplit > 1 ? part + (sp * (long long)(gridDim.z / nsplit) * L + row) * QK + h * AB_DQK : dqkv + row * lddq + h * AB_DQK;
+        const float sc = nsplit > 1 ? 1.f : ab_scale<DQ>();                  // (parts: scaled once summed, ab_sum_parts_kernel)
+        float* dp = nsplit > 1 ? part + (sp * (long long)(gridDim.z / nsplit) * L + row) * QK + h * DQ : dqkv + row * lddq + h * DQ;
 #pragma unroll
-        for (int c = 0; c < 4; ++c)
+        for (int c = 0; c < DQ / 4; ++c)
             *reinterpret_cast<float4*>(dp + 4 * c) = make_float4(dq[2 * c].x * sc, dq[2 * c].y * sc, dq[2 * c + 1].x * sc, dq[2 * c + 1].y * sc);
         if (sp == 0) delta[row * H + h] = dl;
     }
 }
 
-constexpr int AB_Q_TILE = AB_TILE * (AB_DQK + AB_DV + 2);          // floats of one wave's q | dO | LSE | delta tile
-constexpr int AB_KV_LDS = 3 * 64 * (AB_DQK + AB_DV);               // the combine buffer (> 4 staging tiles)
-static_assert(AB_KV_LDS >= 4 * AB_Q_TILE, "LDS plan");
+template <int DQ, int DV> constexpr int AB_Q_TILE = AB_TILE * (DQ + DV + 2);          // floats of one wave's q | dO | LSE | delta tile
+template <int DQ, int DV> constexpr int AB_KV_LDS = 3 * 64 * (DQ + DV);               // the combine buffer (> 4 staging tiles)
+static_assert(AB_KV_LDS<16, 64> >= 4 * AB_Q_TILE<16, 64> && AB_KV_LDS<8, 32> >= 4 * AB_Q_TILE<8, 32>, "LDS plan");
 
 // dK / dV pass (key-major): every query row of the sequence (padded ones included) against this lane's key.
+template <int DQ, int DV>
 __global__ __launch_bounds__(256) void ab_dkdv_kernel(const float* __restrict__ qkv, long long ldq, const float* __restrict__ dO, long long lddo,
                                                       const float* __restrict__ lse, const float* __restrict__ delta, float* __restrict__ dqkv,
                                                       long long lddq, int L, int H, const int* __restrict__ lens, float* __restrict__ part,
                                                       int nsplit) {
-    __shared__ float4 smem4[AB_KV_LDS / 4];
+    __shared__ float4 smem4[AB_KV_LDS<DQ, DV> / 4];
     float* smem = reinterpret_cast<float*>(smem4);
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, h = blockIdx.y;
     const long long s = blockIdx.z / nsplit;
     const int sp = blockIdx.z - (int)s * nsplit;
     const int kj = blockIdx.x * 64 + lane;
     const int kmax = ab_kmax(lens, s, L);
-    const int QK = H * AB_DQK;
+    const int QK = H * DQ;
     const float* base = qkv + s * L * ldq;
     const bool live_block = blockIdx.x * 64 < kmax;               // (uniform) a block of keys beyond every cloud's keys: zeros
-    f2 k[8], v[32], dk[8], dv[32];
+    f2 k[DQ / 2], v[DV / 2], dk[DQ / 2], dv[DV / 2];
 #pragma unroll
-    for (int c = 0; c < 8; ++c) dk[c] = f2{0.f, 0.f};
+    for (int c = 0; c < DQ / 2; ++c) dk[c] = f2{0.f, 0.f};
 #pragma unroll
-    for (int c = 0; c < 32; ++c) dv[c] = f2{0.f, 0.f};
+    for (int c = 0; c < DV / 2; ++c) dv[c] = f2{0.f, 0.f};
     if (kj < kmax) {
-        ab_load16(base + (long long)kj * ldq + QK + h * AB_DQK, k, 1.f);
-        const float* vp = base + (long long)kj * ldq + 2 * QK + h * AB_DV;
+        ab_load(base + (long long)kj * ldq + QK + h * DQ, k, 1.f);
+        const float* vp = base + (long long)kj * ldq + 2 * QK + h * DV;
 #pragma unroll
-        for (int c = 0; c < 16; ++c) {
+        for (int c = 0; c < DV / 4; ++c) {
             const float4 a = *reinterpret_cast<const float4*>(vp + 4 * c);
             v[2 * c] = f2{a.x, a.y};
             v[2 * c + 1] = f2{a.z, a.w};
         }
     } else {
 #pragma unroll
-        for (int c = 0; c < 8; ++c) k[c] = f2{0.f, 0.f};
+        for (int c = 0; c < DQ / 2; ++c) k[c] = f2{0.f, 0.f};
 #pragma unroll
-        for (int c = 0; c < 32; ++c) v[c] = f2{0.f, 0.f};
+        for (int c = 0; c < DV / 2; ++c) v[c] = f2{0.f, 0.f};
     }
-    float* qt = smem + w * AB_Q_TILE;
-    float* gt = qt + AB_TILE * AB_DQK;
-    float* lt = gt + AB_TILE * AB_DV;
+    float* qt = smem + w * AB_Q_TILE<DQ, DV>;
+    float* gt = qt + AB_TILE * DQ;
+    float* lt = gt + AB_TILE * DV;
     float* dt = lt + AB_TILE;
     int t_lo, n_tiles;
     ab_part_tiles(live_block ? L : 0, nsplit, sp, t_lo, n_tiles);
     for (int t0 = t_lo; t0 < n_tiles; t0 += 4) {
         const int t = t0 + w;
         if (t < n_tiles) {
-            ab_stage<AB_DQK / 4>(qt, base + h * AB_DQK, ldq, t * AB_TILE, L, lane, AB_SCALE);
-            ab_stage<AB_DV / 4>(gt, dO + s * L * lddo + h * AB_DV, lddo, t * AB_TILE, L, lane, 1.f);
+            ab_stage<DQ / 4>(qt, base + h * DQ, ldq, t * AB_TILE, L, lane, ab_scale<DQ>());
+            ab_stage<DV / 4>(gt, dO + s * L * lddo + h * DV, lddo, t * AB_TILE, L, lane, 1.f);
             if (lane < AB_TILE) {
                 const int r = t * AB_TILE + lane;
                 lt[lane] = r < L ? lse[(s * L + r) * H + h] : 0.f;
@@ -676,21 +690,21 @@ __global__ __launch_bounds__(256) void ab_dkdv_kernel(const float* __restrict__ 
         if (t < n_tiles) {
             const int nq = min(AB_TILE, L - t * AB_TILE);
             for (int i = 0; i < nq; ++i) {
-                const float p = __expf(ab_dot16(k, qt + i * AB_DQK) - lt[i]);
-                ab_axpy(dv, p, gt + i * AB_DV);
-                const float ds = p * (ab_dot64(v, gt + i * AB_DV) - dt[i]);
-                ab_axpy(dk, ds, qt + i * AB_DQK);
+                const float p = __expf(ab_dotq(k, qt + i * DQ) - lt[i]);
+                ab_axpy(dv, p, gt + i * DV);
+                const float ds = p * (ab_dotv(v, gt + i * DV) - dt[i]);
+                ab_axpy(dk, ds, qt + i * DQ);
             }
         }
         __syncthreads();
     }
-    constexpr int F = AB_DQK + AB_DV;
+    constexpr int F = DQ + DV;
     if (w > 0) {
         float* cb = smem + (w - 1) * F * 64;
 #pragma unroll
-        for (int c = 0; c < 8; ++c) { cb[(2 * c) * 64 + lane] = dk[c].x; cb[(2 * c + 1) * 64 + lane] = dk[c].y; }
+        for (int c = 0; c < DQ / 2; ++c) { cb[(2 * c) * 64 + lane] = dk[c].x; cb[(2 * c + 1) * 64 + lane] = dk[c].y; }
 #pragma unroll
-        for (int c = 0; c < 32; ++c) { cb[(16 + 2 * c) * 64 + lane] = dv[c].x; cb[(17 + 2 * c) * 64 + lane] = dv[c].y; }
+        for (int c = 0; c < DV / 2; ++c) { cb[(DQ + 2 * c) * 64 + lane] = dv[c].x; cb[(DQ + 1 + 2 * c) * 64 + lane] = dv[c].y; }
     }
     __syncthreads();
     if (w == 0 && kj < L) {
@@ -698,55 +712,233 @@ __global__ __launch_bounds__(256) void ab_dkdv_kernel(const float* __restrict__ 
             for (int kk = 0; kk < 3; ++kk) {
                 const float* cb = smem + kk * F * 64;
 #pragma unroll
-                for (int c = 0; c < 8; ++c) dk[c] += f2{cb[(2 * c) * 64 + lane], cb[(2 * c + 1) * 64 + lane]};
+                for (int c = 0; c < DQ / 2; ++c) dk[c] += f2{cb[(2 * c) * 64 + lane], cb[(2 * c + 1) * 64 + lane]};
 #pragma unroll
-                for (int c = 0; c < 32; ++c) dv[c] += f2{cb[(16 + 2 * c) * 64 + lane], cb[(17 + 2 * c) * 64 + lane]};
+                for (int c = 0; c < DV / 2; ++c) dv[c] += f2{cb[(DQ + 2 * c) * 64 + lane], cb[(DQ + 1 + 2 * c) * 64 + lane]};
             }
         if (kj >= kmax) {                                             // a key nobody attends to
 #pragma unroll
-            for (int c = 0; c < 8; ++c) dk[c] = f2{0.f, 0.f};
+            for (int c = 0; c < DQ / 2; ++c) dk[c] = f2{0.f, 0.f};
 #pragma unroll
-            for (int c = 0; c < 32; ++c) dv[c] = f2{0.f, 0.f};
+            for (int c = 0; c < DV / 2; ++c) dv[c] = f2{0.f, 0.f};
         }
-        // parts: rows [dk (QK) | dv (H * 64)] laid out as d_qkv from column QK on, summed by ab_sum_parts_kernel
-        const int W2 = QK + H * AB_DV;
+        // parts: rows [dk (QK) | dv (H * DV)] laid out as d_qkv from column QK on, summed by ab_sum_parts_kernel
+        const int W2 = QK + H * DV;
         float* dkp = nsplit > 1 ? part + (sp * (long long)(gridDim.z / nsplit) * L + s * L + kj) * W2 : dqkv + (s * L + kj) * lddq + QK;
 #pragma unroll
-        for (int c = 0; c < 4; ++c)
-            *reinterpret_cast<float4*>(dkp + h * AB_DQK + 4 * c) = make_float4(dk[2 * c].x, dk[2 * c].y, dk[2 * c + 1].x, dk[2 * c + 1].y);
+        for (int c = 0; c < DQ / 4; ++c)
+            *reinterpret_cast<float4*>(dkp + h * DQ + 4 * c) = make_float4(dk[2 * c].x, dk[2 * c].y, dk[2 * c + 1].x, dk[2 * c + 1].y);
 #pragma unroll
-        for (int c = 0; c < 16; ++c)
-            *reinterpret_cast<float4*>(dkp + QK + h * AB_DV + 4 * c) = make_float4(dv[2 * c].x, dv[2 * c].y, dv[2 * c + 1].x, dv[2 * c + 1].y);
+        for (int c = 0; c < DV / 4; ++c)
+            *reinterpret_cast<float4*>(dkp + QK + h * DV + 4 * c) = make_float4(dv[2 * c].x, dv[2 * c].y, dv[2 * c + 1].x, dv[2 * c + 1].y);
     }
 }
 
-// part: ab_part_floats(S, L, H) floats of scratch (none needed when the problem is not split)
-void launch_attn_fwd(hipStream_t s, const float* qkv, int64_t ldq, float* O, int64_t ldo, float* lse, int64_t S, int L, int H, const int* lens,
-                     float* part) {
+// part: ab_part_floats(S, L, H, DQ, DV) floats of scratch (none needed when the problem is not split)
+template <int DQ, int DV>
+void launch_attn_fwd_t(hipStream_t s, const float* qkv, int64_t ldq, float* O, int64_t ldo, float* lse, int64_t S, int L, int H, const int* lens,
+                       float* part) {
     const int ns = ab_nsplit(S, L, H);
-    hipLaunchKernelGGL(ab_fwd_kernel, dim3((unsigned)cdiv(L, 64), (unsigned)H, (unsigned)(S * ns)), dim3(256), 0, s, qkv, (long long)ldq, O,
-                       (long long)ldo, lse, L, H, lens, part, ns);
+    hipLaunchKernelGGL((ab_fwd_kernel<DQ, DV>), dim3((unsigned)cdiv(L, 64), (unsigned)H, (unsigned)(S * ns)), dim3(256), 0, s, qkv, (long long)ldq,
+                       O, (long long)ldo, lse, L, H, lens, part, ns);
     if (ns > 1) {
         const long long TH = S * L * H;
-        hipLaunchKernelGGL(ab_fwd_merge_kernel, dim3((unsigned)cdiv(TH, 256)), dim3(256), 0, s, part, ns, TH, H, O, (long long)ldo, lse);
+        hipLaunchKernelGGL(ab_fwd_merge_kernel<DV>, dim3((unsigned)cdiv(TH, 256)), dim3(256), 0, s, part, ns, TH, H, O, (long long)ldo, lse);
     }
 }
 
-void launch_attn_bwd(hipStream_t s, const float* qkv, int64_t ldq, const float* O, int64_t ldo, const float* lse, const float* dO,
-                     int64_t lddo, float* delta, float* dqkv, int64_t lddq, int64_t S, int L, int H, const int* lens, float* part) {
+template <int DQ, int DV>
+void launch_attn_bwd_t(hipStream_t s, const float* qkv, int64_t ldq, const float* O, int64_t ldo, const float* lse, const float* dO,
+                       int64_t lddo, float* delta, float* dqkv, int64_t lddq, int64_t S, int L, int H, const int* lens, float* part) {
     const int ns = ab_nsplit(S, L, H);
     const long long T = S * L;
-    const int QK = H * AB_DQK, W2 = QK + H * AB_DV;
+    const int QK = H * DQ, W2 = QK + H * DV;
     const dim3 grid((unsigned)cdiv(L, 64), (unsigned)H, (unsigned)(S * ns));
-    hipLaunchKernelGGL(ab_dq_kernel, grid, dim3(256), 0, s, qkv, (long long)ldq, O, (long long)ldo, dO, (long long)lddo, lse, delta, dqkv,
+    hipLaunchKernelGGL((ab_dq_kernel<DQ, DV>), grid, dim3(256), 0, s, qkv, (long long)ldq, O, (long long)ldo, dO, (long long)lddo, lse, delta, dqkv,
                        (long long)lddq, L, H, lens, part, ns);
     if (ns > 1)
-        hipLaunchKernelGGL(ab_sum_parts_kernel, dim3((unsigned)cdiv(T * QK, 256)), dim3(256), 0, s, part, ns, T, QK, AB_SCALE, dqkv, (long long)lddq);
-    hipLaunchKernelGGL(ab_dkdv_kernel, grid, dim3(256), 0, s, qkv, (long long)ldq, dO, (long long)lddo, lse, delta, dqkv, (long long)lddq, L,
+        hipLaunchKernelGGL(ab_sum_parts_kernel, dim3((unsigned)cdiv(T * QK, 256)), dim3(256), 0, s, part, ns, T, QK, ab_scale<DQ>(), dqkv, (long long)lddq);
+    hipLaunchKernelGGL((ab_dkdv_kernel<DQ, DV>), grid, dim3(256), 0, s, qkv, (long long)ldq, dO, (long long)lddo, lse, delta, dqkv, (long long)lddq, L,
                        H, lens, part, ns);
     if (ns > 1)
         hipLaunchKernelGGL(ab_sum_parts_kernel, dim3((unsigned)cdiv(T * W2, 256)), dim3(256), 0, s, part, ns, T, W2, 1.f, dqkv + QK,
                            (long long)lddq);
+}
+
+// dq: the per-head q / k width, 16 (v: 64) or 8 (v: 32)
+void launch_attn_fwd(hipStream_t s, const float* qkv, int64_t ldq, float* O, int64_t ldo, float* lse, int64_t S, int L, int H, const int* lens,
+                     float* part, int dq = 16) {
+    if (dq == 16) launch_attn_fwd_t<16, 64>(s, qkv, ldq, O, ldo, lse, S, L, H, lens, part);
+    else launch_attn_fwd_t<8, 32>(s, qkv, ldq, O, ldo, lse, S, L, H, lens, part);
+}
+void launch_attn_bwd(hipStream_t s, const float* qkv, int64_t ldq, const float* O, int64_t ldo, const float* lse, const float* dO,
+                     int64_t lddo, float* delta, float* dqkv, int64_t lddq, int64_t S, int L, int H, const int* lens, float* part, int dq = 16) {
+    if (dq == 16) launch_attn_bwd_t<16, 64>(s, qkv, ldq, O, ldo, lse, dO, lddo, delta, dqkv, lddq, S, L, H, lens, part);
+    else launch_attn_bwd_t<8, 32>(s, qkv, ldq, O, ldo, lse, dO, lddo, delta, dqkv, lddq, S, L, H, lens, part);
+}
+
+// ---- attention backward for 16-token sequences at per-head widths (8, 32): the PCTransformer's neighbourhoods ----------------------------
+// One wave owns one sequence: lane = (head h = lane / 16, row = lane % 16), so a head's 16 rows are one DPP row and the 64 lanes are the
+// sequence's 4 x 16 (head, row) pairs.  Nothing but d_qkv is written: no O, no LSE, no 16 x 16 matrix leaves the wave.
+//   pass 1 (query-major): the lane keeps its own q (scaled) and dO in registers; the wave stages the sequence's K | V rows in its LDS
+//           strip.  The lane rebuilds its 16 scores and their soft-max P, dP_j = dO . v_j, delta = sum_j P_j dP_j (= dO . O),
+//           dS_j = P_j (dP_j - delta), and writes dq = sum_j dS_j k_j / sqrt(8).
+//   pass 2 (key-major): the lane acts as key row j of its head.  P and dO, then dS and q, go through the strip (each lane writes its
+//           row, reads column j of its head's rows 0..15 in that order): dv_j = sum_i P_ij dO_i, dk_j = sum_i dS_ij q_i / sqrt(8).
+// The strip is private to the wave: wave-scope fences order its phases, there is no block barrier.  LDS reads of a pass are broadcasts
+// within a head and hit four different banks across the heads ([row][head][channel] layouts; P / dS as [row i][head][j]: lane-linear).
+// Registers: 242 VGPRs, no scratch, 2 waves per SIMD (the 48 KB strip block would allow 3; asking for 3 makes hipcc spill 288 bytes
+// per lane, its schedule hoists the strip reads of the fully unrolled j loops).
+constexpr int A16_L = 16, A16_H = 4, A16_DQ = 8, A16_DV = 32;
+constexpr int A16_QK = A16_H * A16_DQ, A16_V = A16_H * A16_DV;     // 32 q (k) and 128 v channels of a packed row
+constexpr int A16_STRIP = A16_L * 64 + A16_L * A16_V;              // floats per wave: P (or dS) [16][64] | dO [16][128] >= K [16][32] | V [16][128]
+constexpr int A16_WAVES = 4;                                       // sequences per block
+static_assert(A16_STRIP >= A16_L * (A16_QK + A16_V), "LDS plan");
+
+__device__ __forceinline__ void a16_wave_sync() {                  // orders the wave's own LDS traffic (in-order per wave in hardware)
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+__global__ __launch_bounds__(64 * A16_WAVES) void a16_bwd_kernel(const float* __restrict__ qkv, long long ldq, const float* __restrict__ dO,
+                                                                 long long lddo, float* __restrict__ dqkv, long long lddq, long long S) {
+    __shared__ float4 smem4[A16_WAVES * A16_STRIP / 4];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, h = lane >> 4, r = lane & 15;
+    const long long s = (long long)blockIdx.x * A16_WAVES + w;
+    if (s >= S) return;                                            // (wave-uniform; no block barrier below)
+    float* strip = reinterpret_cast<float*>(smem4) + w * A16_STRIP;
+    float* kt = strip;                                             // pass 1: K [16][32]
+    float* vt = strip + A16_L * A16_QK;                            //         V [16][128]
+    const float* base = qkv + s * A16_L * ldq;
+    // the sequence's K | V: 16 rows x 40 float4 (columns 32 .. 191 of the packed rows), 10 per lane
+#pragma unroll
+    for (int it = 0; it < A16_L * (A16_QK + A16_V) / 4 / 64; ++it) {
+        const int e = lane + 64 * it;
+        const int j = e / ((A16_QK + A16_V) / 4), c4 = e - j * ((A16_QK + A16_V) / 4);
+        const float4 v = *reinterpret_cast<const float4*>(base + (long long)j * ldq + A16_QK + 4 * c4);
+        float* dst = c4 < A16_QK / 4 ? kt + j * A16_QK + 4 * c4 : vt + j * A16_V + 4 * (c4 - A16_QK / 4);
+        *reinterpret_cast<float4*>(dst) = v;
+    }
+    f2 q[A16_DQ / 2], g[A16_DV / 2];
+    ab_load(base + (long long)r * ldq + h * A16_DQ, q, ab_scale<A16_DQ>());
+    ab_load(dO + (s * A16_L + r) * lddo + h * A16_DV, g, 1.f);
+    a16_wave_sync();
+    float p[A16_L], ds[A16_L];
+    float m = -INFINITY;
+#pragma unroll
+    for (int j = 0; j < A16_L; ++j) {
+        p[j] = ab_dotq(q, kt + j * A16_QK + h * A16_DQ);
+        m = fmaxf(m, p[j]);
+    }
+    float l = 0.f;
+#pragma unroll
+    for (int j = 0; j < A16_L; ++j) {
+        p[j] = __expf(p[j] - m);
+        l += p[j];
+    }
+    const float inv = 1.0f / l;
+    float delta = 0.f;
+#pragma unroll
+    for (int j = 0; j < A16_L; ++j) {
+        p[j] *= inv;
+        ds[j] = ab_dotv(g, vt + j * A16_V + h * A16_DV);           // dP_j
+        delta = fmaf(p[j], ds[j], delta);
+    }
+    f2 dq[A16_DQ / 2];
+#pragma unroll
+    for (int c = 0; c < A16_DQ / 2; ++c) dq[c] = f2{0.f, 0.f};
+#pragma unroll
+    for (int j = 0; j < A16_L; ++j) {
+        ds[j] = p[j] * (ds[j] - delta);
+        ab_axpy(dq, ds[j], kt + j * A16_QK + h * A16_DQ);
+    }
+    float* out = dqkv + (s * A16_L + r) * lddq;
+    const float sc = ab_scale<A16_DQ>();
+#pragma unroll
+    for (int c = 0; c < A16_DQ / 4; ++c)
+        *reinterpret_cast<float4*>(out + h * A16_DQ + 4 * c) =
+            make_float4(dq[2 * c].x * sc, dq[2 * c].y * sc, dq[2 * c + 1].x * sc, dq[2 * c + 1].y * sc);
+    // ---- pass 2a: dv_j = sum_i P_ij dO_i
+    float* xt = strip;                                             // P, then dS: [i][h][j]
+    float* gt = strip + A16_L * 64;                                // dO [i][h][32], then q [i][h][8]
+    a16_wave_sync();                                               // every lane is done with K | V
+#pragma unroll
+    for (int c = 0; c < A16_L / 4; ++c)
+        *reinterpret_cast<float4*>(xt + r * 64 + h * 16 + 4 * c) = make_float4(p[4 * c], p[4 * c + 1], p[4 * c + 2], p[4 * c + 3]);
+#pragma unroll
+    for (int c = 0; c < A16_DV / 4; ++c)
+        *reinterpret_cast<float4*>(gt + r * A16_V + h * A16_DV + 4 * c) = make_float4(g[2 * c].x, g[2 * c].y, g[2 * c + 1].x, g[2 * c + 1].y);
+    a16_wave_sync();
+    f2 dv[A16_DV / 2];
+#pragma unroll
+    for (int c = 0; c < A16_DV / 2; ++c) dv[c] = f2{0.f, 0.f};
+#pragma unroll
+    for (int i = 0; i < A16_L; ++i) ab_axpy(dv, xt[i * 64 + lane], gt + i * A16_V + h * A16_DV);
+#pragma unroll
+    for (int c = 0; c < A16_DV / 4; ++c)
+        *reinterpret_cast<float4*>(out + 2 * A16_QK + h * A16_DV + 4 * c) = make_float4(dv[2 * c].x, dv[2 * c].y, dv[2 * c + 1].x, dv[2 * c + 1].y);
+    // ---- pass 2b: dk_j = sum_i dS_ij q_i (q already carries 1 / sqrt(8))
+    a16_wave_sync();                                               // every lane is done with P | dO
+#pragma unroll
+    for (int c = 0; c < A16_L / 4; ++c)
+        *reinterpret_cast<float4*>(xt + r * 64 + h * 16 + 4 * c) = make_float4(ds[4 * c], ds[4 * c + 1], ds[4 * c + 2], ds[4 * c + 3]);
+#pragma unroll
+    for (int c = 0; c < A16_DQ / 4; ++c)
+        *reinterpret_cast<float4*>(gt + r * A16_QK + h * A16_DQ + 4 * c) = make_float4(q[2 * c].x, q[2 * c].y, q[2 * c + 1].x, q[2 * c + 1].y);
+    a16_wave_sync();
+    f2 dk[A16_DQ / 2];
+#pragma unroll
+    for (int c = 0; c < A16_DQ / 2; ++c) dk[c] = f2{0.f, 0.f};
+#pragma unroll
+    for (int i = 0; i < A16_L; ++i) ab_axpy(dk, xt[i * 64 + lane], gt + i * A16_QK + h * A16_DQ);
+#pragma unroll
+    for (int c = 0; c < A16_DQ / 4; ++c)
+        *reinterpret_cast<float4*>(out + A16_QK + h * A16_DQ + 4 * c) = make_float4(dk[2 * c].x, dk[2 * c].y, dk[2 * c + 1].x, dk[2 * c + 1].y);
+}
+
+// d_qkv of S sequences of 16 tokens, 4 heads of widths (8, 32); rows 16-byte aligned, leading dimensions multiples of 4
+void launch_attn16_bwd(hipStream_t s, const float* qkv, int64_t ldq, const float* dO, int64_t lddo, float* dqkv, int64_t lddq, int64_t S) {
+    hipLaunchKernelGGL(a16_bwd_kernel, dim3((unsigned)cdiv(S, A16_WAVES)), dim3(64 * A16_WAVES), 0, s, qkv, (long long)ldq, dO, (long long)lddo,
+                       dqkv, (long long)lddq, (long long)S);
+}
+
+// ---- backward of the max || mean pooling over each sequence's rows (launch_pool_max_avg) -----------------------------------------------
+// dX[(s*L + r)*ldd + c] = dY[s*ldy + E + c] / L + (r == r* ? dY[s*ldy + c] : 0), r* = the lowest row holding the column's max (as
+// vb_colmax_bwd_kernel and torch.max(dim)).  Written, not accumulated.  Block: 64 columns x 16 row slices of one sequence.
+__global__ __launch_bounds__(1024) void pb_pool_bwd_kernel(const float* __restrict__ X, long long ldx, const float* __restrict__ dY,
+                                                           long long ldy, float* __restrict__ dX, long long ldd, int L, int E) {
+    __shared__ float s_max[16][64];
+    __shared__ int s_arg[16][64];
+    const int lane = threadIdx.x & 63, sl = threadIdx.x >> 6;
+    const int c = blockIdx.y * 64 + lane;
+    const long long s = blockIdx.x;
+    float best = -INFINITY;
+    int arg = -1;
+    if (c < E) {
+        const float* x = X + s * L * ldx + c;
+        for (int r = sl; r < L; r += 16) {
+            const float v = x[(long long)r * ldx];
+            if (arg < 0 || v > best) { best = v; arg = r; }
+        }
+    }
+    s_max[sl][lane] = best; s_arg[sl][lane] = arg;
+    __syncthreads();
+    if (c >= E) return;
+    best = s_max[0][lane]; arg = s_arg[0][lane];
+    for (int k = 1; k < 16; ++k) {
+        const int a = s_arg[k][lane];
+        const float v = s_max[k][lane];
+        if (a >= 0 && (arg < 0 || v > best || (v == best && a < arg))) { best = v; arg = a; }
+    }
+    const float g_max = dY[s * ldy + c], g_avg = dY[s * ldy + E + c] / (float)L;
+    float* o = dX + s * L * ldd + c;
+    for (int r = sl; r < L; r += 16) o[(long long)r * ldd] = r == arg ? g_avg + g_max : g_avg;
+}
+
+void launch_pool_bwd(hipStream_t s, const float* X, int64_t ldx, const float* dY, int64_t ldy, float* dX, int64_t ldd, int64_t S, int L, int E) {
+    hipLaunchKernelGGL(pb_pool_bwd_kernel, dim3((unsigned)S, (unsigned)cdiv(E, 64)), dim3(1024), 0, s, X, (long long)ldx, dY, (long long)ldy, dX,
+                       (long long)ldd, L, E);
 }
 
 // ---- the network -------------------------------------------------------------------------------------------------------------------
@@ -765,19 +957,54 @@ void vb_linear(hipStream_t s, Rows X, const LinW& w, Rows R, RowsOut Y, int64_t 
     launch_linear(s, X, {w.w, K}, {w.b, act, R}, Y, T, N, K, /*route_rows=*/1);
 }
 
+// An encoder of width E (256: SconeVis, 128: PCTransformer) with VB_H heads: q | k of E / 4 channels, v of E, packed rows of 3 E / 2.
+// Sequences of 16 tokens at the PCTransformer's widths have a backward of their own (a16_bwd_kernel) that rebuilds the soft-max itself.
+inline bool vb_fused16(int N, int E) { return N == 16 && E == 128; }
+
 // x_out = Encoder(x) (x_out NULL: the interior for the backward, LSE included).  The boundary pass (x_out given) needs no LSE: it takes
-// the forward's exact-fp32 MFMA attention (launch_attention, fp32 P V)
-void vb_encoder_fwd(hipStream_t s, const EncW& w, const float* x, float* x_out, const VbInterior& I, int64_t B, int N, const int* lens) {
+// the forward's exact-fp32 MFMA attention (launch_attention, fp32 P V); so does the interior of 16-token sequences
+void vb_encoder_fwd(hipStream_t s, const EncW& w, const float* x, float* x_out, const VbInterior& I, int64_t B, int N, const int* lens,
+                    int E = VB_E) {
     const int64_t T = B * N;
-    launch_layernorm(s, x, VB_E, w.n1g, w.n1b, I.h1, VB_E, T, VB_E);
-    vb_linear(s, {I.h1, VB_E}, w.qkv, {}, {I.qkv, VB_W3}, T, VB_W3, VB_E, ACT_NONE);
-    if (x_out) launch_attention(s, {I.qkv, VB_W3}, {I.O, VB_E}, B, N, VB_H, 64, VB_E, lens, AttnSplit{}, /*pv_half=*/false);
-    else launch_attn_fwd(s, I.qkv, VB_W3, I.O, VB_E, I.lse, B, N, VB_H, lens, I.part);
-    vb_linear(s, {I.O, VB_E}, w.out, {x, VB_E}, {I.xm, VB_E}, T, VB_E, VB_E, ACT_NONE);
-    launch_layernorm(s, I.xm, VB_E, w.n2g, w.n2b, I.h2, VB_E, T, VB_E);
-    vb_linear(s, {I.h2, VB_E}, w.ff1, {}, {I.z, 2 * VB_E}, T, 2 * VB_E, VB_E, ACT_NONE);
-    launch_gelu(s, I.z, 2 * VB_E, I.g, 2 * VB_E, T, 2 * VB_E, 0);
-    if (x_out) vb_linear(s, {I.g, 2 * VB_E}, w.ff2, {I.xm, VB_E}, {x_out, VB_E}, T, VB_E, 2 * VB_E, ACT_NONE);
+    const int QK = E / 4, W3 = 2 * QK + E;
+    launch_layernorm(s, x, E, w.n1g, w.n1b, I.h1, E, T, E);
+    vb_linear(s, {I.h1, E}, w.qkv, {}, {I.qkv, W3}, T, W3, E, ACT_NONE);
+    if (x_out || vb_fused16(N, E)) launch_attention(s, {I.qkv, W3}, {I.O, E}, B, N, VB_H, QK, E, lens, AttnSplit{}, /*pv_half=*/false);
+    else launch_attn_fwd(s, I.qkv, W3, I.O, E, I.lse, B, N, VB_H, lens, I.part, QK / VB_H);
+    vb_linear(s, {I.O, E}, w.out, {x, E}, {I.xm, E}, T, E, E, ACT_NONE);
+    launch_layernorm(s, I.xm, E, w.n2g, w.n2b, I.h2, E, T, E);
+    vb_linear(s, {I.h2, E}, w.ff1, {}, {I.z, 2 * E}, T, 2 * E, E, ACT_NONE);
+    launch_gelu(s, I.z, 2 * E, I.g, 2 * E, T, 2 * E, 0);
+    if (x_out) vb_linear(s, {I.g, 2 * E}, w.ff2, {I.xm, E}, {x_out, E}, T, E, 2 * E, ACT_NONE);
+}
+
+// The gradient buffers of an encoder's backward: dX [T, E] holds the gradient of the encoder's output on entry and of its input on return
+struct VbGrads { float *dX, *dH, *dA, *dQKV, *delta, *part, *wt; };   // part / wt: weight-gradient slabs, transposed weight (gemm_dw / gemm_dx)
+
+// Backward of one encoder (Attention.py:278-300) whose interior I was rebuilt from its input x.  dw: where the gradients of the encoder's
+// ENC_NW table entries go (NULL: none wanted)
+void vb_encoder_bwd(hipStream_t s, const EncW& we, float* const* dw, const float* x, const VbInterior& I, const VbGrads& G, int64_t B, int N,
+                    const int* lens, int E = VB_E) {
+    const int64_t T = B * N;
+    const int QK = E / 4, W3 = 2 * QK + E;
+    float *dX = G.dX, *dH = G.dH, *dA = G.dA, *dQKV = G.dQKV, *part = G.part, *wt = G.wt;
+    auto DW = [&](int slot) { return dw ? dw[slot] : nullptr; };
+    gemm_dw(s, dX, E, I.g, 2 * E, T, E, 2 * E, DW(ENC_FF2 + LIN_W), DW(ENC_FF2 + LIN_B), part);          // ff2
+    gemm_dx(s, dX, E, we.ff2.w, 2 * E, dH, 2 * E, T, E, 2 * E, false, wt);
+    launch_gelu(s, I.z, 2 * E, dH, 2 * E, T, 2 * E, 1);                      // ff1
+    gemm_dw(s, dH, 2 * E, I.h2, E, T, 2 * E, E, DW(ENC_FF1 + LIN_W), DW(ENC_FF1 + LIN_B), part);
+    gemm_dx(s, dH, 2 * E, we.ff1.w, E, dA, E, T, 2 * E, E, false, wt);
+    launch_ln_bwd(s, I.xm, E, we.n2g, dA, E, dX, E, true, DW(ENC_N2G), DW(ENC_N2B), part, T, E);   // norm2 (+ residual)
+    gemm_dw(s, dX, E, I.O, E, T, E, E, DW(ENC_OUT + LIN_W), DW(ENC_OUT + LIN_B), part);        // out
+    gemm_dx(s, dX, E, we.out.w, E, dA, E, T, E, E, false, wt);
+    if (vb_fused16(N, E)) {
+        if (lens) { refuse("vb_encoder_bwd: 16-token sequences take no lens (every key takes part)"); return; }
+        launch_attn16_bwd(s, I.qkv, W3, dA, E, dQKV, W3, B);
+    }
+    else launch_attn_bwd(s, I.qkv, W3, I.O, E, I.lse, dA, E, G.delta, dQKV, W3, B, N, VB_H, lens, I.part, QK / VB_H);
+    gemm_dw(s, dQKV, W3, I.h1, E, T, W3, E, DW(ENC_QKV + LIN_W), DW(ENC_QKV + LIN_B), part);   // qkv
+    gemm_dx(s, dQKV, W3, we.qkv.w, E, dA, E, T, W3, E, false, wt);
+    launch_ln_bwd(s, x, E, we.n1g, dA, E, dX, E, true, DW(ENC_N1G), DW(ENC_N1B), part, T, E);   // norm1 (+ residual)
 }
 
 // The workspace of mcr_scone_vis_backward over T = B * N tokens
@@ -827,6 +1054,118 @@ LinBwdScratch carve_linear_backward(Arena& a, int64_t M, int N, int K) {
 }
 float* carve_layernorm_backward(Arena& a, int64_t M, int E) { return a.f(vb_ln_part_floats(M, E)); }
 
+// ---- PCTransformer (SconeOcc.py:45-130): E = 128, 2 encoders, 4 heads of widths (8, 32) ---------------------------------------------------
+constexpr int PB_E = 128, PB_F = 125, PB_W3 = 2 * 32 + PB_E;        // PB_F: the embedding's inner width (E - 3: the raw points fill the row)
+// Sequences of 16 tokens arrive by the ten thousand (B * Q neighbourhoods): they are processed in chunks of PB_CHUNK16 sequences, a
+// function of (S, L) alone, so the workspace does not grow with S; the chunks' weight gradients are summed in chunk order.
+constexpr int64_t PB_CHUNK16 = 2048;
+inline int64_t pb_chunk(int64_t S, int64_t L) { return L == 16 ? std::min(S, PB_CHUNK16) : S; }
+
+// floats of the table entry `slot` (half = feature_dim / 2)
+inline int pb_slot_floats(int slot, int half) {
+    if (slot == PCT_L1 + LIN_W) return PB_F * 3;
+    if (slot == PCT_L2 + LIN_W) return PB_F * PB_F;
+    if (slot == PCT_L1 + LIN_B || slot == PCT_L2 + LIN_B) return PB_F;
+    if (slot == PCT_LIN0 + LIN_W) return half * PB_E;
+    if (slot == PCT_LIN0 + LIN_B) return half;
+    if (slot >= PCT_ENC && slot < PCT_NG) {
+        switch ((slot - PCT_ENC) % ENC_NW) {
+            case ENC_QKV + LIN_W: return PB_W3 * PB_E;
+            case ENC_QKV + LIN_B: return PB_W3;
+            case ENC_OUT + LIN_W: return PB_E * PB_E;
+            case ENC_FF1 + LIN_W: case ENC_FF2 + LIN_W: return 2 * PB_E * PB_E;
+            case ENC_FF1 + LIN_B: return 2 * PB_E;
+            default: return PB_E;                                   // norm1, norm2, out.bias, ff2.bias
+        }
+    }
+    return PB_E;                                                    // the final norm
+}
+// a later chunk's weight gradients: one contiguous staging area, cut in table order
+struct PbSlots { float* dst[PCT_NW]; int off[PCT_NW + 1]; };
+__global__ __launch_bounds__(256) void pb_add_slots_kernel(PbSlots t, const float* __restrict__ stage) {
+    const int slot = blockIdx.y, n = t.off[slot + 1] - t.off[slot];
+    for (int e = blockIdx.x * 256 + threadIdx.x; e < n; e += gridDim.x * 256) t.dst[slot][e] += stage[t.off[slot] + e];
+}
+
+// The workspace of mcr_pc_transformer_backward: one chunk of Sc sequences (T = Sc * L tokens)
+struct PbScratch {
+    float* X[PCT_N_ENC + 1];                               // the residual stream at the encoder boundaries
+    float *z1, *g1;                                        // the embedding's pre-activation and its GELU
+    float *hn, *y0;                                        // tail: final LayerNorm, linear0's output (what the pooling reads)
+    VbInterior I;                                          // one encoder's interior (the two share it)
+    VbGrads G;
+    float* stage;                                          // weight gradients of the chunks behind the first
+};
+PbScratch carve_pb(Arena& a, int64_t S, int64_t L, int half) {
+    const int64_t Sc = pb_chunk(S, L), T = Sc * L;
+    PbScratch w;
+    for (float*& x : w.X) x = a.f(T * PB_E);
+    w.z1 = a.f(T * PB_F); w.g1 = a.f(T * PB_F);
+    w.hn = a.f(T * PB_E); w.y0 = a.f(T * half);
+    VbInterior& I = w.I;
+    const bool stash = !vb_fused16((int)L, PB_E);           // the 16-token attention backward keeps LSE, delta and parts in the wave
+    I.h1 = a.f(T * PB_E); I.qkv = a.f(T * PB_W3); I.O = a.f(T * PB_E); I.lse = a.f(stash ? T * VB_H : 0);
+    I.xm = a.f(T * PB_E); I.h2 = a.f(T * PB_E); I.z = a.f(T * 2 * PB_E); I.g = a.f(T * 2 * PB_E);
+    I.part = a.f(stash ? ab_part_floats(Sc, (int)L, VB_H, 8, 32) : 0);
+    VbGrads& G = w.G;
+    G.dX = a.f(T * PB_E); G.dH = a.f(T * 2 * PB_E); G.dA = a.f(T * PB_E); G.dQKV = a.f(T * PB_W3); G.delta = a.f(stash ? T * VB_H : 0);
+    G.part = a.f(std::max({vb_gradw_floats(T, 2 * PB_E, PB_E), vb_gradw_floats(T, PB_E, 2 * PB_E), vb_gradw_floats(T, PB_W3, PB_E),
+                           vb_gradw_floats(T, half, PB_E), vb_gradw_floats(T, PB_F, PB_F), vb_ln_part_floats(T, PB_E)}));
+    G.wt = a.f((size_t)2 * PB_E * PB_E);
+    size_t n_stage = 0;
+    if (Sc < S)
+        for (int i = 0; i < PCT_NW; ++i) n_stage += pb_slot_floats(i, half);
+    w.stage = a.f(n_stage);
+    return w;
+}
+AttnBwdScratch carve_attention_backward_pct(Arena& a, int64_t S, int64_t L) {
+    AttnBwdScratch w{};
+    if (L == 16) return w;                                 // (the 16-token kernel keeps everything in the wave)
+    const int64_t T = S * L;
+    w.O = a.f(T * PB_E);
+    w.lse = a.f(T * VB_H);
+    w.delta = a.f(T * VB_H);
+    w.part = a.f(ab_part_floats(S, (int)L, VB_H, 8, 32));
+    return w;
+}
+
+// One chunk: Sc sequences from pc / d_feat on; dw = where the table's gradients go (NULL: none), d_pc (optional) this chunk's rows
+void pb_chunk_backward(hipStream_t s, const PctW& w, const float* pc, const float* d_feat, int64_t Sc, int L, int half, float* const* dw,
+                       float* d_pc, const PbScratch& ws) {
+    const int64_t T = Sc * L;
+    float* const* X = ws.X;
+    const VbInterior& I = ws.I;
+    const VbGrads& G = ws.G;
+    auto DW = [&](int slot) { return dw ? dw[slot] : nullptr; };
+    // ---- forward of the fp32 network: boundaries X0..X2, the embedding's pre-activation, the tail
+    vb_linear(s, {pc, 3}, w.l1, {}, {ws.z1, PB_F}, T, PB_F, 3, ACT_NONE);
+    launch_gelu(s, ws.z1, PB_F, ws.g1, PB_F, T, PB_F, 0);
+    vb_linear(s, {ws.g1, PB_F}, w.l2, {}, {X[0], PB_E}, T, PB_F, PB_F, ACT_NONE);
+    launch_copy2d(s, pc, 3, X[0] + PB_F, PB_E, T, 3);
+    for (int e = 0; e < PCT_N_ENC; ++e) vb_encoder_fwd(s, w.enc[e], X[e], X[e + 1], I, Sc, L, nullptr, PB_E);
+    launch_layernorm(s, X[PCT_N_ENC], PB_E, w.ng, w.nb, ws.hn, PB_E, T, PB_E);
+    vb_linear(s, {ws.hn, PB_E}, w.lin0, {}, {ws.y0, half}, T, half, PB_E, ACT_NONE);
+    // ---- tail (SconeOcc.py:119-126), backwards: pooling, linear0, norm
+    launch_pool_bwd(s, ws.y0, half, d_feat, 2 * half, G.dH, half, Sc, L, half);
+    gemm_dw(s, G.dH, half, ws.hn, PB_E, T, half, PB_E, DW(PCT_LIN0 + LIN_W), DW(PCT_LIN0 + LIN_B), G.part);
+    gemm_dx(s, G.dH, half, w.lin0.w, PB_E, G.dA, PB_E, T, half, PB_E, false, G.wt);
+    launch_ln_bwd(s, X[PCT_N_ENC], PB_E, w.ng, G.dA, PB_E, G.dX, PB_E, false, DW(PCT_NG), DW(PCT_NB), G.part, T, PB_E);
+    // ---- encoders, last to first
+    for (int e = PCT_N_ENC - 1; e >= 0; --e) {
+        vb_encoder_fwd(s, w.enc[e], X[e], nullptr, I, Sc, L, nullptr, PB_E);
+        vb_encoder_bwd(s, w.enc[e], dw ? dw + PCT_ENC + ENC_NW * e : nullptr, X[e], I, G, Sc, L, nullptr, PB_E);
+    }
+    // ---- embedding (Attention.py:98-128): [linear2(GELU(linear1(pc))) | pc]
+    gemm_dw(s, G.dX, PB_E, ws.g1, PB_F, T, PB_F, PB_F, DW(PCT_L2 + LIN_W), DW(PCT_L2 + LIN_B), G.part);
+    gemm_dx(s, G.dX, PB_E, w.l2.w, PB_F, G.dH, PB_F, T, PB_F, PB_F, false, G.wt);
+    launch_gelu(s, ws.z1, PB_F, G.dH, PB_F, T, PB_F, 1);
+    gemm_dw(s, G.dH, PB_F, pc, 3, T, PB_F, 3, DW(PCT_L1 + LIN_W), DW(PCT_L1 + LIN_B), G.part);
+    if (d_pc) {
+        launch_copy2d(s, G.dX + PB_F, PB_E, d_pc, 3, T, 3);
+        gemm_dx(s, G.dH, PB_F, w.l1.w, 3, d_pc, 3, T, PB_F, 3, true, G.wt);
+    }
+}
+
 }  // namespace
 }  // namespace mcr
 
@@ -844,7 +1183,7 @@ int mcr_attention_backward(const float* qkv, int64_t ldq, const float* d_out, in
                            void* stream) {
     const char* who = "mcr_attention_backward";
     MCR_REQUIRE(qkv && d_out && d_qkv, "%s: null pointer", who);
-    MCR_REQUIRE(n_heads > 0 && qk_dim == AB_DQK * n_heads && v_dim == AB_DV * n_heads,
+    MCR_REQUIRE(n_heads > 0 && qk_dim == 16 * n_heads && v_dim == 64 * n_heads,
                 "%s: per-head widths must be 16 (q, k) and 64 (v), got qk_dim %d, v_dim %d for %d heads", who, qk_dim, v_dim, n_heads);
     MCR_REQUIRE(S > 0 && L > 0 && S <= 65535 && L <= (1 << 30), "%s: bad problem size S=%ld L=%ld", who, (long)S, (long)L);
     MCR_REQUIRE(ldq >= 2 * qk_dim + v_dim && ldq % 4 == 0 && ld_dout >= v_dim && ld_dout % 4 == 0 && ld_dqkv >= 2 * qk_dim + v_dim &&
@@ -979,22 +1318,11 @@ int mcr_scone_vis_backward(const float* pts, const float* view_harmonics, const 
     launch_ln_bwd(s, X[3], VB_E, w.ng, dH, VB_E, dX, VB_E, false, DW(VIS_NG), DW(VIS_NB), part, T, VB_E);   // norm
 
     // ---- encoders (Attention.py:278-300), last to first; dX holds the gradient of the encoder's output
+    const VbGrads G{dX, dH, dA, dQKV, delta, part, wt};
     for (int e = 2; e >= 0; --e) {
-        const EncW& we = w.enc[e];
         const int o = VIS_ENC + ENC_NW * e;                               // the encoder's block of the table
-        vb_encoder_fwd(s, we, X[e], nullptr, I, B, iN, lengths);                          // the interior, from the boundary
-        gemm_dw(s, dX, VB_E, I.g, 2 * VB_E, T, VB_E, 2 * VB_E, DW(o + ENC_FF2 + LIN_W), DW(o + ENC_FF2 + LIN_B), part);          // ff2
-        gemm_dx(s, dX, VB_E, we.ff2.w, 2 * VB_E, dH, 2 * VB_E, T, VB_E, 2 * VB_E, false, wt);
-        launch_gelu(s, I.z, 2 * VB_E, dH, 2 * VB_E, T, 2 * VB_E, 1);                      // ff1
-        gemm_dw(s, dH, 2 * VB_E, I.h2, VB_E, T, 2 * VB_E, VB_E, DW(o + ENC_FF1 + LIN_W), DW(o + ENC_FF1 + LIN_B), part);
-        gemm_dx(s, dH, 2 * VB_E, we.ff1.w, VB_E, dA, VB_E, T, 2 * VB_E, VB_E, false, wt);
-        launch_ln_bwd(s, I.xm, VB_E, we.n2g, dA, VB_E, dX, VB_E, true, DW(o + ENC_N2G), DW(o + ENC_N2B), part, T, VB_E);   // norm2 (+ residual)
-        gemm_dw(s, dX, VB_E, I.O, VB_E, T, VB_E, VB_E, DW(o + ENC_OUT + LIN_W), DW(o + ENC_OUT + LIN_B), part);        // out
-        gemm_dx(s, dX, VB_E, we.out.w, VB_E, dA, VB_E, T, VB_E, VB_E, false, wt);
-        launch_attn_bwd(s, I.qkv, VB_W3, I.O, VB_E, I.lse, dA, VB_E, delta, dQKV, VB_W3, B, iN, VB_H, lengths, I.part);
-        gemm_dw(s, dQKV, VB_W3, I.h1, VB_E, T, VB_W3, VB_E, DW(o + ENC_QKV + LIN_W), DW(o + ENC_QKV + LIN_B), part);   // qkv
-        gemm_dx(s, dQKV, VB_W3, we.qkv.w, VB_E, dA, VB_E, T, VB_W3, VB_E, false, wt);
-        launch_ln_bwd(s, X[e], VB_E, we.n1g, dA, VB_E, dX, VB_E, true, DW(o + ENC_N1G), DW(o + ENC_N1B), part, T, VB_E);   // norm1 (+ residual)
+        vb_encoder_fwd(s, w.enc[e], X[e], nullptr, I, B, iN, lengths);                    // the interior, from the boundary
+        vb_encoder_bwd(s, w.enc[e], d_weights ? d_weights + o : nullptr, X[e], I, G, B, iN, lengths);
     }
 
     // ---- embedding (Attention.py:98-128): [res | cloud max of res | pts]
@@ -1006,6 +1334,100 @@ int mcr_scone_vis_backward(const float* pts, const float* view_harmonics, const 
     if (d_pts) {
         launch_copy2d(s, dX + 2 * VB_F, VB_E, d_pts, 4, T, 4);
         gemm_dx(s, dH, VB_F, w.l1.w, 4, d_pts, 4, T, VB_F, 4, true, wt);
+    }
+    MCR_LAUNCH_CHECK(who);
+    return 0;
+}
+
+// ---- PCTransformer ---------------------------------------------------------------------------------------------------------------------
+size_t mcr_attention_backward_pct_workspace_bytes(int64_t S, int64_t L) {
+    return measure(carve_attention_backward_pct, S, L) + VB_BLOCK_WS_SLACK;
+}
+
+int mcr_attention_backward_pct(const float* qkv, int64_t ldq, const float* d_out, int64_t ld_dout, float* d_qkv, int64_t ld_dqkv, int64_t S,
+                               int64_t L, int n_heads, int qk_dim, int v_dim, const int* lens, void* workspace, size_t workspace_bytes,
+                               void* stream) {
+    const char* who = "mcr_attention_backward_pct";
+    MCR_REQUIRE(qkv && d_out && d_qkv, "%s: null pointer", who);
+    MCR_REQUIRE(n_heads == VB_H && qk_dim == 8 * n_heads && v_dim == 32 * n_heads,
+                "%s: 4 heads of widths 8 (q, k) and 32 (v) expected, got qk_dim %d, v_dim %d for %d heads", who, qk_dim, v_dim, n_heads);
+    MCR_REQUIRE(S > 0 && L > 0 && (L == 16 || S <= 65535) && L <= (1 << 30) && S <= (1ll << 31), "%s: bad problem size S=%ld L=%ld (S <= 65535 unless L == 16)",
+                who, (long)S, (long)L);
+    MCR_REQUIRE(L != 16 || !lens, "%s: sequences of 16 tokens take no lens (every key takes part)", who);
+    MCR_REQUIRE(ldq >= 2 * qk_dim + v_dim && ldq % 4 == 0 && ld_dout >= v_dim && ld_dout % 4 == 0 && ld_dqkv >= 2 * qk_dim + v_dim &&
+                    ld_dqkv % 4 == 0,
+                "%s: leading dimensions must cover the rows and be multiples of 4", who);
+    MCR_REQUIRE(((uintptr_t)qkv | (uintptr_t)d_out | (uintptr_t)d_qkv) % 16 == 0, "%s: operands must be 16-byte aligned", who);
+    hipStream_t s = (hipStream_t)stream;
+    if (L == 16) {
+        launch_attn16_bwd(s, qkv, ldq, d_out, ld_dout, d_qkv, ld_dqkv, S);
+        MCR_LAUNCH_CHECK(who);
+        return 0;
+    }
+    MCR_REQUIRE(workspace && workspace_bytes >= mcr_attention_backward_pct_workspace_bytes(S, L), "%s: workspace too small", who);
+    MCR_REQUIRE((uintptr_t)workspace % 16 == 0, "%s: workspace must be 16-byte aligned", who);
+    Arena a{(char*)workspace, workspace_bytes};
+    const AttnBwdScratch ws = carve_attention_backward_pct(a, S, L);
+    MCR_REQUIRE(a.ok(), "%s: workspace overflow", who);
+    launch_attn_fwd(s, qkv, ldq, ws.O, v_dim, ws.lse, S, (int)L, n_heads, lens, ws.part, 8);
+    launch_attn_bwd(s, qkv, ldq, ws.O, v_dim, ws.lse, d_out, ld_dout, ws.delta, d_qkv, ld_dqkv, S, (int)L, n_heads, lens, ws.part, 8);
+    MCR_LAUNCH_CHECK(who);
+    return 0;
+}
+
+int mcr_pool_max_avg_backward(const float* X, int64_t ldx, const float* dY, int64_t ldy, float* dX, int64_t ld_dx, int64_t S, int64_t L, int E,
+                              void* stream) {
+    const char* who = "mcr_pool_max_avg_backward";
+    MCR_REQUIRE(X && dY && dX, "%s: null pointer", who);
+    MCR_REQUIRE(S > 0 && L > 0 && E > 0 && S <= (1ll << 31) - 1 && L <= (1 << 30) && E <= 64 * 65535, "%s: bad problem size", who);
+    MCR_REQUIRE(ldx >= E && ldy >= 2 * E && ld_dx >= E, "%s: leading dimension too small", who);
+    launch_pool_bwd((hipStream_t)stream, X, ldx, dY, ldy, dX, ld_dx, S, (int)L, E);
+    MCR_LAUNCH_CHECK(who);
+    return 0;
+}
+
+int mcr_pc_transformer_backward_chunk(int64_t S, int64_t L) { return (S > 0 && L > 0) ? (int)std::min<int64_t>(pb_chunk(S, L), INT32_MAX) : 0; }
+
+size_t mcr_pc_transformer_backward_workspace_bytes(int64_t S, int64_t L) {
+    return (S > 0 && L > 0) ? measure(carve_pb, S, L, 256) + VB_WS_SLACK : 0;          // (sized for the wider feature_dim, 512)
+}
+
+int mcr_pc_transformer_backward(const float* pc, const float* d_features, int64_t S, int64_t L, int feature_dim, const float* const* weights,
+                                int n_weights, float* const* d_weights, float* d_pc, void* workspace, size_t workspace_bytes, void* stream) {
+    const char* who = "mcr_pc_transformer_backward";
+    MCR_REQUIRE(pc && d_features && weights, "%s: null pointer", who);
+    if (check_table(who, PCT_TABLE, weights, n_weights, PCT_NW)) return 1;                  // (the planes tails are accepted and ignored)
+    MCR_REQUIRE(feature_dim == 256 || feature_dim == 512, "%s: feature_dim must be 256 or 512", who);
+    MCR_REQUIRE(S > 0 && L > 0 && (L == 16 || S <= 65535) && L <= (1 << 24) && S <= (1ll << 31) / L,
+                "%s: bad problem size S=%ld L=%ld (S <= 65535 unless L == 16)", who, (long)S, (long)L);
+    MCR_REQUIRE(workspace && workspace_bytes >= mcr_pc_transformer_backward_workspace_bytes(S, L), "%s: workspace too small", who);
+    MCR_REQUIRE((uintptr_t)workspace % 16 == 0, "%s: workspace must be 16-byte aligned", who);
+    if (d_weights)
+        for (int i = 0; i < PCT_NW; ++i) MCR_REQUIRE(d_weights[i], "%s: d_weights[%d] is null", who, i);
+    MCR_REQUIRE(((uintptr_t)pc | (uintptr_t)d_features) % 16 == 0, "%s: operands must be 16-byte aligned", who);
+    if (!d_weights && !d_pc) return 0;
+    hipStream_t s = (hipStream_t)stream;
+    const PctW w = read_pct(weights);
+    const int half = feature_dim / 2;
+    Arena a{(char*)workspace, workspace_bytes};
+    const PbScratch ws = carve_pb(a, S, L, half);
+    MCR_REQUIRE(a.ok(), "%s: workspace overflow", who);
+    const int64_t Sc = pb_chunk(S, L);
+    // the chunks behind the first leave their weight gradients in ws.stage, cut in table order, and are added in chunk order
+    PbSlots slots{};
+    float* stage_tab[PCT_NW];
+    if (d_weights && Sc < S)
+        for (int i = 0; i < PCT_NW; ++i) {
+            slots.dst[i] = d_weights[i];
+            slots.off[i + 1] = slots.off[i] + pb_slot_floats(i, half);
+            stage_tab[i] = ws.stage + slots.off[i];
+        }
+    for (int64_t s0 = 0; s0 < S; s0 += Sc) {
+        const int64_t n = std::min(Sc, S - s0);
+        float* const* dw = !d_weights ? nullptr : s0 == 0 ? d_weights : stage_tab;
+        pb_chunk_backward(s, w, pc + s0 * L * 3, d_features + s0 * feature_dim, n, (int)L, half, dw, d_pc ? d_pc + s0 * L * 3 : nullptr, ws);
+        if (d_weights && s0 > 0)
+            hipLaunchKernelGGL(pb_add_slots_kernel, dim3(64, PCT_NW), dim3(256), 0, s, slots, (const float*)ws.stage);
     }
     MCR_LAUNCH_CHECK(who);
     return 0;

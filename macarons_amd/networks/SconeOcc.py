@@ -89,8 +89,39 @@ class PCTransformer(nn.Module):
         t += [_f32c(self.norm.weight), _f32c(self.norm.bias), _f32c(self.linear0.weight), _f32c(self.linear0.bias)]
         return t
 
+    def _grad_slots(self):
+        """(parameters, slots): every parameter of the module with its place in weight_table() -- (table index, row slice or None);
+        w_q / w_k / w_v are rows 0:32 / 32:64 / 64:192 of their encoder's packed qkv entries."""
+        slots = {id(t): (k, None) for k, t in enumerate((self.embedding.linear1.weight, self.embedding.linear1.bias,
+                                                          self.embedding.linear2.weight, self.embedding.linear2.bias))}
+        for e, enc in enumerate(self.encoders):
+            o = 4 + 12 * e
+            qk = enc.mhsa.w_q.weight.shape[0]
+            rows = ((0, qk), (qk, 2 * qk), (2 * qk, 2 * qk + enc.mhsa.w_v.weight.shape[0]))
+            for lin, r in zip((enc.mhsa.w_q, enc.mhsa.w_k, enc.mhsa.w_v), rows):
+                slots[id(lin.weight)], slots[id(lin.bias)] = (o + 2, r), (o + 3, r)
+            for k, t in enumerate((enc.norm1.weight, enc.norm1.bias)):
+                slots[id(t)] = (o + k, None)
+            for k, t in enumerate((enc.mhsa.out.weight, enc.mhsa.out.bias, enc.norm2.weight, enc.norm2.bias, enc.ff.linear1.weight,
+                                   enc.ff.linear1.bias, enc.ff.linear2.weight, enc.ff.linear2.bias)):
+                slots[id(t)] = (o + 4 + k, None)
+        for k, t in enumerate((self.norm.weight, self.norm.bias, self.linear0.weight, self.linear0.bias)):
+            slots[id(t)] = (28 + k, None)
+        params = tuple(self.parameters())
+        missing = [n for n, p in self.named_parameters() if id(p) not in slots]
+        if missing:
+            raise NotImplementedError(f"PCTransformer HIP backward: parameters outside the weight table: {missing}")
+        return params, tuple(slots[id(p)] for p in params)
+
     def forward(self, pc, mask=None):
-        """pc [n_clouds, seq_len, 3] -> [n_clouds, feature_dim]."""
+        """pc [n_clouds, seq_len, 3] -> [n_clouds, feature_dim].  Differentiable (once) without a mask: HIP forward, HIP backward
+        (autograd.PCTransformerFunction); the mask= path is inference only."""
+        if mask is None and self._is_default_arch() and A.needs_grad(self, pc):
+            params, slots = self._grad_slots()
+            return A.PCTransformerFunction.apply(self._forward_hip, self.weight_table, slots, self.feature_dim, pc, *params)
+        return self._forward_hip(pc, mask)
+
+    def _forward_hip(self, pc, mask=None):
         _inference_only(self, pc)
         if not self._is_default_arch():
             raise NotImplementedError("the fused MI355X PCTransformer implements the reference's default architecture")

@@ -501,6 +501,72 @@ def attention_backward(qkv, d_out, n_heads=4, lens=None):
     return d_qkv
 
 
+def attention_backward_pct(qkv, d_out, lens=None):
+    """attention_backward at the PCTransformer's widths: 4 heads of 8 (q, k) and 32 (v), qkv [S,L,192], d_out [S,L,128] -> d_qkv
+    [S,L,192] (mcr_attention_backward_pct).  L == 16: the one-wave-per-sequence kernel, any S, no lens; else S <= 65535."""
+    qkv, d_out = _req(qkv, "qkv"), _req(d_out, "d_out")
+    S, L, W = qkv.shape
+    if W != 192 or d_out.shape != (S, L, 128):
+        raise ValueError("attention_backward_pct: qkv [S,L,192] and d_out [S,L,128] expected")
+    if lens is not None:
+        lens = _req(lens, "lens", torch.int32).reshape(-1)
+        if lens.numel() != S:
+            raise ValueError("lens must hold one length per sequence")
+    d_qkv = torch.empty_like(qkv)
+    L_ = lib()
+    ws = _workspace(qkv.device, int(L_.mcr_attention_backward_pct_workspace_bytes(c_i64(S), c_i64(L))))
+    with torch.cuda.device(qkv.device):
+        check(L_.mcr_attention_backward_pct(_p(qkv), c_i64(W), _p(d_out), c_i64(128), _p(d_qkv), c_i64(W), c_i64(S), c_i64(L), c_int(4),
+                                            c_int(32), c_int(128), _p(lens) if lens is not None else c_vp(0), _p(ws), c_size(ws.numel()),
+                                            _stream()), "mcr_attention_backward_pct")
+    return d_qkv
+
+
+def pool_max_avg_backward(x, d_y):
+    """Gradient of pool_max_avg: x [S,L,E], d_y [S,2E] -> d_x [S,L,E] (the max's share to the lowest row holding it)."""
+    x, d_y = _req(x, "x"), _req(d_y, "d_y")
+    S, L, E = x.shape
+    if d_y.shape != (S, 2 * E):
+        raise ValueError(f"pool_max_avg_backward: d_y [{S},{2 * E}] expected, got {tuple(d_y.shape)}")
+    d_x = torch.empty_like(x)
+    with torch.cuda.device(x.device):
+        check(lib().mcr_pool_max_avg_backward(_p(x), c_i64(E), _p(d_y), c_i64(2 * E), _p(d_x), c_i64(E), c_i64(S), c_i64(L), c_int(E),
+                                              _stream()), "mcr_pool_max_avg_backward")
+    return d_x
+
+
+def pc_transformer_backward_chunk(S, L):
+    """Sequences per chunk of pc_transformer_backward (mcr_pc_transformer_backward_chunk: a function of (S, L) alone)."""
+    return int(lib().mcr_pc_transformer_backward_chunk(c_i64(S), c_i64(L)))
+
+
+def pc_transformer_backward(pc, d_features, weights, feature_dim, need=(True, True)):
+    """Gradients of pc_transformer_forward given d_features [S, feature_dim]: (d_weights, d_pc [S,L,3]); `need` = (params, pc) selects
+    what is computed (None for the rest).  d_weights: one tensor per entry of the 32-entry weight table (table order and shapes; the
+    packed qkv weight / bias one entry each).  The fp32 network's gradient whatever the variant (mcr_pc_transformer_backward: HIP
+    kernels only, deterministic; 16-token sequences are chunked inside the entry)."""
+    pc = _req(pc, "pc")
+    d_features = _req(d_features, "d_features")     # .contiguous(): y.sum().backward() hands in an expanded, zero-stride tensor
+    S, L, d = pc.shape
+    if d != 3 or d_features.shape != (S, feature_dim):
+        raise ValueError(f"PCTransformer backward needs pc [S,L,3] and d_features [S,{feature_dim}]; got {tuple(pc.shape)}, "
+                         f"{tuple(d_features.shape)}")
+    tensors = weights[0] if isinstance(weights, tuple) else weights
+    need_w, need_p = (bool(x) for x in need)
+    dev = pc.device
+    d_w = [torch.empty(tuple(t.shape), dtype=torch.float32, device=dev) for t in tensors[:32]] if need_w else None
+    d_pc = torch.empty((S, L, 3), dtype=torch.float32, device=dev) if need_p else None
+    L_ = lib()
+    ws = _workspace(dev, int(L_.mcr_pc_transformer_backward_workspace_bytes(c_i64(S), c_i64(L))))
+    dtab = (ctypes.c_void_p * 32)(*[t.data_ptr() for t in d_w]) if need_w else None
+    with torch.cuda.device(dev):
+        check(L_.mcr_pc_transformer_backward(_p(pc), _p(d_features), c_i64(S), c_i64(L), c_int(feature_dim), _ptr_table(weights),
+                                             c_int(_n_weights(weights)), dtab if dtab is not None else c_vp(None),
+                                             _p(d_pc) if d_pc is not None else c_vp(None), _p(ws), c_size(ws.numel()), _stream()),
+              "mcr_pc_transformer_backward")
+    return d_w, d_pc
+
+
 def linear_backward(x, weight, d_y, z=None, gelu=False, d_x=None, need=(True, True, True)):
     """Gradient of linear(x, weight, bias, gelu) given d_y: (d_x, d_w, d_b).  z: the pre-activation (needed with gelu).  d_x given:
     the input gradient is ADDED to it (in place), else a new tensor; `need` = (x, weight, bias).  mcr_linear_backward."""
