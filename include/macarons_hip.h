@@ -310,6 +310,29 @@ size_t mcr_pc_transformer_backward_workspace_bytes(int64_t S, int64_t L);
 int mcr_pc_transformer_backward(const float* pc, const float* d_features, int64_t S, int64_t L, int feature_dim,
                                 const float* const* weights, int n_weights, float* const* d_weights, float* d_pc, void* workspace,
                                 size_t workspace_bytes, void* stream);
+/* mcr_scone_occ_backward: gradient of mcr_scone_occ_forward given d_out [B,Q,1] and the neighbour selection, computed on the fp32
+ *   network whatever the call's variant (as mcr_scone_vis_backward: no fp16 plane is used, no range guard applies).
+ *   pc_global, Lg, pc_scale, M_scale (HOST arrays of 3, every M_scale[i] >= 16), x, view_harmonics, weights: as the forward; weights is the
+ *   SCONE_OCC table (140 entries; the PLANES / END PLANES tails are accepted and ignored).
+ *   knn_idx: HOST array of 3 DEVICE pointers to int64 [B,Q,16], the 16 nearest points of pc_scale[i][b] of every query (what the
+ *   forward's search selects; an index outside [0, M_scale[i]) is clamped into the cloud).  The selection carries no gradient.
+ *   d_weights (may be NULL: no parameter gradients): 140 DEVICE pointers in the table's order and shapes (every transformer's packed qkv
+ *   weight [192,128] and bias [192] one entry each); written, not accumulated.  d_x [B,Q,3] and d_view_harmonics [B,Q,64] may be NULL;
+ *   all three NULL: returns 0 at once.  There is no gradient for the surface points.
+ *   The global transformer's forward runs once; then, cloud by cloud, the queries are processed in chunks of q_chunk rows (0: the default,
+ *   mcr_scone_occ_backward_chunk(Q) = the 16-token chunk of mcr_pc_transformer_backward; else a multiple of 16, >= 16; a chunk never
+ *   crosses a cloud): gather, local transformers, x embedding and head forward, then their backward; the chunks' weight gradients and their
+ *   shares of the global features' gradient are summed in chunk order; the global transformer's backward runs last.  The workspace holds
+ *   one chunk whatever Q is.  Two calls give identical bits; the bits may depend on q_chunk (another summation order of the chunks).
+ *   pc_global, pc_scale[i], knn_idx[i], x, view_harmonics, d_out, the outputs and the workspace 16-byte aligned.
+ *   workspace: mcr_scone_occ_backward_workspace_bytes(B, Q, Lg, q_chunk) bytes.  Deterministic (no float atomics), no host
+ *   synchronisation. */
+int mcr_scone_occ_backward_chunk(int64_t Q);
+size_t mcr_scone_occ_backward_workspace_bytes(int64_t B, int64_t Q, int64_t Lg, int64_t q_chunk);
+int mcr_scone_occ_backward(const float* pc_global, int64_t Lg, const float* const* pc_scale, const int64_t* M_scale, const float* x,
+                           const float* view_harmonics, const int64_t* const* knn_idx, const float* d_out, int64_t B, int64_t Q,
+                           const float* const* weights, int n_weights, float* const* d_weights, float* d_x, float* d_view_harmonics,
+                           int64_t q_chunk, void* workspace, size_t workspace_bytes, void* stream);
 size_t mcr_scone_occ_workspace_bytes(int64_t B, int64_t Q, int64_t Lg);
 int mcr_scone_occ_forward(const float* pc_global, int64_t Lg, const float* const* pc_scale, const int64_t* M_scale,
                           const float* x, const float* view_harmonics, float* out, int64_t B, int64_t Q,

@@ -8,7 +8,10 @@ SconeOcc's entry point is still wrapped in a torch.autograd.Function whose backw
 mathematics with plain torch ops on the same device (composite functions below, written against the modules' own parameters) under
 autograd and back-propagates through that; env MCR_SCONE_VIS_BWD=composite puts SconeVis back on that path (A/B).  Opt-in, env
 MCR_SCONE_OCC_BWD=pct: that recomputation evaluates SconeOcc's four PCTransformers -- almost all of its work -- through
-PCTransformerFunction (HIP forward and backward); the gather, the offsets, the x-embedding and the head stay torch.  The composites
+PCTransformerFunction (HIP forward and backward); the gather, the offsets, the x-embedding and the head stay torch.  Opt-in,
+MCR_SCONE_OCC_BWD=hip: no recomputation in torch at all -- SconeOccFunction below hands the whole backward (gather, local transformers,
+x-embedding, head, global transformer) to one entry, mcr_scone_occ_backward, for the parameters, x and the view harmonics; a gradient
+for the surface points pc is not computed there, so a forward whose pc requires one takes the pct route.  The composites
 are ordinary differentiable torch code, so they are also what the parity tests differentiate numerically (tests/test_autograd.py:
 fp64 finite differences on CPU; on the GPU the composite forward must reproduce the HIP forward to 1e-4, which makes its gradient
 the gradient of the kernels' function) and the second reference of the HIP backward's tests.
@@ -134,13 +137,16 @@ def pc_transformer(pct, x):
 
 
 def scone_occ_backward_mode():
-    """'composite' (default) or 'pct' (env MCR_SCONE_OCC_BWD=pct: the four PCTransformers of the recomputation on the HIP backward)."""
-    return "pct" if os.environ.get("MCR_SCONE_OCC_BWD", "").lower() == "pct" else "composite"
+    """'composite' (default), 'pct' (env MCR_SCONE_OCC_BWD=pct: the four PCTransformers of the recomputation on the HIP backward) or
+    'hip' (MCR_SCONE_OCC_BWD=hip: the whole network's backward behind one entry, SconeOccFunction; with a gradient wanted for the surface
+    points, the 'pct' route).  Anything else: 'composite'."""
+    mode = os.environ.get("MCR_SCONE_OCC_BWD", "").lower()
+    return mode if mode in ("pct", "hip") else "composite"
 
 
 def scone_occ(model, pc_global, scales, x, view_harmonics, knn_idx):
     """SconeOcc.forward (SconeOcc.py:250-347) given the down-sampled clouds and, per scale, the neighbour indices [B,Q,16]."""
-    if scone_occ_backward_mode() == "pct":          # the module's own forward: PCTransformerFunction where a gradient is needed
+    if scone_occ_backward_mode() in ("pct", "hip"):  # the module's own forward: PCTransformerFunction where a gradient is needed
         return _scone_occ(lambda pct, pc: pct(pc), model, pc_global, scales, x, view_harmonics, knn_idx)
     return _scone_occ(pc_transformer, model, pc_global, scales, x, view_harmonics, knn_idx)
 
@@ -269,3 +275,44 @@ class PCTransformerFunction(torch.autograd.Function):
             g = d_w[idx] if rows is None else d_w[idx][rows[0]:rows[1]]
             grads.append(g.to(ctx.param_dtypes[j]))
         return (None, None, None, None, d_pc.to(pc.dtype) if d_pc is not None else None, *grads)
+
+
+# ---- SconeOcc: HIP forward + HIP backward ----------------------------------------------------------------------------------------
+class SconeOccFunction(torch.autograd.Function):
+    """apply(hip_fn, table_fn, slots, k, pc_global, scales, x, view_harmonics, *params): forward = hip_fn(pc_global, scales, x,
+    view_harmonics) without a graph; backward = ops.scone_occ_backward (mcr_scone_occ_backward: the gradient of the fp32 network, HIP
+    kernels only) on the weight table table_fn() returns, with the k neighbour indices of every scale taken by ops.knn_points on the
+    detached inputs, as the composite route takes them.  slots[j] = (table index, row slice or None) of params[j] -- the packed qkv
+    entries of the four transformers hand rows 0:32, 32:64 and 64:192 to w_q, w_k and w_v.  The clouds (pc_global, the list `scales`)
+    get no gradient.  Differentiable once."""
+
+    @staticmethod
+    def forward(ctx, hip_fn, table_fn, slots, k, pc_global, scales, x, view_harmonics, *params):
+        ctx.table_fn, ctx.slots, ctx.k = table_fn, slots, k
+        ctx.param_dtypes = tuple(p.dtype for p in params)
+        ctx.save_for_backward(pc_global, x, view_harmonics, *scales)
+        with torch.no_grad():
+            return hip_fn(pc_global, scales, x, view_harmonics)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        if torch.is_grad_enabled():
+            raise RuntimeError("SconeOcc.forward is differentiable once: its HIP backward builds no graph (create_graph is not supported)")
+        from . import ops
+        pc_global, x, vh, *scales = ctx.saved_tensors
+        need_x, need_v = ctx.needs_input_grad[6], ctx.needs_input_grad[7]
+        need_w = any(ctx.needs_input_grad[8:])
+        xq = x.detach().float().contiguous()
+        sc = [s_.detach().float().contiguous() for s_ in scales]
+        idx = [ops.knn_points(xq, s_, ctx.k)[2] for s_ in sc]
+        d_w, d_x, d_vh = ops.scone_occ_backward(pc_global.detach().float(), sc, xq, vh.detach().float(), idx, grad_out.float(),
+                                                ctx.table_fn(), need=(need_w, need_x, need_v))
+        grads = []
+        for j, (i, rows) in enumerate(ctx.slots):
+            if not ctx.needs_input_grad[8 + j]:
+                grads.append(None)
+                continue
+            g = d_w[i] if rows is None else d_w[i][rows[0]:rows[1]]
+            grads.append(g.to(ctx.param_dtypes[j]))
+        return (None, None, None, None, None, None, d_x.to(x.dtype) if d_x is not None else None,
+                d_vh.to(vh.dtype) if d_vh is not None else None, *grads)

@@ -29,6 +29,13 @@
 // per-head widths (16, 64) and (8, 32).  Sequences of 16 tokens have a fused attention backward of their own (a16_bwd_kernel: one wave per
 // sequence, nothing but d_qkv written) and are processed in chunks of PB_CHUNK16 sequences INSIDE the entry, their weight gradients
 // summed in chunk order: the workspace holds one chunk whatever S is.  The tail's pooling has its own backward (pb_pool_bwd_kernel).
+//
+// SconeOcc backward (SconeOcc.py:250-347): mcr_scone_occ_backward, the network around the four PCTransformers behind one entry, given
+// the neighbour indices.  The global transformer's forward runs once; then, cloud by cloud and chunk by chunk of its queries, the
+// neighbourhoods are gathered as offsets (so_gather_kernel), the three local transformers, the x-embedding and the head run forward and
+// backward on the chunk functions above (pb_chunk_forward / pb_chunk_backward) and the launchers of this file; the query's share of the
+// offsets' gradient is so_dx_sub_kernel.  Weight gradients of the chunks behind the first are staged and added in chunk order, as are
+// the chunks' column sums of the global features' gradient; the global transformer's backward runs last.  No gradient for the clouds.
 #include "nn_kernels.h"
 #include "net_layout.h"
 #include <algorithm>
@@ -1096,8 +1103,9 @@ struct PbScratch {
     VbGrads G;
     float* stage;                                          // weight gradients of the chunks behind the first
 };
-PbScratch carve_pb(Arena& a, int64_t S, int64_t L, int half) {
-    const int64_t Sc = pb_chunk(S, L), T = Sc * L;
+// one chunk of Sc sequences; with_stage: the staging area of the chunks behind the first
+PbScratch carve_pb_chunk(Arena& a, int64_t Sc, int64_t L, int half, bool with_stage) {
+    const int64_t T = Sc * L;
     PbScratch w;
     for (float*& x : w.X) x = a.f(T * PB_E);
     w.z1 = a.f(T * PB_F); w.g1 = a.f(T * PB_F);
@@ -1113,10 +1121,14 @@ PbScratch carve_pb(Arena& a, int64_t S, int64_t L, int half) {
                            vb_gradw_floats(T, half, PB_E), vb_gradw_floats(T, PB_F, PB_F), vb_ln_part_floats(T, PB_E)}));
     G.wt = a.f((size_t)2 * PB_E * PB_E);
     size_t n_stage = 0;
-    if (Sc < S)
+    if (with_stage)
         for (int i = 0; i < PCT_NW; ++i) n_stage += pb_slot_floats(i, half);
     w.stage = a.f(n_stage);
     return w;
+}
+PbScratch carve_pb(Arena& a, int64_t S, int64_t L, int half) {
+    const int64_t Sc = pb_chunk(S, L);
+    return carve_pb_chunk(a, Sc, L, half, Sc < S);
 }
 AttnBwdScratch carve_attention_backward_pct(Arena& a, int64_t S, int64_t L) {
     AttnBwdScratch w{};
@@ -1129,15 +1141,12 @@ AttnBwdScratch carve_attention_backward_pct(Arena& a, int64_t S, int64_t L) {
     return w;
 }
 
-// One chunk: Sc sequences from pc / d_feat on; dw = where the table's gradients go (NULL: none), d_pc (optional) this chunk's rows
-void pb_chunk_backward(hipStream_t s, const PctW& w, const float* pc, const float* d_feat, int64_t Sc, int L, int half, float* const* dw,
-                       float* d_pc, const PbScratch& ws) {
+// Forward of the fp32 network over one chunk of Sc sequences: boundaries X0..X2, the embedding's pre-activation, the tail up to
+// linear0's output ws.y0 (what the pooling reads)
+void pb_chunk_forward(hipStream_t s, const PctW& w, const float* pc, int64_t Sc, int L, int half, const PbScratch& ws) {
     const int64_t T = Sc * L;
     float* const* X = ws.X;
     const VbInterior& I = ws.I;
-    const VbGrads& G = ws.G;
-    auto DW = [&](int slot) { return dw ? dw[slot] : nullptr; };
-    // ---- forward of the fp32 network: boundaries X0..X2, the embedding's pre-activation, the tail
     vb_linear(s, {pc, 3}, w.l1, {}, {ws.z1, PB_F}, T, PB_F, 3, ACT_NONE);
     launch_gelu(s, ws.z1, PB_F, ws.g1, PB_F, T, PB_F, 0);
     vb_linear(s, {ws.g1, PB_F}, w.l2, {}, {X[0], PB_E}, T, PB_F, PB_F, ACT_NONE);
@@ -1145,8 +1154,21 @@ void pb_chunk_backward(hipStream_t s, const PctW& w, const float* pc, const floa
     for (int e = 0; e < PCT_N_ENC; ++e) vb_encoder_fwd(s, w.enc[e], X[e], X[e + 1], I, Sc, L, nullptr, PB_E);
     launch_layernorm(s, X[PCT_N_ENC], PB_E, w.ng, w.nb, ws.hn, PB_E, T, PB_E);
     vb_linear(s, {ws.hn, PB_E}, w.lin0, {}, {ws.y0, half}, T, half, PB_E, ACT_NONE);
+}
+
+// One chunk: Sc sequences from pc / d_feat on; dw = where the table's gradients go (NULL: none), d_pc (optional) this chunk's rows;
+// ld_feat: the leading dimension of d_feat (0: 2 * half, dense rows); forward_done: ws still holds pb_chunk_forward's results for this
+// very chunk (nothing has written it since), so the forward is not run again
+void pb_chunk_backward(hipStream_t s, const PctW& w, const float* pc, const float* d_feat, int64_t Sc, int L, int half, float* const* dw,
+                       float* d_pc, const PbScratch& ws, int64_t ld_feat = 0, bool forward_done = false) {
+    const int64_t T = Sc * L;
+    float* const* X = ws.X;
+    const VbInterior& I = ws.I;
+    const VbGrads& G = ws.G;
+    auto DW = [&](int slot) { return dw ? dw[slot] : nullptr; };
+    if (!forward_done) pb_chunk_forward(s, w, pc, Sc, L, half, ws);
     // ---- tail (SconeOcc.py:119-126), backwards: pooling, linear0, norm
-    launch_pool_bwd(s, ws.y0, half, d_feat, 2 * half, G.dH, half, Sc, L, half);
+    launch_pool_bwd(s, ws.y0, half, d_feat, ld_feat > 0 ? ld_feat : 2 * half, G.dH, half, Sc, L, half);
     gemm_dw(s, G.dH, half, ws.hn, PB_E, T, half, PB_E, DW(PCT_LIN0 + LIN_W), DW(PCT_LIN0 + LIN_B), G.part);
     gemm_dx(s, G.dH, half, w.lin0.w, PB_E, G.dA, PB_E, T, half, PB_E, false, G.wt);
     launch_ln_bwd(s, X[PCT_N_ENC], PB_E, w.ng, G.dA, PB_E, G.dX, PB_E, false, DW(PCT_NG), DW(PCT_NB), G.part, T, PB_E);
@@ -1164,6 +1186,106 @@ void pb_chunk_backward(hipStream_t s, const PctW& w, const float* pc, const floa
         launch_copy2d(s, G.dX + PB_F, PB_E, d_pc, 3, T, 3);
         gemm_dx(s, G.dH, PB_F, w.l1.w, 3, d_pc, 3, T, PB_F, 3, true, G.wt);
     }
+}
+
+
+// ---- SconeOcc (SconeOcc.py:250-347): the network around the four PCTransformers -------------------------------------------------------
+constexpr int SO_K = 16;                                            // neighbours per query and scale
+constexpr int SO_G = 512, SO_LF = 256, SO_XE = 512, SO_VH = 64;     // widths of the head's input: global | 3 x local | x-embedding | harmonics
+constexpr int SO_LOC = SO_G, SO_XCOL = SO_LOC + 3 * SO_LF, SO_VCOL = SO_XCOL + SO_XE, SO_H = SO_VCOL + SO_VH;   // its columns (1856 in all)
+constexpr int SO_L1 = 512, SO_L2 = 256;                             // the head's hidden widths
+constexpr int SO_HEAD_NW = 6 * LIN_NW;                              // x_embedding.linear{1,2,3}, linear{1,2,3}: the table from OCC_XE on
+static_assert(SO_H == 1856 && OCC_LIN == OCC_XE + 3 * LIN_NW && SO_HEAD_NW <= PCT_NW, "SconeOcc head layout");
+
+// floats of the table entry OCC_XE + slot
+inline int so_head_slot_floats(int slot) {
+    constexpr int n[6] = {SO_XE / 4, SO_XE / 2, SO_XE, SO_L1, SO_L2, 1}, k[6] = {3, SO_XE / 4, SO_XE / 2, SO_H, SO_L1, SO_L2};
+    return slot % LIN_NW == LIN_W ? n[slot / LIN_NW] * k[slot / LIN_NW] : n[slot / LIN_NW];
+}
+
+// off[(r*16 + j)*3 + c] = pc[idx[r*16 + j]*3 + c] - x[r*3 + c]: the neighbourhoods of `rows` queries of one cloud of M points, as offsets
+// (SconeOcc.py:296-300; the fp32 subtraction torch performs).  One thread per (query, neighbour); an index outside the cloud is clamped
+// into it (never an access out of bounds).
+__global__ __launch_bounds__(256) void so_gather_kernel(const float* __restrict__ pc, long long M, const long long* __restrict__ idx,
+                                                        const float* __restrict__ x, float* __restrict__ off, long long rows) {
+    const long long e = blockIdx.x * 256ll + threadIdx.x;
+    if (e >= rows * SO_K) return;
+    const long long r = e / SO_K;
+    const long long i = min(max(idx[e], 0ll), M - 1);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) off[e * 3 + c] = pc[i * 3 + c] - x[r * 3 + c];
+}
+
+// d_x[r*3 + c] -= sum_j d_off[(r*16 + j)*3 + c], j ascending: the query's share of its neighbourhood's offsets.  One thread per (query,
+// channel) owns its output: no atomics.
+__global__ __launch_bounds__(256) void so_dx_sub_kernel(const float* __restrict__ d_off, float* __restrict__ d_x, long long rows) {
+    const long long e = blockIdx.x * 256ll + threadIdx.x;
+    if (e >= rows * 3) return;
+    const long long r = e / 3;
+    const int c = (int)(e - r * 3);
+    float acc = 0.f;
+#pragma unroll
+    for (int j = 0; j < SO_K; ++j) acc += d_off[(r * SO_K + j) * 3 + c];
+    d_x[e] -= acc;
+}
+
+void launch_so_gather(hipStream_t s, const float* pc, int64_t M, const int64_t* idx, const float* x, float* off, int64_t rows) {
+    hipLaunchKernelGGL(so_gather_kernel, dim3((unsigned)cdiv(rows * SO_K, 256)), dim3(256), 0, s, pc, (long long)M, (const long long*)idx, x, off,
+                       (long long)rows);
+}
+void launch_so_dx_sub(hipStream_t s, const float* d_off, float* d_x, int64_t rows) {
+    hipLaunchKernelGGL(so_dx_sub_kernel, dim3((unsigned)cdiv(rows * 3, 256)), dim3(256), 0, s, d_off, d_x, (long long)rows);
+}
+
+inline int64_t so_chunk(int64_t Q, int64_t q_chunk) { return std::min<int64_t>(q_chunk > 0 ? q_chunk : PB_CHUNK16, Q); }
+
+// The workspace of mcr_scone_occ_backward: what outlives a chunk (the global features and their gradient), then one chunk of Qc queries
+// OVER the global transformer's scratch -- the two are never alive together (the global forward runs first, its backward last).
+struct SoScratch {
+    float *gfeat, *dG, *gtmp;                              // [B, 512] global features and their gradient; one chunk's partial of a row of it
+    float *off[3], *d_off;                                 // the chunk's neighbourhoods [Qc, 16, 3] per scale; the gradient of one of them
+    float *ze1, *ge1, *ze2, *ge2, *ze3;                    // x-embedding: pre-activations and GELUs
+    float *h, *z1, *g1, *z2, *g2, *z3;                     // head: input [Qc, 1856], pre-activations and GELUs
+    float *dH, *d1, *d2, *dz3;                             // gradients: head input; 512- and 256-wide layers (the x-embedding's 128 / 256 too); output
+    float *part, *wt;                                      // weight-gradient slabs; transposed weight
+    float* stage;                                          // weight gradients of the chunks behind the first: 3 PCT tables, then the head's
+    PbScratch local[3];                                    // one 16-token chunk per scale: each keeps what its forward leaves (boundaries, embedding
+                                                           // and tail), the three share the encoder interior and the gradient buffers
+    PbScratch global;                                      // B sequences of Lg tokens
+};
+inline size_t so_stage_pct_floats() {
+    size_t n = 0;
+    for (int i = 0; i < PCT_NW; ++i) n += pb_slot_floats(i, SO_LF / 2);
+    return n;
+}
+SoScratch carve_so(Arena& a, int64_t B, int64_t Qc, int64_t Lg) {
+    SoScratch w;
+    w.gfeat = a.f(B * SO_G); w.dG = a.f(B * SO_G); w.gtmp = a.f(SO_G);
+    Arena c = a.rest(), g = a.rest();
+    for (float*& o : w.off) o = c.f(Qc * SO_K * 3);
+    w.d_off = c.f(Qc * SO_K * 3);
+    w.ze1 = c.f(Qc * (SO_XE / 4)); w.ge1 = c.f(Qc * (SO_XE / 4)); w.ze2 = c.f(Qc * (SO_XE / 2)); w.ge2 = c.f(Qc * (SO_XE / 2));
+    w.ze3 = c.f(Qc * SO_XE);
+    w.h = c.f(Qc * SO_H); w.z1 = c.f(Qc * SO_L1); w.g1 = c.f(Qc * SO_L1); w.z2 = c.f(Qc * SO_L2); w.g2 = c.f(Qc * SO_L2); w.z3 = c.f(Qc);
+    w.dH = c.f(Qc * SO_H); w.d1 = c.f(Qc * SO_L1); w.d2 = c.f(Qc * SO_L2); w.dz3 = c.f(Qc);
+    w.part = c.f(std::max({vb_gradw_floats(Qc, SO_L1, SO_H), vb_gradw_floats(Qc, SO_L2, SO_L1), vb_gradw_floats(Qc, 1, SO_L2),
+                           vb_gradw_floats(Qc, SO_XE, SO_XE / 2), vb_gradw_floats(Qc, SO_XE / 2, SO_XE / 4), vb_gradw_floats(Qc, SO_XE / 4, 3)}));
+    w.wt = c.f((size_t)SO_L1 * SO_H);
+    size_t n_stage = 3 * so_stage_pct_floats();
+    for (int i = 0; i < SO_HEAD_NW; ++i) n_stage += so_head_slot_floats(i);
+    w.stage = c.f(n_stage);
+    w.local[0] = carve_pb_chunk(c, Qc, SO_K, SO_LF / 2, false);
+    for (int i = 1; i < 3; ++i) {
+        PbScratch& l = w.local[i];
+        const int64_t T = Qc * SO_K;
+        l = w.local[0];
+        for (float*& x : l.X) x = c.f(T * PB_E);
+        l.z1 = c.f(T * PB_F); l.g1 = c.f(T * PB_F);
+        l.hn = c.f(T * PB_E); l.y0 = c.f(T * (SO_LF / 2));
+    }
+    w.global = carve_pb_chunk(g, B, Lg, SO_G / 2, false);
+    a.off += std::max(c.off, g.off);
+    return w;
 }
 
 }  // namespace
@@ -1429,6 +1551,156 @@ int mcr_pc_transformer_backward(const float* pc, const float* d_features, int64_
         if (d_weights && s0 > 0)
             hipLaunchKernelGGL(pb_add_slots_kernel, dim3(64, PCT_NW), dim3(256), 0, s, slots, (const float*)ws.stage);
     }
+    MCR_LAUNCH_CHECK(who);
+    return 0;
+}
+
+// ---- SconeOcc ------------------------------------------------------------------------------------------------------------------------
+int mcr_scone_occ_backward_chunk(int64_t Q) { return Q > 0 ? (int)so_chunk(Q, 0) : 0; }
+
+size_t mcr_scone_occ_backward_workspace_bytes(int64_t B, int64_t Q, int64_t Lg, int64_t q_chunk) {
+    return (B > 0 && Q > 0 && Lg > 0 && q_chunk >= 0) ? measure(carve_so, B, so_chunk(Q, q_chunk), Lg) + VB_WS_SLACK : 0;
+}
+
+int mcr_scone_occ_backward(const float* pc_global, int64_t Lg, const float* const* pc_scale, const int64_t* M_scale, const float* x,
+                           const float* view_harmonics, const int64_t* const* knn_idx, const float* d_out, int64_t B, int64_t Q,
+                           const float* const* weights, int n_weights, float* const* d_weights, float* d_x, float* d_view_harmonics,
+                           int64_t q_chunk, void* workspace, size_t workspace_bytes, void* stream) {
+    const char* who = "mcr_scone_occ_backward";
+    MCR_REQUIRE(pc_global && pc_scale && M_scale && x && view_harmonics && knn_idx && d_out && weights, "%s: null pointer", who);
+    if (check_table(who, OCC_TABLE, weights, n_weights, OCC_NW)) return 1;                  // (the planes tails are accepted and ignored)
+    MCR_REQUIRE(B > 0 && Q > 0 && Lg > 0 && B <= 65535 && Q <= (1ll << 24) && Lg <= (1 << 24) && B <= (1ll << 31) / Lg &&
+                    (Lg != SO_K || B <= PB_CHUNK16),
+                "%s: bad problem size B=%ld Q=%ld Lg=%ld", who, (long)B, (long)Q, (long)Lg);
+    for (int i = 0; i < 3; ++i) {
+        MCR_REQUIRE(pc_scale[i] && knn_idx[i], "%s: scale %d: null pointer", who, i);
+        MCR_REQUIRE(M_scale[i] >= SO_K, "%s: scale %d has %ld points (< k = 16)", who, i, (long)M_scale[i]);
+        MCR_REQUIRE(((uintptr_t)pc_scale[i] | (uintptr_t)knn_idx[i]) % 16 == 0, "%s: operands must be 16-byte aligned", who);
+    }
+    MCR_REQUIRE(q_chunk == 0 || (q_chunk >= 16 && q_chunk % 16 == 0 && q_chunk <= (1 << 20)),
+                "%s: q_chunk must be 0 (the default) or a multiple of 16 in [16, 2^20], got %ld", who, (long)q_chunk);
+    MCR_REQUIRE(((uintptr_t)pc_global | (uintptr_t)x | (uintptr_t)view_harmonics | (uintptr_t)d_out | (uintptr_t)d_x |
+                 (uintptr_t)d_view_harmonics) % 16 == 0, "%s: operands must be 16-byte aligned", who);
+    MCR_REQUIRE(workspace && workspace_bytes >= mcr_scone_occ_backward_workspace_bytes(B, Q, Lg, q_chunk), "%s: workspace too small", who);
+    MCR_REQUIRE((uintptr_t)workspace % 16 == 0, "%s: workspace must be 16-byte aligned", who);
+    if (d_weights)
+        for (int i = 0; i < OCC_NW; ++i) MCR_REQUIRE(d_weights[i], "%s: d_weights[%d] is null", who, i);
+    if (!d_weights && !d_x && !d_view_harmonics) return 0;
+    hipStream_t s = (hipStream_t)stream;
+    const OccW w = read_occ_table(weights, OCC_NW);
+    const int64_t Qc = so_chunk(Q, q_chunk);
+    Arena a{(char*)workspace, workspace_bytes};
+    const SoScratch ws = carve_so(a, B, Qc, Lg);
+    MCR_REQUIRE(a.ok(), "%s: workspace overflow", who);
+    float *part = ws.part, *wt = ws.wt;
+    const bool deep = d_weights || d_x;                    // anything below the head's input wanted
+    // the chunks behind the first leave their weight gradients in ws.stage, cut in table order, and are added in chunk order
+    float* stage_tab[OCC_NW] = {};
+    PbSlots slots_local[3] = {}, slots_head{};
+    const float* stage_local[3] = {};
+    const float* stage_head = nullptr;
+    if (d_weights) {
+        const size_t n_pct = so_stage_pct_floats();
+        for (int i = 0; i < 3; ++i) {
+            stage_local[i] = ws.stage + i * n_pct;
+            for (int k = 0; k < PCT_NW; ++k) {
+                slots_local[i].dst[k] = d_weights[OCC_LOCAL + i * PCT_NW + k];
+                slots_local[i].off[k + 1] = slots_local[i].off[k] + pb_slot_floats(k, SO_LF / 2);
+                stage_tab[OCC_LOCAL + i * PCT_NW + k] = ws.stage + i * n_pct + slots_local[i].off[k];
+            }
+        }
+        stage_head = ws.stage + 3 * n_pct;
+        for (int k = 0; k < SO_HEAD_NW; ++k) {
+            slots_head.dst[k] = d_weights[OCC_XE + k];
+            slots_head.off[k + 1] = slots_head.off[k] + so_head_slot_floats(k);
+            stage_tab[OCC_XE + k] = ws.stage + 3 * n_pct + slots_head.off[k];
+        }
+    }
+    PbSlots slot_g{};                                      // one row of the global features' gradient
+    slot_g.off[1] = SO_G;
+
+    // ---- 1. the global transformer's forward: [B, 512]
+    pb_chunk_forward(s, w.global, pc_global, B, (int)Lg, SO_G / 2, ws.global);
+    launch_pool_max_avg(s, ws.global.y0, SO_G / 2, ws.gfeat, SO_G, B, (int)Lg, SO_G / 2);
+
+    // ---- 2. cloud by cloud, chunk by chunk
+    for (int64_t b = 0; b < B; ++b)
+        for (int64_t q0 = 0; q0 < Q; q0 += Qc) {
+            const int64_t n = std::min(Qc, Q - q0), r0 = b * Q + q0;
+            const bool first = b == 0 && q0 == 0;
+            float* const* dw = !d_weights ? nullptr : first ? d_weights : stage_tab;
+            auto DW = [&](int slot) { return dw ? dw[slot] : nullptr; };
+            const float* xc = x + r0 * 3;
+            float* dxc = d_x ? d_x + r0 * 3 : nullptr;
+            // (a) the neighbourhoods as offsets, (b) the local features, straight into the head's input
+            for (int i = 0; i < 3; ++i) {
+                launch_so_gather(s, pc_scale[i] + b * M_scale[i] * 3, M_scale[i], knn_idx[i] + r0 * SO_K, xc, ws.off[i], n);
+                pb_chunk_forward(s, w.local[i], ws.off[i], n, SO_K, SO_LF / 2, ws.local[i]);
+                launch_pool_max_avg(s, ws.local[i].y0, SO_LF / 2, ws.h + SO_LOC + i * SO_LF, SO_H, n, SO_K, SO_LF / 2);
+            }
+            // (c) the x-embedding (SconeOcc.py:7-42)
+            vb_linear(s, {xc, 3}, w.xe1, {}, {ws.ze1, SO_XE / 4}, n, SO_XE / 4, 3, ACT_NONE);
+            launch_gelu(s, ws.ze1, SO_XE / 4, ws.ge1, SO_XE / 4, n, SO_XE / 4, 0);
+            vb_linear(s, {ws.ge1, SO_XE / 4}, w.xe2, {}, {ws.ze2, SO_XE / 2}, n, SO_XE / 2, SO_XE / 4, ACT_NONE);
+            launch_gelu(s, ws.ze2, SO_XE / 2, ws.ge2, SO_XE / 2, n, SO_XE / 2, 0);
+            vb_linear(s, {ws.ge2, SO_XE / 2}, w.xe3, {}, {ws.ze3, SO_XE}, n, SO_XE, SO_XE / 2, ACT_NONE);
+            launch_gelu(s, ws.ze3, SO_XE, ws.h + SO_XCOL, SO_H, n, SO_XE, 0);
+            // (d) the head (SconeOcc.py:334-342): GELU behind every layer, the last included
+            launch_copy2d(s, ws.gfeat + b * SO_G, 0, ws.h, SO_H, n, SO_G);
+            launch_copy2d(s, view_harmonics + r0 * SO_VH, SO_VH, ws.h + SO_VCOL, SO_H, n, SO_VH);
+            vb_linear(s, {ws.h, SO_H}, w.lin1, {}, {ws.z1, SO_L1}, n, SO_L1, SO_H, ACT_NONE);
+            launch_gelu(s, ws.z1, SO_L1, ws.g1, SO_L1, n, SO_L1, 0);
+            vb_linear(s, {ws.g1, SO_L1}, w.lin2, {}, {ws.z2, SO_L2}, n, SO_L2, SO_L1, ACT_NONE);
+            launch_gelu(s, ws.z2, SO_L2, ws.g2, SO_L2, n, SO_L2, 0);
+            vb_linear(s, {ws.g2, SO_L2}, w.lin3, {}, {ws.z3, 1}, n, 1, SO_L2, ACT_NONE);
+            // (e) the head, backwards
+            launch_copy2d(s, d_out + r0, 1, ws.dz3, 1, n, 1);
+            launch_gelu(s, ws.z3, 1, ws.dz3, 1, n, 1, 1);                                                   // linear3
+            gemm_dw(s, ws.dz3, 1, ws.g2, SO_L2, n, 1, SO_L2, DW(OCC_LIN + 2 * LIN_NW + LIN_W), DW(OCC_LIN + 2 * LIN_NW + LIN_B), part);
+            gemm_dx(s, ws.dz3, 1, w.lin3.w, SO_L2, ws.d2, SO_L2, n, 1, SO_L2, false, wt);
+            launch_gelu(s, ws.z2, SO_L2, ws.d2, SO_L2, n, SO_L2, 1);                                        // linear2
+            gemm_dw(s, ws.d2, SO_L2, ws.g1, SO_L1, n, SO_L2, SO_L1, DW(OCC_LIN + LIN_NW + LIN_W), DW(OCC_LIN + LIN_NW + LIN_B), part);
+            gemm_dx(s, ws.d2, SO_L2, w.lin2.w, SO_L1, ws.d1, SO_L1, n, SO_L2, SO_L1, false, wt);
+            launch_gelu(s, ws.z1, SO_L1, ws.d1, SO_L1, n, SO_L1, 1);                                        // linear1
+            gemm_dw(s, ws.d1, SO_L1, ws.h, SO_H, n, SO_L1, SO_H, DW(OCC_LIN + LIN_W), DW(OCC_LIN + LIN_B), part);
+            gemm_dx(s, ws.d1, SO_L1, w.lin1.w, SO_H, ws.dH, SO_H, n, SO_L1, SO_H, false, wt);
+            // (f) what leaves the head's input as it is: the harmonics' columns, the global features' (summed over the chunk's rows: the
+            // bias half of a weight-gradient product of depth 0, then chunk by chunk in order)
+            if (d_view_harmonics) launch_copy2d(s, ws.dH + SO_VCOL, SO_H, d_view_harmonics + r0 * SO_VH, SO_VH, n, SO_VH);
+            if (!deep) continue;
+            if (d_weights) {
+                gemm_dw(s, ws.dH, SO_H, nullptr, 0, n, SO_G, 0, nullptr, q0 == 0 ? ws.dG + b * SO_G : ws.gtmp, part);
+                if (q0 > 0) {
+                    slot_g.dst[0] = ws.dG + b * SO_G;
+                    hipLaunchKernelGGL(pb_add_slots_kernel, dim3(2, 1), dim3(256), 0, s, slot_g, (const float*)ws.gtmp);
+                }
+            }
+            // (g) the x-embedding, backwards
+            float* dxe = ws.dH + SO_XCOL;
+            launch_gelu(s, ws.ze3, SO_XE, dxe, SO_H, n, SO_XE, 1);
+            gemm_dw(s, dxe, SO_H, ws.ge2, SO_XE / 2, n, SO_XE, SO_XE / 2, DW(OCC_XE + 2 * LIN_NW + LIN_W), DW(OCC_XE + 2 * LIN_NW + LIN_B), part);
+            gemm_dx(s, dxe, SO_H, w.xe3.w, SO_XE / 2, ws.d2, SO_XE / 2, n, SO_XE, SO_XE / 2, false, wt);
+            launch_gelu(s, ws.ze2, SO_XE / 2, ws.d2, SO_XE / 2, n, SO_XE / 2, 1);
+            gemm_dw(s, ws.d2, SO_XE / 2, ws.ge1, SO_XE / 4, n, SO_XE / 2, SO_XE / 4, DW(OCC_XE + LIN_NW + LIN_W), DW(OCC_XE + LIN_NW + LIN_B), part);
+            gemm_dx(s, ws.d2, SO_XE / 2, w.xe2.w, SO_XE / 4, ws.d1, SO_XE / 4, n, SO_XE / 2, SO_XE / 4, false, wt);
+            launch_gelu(s, ws.ze1, SO_XE / 4, ws.d1, SO_XE / 4, n, SO_XE / 4, 1);
+            gemm_dw(s, ws.d1, SO_XE / 4, xc, 3, n, SO_XE / 4, 3, DW(OCC_XE + LIN_W), DW(OCC_XE + LIN_B), part);
+            if (dxc) gemm_dx(s, ws.d1, SO_XE / 4, w.xe1.w, 3, dxc, 3, n, SO_XE / 4, 3, false, wt);
+            // (h) the local transformers, backwards, from what (b) left in each scale's scratch (no second forward; each encoder's
+            // interior is rebuilt from its boundary as ever); the query's share of the offsets
+            for (int i = 0; i < 3; ++i) {
+                pb_chunk_backward(s, w.local[i], ws.off[i], ws.dH + SO_LOC + i * SO_LF, n, SO_K, SO_LF / 2,
+                                  dw ? dw + OCC_LOCAL + i * PCT_NW : nullptr, dxc ? ws.d_off : nullptr, ws.local[i], SO_H, /*forward_done=*/true);
+                if (dxc) launch_so_dx_sub(s, ws.d_off, dxc, n);
+            }
+            if (d_weights && !first) {
+                for (int i = 0; i < 3; ++i) hipLaunchKernelGGL(pb_add_slots_kernel, dim3(64, PCT_NW), dim3(256), 0, s, slots_local[i], stage_local[i]);
+                hipLaunchKernelGGL(pb_add_slots_kernel, dim3(64, SO_HEAD_NW), dim3(256), 0, s, slots_head, stage_head);
+            }
+        }
+
+    // ---- 3. the global transformer, backwards (its forward is rebuilt: the chunks have used its scratch)
+    if (d_weights) pb_chunk_backward(s, w.global, pc_global, ws.dG, B, (int)Lg, SO_G / 2, d_weights + OCC_GLOBAL, nullptr, ws.global, SO_G);
     MCR_LAUNCH_CHECK(who);
     return 0;
 }

@@ -235,6 +235,25 @@ class SconeOcc(RangeGuard, nn.Module):
             t += [_f32c(lin.weight), _f32c(lin.bias)]
         return t
 
+    def _grad_slots(self):
+        """(parameters, slots): every parameter of the module with its place in weight_table() -- (table index, row slice or None); the
+        four transformers' w_q / w_k / w_v are rows 0:32 / 32:64 / 64:192 of their encoder's packed qkv entries."""
+        slots, o = {}, 0
+        for t in (self.global_transformer, *self.local_transformers):
+            ps, sl = t._grad_slots()
+            for p_, (k, rows) in zip(ps, sl):
+                slots[id(p_)] = (o + k, rows)
+            o += len(t.weight_table())
+        for lin in (self.x_embedding.linear1, self.x_embedding.linear2, self.x_embedding.linear3, self.linear1, self.linear2,
+                    self.linear3):
+            slots[id(lin.weight)], slots[id(lin.bias)] = (o, None), (o + 1, None)
+            o += 2
+        params = tuple(self.parameters())
+        missing = [n for n, p_ in self.named_parameters() if id(p_) not in slots]
+        if missing:
+            raise NotImplementedError(f"SconeOcc HIP backward: parameters outside the weight table: {missing}")
+        return params, tuple(slots[id(p_)] for p_ in params)
+
     def weight_table_with_planes(self):
         """weight_table() + the global transformer's encoder weights as fp16 hi/lo planes (8 blobs): see SconeVis.weight_table_with_planes."""
         t = self.weight_table()
@@ -497,7 +516,12 @@ class SconeOcc(RangeGuard, nn.Module):
             elif guard in ("sync", "async"):
                 self._range_flag.zero_()
             flag = self._range_flag
-        if A.needs_grad(self, pc, x, view_harmonics):   # trainers: HIP forward, composite-torch backward (autograd.py)
+        if A.needs_grad(self, pc, x, view_harmonics) and A.scone_occ_backward_mode() == "hip" and not pc.requires_grad:
+            # HIP forward, HIP backward (autograd.SconeOccFunction); a gradient for the surface points takes the `pct` route below
+            params, slots = self._grad_slots()
+            res = A.SconeOccFunction.apply(lambda g_, sc_, x_, vh_: run(variant, g_, sc_, x_, vh_, None), self.weight_table, slots,
+                                           self.k_for_knn, pc_global, scales, x, view_harmonics, *params)
+        elif A.needs_grad(self, pc, x, view_harmonics):   # trainers: HIP forward, composite-torch backward (autograd.py)
             pidx = [p.to(dev) for p in perms]
 
             def clouds(pc_):

@@ -567,6 +567,52 @@ def pc_transformer_backward(pc, d_features, weights, feature_dim, need=(True, Tr
     return d_w, d_pc
 
 
+def scone_occ_backward_chunk(Q):
+    """Queries per chunk of scone_occ_backward at q_chunk=0 (mcr_scone_occ_backward_chunk: the 16-token chunk of pc_transformer_backward)."""
+    return int(lib().mcr_scone_occ_backward_chunk(c_i64(Q)))
+
+
+def scone_occ_backward(pc_global, pc_scales, x, view_harmonics, knn_idx, d_out, weights, need=(True, True, True), q_chunk=0):
+    """Gradients of scone_occ_forward given d_out [B,Q,1] and, per scale, the neighbour indices knn_idx[i] [B,Q,16] (int64, what
+    knn_points returns; no gradient flows through the selection): (d_weights, d_x [B,Q,3], d_vh [B,Q,64]); `need` = (params, x, vh)
+    selects what is computed (None for the rest; nothing needed: no launch).  d_weights: one tensor per entry of the 140-entry weight
+    table (table order and shapes; every transformer's packed qkv weight / bias one entry each).  There is no gradient for the
+    surface points.  The fp32 network's gradient whatever the variant (mcr_scone_occ_backward: HIP kernels only, deterministic; the
+    queries are processed in chunks of q_chunk rows inside the entry, 0 = scone_occ_backward_chunk(Q); the bits may depend on q_chunk)."""
+    pc_global, x, view_harmonics = _req(pc_global, "pc_global"), _req(x, "x"), _req(view_harmonics, "view_harmonics")
+    d_out = _req(d_out, "d_out")                # .contiguous(): y.sum().backward() hands in an expanded, zero-stride tensor
+    pc_scales = [_req(p, f"pc_scales[{i}]") for i, p in enumerate(pc_scales)]
+    knn_idx = [_req(t, f"knn_idx[{i}]", torch.int64) for i, t in enumerate(knn_idx)]
+    B, Q, d = x.shape
+    Lg = pc_global.shape[1]
+    if (d != 3 or len(pc_scales) != 3 or len(knn_idx) != 3 or pc_global.shape != (B, Lg, 3) or view_harmonics.shape != (B, Q, 64)
+            or d_out.numel() != B * Q or any(p.dim() != 3 or p.shape[0] != B or p.shape[2] != 3 for p in pc_scales)
+            or any(t.shape != (B, Q, 16) for t in knn_idx)):
+        raise ValueError("SconeOcc backward needs pc_global [B,Lg,3], three pc_scales [B,M_i,3], x [B,Q,3], view_harmonics [B,Q,64], three "
+                         "knn_idx [B,Q,16] and d_out [B,Q,1]")
+    tensors = weights[0] if isinstance(weights, tuple) else weights
+    need_w, need_x, need_v = (bool(t) for t in need)
+    if not (need_w or need_x or need_v):
+        return None, None, None
+    dev = x.device
+    d_w = [torch.empty(tuple(t.shape), dtype=torch.float32, device=dev) for t in tensors[:140]] if need_w else None
+    d_x = torch.empty((B, Q, 3), dtype=torch.float32, device=dev) if need_x else None
+    d_vh = torch.empty((B, Q, 64), dtype=torch.float32, device=dev) if need_v else None
+    L_ = lib()
+    ws = _workspace(dev, int(L_.mcr_scone_occ_backward_workspace_bytes(c_i64(B), c_i64(Q), c_i64(Lg), c_i64(q_chunk))))
+    dtab = (ctypes.c_void_p * 140)(*[t.data_ptr() for t in d_w]) if need_w else None
+    sc = (ctypes.c_void_p * 3)(*[p.data_ptr() for p in pc_scales])
+    ms = (ctypes.c_int64 * 3)(*[p.shape[1] for p in pc_scales])
+    idx = (ctypes.c_void_p * 3)(*[t.data_ptr() for t in knn_idx])
+    ptr = lambda t: _p(t) if t is not None else c_vp(None)
+    with torch.cuda.device(dev):
+        check(L_.mcr_scone_occ_backward(_p(pc_global), c_i64(Lg), sc, ms, _p(x), _p(view_harmonics), idx, _p(d_out), c_i64(B), c_i64(Q),
+                                        _ptr_table(weights), c_int(_n_weights(weights)), dtab if dtab is not None else c_vp(None),
+                                        ptr(d_x), ptr(d_vh), c_i64(q_chunk), _p(ws), c_size(ws.numel()), _stream()),
+              "mcr_scone_occ_backward")
+    return d_w, d_x, d_vh
+
+
 def linear_backward(x, weight, d_y, z=None, gelu=False, d_x=None, need=(True, True, True)):
     """Gradient of linear(x, weight, bias, gelu) given d_y: (d_x, d_w, d_b).  z: the pre-activation (needed with gelu).  d_x given:
     the input gradient is ADDED to it (in place), else a new tensor; `need` = (x, weight, bias).  mcr_linear_backward."""
