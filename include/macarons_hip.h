@@ -633,6 +633,17 @@ int mcr_camera_boxes(const float* sampled, const int* n_unique, int64_t K, int S
 int mcr_macarons_gain_indexed(const float* vis_unique, const float* world_unique, const int64_t* inverse, const int* n_unique,
                               const float* cam_world, const float* volume, float distance_th, int factor_mode, int64_t K, int S,
                               float* gains, void* stream);
+/* mcr_macarons_gain_backward: gradients of mcr_macarons_gain_indexed for an incoming grad_gains [K] (train_macarons.py:438-444 -> :1259):
+ *   d_vis [K,S]: d_vis[k,u] = (grad_gains[k] * volume[k] / S) * #{s : inverse[k,s] == u} * factor(|world[k,u] - cam_world[k]|); rows
+ *   u >= n_unique[k] and every row of a camera with n_unique[k] == 0 are exactly 0;  d_volume [K] (NULL: skipped) = grad_gains[k] * the
+ *   forward's mean of camera k (accumulated as the forward accumulates it), 0 when n_unique[k] == 0.  world rows have pts_dim >= 3 floats.
+ *   inverse == NULL and n_unique == NULL: the identity map, every camera non-empty -- the backward of mcr_macarons_gain (vis = its
+ *   input before the in-place scaling).  The counts are an integer LDS histogram (no floating-point atomics: bit-reproducible), which
+ *   limits S to 8192; an inverse entry outside [0, S) is skipped. */
+int mcr_macarons_gain_backward(const float* grad_gains, const float* vis, const float* world, int pts_dim,
+                               const int64_t* inverse /*NULL: identity*/, const int* n_unique /*NULL: all non-empty*/,
+                               const float* cam_world, const float* volume, float distance_th, int factor_mode,
+                               int64_t K, int S, float* d_vis, float* d_volume /*NULL: skip*/, void* stream);
 int mcr_philox_uniform_rows(uint64_t seed, uint64_t offset, int64_t K, int S, int mapping, float* out, void* stream);
 
 #ifdef __cplusplus

@@ -11,7 +11,9 @@ MCR_SCONE_OCC_BWD=pct: that recomputation evaluates SconeOcc's four PCTransforme
 PCTransformerFunction (HIP forward and backward); the gather, the offsets, the x-embedding and the head stay torch.  Opt-in,
 MCR_SCONE_OCC_BWD=hip: no recomputation in torch at all -- SconeOccFunction below hands the whole backward (gather, local transformers,
 x-embedding, head, global transformer) to one entry, mcr_scone_occ_backward, for the parameters, x and the view harmonics; a gradient
-for the surface points pc is not computed there, so a forward whose pc requires one takes the pct route.  The composites
+for the surface points pc is not computed there, so a forward whose pc requires one takes the pct route.  The MACARONS-regime gain
+(ops.macarons_gain_indexed / macarons_gain_) is HIP both ways as well: MacaronsGainFunction below, backward mcr_macarons_gain_backward, with
+gradients for the per-point visibility gains and the volumes and for nothing else.  The composites
 are ordinary differentiable torch code, so they are also what the parity tests differentiate numerically (tests/test_autograd.py:
 fp64 finite differences on CPU; on the GPU the composite forward must reproduce the HIP forward to 1e-4, which makes its gradient
 the gradient of the kernels' function) and the second reference of the HIP backward's tests.
@@ -73,6 +75,25 @@ def visibilities(pts, harmonics, X_cam, use_sigmoid=True):
 def coverage_gain(pts, harmonics, X_cam, use_sigmoid=True):
     """[B,C]: SconeVis.compute_coverage_gain (SconeVis.py:210-252)."""
     return visibilities(pts, harmonics, X_cam, use_sigmoid).mean(dim=-1)
+
+
+def macarons_gain(vis_u, world_u, inverse, n_unique, cam_world, volume, distance_th, smooth=False):
+    """[K]: the MACARONS-regime gain (macarons_utils.py:1668-1704, ops.macarons_gain_indexed) in differentiable torch ops, in the dtype of
+    its inputs: gains[k] = mean_s vis_u[k, inverse[k,s]] * factor(|world_u[k, inverse[k,s]] - cam_world[k]|) * volume[k], 0 where
+    n_unique[k] == 0.  vis_u [K,S], world_u [K,S,>=3], inverse int64 [K,S], n_unique [K], cam_world [K,3], volume [K].  inverse None and
+    n_unique None: the identity map, every camera non-empty (ops.macarons_gain_).  factor: min(1, (th / d)^2), or with smooth
+    1 / (1 + (d / th)^2)."""
+    vis, world = vis_u, world_u[..., :3]
+    if inverse is not None:
+        vis = torch.gather(vis_u, 1, inverse)
+        world = torch.gather(world, 1, inverse[..., None].expand(-1, -1, 3))
+    d = torch.linalg.norm(world - cam_world[:, None, :], dim=-1)
+    if smooth:
+        f = 1.0 / (1.0 + (d / distance_th) ** 2)
+    else:
+        f = (distance_th / d.clamp(min=distance_th)) ** 2
+    gains = (vis * f).mean(dim=1) * volume
+    return gains if n_unique is None else torch.where(n_unique > 0, gains, torch.zeros_like(gains))
 
 
 # ---- the networks --------------------------------------------------------------------------------------------------------------
@@ -316,3 +337,32 @@ class SconeOccFunction(torch.autograd.Function):
             grads.append(g.to(ctx.param_dtypes[j]))
         return (None, None, None, None, None, None, d_x.to(x.dtype) if d_x is not None else None,
                 d_vh.to(vh.dtype) if d_vh is not None else None, *grads)
+
+
+# ---- MACARONS-regime gain: HIP forward + HIP backward ----------------------------------------------------------------------------
+class MacaronsGainFunction(torch.autograd.Function):
+    """apply(vis, world, inverse, n_unique, cam_world, volume, distance_th, smooth) -> gains [K]: forward = ops.macarons_gain_indexed
+    without a graph (inverse and n_unique None, the identity form: ops.macarons_gain_ on a private copy of vis, which it scales in
+    place) -- the values keep the bits of those calls; backward = one ops.macarons_gain_backward (mcr_macarons_gain_backward).
+    Gradients go to vis and, if it requires one, to volume; world, inverse, n_unique and cam_world are constants of the graph.
+    Differentiable once."""
+
+    @staticmethod
+    def forward(ctx, vis, world, inverse, n_unique, cam_world, volume, distance_th, smooth):
+        from . import ops
+        ctx.distance_th, ctx.smooth = float(distance_th), bool(smooth)
+        ctx.save_for_backward(vis, world, inverse, n_unique, cam_world, volume)
+        with torch.no_grad():
+            if inverse is None and n_unique is None:
+                return ops.macarons_gain_(vis.clone(), world, cam_world, volume, distance_th, smooth)
+            return ops.macarons_gain_indexed(vis, world, inverse, n_unique, cam_world, volume, distance_th, smooth)
+
+    @staticmethod
+    def backward(ctx, grad_gains):
+        if torch.is_grad_enabled():
+            raise RuntimeError("the MACARONS gain is differentiable once: its HIP backward builds no graph (create_graph is not supported)")
+        from . import ops
+        vis, world, inverse, n_unique, cam_world, volume = ctx.saved_tensors
+        d_vis, d_volume = ops.macarons_gain_backward(grad_gains.float().contiguous(), vis, world, inverse, n_unique, cam_world, volume,
+                                                     ctx.distance_th, ctx.smooth, need_volume=ctx.needs_input_grad[5])
+        return (d_vis if ctx.needs_input_grad[0] else None, None, None, None, None, d_volume, None, None)

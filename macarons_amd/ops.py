@@ -1407,6 +1407,39 @@ def macarons_gain_indexed(vis_unique, world_unique, inverse, n_unique, cam_world
     return gains
 
 
+def macarons_gain_backward(grad_gains, vis, world, inverse, n_unique, cam_world, volume, distance_th, smooth=False, need_volume=False):
+    """(d_vis [K,S], d_volume [K] or None): gradients of macarons_gain_indexed for grad_gains [K] with respect to the per-unique-point
+    gains vis [K,S] and, with need_volume, the volumes (mcr_macarons_gain_backward).  world [K,S,>=3].  inverse None and n_unique None:
+    the identity map, every camera non-empty -- the backward of macarons_gain_ (vis = its input before the in-place scaling)."""
+    grad_gains, vis, world = _req(grad_gains, "grad_gains"), _req(vis, "vis"), _req(world, "world")
+    if (inverse is None) != (n_unique is None):
+        raise ValueError("inverse and n_unique go together (both None: the identity form)")
+    K, S = vis.shape
+    if grad_gains.shape != (K,):
+        raise ValueError(f"grad_gains must be [K] = {(K,)}, got {tuple(grad_gains.shape)}")
+    if world.dim() != 3 or world.shape[:2] != (K, S) or world.shape[2] < 3:
+        raise ValueError(f"world must be [K,S,>=3] with [K,S] = {(K, S)}, got {tuple(world.shape)}")
+    if inverse is not None and tuple(inverse.shape) != (K, S):
+        raise ValueError(f"inverse must be [K,S] = {(K, S)}, got {tuple(inverse.shape)}")
+    if inverse is not None:
+        inverse, n_unique = _req(inverse, "inverse", torch.int64), _req(n_unique, "n_unique", torch.int32)
+        if n_unique.numel() != K:
+            raise ValueError(f"n_unique must be [K] = {(K,)}, got {tuple(n_unique.shape)}")
+    cam_world, volume = _req(cam_world, "cam_world"), _req(volume, "volume")
+    if cam_world.numel() != 3 * K or volume.numel() != K:
+        raise ValueError(f"cam_world must be [K,3] and volume [K] with K = {K}, got {tuple(cam_world.shape)} and {tuple(volume.shape)}")
+    d_vis = torch.empty((K, S), dtype=torch.float32, device=vis.device)
+    d_volume = torch.empty(K, dtype=torch.float32, device=vis.device) if need_volume else None
+    with torch.cuda.device(vis.device):
+        check(lib().mcr_macarons_gain_backward(_p(grad_gains), _p(vis), _p(world), c_int(world.shape[2]),
+                                               _p(inverse) if inverse is not None else c_vp(0),
+                                               _p(n_unique) if n_unique is not None else c_vp(0),
+                                               _p(cam_world), _p(volume), c_f32(float(distance_th)),
+                                               c_int(int(bool(smooth))), c_i64(K), c_int(S), _p(d_vis),
+                                               _p(d_volume) if need_volume else c_vp(0), _stream()), "mcr_macarons_gain_backward")
+    return d_vis, d_volume
+
+
 _PHILOX_MAPPING = 1          # rocRAND's (0, 1] map (what torch.rand uses on ROCm); tests/test_glue_gpu.py pins it against torch.rand
 
 

@@ -9,6 +9,7 @@ import os
 import numpy as np
 import torch
 
+from .. import autograd as A
 from .. import ops
 from .scone_utils import sample_proxy_points  # noqa: F401  (same sampler as the SCONE regime)
 
@@ -60,7 +61,7 @@ def get_distance_factor_smooth(params, pts, X_cam, fov_camera, cell_resolution):
 def predict_coverage_gain_for_cameras(visibility_model, X_world, proxy_view_harmonics, occ_probs, cameras, X_cam_world,
                                       prediction_view_matrices, prediction_box_diag, seq_len=2048, min_occ=0.1,
                                       distance_th=17., samples=None, smooth=False, return_parts=False, record=None,
-                                      uniform_draws="per_camera"):
+                                      uniform_draws="per_camera", differentiable=False):
     """The per-neighbour-camera scoring loop of testers/scene.py:434-454 around
     predict_coverage_gain_for_single_camera (macarons_utils.py:1580-1738), for K cameras AT ONCE and without a host
     synchronisation (the reference runs one SconeVis forward and reads a count back per camera):
@@ -73,7 +74,19 @@ def predict_coverage_gain_for_cameras(visibility_model, X_world, proxy_view_harm
     factored per-point gains [N] and sampled world points [N,4]).
     Uniforms (`samples` None): uniform_draws="per_camera" (default) = what upstream's K calls draw one after the other,
     torch.rand(S, 1, device=...) inside every per-camera call (scone_utils.py:1052), bit for bit and with the same effect on the device
-    generator -- from ONE launch (ops.uniform_rows: torch's Philox indexing restated); "batched" = one torch.rand(K, S) (another stream)."""
+    generator -- from ONE launch (ops.uniform_rows: torch's Philox indexing restated); "batched" = one torch.rand(K, S) (another stream).
+    Gradients (upstream's online trainer back-propagates cov_loss through this chain, train_macarons.py:438-444 -> :507 / :753 -> :1259):
+    with differentiable=True, gradients enabled and a parameter of visibility_model (or proxy_view_harmonics) requiring one, `gains`
+    carries a graph whose backward is HIP end to end -- autograd.MacaronsGainFunction (mcr_macarons_gain_backward), the scorer operator's Autograd kernel
+    (mcr_sh_scorer_backward, per pair) and SconeVisFunction (mcr_scone_vis_backward with `lengths`): one padded SconeVis call and one
+    weight-gradient pass for all K cameras.  The values are the no-grad call's, bit for bit.  X_world, occ_probs (through the sampling
+    and through the volume) and proxy_view_harmonics (through the gather of the sampled rows) are constants of that graph, as in
+    upstream's trainer, which produces them under no_grad (train_macarons.py:283-284); so are the per-camera lists of return_parts
+    (detached, as without gradients).  An empty frustum scores 0 and sends an all-zero, finite contribution to every parameter: one graph
+    covers all K cameras, so every parameter always receives a gradient tensor -- what upstream's dummy forward pass
+    (macarons_utils.py:1707-1736) is there to guarantee.  The graph is asked for by keyword because callers of the inference path hold
+    models whose parameters require gradients too, and read `gains` back as plain values; without the keyword, or without gradients,
+    the function takes the code path it always took."""
     K = cameras.shape[0]
     dev = X_world.device
     S = seq_len
@@ -101,13 +114,23 @@ def predict_coverage_gain_for_cameras(visibility_model, X_world, proxy_view_harm
     # ---- ONE SconeVis forward over the K padded clouds (:1664), ONE scorer launch on the UNIQUE points (C = 1 per cloud, :1683), ONE
     # gain launch that reads the Monte-Carlo duplicates (:1668-1671) through the inverse map
     harm = visibility_model(pts, view_harmonics=res_h, lengths=nu)
-    vis_u = ops.sh_visibilities(pts, harm, cam_view.view(K, 1, 3), True).view(K, S)
+    differentiable = differentiable and A.needs_grad(visibility_model, proxy_view_harmonics)
+    if differentiable:                  # trainers: the same C entry behind the operator's Autograd kernel, then the gain with its HIP backward
+        from ..networks.SconeVis import SconeVis
+        vis_u = SconeVis._scorer_ops().sh_visibilities(pts, harm, cam_view.view(K, 1, 3), True).view(K, S)
+        gains = A.MacaronsGainFunction.apply(vis_u, res, inv, nu, xc, vol, distance_th, smooth)
+        if not return_parts:
+            return gains
+        vis_u = vis_u.detach()                                                            # the lists below: values only, as without gradients
+    else:
+        vis_u = ops.sh_visibilities(pts, harm, cam_view.view(K, 1, 3), True).view(K, S)
     if return_parts:
         gi = inv[..., None]
         world = torch.gather(res, 1, gi.expand(-1, -1, 4)).contiguous()
         vis = torch.gather(vis_u, 1, inv).contiguous()
-        gains = ops.macarons_gain_(vis, world, xc, vol, distance_th, smooth)               # :1699-1704 (vis scaled in place)
-        gains = torch.where(nu > 0, gains, torch.zeros_like(gains))                       # empty frustum: gain 0 (:1707-1736)
+        parts_gains = ops.macarons_gain_(vis, world, xc, vol, distance_th, smooth)         # :1699-1704 (vis scaled in place)
+        if not differentiable:          # (with a graph: `gains` above -- the same sum in the same order, read through the inverse map)
+            gains = torch.where(nu > 0, parts_gains, torch.zeros_like(parts_gains))       # empty frustum: gain 0 (:1707-1736)
         n_host = nu.tolist()
         return (gains, [vis[k] if n_host[k] > 0 else None for k in range(K)],
                 [world[k] if n_host[k] > 0 else None for k in range(K)])
