@@ -212,7 +212,10 @@ int mcr_linear_planes_dot(const void* Xh, const void* Xl, int64_t ldx, const voi
  *   workspace: mcr_attention_backward_pct_workspace_bytes(S, L).
  * mcr_pool_max_avg_backward: for mcr_pool_max_avg given dY [S, ldy] = [d_max (E) | d_avg (E)]: dX[(s, r), c] = d_avg[s, c] / L, plus
  *   d_max[s, c] on the lowest row r holding the column's max (torch.max(dim)'s choice on ties).  Written, not accumulated.  Any S;
- *   leading dimensions >= the row (ldy >= 2 E), operands 4-byte aligned. */
+ *   leading dimensions >= the row (ldy >= 2 E), operands 4-byte aligned.
+ * mcr_pool_max_avg_backward_lens: the same for padded sequences (mcr_pool_max_avg's lens form; lens: DEVICE int[S]): with n = min(L,
+ *   max(1, lens[s])) the arg-max runs over the first n rows (ties: the lowest row), the mean's share is d_avg / n, and rows >= n are
+ *   written as exact zeros. */
 size_t mcr_attention_backward_workspace_bytes(int64_t S, int64_t L, int n_heads, int v_dim);
 int mcr_attention_backward(const float* qkv, int64_t ldq, const float* d_out, int64_t ld_dout, float* d_qkv, int64_t ld_dqkv, int64_t S,
                            int64_t L, int n_heads, int qk_dim, int v_dim, const int* lens, void* workspace, size_t workspace_bytes,
@@ -233,6 +236,8 @@ int mcr_attention_backward_pct(const float* qkv, int64_t ldq, const float* d_out
                                void* stream);
 int mcr_pool_max_avg_backward(const float* X, int64_t ldx, const float* dY, int64_t ldy, float* dX, int64_t ld_dx, int64_t S, int64_t L,
                               int E, void* stream);
+int mcr_pool_max_avg_backward_lens(const float* X, int64_t ldx, const float* dY, int64_t ldy, float* dX, int64_t ld_dx, int64_t S,
+                                   int64_t L, int E, const int* lens, void* stream);
 
 /* ---- network forwards -----------------------------------------------------------------------------------
  * Weight tables are arrays of device pointers to contiguous fp32 tensors in nn.Module layout ([out,in] weights):
@@ -333,6 +338,36 @@ int mcr_scone_occ_backward(const float* pc_global, int64_t Lg, const float* cons
                            const float* view_harmonics, const int64_t* const* knn_idx, const float* d_out, int64_t B, int64_t Q,
                            const float* const* weights, int n_weights, float* const* d_weights, float* d_x, float* d_view_harmonics,
                            int64_t q_chunk, void* workspace, size_t workspace_bytes, void* stream);
+/* mcr_scone_occ_backward_ragged: the gradient of J independent mcr_scone_occ_forward calls of different sizes (the jobs of the ragged
+ *   occupancy pass) given d_out [T], T = the jobs' query rows one behind the other; weight gradients summed over the jobs.  Computed on
+ *   the fp32 network whatever the call's variant; no gradient for any cloud.
+ *   pc_global [J,Lg,3]: every job's global sequence padded to Lg rows, global_len (DEVICE int[J]): its valid rows, n = min(Lg,
+ *   max(1, global_len[j])) -- keys >= n are masked, the pooling runs over the first n rows (mean divided by n).  What the padding rows
+ *   hold is never used (NaN included): the entry works on a copy whose padding is the sequence's row 0.  Lg == 16 is refused.
+ *   offsets: HOST array of 3 DEVICE pointers to [T,16,3], the neighbourhoods of every query row and scale as neighbour minus query (what
+ *   mcr_knn_offsets_segmented writes): the entry takes no clouds and no indices.  The selection carries no gradient; the query's share
+ *   of the offsets' gradient goes to d_x.
+ *   x [T,3], view_harmonics [T,64]; row_job (DEVICE int[T], non-decreasing): the job of every row (a value outside [0, J) is clamped);
+ *   job_rows (DEVICE int64[J+1]): job j = rows [job_rows[j], job_rows[j+1]) (clamped into [0, T]); the two must agree.  A job may have
+ *   no rows: its sequence then contributes exact zeros.
+ *   weights, d_weights (may be NULL), d_x [T,3] and d_view_harmonics [T,64] (may be NULL; all three NULL: returns 0 at once): as
+ *   mcr_scone_occ_backward.
+ *   Schedule: the global transformer's forward over the J padded sequences; then the rows [0, T) in chunks of q_chunk rows (0: the
+ *   default, mcr_scone_occ_backward_chunk(T); else a multiple of 16 in [16, 2^20]) -- a chunk may span any number of jobs -- each running
+ *   local transformers, x embedding and head forward and backward as mcr_scone_occ_backward does, the chunks' weight gradients summed in
+ *   chunk order, each job's share of the global features' gradient summed in row order; then the global transformer's backward job by
+ *   job, summed in job order (one job's share depends on that job alone: adding or removing a job without rows changes no bit).
+ *   Two calls give identical bits; the bits may depend on q_chunk.
+ *   Workspace: mcr_scone_occ_backward_ragged_workspace_bytes(J, T, Lg, q_chunk) bytes: one chunk of rows whatever T is, plus the J global
+ *   sequences' forward OVER the chunk's scratch, so beyond the chunk's size it is linear in J (at Lg = 2048: the 681 MB of a 2048-row
+ *   chunk up to J = 29, about 23 MB per job beyond); J <= 16384 (refused beyond; the global sequences are not processed in groups).
+ *   pc_global, offsets[i], x, view_harmonics, d_out, the outputs and the workspace 16-byte aligned.  Deterministic (no float
+ *   atomics), no host synchronisation, no read-back. */
+size_t mcr_scone_occ_backward_ragged_workspace_bytes(int64_t J, int64_t T, int64_t Lg, int64_t q_chunk);
+int mcr_scone_occ_backward_ragged(const float* pc_global, const int* global_len, int64_t Lg, const float* const* offsets, const float* x,
+                                  const float* view_harmonics, const int* row_job, const int64_t* job_rows, const float* d_out, int64_t J,
+                                  int64_t T, const float* const* weights, int n_weights, float* const* d_weights, float* d_x,
+                                  float* d_view_harmonics, int64_t q_chunk, void* workspace, size_t workspace_bytes, void* stream);
 size_t mcr_scone_occ_workspace_bytes(int64_t B, int64_t Q, int64_t Lg);
 int mcr_scone_occ_forward(const float* pc_global, int64_t Lg, const float* const* pc_scale, const int64_t* M_scale,
                           const float* x, const float* view_harmonics, float* out, int64_t B, int64_t Q,

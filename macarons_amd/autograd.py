@@ -186,6 +186,34 @@ def _scone_occ(pc_transformer, model, pc_global, scales, x, view_harmonics, knn_
     return F.gelu(_lin(F.gelu(_lin(F.gelu(_lin(h, model.linear1)), model.linear2)), model.linear3))
 
 
+def scone_occ_ragged(model, pc_global, global_len, offsets, x, view_harmonics, row_job):
+    """The ragged occupancy pass (SconeOcc.forward_ragged: J forward() calls of different sizes) as one differentiable torch composite,
+    in the dtype of its inputs: pc_global [J,Lg,3] padded sequences of global_len [J] valid rows (clamped to [1, Lg]), offsets per scale
+    [T,16,3] (neighbour minus query), x [T,3], view_harmonics [T,64], row_job [T] -> [T,1].  The global transformer masks the padded
+    keys and pools over each sequence's valid rows (max; mean divided by their number); the padding rows are never read (they are
+    replaced by the sequence's first row before anything else).  The neighbourhoods have the value of `offsets` and gradient -1
+    towards x; the selection and the clouds carry none."""
+    J, Lg = pc_global.shape[0], pc_global.shape[1]
+    n = global_len.to(pc_global.device).long().clamp(1, Lg)
+    valid = torch.arange(Lg, device=pc_global.device)[None, :, None] < n.view(-1, 1, 1)
+    t = model.global_transformer
+    h = embedding(t.embedding, torch.where(valid, pc_global.detach(), pc_global.detach()[:, :1]))
+    for enc in t.encoders:
+        h = encoder(enc, h, n)
+    h = _lin(F.layer_norm(h, (h.shape[-1],), t.norm.weight, t.norm.bias), t.linear0)
+    g_max = torch.where(valid, h, torch.full_like(h, float("-inf"))).max(dim=1)[0]
+    g_avg = torch.where(valid, h, torch.zeros_like(h)).sum(dim=1) / n[:, None].to(h.dtype)
+    feats = [torch.cat((g_max, g_avg), dim=-1)[row_job.long()]]
+    to_x = (x.detach() - x)[:, None, :]
+    for off, lt in zip(offsets, model.local_transformers):
+        feats.append(pc_transformer(lt, off.detach() + to_x))
+    xe = model.x_embedding
+    feats.append(F.gelu(_lin(F.gelu(_lin(F.gelu(_lin(x, xe.linear1)), xe.linear2)), xe.linear3)))
+    feats.append(view_harmonics)
+    h = torch.cat(feats, dim=-1)
+    return F.gelu(_lin(F.gelu(_lin(F.gelu(_lin(h, model.linear1)), model.linear2)), model.linear3))
+
+
 # ---- HIP forward + composite backward --------------------------------------------------------------------------------------
 class _HipForwardTorchBackward(torch.autograd.Function):
     """apply(hip_fn, torch_fn, n_tensor_inputs, *tensor_inputs_then_params): forward = hip_fn(*inputs) without a graph;
@@ -337,6 +365,46 @@ class SconeOccFunction(torch.autograd.Function):
             grads.append(g.to(ctx.param_dtypes[j]))
         return (None, None, None, None, None, None, d_x.to(x.dtype) if d_x is not None else None,
                 d_vh.to(vh.dtype) if d_vh is not None else None, *grads)
+
+
+class SconeOccRaggedFunction(torch.autograd.Function):
+    """apply(hip_fn, table_fn, slots, scale_sizes, query_sizes, pc_global, global_len, clouds, row_job, x, view_harmonics, *params):
+    forward = hip_fn() (the ragged HIP forward on these very tensors) without a graph; backward = the three scales' neighbourhood
+    offsets by ops.knn_offsets_segmented on the detached inputs (clouds[i]: the jobs' scale-i clouds one behind the other,
+    scale_sizes[i]: their sizes), then ONE ops.scone_occ_backward_ragged (mcr_scone_occ_backward_ragged: the gradient of the fp32
+    network, HIP kernels only, weight gradients summed over the jobs).  slots as SconeOccFunction.  The clouds get no gradient.
+    Differentiable once."""
+
+    @staticmethod
+    def forward(ctx, hip_fn, table_fn, slots, scale_sizes, query_sizes, pc_global, global_len, clouds, row_job, x, view_harmonics, *params):
+        ctx.table_fn, ctx.slots, ctx.scale_sizes, ctx.query_sizes = table_fn, slots, scale_sizes, [int(q) for q in query_sizes]
+        ctx.param_dtypes = tuple(p.dtype for p in params)
+        ctx.save_for_backward(pc_global, global_len, row_job, x, view_harmonics, *clouds)
+        with torch.no_grad():
+            return hip_fn()
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        if torch.is_grad_enabled():
+            raise RuntimeError("SconeOcc.forward_ragged is differentiable once: its HIP backward builds no graph (create_graph is not "
+                               "supported)")
+        from . import ops
+        pc_global, global_len, row_job, x, vh, *clouds = ctx.saved_tensors
+        need_x, need_v = ctx.needs_input_grad[9], ctx.needs_input_grad[10]
+        need_w = any(ctx.needs_input_grad[11:])
+        xq = x.detach().float().contiguous()
+        offsets = [ops.knn_offsets_segmented(xq, c_.detach().float().contiguous(), sizes, ctx.query_sizes)
+                   for c_, sizes in zip(clouds, ctx.scale_sizes)]
+        d_w, d_x, d_vh = ops.scone_occ_backward_ragged(pc_global.detach().float(), global_len, offsets, xq, vh.detach().float(), row_job,
+                                                       ctx.query_sizes, grad_out.float(), ctx.table_fn(), need=(need_w, need_x, need_v))
+        grads = []
+        for j, (i, rows) in enumerate(ctx.slots):
+            if not ctx.needs_input_grad[11 + j]:
+                grads.append(None)
+                continue
+            g = d_w[i] if rows is None else d_w[i][rows[0]:rows[1]]
+            grads.append(g.to(ctx.param_dtypes[j]))
+        return (None,) * 9 + (d_x.to(x.dtype) if d_x is not None else None, d_vh.to(vh.dtype) if d_vh is not None else None, *grads)
 
 
 # ---- MACARONS-regime gain: HIP forward + HIP backward ----------------------------------------------------------------------------

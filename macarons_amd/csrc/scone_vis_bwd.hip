@@ -36,6 +36,14 @@
 // backward on the chunk functions above (pb_chunk_forward / pb_chunk_backward) and the launchers of this file; the query's share of the
 // offsets' gradient is so_dx_sub_kernel.  Weight gradients of the chunks behind the first are staged and added in chunk order, as are
 // the chunks' column sums of the global features' gradient; the global transformer's backward runs last.  No gradient for the clouds.
+//
+// Ragged SconeOcc backward: mcr_scone_occ_backward_ragged, the gradient of J such calls of different sizes (the jobs of
+// SconeOcc.forward_ragged) with the weight gradients summed over the jobs.  The neighbourhood offsets are an input, so everything but
+// the global features is row-wise: the rows of all jobs are packed into full chunks that run the same chunk function
+// (so_chunk_fwd_bwd).  The global transformer runs forward over the J padded sequences with their lengths (keys masked, pooling over
+// the valid rows; so_pad_global_kernel first overwrites the padding), its features reach the rows through so_bcast_rows_kernel, their
+// gradient comes back per job through so_seg_colsum_kernel, and its backward runs last, job by job in job order with lengths
+// (pb_pool_bwd_lens_kernel hands exact zeros to the padded rows), the jobs behind the first through a staging area.
 #include "nn_kernels.h"
 #include "net_layout.h"
 #include <algorithm>
@@ -943,7 +951,49 @@ __global__ __launch_bounds__(1024) void pb_pool_bwd_kernel(const float* __restri
     for (int r = sl; r < L; r += 16) o[(long long)r * ldd] = r == arg ? g_avg + g_max : g_avg;
 }
 
-void launch_pool_bwd(hipStream_t s, const float* X, int64_t ldx, const float* dY, int64_t ldy, float* dX, int64_t ldd, int64_t S, int L, int E) {
+// ... of padded sequences (launch_pool_max_avg with lens): with n = min(L, max(1, lens[s])) the arg-max runs over the first n rows (ties:
+// the lowest row), the mean's share is dY / n, and rows >= n are written as exact zeros.  A kernel of its own: pb_pool_bwd_kernel stays
+// what it is.
+__global__ __launch_bounds__(1024) void pb_pool_bwd_lens_kernel(const float* __restrict__ X, long long ldx, const float* __restrict__ dY,
+                                                                long long ldy, float* __restrict__ dX, long long ldd, int L, int E,
+                                                                const int* __restrict__ lens) {
+    __shared__ float s_max[16][64];
+    __shared__ int s_arg[16][64];
+    const int lane = threadIdx.x & 63, sl = threadIdx.x >> 6;
+    const int c = blockIdx.y * 64 + lane;
+    const long long s = blockIdx.x;
+    const int n = min(L, max(1, lens[s]));
+    float best = -INFINITY;
+    int arg = -1;
+    if (c < E) {
+        const float* x = X + s * L * ldx + c;
+        for (int r = sl; r < n; r += 16) {
+            const float v = x[(long long)r * ldx];
+            if (arg < 0 || v > best) { best = v; arg = r; }
+        }
+    }
+    s_max[sl][lane] = best; s_arg[sl][lane] = arg;
+    __syncthreads();
+    if (c >= E) return;
+    best = s_max[0][lane]; arg = s_arg[0][lane];
+    for (int k = 1; k < 16; ++k) {
+        const int a = s_arg[k][lane];
+        const float v = s_max[k][lane];
+        if (a >= 0 && (arg < 0 || v > best || (v == best && a < arg))) { best = v; arg = a; }
+    }
+    const float g_max = dY[s * ldy + c], g_avg = dY[s * ldy + E + c] / (float)n;
+    float* o = dX + s * L * ldd + c;
+    for (int r = sl; r < L; r += 16) o[(long long)r * ldd] = r >= n ? 0.f : r == arg ? g_avg + g_max : g_avg;
+}
+
+// lens (optional, DEVICE int[S]): the valid rows of every sequence
+void launch_pool_bwd(hipStream_t s, const float* X, int64_t ldx, const float* dY, int64_t ldy, float* dX, int64_t ldd, int64_t S, int L, int E,
+                     const int* lens = nullptr) {
+    if (lens) {
+        hipLaunchKernelGGL(pb_pool_bwd_lens_kernel, dim3((unsigned)S, (unsigned)cdiv(E, 64)), dim3(1024), 0, s, X, (long long)ldx, dY,
+                           (long long)ldy, dX, (long long)ldd, L, E, lens);
+        return;
+    }
     hipLaunchKernelGGL(pb_pool_bwd_kernel, dim3((unsigned)S, (unsigned)cdiv(E, 64)), dim3(1024), 0, s, X, (long long)ldx, dY, (long long)ldy, dX,
                        (long long)ldd, L, E);
 }
@@ -1143,7 +1193,9 @@ AttnBwdScratch carve_attention_backward_pct(Arena& a, int64_t S, int64_t L) {
 
 // Forward of the fp32 network over one chunk of Sc sequences: boundaries X0..X2, the embedding's pre-activation, the tail up to
 // linear0's output ws.y0 (what the pooling reads)
-void pb_chunk_forward(hipStream_t s, const PctW& w, const float* pc, int64_t Sc, int L, int half, const PbScratch& ws) {
+// lens (optional, DEVICE int[Sc]): padded sequences -- the keys of sequence i are its first min(L, max(1, lens[i])) rows
+void pb_chunk_forward(hipStream_t s, const PctW& w, const float* pc, int64_t Sc, int L, int half, const PbScratch& ws,
+                      const int* lens = nullptr) {
     const int64_t T = Sc * L;
     float* const* X = ws.X;
     const VbInterior& I = ws.I;
@@ -1151,31 +1203,32 @@ void pb_chunk_forward(hipStream_t s, const PctW& w, const float* pc, int64_t Sc,
     launch_gelu(s, ws.z1, PB_F, ws.g1, PB_F, T, PB_F, 0);
     vb_linear(s, {ws.g1, PB_F}, w.l2, {}, {X[0], PB_E}, T, PB_F, PB_F, ACT_NONE);
     launch_copy2d(s, pc, 3, X[0] + PB_F, PB_E, T, 3);
-    for (int e = 0; e < PCT_N_ENC; ++e) vb_encoder_fwd(s, w.enc[e], X[e], X[e + 1], I, Sc, L, nullptr, PB_E);
+    for (int e = 0; e < PCT_N_ENC; ++e) vb_encoder_fwd(s, w.enc[e], X[e], X[e + 1], I, Sc, L, lens, PB_E);
     launch_layernorm(s, X[PCT_N_ENC], PB_E, w.ng, w.nb, ws.hn, PB_E, T, PB_E);
     vb_linear(s, {ws.hn, PB_E}, w.lin0, {}, {ws.y0, half}, T, half, PB_E, ACT_NONE);
 }
 
 // One chunk: Sc sequences from pc / d_feat on; dw = where the table's gradients go (NULL: none), d_pc (optional) this chunk's rows;
 // ld_feat: the leading dimension of d_feat (0: 2 * half, dense rows); forward_done: ws still holds pb_chunk_forward's results for this
-// very chunk (nothing has written it since), so the forward is not run again
+// very chunk (nothing has written it since), so the forward is not run again; lens: as pb_chunk_forward, the pooling's too (padded
+// rows then receive exact zeros from the pooling's backward and hand exact zeros on: nothing of them reaches a gradient)
 void pb_chunk_backward(hipStream_t s, const PctW& w, const float* pc, const float* d_feat, int64_t Sc, int L, int half, float* const* dw,
-                       float* d_pc, const PbScratch& ws, int64_t ld_feat = 0, bool forward_done = false) {
+                       float* d_pc, const PbScratch& ws, int64_t ld_feat = 0, bool forward_done = false, const int* lens = nullptr) {
     const int64_t T = Sc * L;
     float* const* X = ws.X;
     const VbInterior& I = ws.I;
     const VbGrads& G = ws.G;
     auto DW = [&](int slot) { return dw ? dw[slot] : nullptr; };
-    if (!forward_done) pb_chunk_forward(s, w, pc, Sc, L, half, ws);
+    if (!forward_done) pb_chunk_forward(s, w, pc, Sc, L, half, ws, lens);
     // ---- tail (SconeOcc.py:119-126), backwards: pooling, linear0, norm
-    launch_pool_bwd(s, ws.y0, half, d_feat, ld_feat > 0 ? ld_feat : 2 * half, G.dH, half, Sc, L, half);
+    launch_pool_bwd(s, ws.y0, half, d_feat, ld_feat > 0 ? ld_feat : 2 * half, G.dH, half, Sc, L, half, lens);
     gemm_dw(s, G.dH, half, ws.hn, PB_E, T, half, PB_E, DW(PCT_LIN0 + LIN_W), DW(PCT_LIN0 + LIN_B), G.part);
     gemm_dx(s, G.dH, half, w.lin0.w, PB_E, G.dA, PB_E, T, half, PB_E, false, G.wt);
     launch_ln_bwd(s, X[PCT_N_ENC], PB_E, w.ng, G.dA, PB_E, G.dX, PB_E, false, DW(PCT_NG), DW(PCT_NB), G.part, T, PB_E);
     // ---- encoders, last to first
     for (int e = PCT_N_ENC - 1; e >= 0; --e) {
-        vb_encoder_fwd(s, w.enc[e], X[e], nullptr, I, Sc, L, nullptr, PB_E);
-        vb_encoder_bwd(s, w.enc[e], dw ? dw + PCT_ENC + ENC_NW * e : nullptr, X[e], I, G, Sc, L, nullptr, PB_E);
+        vb_encoder_fwd(s, w.enc[e], X[e], nullptr, I, Sc, L, lens, PB_E);
+        vb_encoder_bwd(s, w.enc[e], dw ? dw + PCT_ENC + ENC_NW * e : nullptr, X[e], I, G, Sc, L, lens, PB_E);
     }
     // ---- embedding (Attention.py:98-128): [linear2(GELU(linear1(pc))) | pc]
     gemm_dw(s, G.dX, PB_E, ws.g1, PB_F, T, PB_F, PB_F, DW(PCT_L2 + LIN_W), DW(PCT_L2 + LIN_B), G.part);
@@ -1258,10 +1311,8 @@ inline size_t so_stage_pct_floats() {
     for (int i = 0; i < PCT_NW; ++i) n += pb_slot_floats(i, SO_LF / 2);
     return n;
 }
-SoScratch carve_so(Arena& a, int64_t B, int64_t Qc, int64_t Lg) {
-    SoScratch w;
-    w.gfeat = a.f(B * SO_G); w.dG = a.f(B * SO_G); w.gtmp = a.f(SO_G);
-    Arena c = a.rest(), g = a.rest();
+// one chunk of Qc queries (everything of SoScratch but what outlives a chunk and the global transformer's scratch)
+void carve_so_chunk(Arena& c, SoScratch& w, int64_t Qc) {
     for (float*& o : w.off) o = c.f(Qc * SO_K * 3);
     w.d_off = c.f(Qc * SO_K * 3);
     w.ze1 = c.f(Qc * (SO_XE / 4)); w.ge1 = c.f(Qc * (SO_XE / 4)); w.ze2 = c.f(Qc * (SO_XE / 2)); w.ge2 = c.f(Qc * (SO_XE / 2));
@@ -1283,10 +1334,198 @@ SoScratch carve_so(Arena& a, int64_t B, int64_t Qc, int64_t Lg) {
         l.z1 = c.f(T * PB_F); l.g1 = c.f(T * PB_F);
         l.hn = c.f(T * PB_E); l.y0 = c.f(T * (SO_LF / 2));
     }
+}
+SoScratch carve_so(Arena& a, int64_t B, int64_t Qc, int64_t Lg) {
+    SoScratch w;
+    w.gfeat = a.f(B * SO_G); w.dG = a.f(B * SO_G); w.gtmp = a.f(SO_G);
+    Arena c = a.rest(), g = a.rest();
+    carve_so_chunk(c, w, Qc);
     w.global = carve_pb_chunk(g, B, Lg, SO_G / 2, false);
     a.off += std::max(c.off, g.off);
     return w;
 }
+
+// The workspace of mcr_scone_occ_backward_ragged: as SoScratch over J jobs (so.global: the J padded sequences' forward), plus the padded
+// sequences with their padding overwritten, and ONE sequence's scratch for the global transformer's backward, which runs job by job
+// (the jobs behind the first through a staging area of their own)
+struct SoRaggedScratch {
+    SoScratch so;
+    float* pcg;                                            // [J, Lg, 3]: pc_global, rows >= the length = the sequence's row 0
+    PbScratch global1;                                     // one sequence of Lg tokens (with its staging area)
+};
+SoRaggedScratch carve_so_ragged(Arena& a, int64_t J, int64_t Qc, int64_t Lg) {
+    SoRaggedScratch r;
+    SoScratch& w = r.so;
+    w.gfeat = a.f(J * SO_G); w.dG = a.f(J * SO_G); w.gtmp = nullptr;
+    r.pcg = a.f(J * Lg * 3);
+    Arena c = a.rest(), g = a.rest(), g1 = a.rest();
+    carve_so_chunk(c, w, Qc);
+    w.global = carve_pb_chunk(g, J, Lg, SO_G / 2, false);
+    r.global1 = carve_pb_chunk(g1, 1, Lg, SO_G / 2, true);
+    a.off += std::max({c.off, g.off, g1.off});
+    return r;
+}
+
+// ---- the ragged pass: rows of J jobs packed into chunks -------------------------------------------------------------------------------
+// dst[(j*L + r)*3 + c] = src[(j*L + (r < n ? r : 0))*3 + c], n = min(L, max(1, lens[j])): the padded sequences with their padding
+// overwritten by a valid row.  The forward masks the padded keys, but the weight-gradient products of the backward multiply every row's
+// (zero) gradient with what the row holds: 0 x NaN would be NaN.  One thread per (row, channel).
+__global__ __launch_bounds__(256) void so_pad_global_kernel(const float* __restrict__ src, const int* __restrict__ lens,
+                                                            float* __restrict__ dst, long long J, int L) {
+    const long long e = blockIdx.x * 256ll + threadIdx.x;
+    if (e >= J * L * 3) return;
+    const long long row = e / 3;
+    const int c = (int)(e - row * 3);
+    const long long j = row / L;
+    const int r = (int)(row - j * L);
+    const int n = min(L, max(1, lens[j]));
+    dst[e] = src[(j * L + (r < n ? r : 0)) * 3 + c];
+}
+
+// h[r*ldh + c] = gfeat[row_job[r]*512 + c] (c < 512): every row's job's global features into the head's input.  One thread per (row,
+// column), consecutive threads on consecutive columns; a job outside [0, J) is clamped into it (never an access out of bounds).
+__global__ __launch_bounds__(256) void so_bcast_rows_kernel(const float* __restrict__ gfeat, const int* __restrict__ row_job, long long J,
+                                                            float* __restrict__ h, long long ldh, long long rows) {
+    const long long e = blockIdx.x * 256ll + threadIdx.x;
+    if (e >= rows * SO_G) return;
+    const long long r = e / SO_G;
+    const int c = (int)(e - r * SO_G);
+    const long long j = min(max((long long)row_job[r], 0ll), J - 1);
+    h[r * ldh + c] = gfeat[j * SO_G + c];
+}
+
+// dG[j*512 + c] += sum of dH[(r - r0)*ldh + c] over the rows r of job j inside the chunk [r0, r0 + rows), r ascending; job j = rows
+// [job_rows[j], job_rows[j + 1]) (clamped into the chunk: never an access out of bounds).  One thread owns each (j, c): no atomics, and
+// the chunks run one behind the other on the stream, so the sum has one order.  A job without rows in the chunk is left alone.
+__global__ __launch_bounds__(256) void so_seg_colsum_kernel(const float* __restrict__ dH, long long ldh, const long long* __restrict__ job_rows,
+                                                            long long J, long long r0, long long rows, float* __restrict__ dG) {
+    const long long e = blockIdx.x * 256ll + threadIdx.x;
+    if (e >= J * SO_G) return;
+    const long long j = e / SO_G;
+    const int c = (int)(e - j * SO_G);
+    const long long lo = min(max(job_rows[j], r0), r0 + rows) - r0, hi = min(max(job_rows[j + 1], r0), r0 + rows) - r0;
+    if (lo >= hi) return;
+    float acc = 0.f;
+#pragma unroll 8
+    for (long long r = lo; r < hi; ++r) acc += dH[r * ldh + c];
+    dG[e] += acc;
+}
+
+// How a chunk's rows meet the global features: all of one cloud (row_job NULL: gfeat / dG are that cloud's rows of 512, and the cloud's
+// first chunk writes dG where the later ones add), or every row with its job (gfeat / dG [J, 512]; row_job: the chunk's slice, r0: its
+// first row)
+struct SoGlobalRows {
+    const float* gfeat; float* dG; float* gtmp; bool first_of_cloud;
+    const int* row_job; const long long* job_rows; int64_t J, r0;
+};
+
+// the chunks behind the first leave their weight gradients in the staging area, cut in table order, and are added in chunk order
+struct SoStage {
+    float* tab[OCC_NW] = {};
+    PbSlots local[3] = {}, head{};
+    const float* stage_local[3] = {};
+    const float* stage_head = nullptr;
+};
+void so_stage_init(SoStage& st, float* const* d_weights, float* stage) {
+    const size_t n_pct = so_stage_pct_floats();
+    for (int i = 0; i < 3; ++i) {
+        st.stage_local[i] = stage + i * n_pct;
+        for (int k = 0; k < PCT_NW; ++k) {
+            st.local[i].dst[k] = d_weights[OCC_LOCAL + i * PCT_NW + k];
+            st.local[i].off[k + 1] = st.local[i].off[k] + pb_slot_floats(k, SO_LF / 2);
+            st.tab[OCC_LOCAL + i * PCT_NW + k] = stage + i * n_pct + st.local[i].off[k];
+        }
+    }
+    st.stage_head = stage + 3 * n_pct;
+    for (int k = 0; k < SO_HEAD_NW; ++k) {
+        st.head.dst[k] = d_weights[OCC_XE + k];
+        st.head.off[k + 1] = st.head.off[k] + so_head_slot_floats(k);
+        st.tab[OCC_XE + k] = stage + 3 * n_pct + st.head.off[k];
+    }
+}
+void so_stage_add(hipStream_t s, const SoStage& st) {
+    for (int i = 0; i < 3; ++i) hipLaunchKernelGGL(pb_add_slots_kernel, dim3(64, PCT_NW), dim3(256), 0, s, st.local[i], st.stage_local[i]);
+    hipLaunchKernelGGL(pb_add_slots_kernel, dim3(64, SO_HEAD_NW), dim3(256), 0, s, st.head, st.stage_head);
+}
+
+// One chunk of n rows, forward and backward, given its neighbourhoods as offsets off[i] [n, 16, 3]: (b) the local features, (c) the
+// x-embedding, (d) the head, then (e) - (h) their backward.  xc / vhc / d_out_c / dxc / dvhc: the chunk's rows of the operands (dxc, dvhc
+// may be NULL); dw: where this chunk's weight gradients go (NULL: none wanted); deep: anything below the head's input wanted
+void so_chunk_fwd_bwd(hipStream_t s, const OccW& w, const SoScratch& ws, const float* const* off, const float* xc, const float* vhc,
+                      const float* d_out_c, int64_t n, float* const* dw, float* dxc, float* dvhc, bool deep, const SoGlobalRows& g) {
+    float *part = ws.part, *wt = ws.wt;
+    auto DW = [&](int slot) { return dw ? dw[slot] : nullptr; };
+    // (b) the local features, straight into the head's input
+    for (int i = 0; i < 3; ++i) {
+        pb_chunk_forward(s, w.local[i], off[i], n, SO_K, SO_LF / 2, ws.local[i]);
+        launch_pool_max_avg(s, ws.local[i].y0, SO_LF / 2, ws.h + SO_LOC + i * SO_LF, SO_H, n, SO_K, SO_LF / 2);
+    }
+    // (c) the x-embedding (SconeOcc.py:7-42)
+    vb_linear(s, {xc, 3}, w.xe1, {}, {ws.ze1, SO_XE / 4}, n, SO_XE / 4, 3, ACT_NONE);
+    launch_gelu(s, ws.ze1, SO_XE / 4, ws.ge1, SO_XE / 4, n, SO_XE / 4, 0);
+    vb_linear(s, {ws.ge1, SO_XE / 4}, w.xe2, {}, {ws.ze2, SO_XE / 2}, n, SO_XE / 2, SO_XE / 4, ACT_NONE);
+    launch_gelu(s, ws.ze2, SO_XE / 2, ws.ge2, SO_XE / 2, n, SO_XE / 2, 0);
+    vb_linear(s, {ws.ge2, SO_XE / 2}, w.xe3, {}, {ws.ze3, SO_XE}, n, SO_XE, SO_XE / 2, ACT_NONE);
+    launch_gelu(s, ws.ze3, SO_XE, ws.h + SO_XCOL, SO_H, n, SO_XE, 0);
+    // (d) the head (SconeOcc.py:334-342): GELU behind every layer, the last included
+    if (g.row_job)
+        hipLaunchKernelGGL(so_bcast_rows_kernel, dim3((unsigned)cdiv(n * SO_G, 256)), dim3(256), 0, s, g.gfeat, g.row_job, (long long)g.J, ws.h,
+                           (long long)SO_H, (long long)n);
+    else launch_copy2d(s, g.gfeat, 0, ws.h, SO_H, n, SO_G);
+    launch_copy2d(s, vhc, SO_VH, ws.h + SO_VCOL, SO_H, n, SO_VH);
+    vb_linear(s, {ws.h, SO_H}, w.lin1, {}, {ws.z1, SO_L1}, n, SO_L1, SO_H, ACT_NONE);
+    launch_gelu(s, ws.z1, SO_L1, ws.g1, SO_L1, n, SO_L1, 0);
+    vb_linear(s, {ws.g1, SO_L1}, w.lin2, {}, {ws.z2, SO_L2}, n, SO_L2, SO_L1, ACT_NONE);
+    launch_gelu(s, ws.z2, SO_L2, ws.g2, SO_L2, n, SO_L2, 0);
+    vb_linear(s, {ws.g2, SO_L2}, w.lin3, {}, {ws.z3, 1}, n, 1, SO_L2, ACT_NONE);
+    // (e) the head, backwards
+    launch_copy2d(s, d_out_c, 1, ws.dz3, 1, n, 1);
+    launch_gelu(s, ws.z3, 1, ws.dz3, 1, n, 1, 1);                                                   // linear3
+    gemm_dw(s, ws.dz3, 1, ws.g2, SO_L2, n, 1, SO_L2, DW(OCC_LIN + 2 * LIN_NW + LIN_W), DW(OCC_LIN + 2 * LIN_NW + LIN_B), part);
+    gemm_dx(s, ws.dz3, 1, w.lin3.w, SO_L2, ws.d2, SO_L2, n, 1, SO_L2, false, wt);
+    launch_gelu(s, ws.z2, SO_L2, ws.d2, SO_L2, n, SO_L2, 1);                                        // linear2
+    gemm_dw(s, ws.d2, SO_L2, ws.g1, SO_L1, n, SO_L2, SO_L1, DW(OCC_LIN + LIN_NW + LIN_W), DW(OCC_LIN + LIN_NW + LIN_B), part);
+    gemm_dx(s, ws.d2, SO_L2, w.lin2.w, SO_L1, ws.d1, SO_L1, n, SO_L2, SO_L1, false, wt);
+    launch_gelu(s, ws.z1, SO_L1, ws.d1, SO_L1, n, SO_L1, 1);                                        // linear1
+    gemm_dw(s, ws.d1, SO_L1, ws.h, SO_H, n, SO_L1, SO_H, DW(OCC_LIN + LIN_W), DW(OCC_LIN + LIN_B), part);
+    gemm_dx(s, ws.d1, SO_L1, w.lin1.w, SO_H, ws.dH, SO_H, n, SO_L1, SO_H, false, wt);
+    // (f) what leaves the head's input as it is: the harmonics' columns, the global features' (summed over the chunk's rows -- one
+    // cloud: the bias half of a weight-gradient product of depth 0, then chunk by chunk in order; jobs: so_seg_colsum_kernel)
+    if (dvhc) launch_copy2d(s, ws.dH + SO_VCOL, SO_H, dvhc, SO_VH, n, SO_VH);
+    if (!deep) return;
+    if (dw && g.row_job) {
+        hipLaunchKernelGGL(so_seg_colsum_kernel, dim3((unsigned)cdiv(g.J * SO_G, 256)), dim3(256), 0, s, (const float*)ws.dH, (long long)SO_H,
+                           g.job_rows, (long long)g.J, (long long)g.r0, (long long)n, g.dG);
+    } else if (dw) {
+        gemm_dw(s, ws.dH, SO_H, nullptr, 0, n, SO_G, 0, nullptr, g.first_of_cloud ? g.dG : g.gtmp, part);
+        if (!g.first_of_cloud) {
+            PbSlots slot_g{};                              // one row of the global features' gradient
+            slot_g.off[1] = SO_G;
+            slot_g.dst[0] = g.dG;
+            hipLaunchKernelGGL(pb_add_slots_kernel, dim3(2, 1), dim3(256), 0, s, slot_g, (const float*)g.gtmp);
+        }
+    }
+    // (g) the x-embedding, backwards
+    float* dxe = ws.dH + SO_XCOL;
+    launch_gelu(s, ws.ze3, SO_XE, dxe, SO_H, n, SO_XE, 1);
+    gemm_dw(s, dxe, SO_H, ws.ge2, SO_XE / 2, n, SO_XE, SO_XE / 2, DW(OCC_XE + 2 * LIN_NW + LIN_W), DW(OCC_XE + 2 * LIN_NW + LIN_B), part);
+    gemm_dx(s, dxe, SO_H, w.xe3.w, SO_XE / 2, ws.d2, SO_XE / 2, n, SO_XE, SO_XE / 2, false, wt);
+    launch_gelu(s, ws.ze2, SO_XE / 2, ws.d2, SO_XE / 2, n, SO_XE / 2, 1);
+    gemm_dw(s, ws.d2, SO_XE / 2, ws.ge1, SO_XE / 4, n, SO_XE / 2, SO_XE / 4, DW(OCC_XE + LIN_NW + LIN_W), DW(OCC_XE + LIN_NW + LIN_B), part);
+    gemm_dx(s, ws.d2, SO_XE / 2, w.xe2.w, SO_XE / 4, ws.d1, SO_XE / 4, n, SO_XE / 2, SO_XE / 4, false, wt);
+    launch_gelu(s, ws.ze1, SO_XE / 4, ws.d1, SO_XE / 4, n, SO_XE / 4, 1);
+    gemm_dw(s, ws.d1, SO_XE / 4, xc, 3, n, SO_XE / 4, 3, DW(OCC_XE + LIN_W), DW(OCC_XE + LIN_B), part);
+    if (dxc) gemm_dx(s, ws.d1, SO_XE / 4, w.xe1.w, 3, dxc, 3, n, SO_XE / 4, 3, false, wt);
+    // (h) the local transformers, backwards, from what (b) left in each scale's scratch (no second forward; each encoder's
+    // interior is rebuilt from its boundary as ever); the query's share of the offsets
+    for (int i = 0; i < 3; ++i) {
+        pb_chunk_backward(s, w.local[i], off[i], ws.dH + SO_LOC + i * SO_LF, n, SO_K, SO_LF / 2, dw ? dw + OCC_LOCAL + i * PCT_NW : nullptr,
+                          dxc ? ws.d_off : nullptr, ws.local[i], SO_H, /*forward_done=*/true);
+        if (dxc) launch_so_dx_sub(s, ws.d_off, dxc, n);
+    }
+}
+
+constexpr int64_t SO_RAGGED_MAX_J = 16384;                           // jobs of one mcr_scone_occ_backward_ragged call
 
 }  // namespace
 }  // namespace mcr
@@ -1508,6 +1747,17 @@ int mcr_pool_max_avg_backward(const float* X, int64_t ldx, const float* dY, int6
     return 0;
 }
 
+int mcr_pool_max_avg_backward_lens(const float* X, int64_t ldx, const float* dY, int64_t ldy, float* dX, int64_t ld_dx, int64_t S, int64_t L,
+                                   int E, const int* lens, void* stream) {
+    const char* who = "mcr_pool_max_avg_backward_lens";
+    MCR_REQUIRE(X && dY && dX && lens, "%s: null pointer", who);
+    MCR_REQUIRE(S > 0 && L > 0 && E > 0 && S <= (1ll << 31) - 1 && L <= (1 << 30) && E <= 64 * 65535, "%s: bad problem size", who);
+    MCR_REQUIRE(ldx >= E && ldy >= 2 * E && ld_dx >= E, "%s: leading dimension too small", who);
+    launch_pool_bwd((hipStream_t)stream, X, ldx, dY, ldy, dX, ld_dx, S, (int)L, E, lens);
+    MCR_LAUNCH_CHECK(who);
+    return 0;
+}
+
 int mcr_pc_transformer_backward_chunk(int64_t S, int64_t L) { return (S > 0 && L > 0) ? (int)std::min<int64_t>(pb_chunk(S, L), INT32_MAX) : 0; }
 
 size_t mcr_pc_transformer_backward_workspace_bytes(int64_t S, int64_t L) {
@@ -1592,32 +1842,9 @@ int mcr_scone_occ_backward(const float* pc_global, int64_t Lg, const float* cons
     Arena a{(char*)workspace, workspace_bytes};
     const SoScratch ws = carve_so(a, B, Qc, Lg);
     MCR_REQUIRE(a.ok(), "%s: workspace overflow", who);
-    float *part = ws.part, *wt = ws.wt;
     const bool deep = d_weights || d_x;                    // anything below the head's input wanted
-    // the chunks behind the first leave their weight gradients in ws.stage, cut in table order, and are added in chunk order
-    float* stage_tab[OCC_NW] = {};
-    PbSlots slots_local[3] = {}, slots_head{};
-    const float* stage_local[3] = {};
-    const float* stage_head = nullptr;
-    if (d_weights) {
-        const size_t n_pct = so_stage_pct_floats();
-        for (int i = 0; i < 3; ++i) {
-            stage_local[i] = ws.stage + i * n_pct;
-            for (int k = 0; k < PCT_NW; ++k) {
-                slots_local[i].dst[k] = d_weights[OCC_LOCAL + i * PCT_NW + k];
-                slots_local[i].off[k + 1] = slots_local[i].off[k] + pb_slot_floats(k, SO_LF / 2);
-                stage_tab[OCC_LOCAL + i * PCT_NW + k] = ws.stage + i * n_pct + slots_local[i].off[k];
-            }
-        }
-        stage_head = ws.stage + 3 * n_pct;
-        for (int k = 0; k < SO_HEAD_NW; ++k) {
-            slots_head.dst[k] = d_weights[OCC_XE + k];
-            slots_head.off[k + 1] = slots_head.off[k] + so_head_slot_floats(k);
-            stage_tab[OCC_XE + k] = ws.stage + 3 * n_pct + slots_head.off[k];
-        }
-    }
-    PbSlots slot_g{};                                      // one row of the global features' gradient
-    slot_g.off[1] = SO_G;
+    SoStage st;
+    if (d_weights) so_stage_init(st, d_weights, ws.stage);
 
     // ---- 1. the global transformer's forward: [B, 512]
     pb_chunk_forward(s, w.global, pc_global, B, (int)Lg, SO_G / 2, ws.global);
@@ -1628,79 +1855,99 @@ int mcr_scone_occ_backward(const float* pc_global, int64_t Lg, const float* cons
         for (int64_t q0 = 0; q0 < Q; q0 += Qc) {
             const int64_t n = std::min(Qc, Q - q0), r0 = b * Q + q0;
             const bool first = b == 0 && q0 == 0;
-            float* const* dw = !d_weights ? nullptr : first ? d_weights : stage_tab;
-            auto DW = [&](int slot) { return dw ? dw[slot] : nullptr; };
-            const float* xc = x + r0 * 3;
-            float* dxc = d_x ? d_x + r0 * 3 : nullptr;
-            // (a) the neighbourhoods as offsets, (b) the local features, straight into the head's input
-            for (int i = 0; i < 3; ++i) {
-                launch_so_gather(s, pc_scale[i] + b * M_scale[i] * 3, M_scale[i], knn_idx[i] + r0 * SO_K, xc, ws.off[i], n);
-                pb_chunk_forward(s, w.local[i], ws.off[i], n, SO_K, SO_LF / 2, ws.local[i]);
-                launch_pool_max_avg(s, ws.local[i].y0, SO_LF / 2, ws.h + SO_LOC + i * SO_LF, SO_H, n, SO_K, SO_LF / 2);
-            }
-            // (c) the x-embedding (SconeOcc.py:7-42)
-            vb_linear(s, {xc, 3}, w.xe1, {}, {ws.ze1, SO_XE / 4}, n, SO_XE / 4, 3, ACT_NONE);
-            launch_gelu(s, ws.ze1, SO_XE / 4, ws.ge1, SO_XE / 4, n, SO_XE / 4, 0);
-            vb_linear(s, {ws.ge1, SO_XE / 4}, w.xe2, {}, {ws.ze2, SO_XE / 2}, n, SO_XE / 2, SO_XE / 4, ACT_NONE);
-            launch_gelu(s, ws.ze2, SO_XE / 2, ws.ge2, SO_XE / 2, n, SO_XE / 2, 0);
-            vb_linear(s, {ws.ge2, SO_XE / 2}, w.xe3, {}, {ws.ze3, SO_XE}, n, SO_XE, SO_XE / 2, ACT_NONE);
-            launch_gelu(s, ws.ze3, SO_XE, ws.h + SO_XCOL, SO_H, n, SO_XE, 0);
-            // (d) the head (SconeOcc.py:334-342): GELU behind every layer, the last included
-            launch_copy2d(s, ws.gfeat + b * SO_G, 0, ws.h, SO_H, n, SO_G);
-            launch_copy2d(s, view_harmonics + r0 * SO_VH, SO_VH, ws.h + SO_VCOL, SO_H, n, SO_VH);
-            vb_linear(s, {ws.h, SO_H}, w.lin1, {}, {ws.z1, SO_L1}, n, SO_L1, SO_H, ACT_NONE);
-            launch_gelu(s, ws.z1, SO_L1, ws.g1, SO_L1, n, SO_L1, 0);
-            vb_linear(s, {ws.g1, SO_L1}, w.lin2, {}, {ws.z2, SO_L2}, n, SO_L2, SO_L1, ACT_NONE);
-            launch_gelu(s, ws.z2, SO_L2, ws.g2, SO_L2, n, SO_L2, 0);
-            vb_linear(s, {ws.g2, SO_L2}, w.lin3, {}, {ws.z3, 1}, n, 1, SO_L2, ACT_NONE);
-            // (e) the head, backwards
-            launch_copy2d(s, d_out + r0, 1, ws.dz3, 1, n, 1);
-            launch_gelu(s, ws.z3, 1, ws.dz3, 1, n, 1, 1);                                                   // linear3
-            gemm_dw(s, ws.dz3, 1, ws.g2, SO_L2, n, 1, SO_L2, DW(OCC_LIN + 2 * LIN_NW + LIN_W), DW(OCC_LIN + 2 * LIN_NW + LIN_B), part);
-            gemm_dx(s, ws.dz3, 1, w.lin3.w, SO_L2, ws.d2, SO_L2, n, 1, SO_L2, false, wt);
-            launch_gelu(s, ws.z2, SO_L2, ws.d2, SO_L2, n, SO_L2, 1);                                        // linear2
-            gemm_dw(s, ws.d2, SO_L2, ws.g1, SO_L1, n, SO_L2, SO_L1, DW(OCC_LIN + LIN_NW + LIN_W), DW(OCC_LIN + LIN_NW + LIN_B), part);
-            gemm_dx(s, ws.d2, SO_L2, w.lin2.w, SO_L1, ws.d1, SO_L1, n, SO_L2, SO_L1, false, wt);
-            launch_gelu(s, ws.z1, SO_L1, ws.d1, SO_L1, n, SO_L1, 1);                                        // linear1
-            gemm_dw(s, ws.d1, SO_L1, ws.h, SO_H, n, SO_L1, SO_H, DW(OCC_LIN + LIN_W), DW(OCC_LIN + LIN_B), part);
-            gemm_dx(s, ws.d1, SO_L1, w.lin1.w, SO_H, ws.dH, SO_H, n, SO_L1, SO_H, false, wt);
-            // (f) what leaves the head's input as it is: the harmonics' columns, the global features' (summed over the chunk's rows: the
-            // bias half of a weight-gradient product of depth 0, then chunk by chunk in order)
-            if (d_view_harmonics) launch_copy2d(s, ws.dH + SO_VCOL, SO_H, d_view_harmonics + r0 * SO_VH, SO_VH, n, SO_VH);
-            if (!deep) continue;
-            if (d_weights) {
-                gemm_dw(s, ws.dH, SO_H, nullptr, 0, n, SO_G, 0, nullptr, q0 == 0 ? ws.dG + b * SO_G : ws.gtmp, part);
-                if (q0 > 0) {
-                    slot_g.dst[0] = ws.dG + b * SO_G;
-                    hipLaunchKernelGGL(pb_add_slots_kernel, dim3(2, 1), dim3(256), 0, s, slot_g, (const float*)ws.gtmp);
-                }
-            }
-            // (g) the x-embedding, backwards
-            float* dxe = ws.dH + SO_XCOL;
-            launch_gelu(s, ws.ze3, SO_XE, dxe, SO_H, n, SO_XE, 1);
-            gemm_dw(s, dxe, SO_H, ws.ge2, SO_XE / 2, n, SO_XE, SO_XE / 2, DW(OCC_XE + 2 * LIN_NW + LIN_W), DW(OCC_XE + 2 * LIN_NW + LIN_B), part);
-            gemm_dx(s, dxe, SO_H, w.xe3.w, SO_XE / 2, ws.d2, SO_XE / 2, n, SO_XE, SO_XE / 2, false, wt);
-            launch_gelu(s, ws.ze2, SO_XE / 2, ws.d2, SO_XE / 2, n, SO_XE / 2, 1);
-            gemm_dw(s, ws.d2, SO_XE / 2, ws.ge1, SO_XE / 4, n, SO_XE / 2, SO_XE / 4, DW(OCC_XE + LIN_NW + LIN_W), DW(OCC_XE + LIN_NW + LIN_B), part);
-            gemm_dx(s, ws.d2, SO_XE / 2, w.xe2.w, SO_XE / 4, ws.d1, SO_XE / 4, n, SO_XE / 2, SO_XE / 4, false, wt);
-            launch_gelu(s, ws.ze1, SO_XE / 4, ws.d1, SO_XE / 4, n, SO_XE / 4, 1);
-            gemm_dw(s, ws.d1, SO_XE / 4, xc, 3, n, SO_XE / 4, 3, DW(OCC_XE + LIN_W), DW(OCC_XE + LIN_B), part);
-            if (dxc) gemm_dx(s, ws.d1, SO_XE / 4, w.xe1.w, 3, dxc, 3, n, SO_XE / 4, 3, false, wt);
-            // (h) the local transformers, backwards, from what (b) left in each scale's scratch (no second forward; each encoder's
-            // interior is rebuilt from its boundary as ever); the query's share of the offsets
-            for (int i = 0; i < 3; ++i) {
-                pb_chunk_backward(s, w.local[i], ws.off[i], ws.dH + SO_LOC + i * SO_LF, n, SO_K, SO_LF / 2,
-                                  dw ? dw + OCC_LOCAL + i * PCT_NW : nullptr, dxc ? ws.d_off : nullptr, ws.local[i], SO_H, /*forward_done=*/true);
-                if (dxc) launch_so_dx_sub(s, ws.d_off, dxc, n);
-            }
-            if (d_weights && !first) {
-                for (int i = 0; i < 3; ++i) hipLaunchKernelGGL(pb_add_slots_kernel, dim3(64, PCT_NW), dim3(256), 0, s, slots_local[i], stage_local[i]);
-                hipLaunchKernelGGL(pb_add_slots_kernel, dim3(64, SO_HEAD_NW), dim3(256), 0, s, slots_head, stage_head);
-            }
+            // (a) the neighbourhoods as offsets
+            for (int i = 0; i < 3; ++i)
+                launch_so_gather(s, pc_scale[i] + b * M_scale[i] * 3, M_scale[i], knn_idx[i] + r0 * SO_K, x + r0 * 3, ws.off[i], n);
+            so_chunk_fwd_bwd(s, w, ws, ws.off, x + r0 * 3, view_harmonics + r0 * SO_VH, d_out + r0, n,
+                             !d_weights ? nullptr : first ? d_weights : st.tab, d_x ? d_x + r0 * 3 : nullptr,
+                             d_view_harmonics ? d_view_harmonics + r0 * SO_VH : nullptr, deep,
+                             SoGlobalRows{ws.gfeat + b * SO_G, ws.dG + b * SO_G, ws.gtmp, q0 == 0, nullptr, nullptr, 0, 0});
+            if (deep && d_weights && !first) so_stage_add(s, st);
         }
 
     // ---- 3. the global transformer, backwards (its forward is rebuilt: the chunks have used its scratch)
     if (d_weights) pb_chunk_backward(s, w.global, pc_global, ws.dG, B, (int)Lg, SO_G / 2, d_weights + OCC_GLOBAL, nullptr, ws.global, SO_G);
+    MCR_LAUNCH_CHECK(who);
+    return 0;
+}
+
+
+// ---- SconeOcc, ragged: J jobs of different sizes, their rows packed into chunks ----------------------------------------------------------
+size_t mcr_scone_occ_backward_ragged_workspace_bytes(int64_t J, int64_t T, int64_t Lg, int64_t q_chunk) {
+    return (J > 0 && T > 0 && Lg > 0 && q_chunk >= 0) ? measure(carve_so_ragged, J, so_chunk(T, q_chunk), Lg) + VB_WS_SLACK : 0;
+}
+
+int mcr_scone_occ_backward_ragged(const float* pc_global, const int* global_len, int64_t Lg, const float* const* offsets, const float* x,
+                                  const float* view_harmonics, const int* row_job, const int64_t* job_rows, const float* d_out, int64_t J,
+                                  int64_t T, const float* const* weights, int n_weights, float* const* d_weights, float* d_x,
+                                  float* d_view_harmonics, int64_t q_chunk, void* workspace, size_t workspace_bytes, void* stream) {
+    const char* who = "mcr_scone_occ_backward_ragged";
+    MCR_REQUIRE(pc_global && global_len && offsets && x && view_harmonics && row_job && job_rows && d_out && weights, "%s: null pointer", who);
+    if (check_table(who, OCC_TABLE, weights, n_weights, OCC_NW)) return 1;                  // (the planes tails are accepted and ignored)
+    MCR_REQUIRE(J > 0 && T > 0 && Lg > 0 && J <= SO_RAGGED_MAX_J && T <= (1ll << 24) && Lg <= (1 << 24) && J <= (1ll << 31) / Lg,
+                "%s: bad problem size J=%ld T=%ld Lg=%ld (J <= %ld)", who, (long)J, (long)T, (long)Lg, (long)SO_RAGGED_MAX_J);
+    MCR_REQUIRE(Lg != SO_K, "%s: global sequences of 16 tokens are not supported (their fused attention backward takes no lens)", who);
+    for (int i = 0; i < 3; ++i) {
+        MCR_REQUIRE(offsets[i], "%s: scale %d: null pointer", who, i);
+        MCR_REQUIRE((uintptr_t)offsets[i] % 16 == 0, "%s: operands must be 16-byte aligned", who);
+    }
+    MCR_REQUIRE(q_chunk == 0 || (q_chunk >= 16 && q_chunk % 16 == 0 && q_chunk <= (1 << 20)),
+                "%s: q_chunk must be 0 (the default) or a multiple of 16 in [16, 2^20], got %ld", who, (long)q_chunk);
+    MCR_REQUIRE(((uintptr_t)pc_global | (uintptr_t)x | (uintptr_t)view_harmonics | (uintptr_t)d_out | (uintptr_t)d_x |
+                 (uintptr_t)d_view_harmonics) % 16 == 0, "%s: operands must be 16-byte aligned", who);
+    MCR_REQUIRE((uintptr_t)global_len % 4 == 0 && (uintptr_t)row_job % 4 == 0 && (uintptr_t)job_rows % 8 == 0,
+                "%s: global_len, row_job (4 bytes) and job_rows (8 bytes) must be aligned to their element", who);
+    MCR_REQUIRE(workspace && workspace_bytes >= mcr_scone_occ_backward_ragged_workspace_bytes(J, T, Lg, q_chunk), "%s: workspace too small", who);
+    MCR_REQUIRE((uintptr_t)workspace % 16 == 0, "%s: workspace must be 16-byte aligned", who);
+    if (d_weights)
+        for (int i = 0; i < OCC_NW; ++i) MCR_REQUIRE(d_weights[i], "%s: d_weights[%d] is null", who, i);
+    if (!d_weights && !d_x && !d_view_harmonics) return 0;
+    hipStream_t s = (hipStream_t)stream;
+    const OccW w = read_occ_table(weights, OCC_NW);
+    const int64_t Qc = so_chunk(T, q_chunk);
+    Arena a{(char*)workspace, workspace_bytes};
+    const SoRaggedScratch rs = carve_so_ragged(a, J, Qc, Lg);
+    MCR_REQUIRE(a.ok(), "%s: workspace overflow", who);
+    const SoScratch& ws = rs.so;
+    const bool deep = d_weights || d_x;
+    SoStage st;
+    if (d_weights) so_stage_init(st, d_weights, ws.stage);
+
+    // ---- 1. the global transformer's forward over the J padded sequences: [J, 512]; nothing of the caller's padding is read again
+    hipLaunchKernelGGL(so_pad_global_kernel, dim3((unsigned)cdiv(J * Lg * 3, 256)), dim3(256), 0, s, pc_global, global_len, rs.pcg, (long long)J,
+                       (int)Lg);
+    pb_chunk_forward(s, w.global, rs.pcg, J, (int)Lg, SO_G / 2, ws.global, global_len);
+    launch_pool_max_avg(s, ws.global.y0, SO_G / 2, ws.gfeat, SO_G, J, (int)Lg, SO_G / 2, global_len);
+    if (d_weights)
+        if (int e = check_hip(hipMemsetAsync(ws.dG, 0, (size_t)J * SO_G * sizeof(float), s), who)) return e;
+
+    // ---- 2. the rows of all jobs, chunk by chunk
+    const float* off[3];
+    for (int64_t r0 = 0; r0 < T; r0 += Qc) {
+        const int64_t n = std::min(Qc, T - r0);
+        for (int i = 0; i < 3; ++i) off[i] = offsets[i] + r0 * SO_K * 3;
+        so_chunk_fwd_bwd(s, w, ws, off, x + r0 * 3, view_harmonics + r0 * SO_VH, d_out + r0, n, !d_weights ? nullptr : r0 == 0 ? d_weights : st.tab,
+                         d_x ? d_x + r0 * 3 : nullptr, d_view_harmonics ? d_view_harmonics + r0 * SO_VH : nullptr, deep,
+                         SoGlobalRows{ws.gfeat, ws.dG, nullptr, false, row_job + r0, (const long long*)job_rows, J, r0});
+        if (deep && d_weights && r0 > 0) so_stage_add(s, st);
+    }
+
+    // ---- 3. the global transformer, backwards, job by job in job order (its forward is rebuilt: the chunks have used its scratch).  One
+    // job's gradient depends on nothing but that job -- a job without rows has dG = 0 and adds exact zeros
+    if (d_weights) {
+        PbSlots slots{};
+        float* stage_tab[PCT_NW];
+        for (int i = 0; i < PCT_NW; ++i) {
+            slots.dst[i] = d_weights[OCC_GLOBAL + i];
+            slots.off[i + 1] = slots.off[i] + pb_slot_floats(i, SO_G / 2);
+            stage_tab[i] = rs.global1.stage + slots.off[i];
+        }
+        for (int64_t j = 0; j < J; ++j) {
+            pb_chunk_backward(s, w.global, rs.pcg + j * Lg * 3, ws.dG + j * SO_G, 1, (int)Lg, SO_G / 2, j == 0 ? d_weights + OCC_GLOBAL : stage_tab,
+                              nullptr, rs.global1, SO_G, false, global_len + j);
+            if (j > 0) hipLaunchKernelGGL(pb_add_slots_kernel, dim3(64, PCT_NW), dim3(256), 0, s, slots, (const float*)rs.global1.stage);
+        }
+    }
     MCR_LAUNCH_CHECK(who);
     return 0;
 }

@@ -291,16 +291,34 @@ class SconeOcc(RangeGuard, nn.Module):
             return pc[:, p].contiguous()
         return torch.gather(pc, 1, p[..., None].expand(-1, -1, pc.shape[-1])).contiguous()
 
-    def forward_ragged(self, pc, cloud_sizes, x, view_harmonics, query_sizes, perms=None, index_arrays=None, out=None):
+    def forward_ragged(self, pc, cloud_sizes, x, view_harmonics, query_sizes, perms=None, index_arrays=None, out=None,
+                       differentiable=False):
         """J forward() calls of different sizes as ONE launch sequence (extension; the reference calls forward once per grid cell and
         chunk from a Python loop, macarons_utils.py:1395-1540).  Job j: surface cloud = the next cloud_sizes[j] rows of pc [sum M, 3],
         queries = the next query_sizes[j] rows of x [T,3] / view_harmonics [T,64] (host lists).  perms: per job the three index
         tensors draw_perms(cloud_sizes[j]) returns; None = drawn here in job order on the CPU generator, exactly the draws J
         sequential forward() calls would make; index_arrays: the uploaded index arrays of an earlier pass (`last_ragged_perms`: a
         caller that repeats a pass, or hands rank 0's draws to every rank).
-        -> [T,1] (`out`: written there).  Inference only (no autograd graph).  = forward_ragged_begin + forward_ragged_finish."""
+        -> [T,1] (`out`: written there).  = forward_ragged_begin + forward_ragged_finish.
+        differentiable=True, with gradients enabled and a parameter, x or view_harmonics requiring one: the result carries ONE autograd
+        node (autograd.SconeOccRaggedFunction) whose backward is HIP end to end -- the three scales' offsets, then
+        mcr_scone_occ_backward_ragged over the rows of all jobs, weight gradients summed over the jobs; the values are the bits of the
+        call without the keyword on the same draws (the same launches, without the range flag, as forward() under
+        MCR_SCONE_OCC_BWD=hip; that variable is not consulted here).  The clouds get no gradient: pc.requires_grad is refused
+        (NotImplementedError), and so is out= (ValueError).  Without the keyword, under no_grad or with nothing requiring a gradient
+        the call builds no graph."""
+        self._check_differentiable(differentiable, pc, out)
         h = self.forward_ragged_begin(pc, cloud_sizes, x, view_harmonics, query_sizes)
-        return self.forward_ragged_finish(h, perms=perms, index_arrays=index_arrays, out=out)
+        return self.forward_ragged_finish(h, perms=perms, index_arrays=index_arrays, out=out, differentiable=differentiable)
+
+    @staticmethod
+    def _check_differentiable(differentiable, pc, out):
+        if not differentiable:
+            return
+        if pc.requires_grad:
+            raise NotImplementedError("forward_ragged(differentiable=True): the clouds get no gradient on this path (pc.requires_grad)")
+        if out is not None:
+            raise ValueError("forward_ragged(differentiable=True) returns a new tensor that carries the graph: out= cannot be given")
 
     def forward_ragged_begin(self, pc, cloud_sizes, x, view_harmonics, query_sizes, row_job=None, arena="scone_occ_ragged"):
         """First half of forward_ragged: what needs no hidden draw is uploaded and LAUNCHED (phase 1: the x embedding, the scale-0 search
@@ -354,10 +372,12 @@ class SconeOcc(RangeGuard, nn.Module):
             phase1(variant)
         return {"pc": pc, "x": x, "vh": view_harmonics, "J": J, "Lg": Lg, "variant": variant, "off0": off0, "d_off0": d_off0,
                 "d_row_job": d_row_job, "d_blocks": d_blocks, "state": state, "caches": caches, "phase1": phase1,
-                "cloud_sizes": cloud_sizes, "arena": arena, "epoch1": ops.scone_occ_epoch(dev, arena)}
+                "cloud_sizes": cloud_sizes, "query_sizes": query_sizes, "arena": arena, "epoch1": ops.scone_occ_epoch(dev, arena)}
 
-    def forward_ragged_finish(self, h, perms=None, index_arrays=None, out=None):
-        """Second half of forward_ragged: the hidden draws (unless given), the down-sampled clouds, phase 2."""
+    def forward_ragged_finish(self, h, perms=None, index_arrays=None, out=None, differentiable=False):
+        """Second half of forward_ragged: the hidden draws (unless given), the down-sampled clouds, phase 2.  differentiable: see
+        forward_ragged."""
+        self._check_differentiable(differentiable, h["pc"], out)
         L = _lib.lib()
         pc, x, view_harmonics, J, Lg, variant, off0 = h["pc"], h["x"], h["vh"], h["J"], h["Lg"], h["variant"], h["off0"]
         cloud_sizes, d_off0, d_row_job, d_blocks, state, caches, phase1 = (h["cloud_sizes"], h["d_off0"], h["d_row_job"], h["d_blocks"],
@@ -416,6 +436,14 @@ class SconeOcc(RangeGuard, nn.Module):
             blobs, head, table = state[v] if v in state else caches(v)
             return ops.scone_occ_forward_ragged(pc_global, g_len_d, [pc, pc1, pc2], [d_off0, d_off1, d_off2], x, view_harmonics,
                                                 d_row_job, d_blocks, table, blobs, head, flag, phase=2, out=out_, arena=h["arena"])
+        if differentiable and A.needs_grad(self, x, view_harmonics):
+            # HIP forward (the launches below, no range flag), HIP backward: one node over the rows of all jobs
+            params, slots = self._grad_slots()
+            sz = [self.scale_sizes(int(m)) for m in cloud_sizes]
+            return A.SconeOccRaggedFunction.apply(
+                lambda: run(variant, None, ops.scone_occ_epoch(dev, h["arena"]) != h["epoch1"], None), self.weight_table, slots,
+                [[s_[i] for s_ in sz] for i in range(self.n_scale)], h["query_sizes"], pc_global, g_len_d, [pc, pc1, pc2], d_row_job,
+                x, view_harmonics, *params)
         flag = None
         guard = self._effective_guard()
         if variant in (6, 7) and guard != "off":

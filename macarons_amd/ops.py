@@ -522,13 +522,23 @@ def attention_backward_pct(qkv, d_out, lens=None):
     return d_qkv
 
 
-def pool_max_avg_backward(x, d_y):
-    """Gradient of pool_max_avg: x [S,L,E], d_y [S,2E] -> d_x [S,L,E] (the max's share to the lowest row holding it)."""
+def pool_max_avg_backward(x, d_y, lens=None):
+    """Gradient of pool_max_avg: x [S,L,E], d_y [S,2E] -> d_x [S,L,E] (the max's share to the lowest row holding it).  lens (int32
+    device [S], optional): padded sequences -- sequence s pools its first n = min(L, max(1, lens[s])) rows (mean divided by n), the rows
+    beyond receive exact zeros (mcr_pool_max_avg_backward_lens)."""
     x, d_y = _req(x, "x"), _req(d_y, "d_y")
     S, L, E = x.shape
     if d_y.shape != (S, 2 * E):
         raise ValueError(f"pool_max_avg_backward: d_y [{S},{2 * E}] expected, got {tuple(d_y.shape)}")
     d_x = torch.empty_like(x)
+    if lens is not None:
+        lens = _req(lens, "lens", torch.int32).reshape(-1)
+        if lens.numel() != S:
+            raise ValueError("lens must hold one length per sequence")
+        with torch.cuda.device(x.device):
+            check(lib().mcr_pool_max_avg_backward_lens(_p(x), c_i64(E), _p(d_y), c_i64(2 * E), _p(d_x), c_i64(E), c_i64(S), c_i64(L), c_int(E),
+                                                       _p(lens), _stream()), "mcr_pool_max_avg_backward_lens")
+        return d_x
     with torch.cuda.device(x.device):
         check(lib().mcr_pool_max_avg_backward(_p(x), c_i64(E), _p(d_y), c_i64(2 * E), _p(d_x), c_i64(E), c_i64(S), c_i64(L), c_int(E),
                                               _stream()), "mcr_pool_max_avg_backward")
@@ -610,6 +620,51 @@ def scone_occ_backward(pc_global, pc_scales, x, view_harmonics, knn_idx, d_out, 
                                         _ptr_table(weights), c_int(_n_weights(weights)), dtab if dtab is not None else c_vp(None),
                                         ptr(d_x), ptr(d_vh), c_i64(q_chunk), _p(ws), c_size(ws.numel()), _stream()),
               "mcr_scone_occ_backward")
+    return d_w, d_x, d_vh
+
+
+def scone_occ_backward_ragged(pc_global, global_len, offsets, x, view_harmonics, row_job, query_sizes, d_out, weights,
+                              need=(True, True, True), q_chunk=0):
+    """Gradients of the ragged occupancy pass (J jobs of different sizes, scone_occ_forward_ragged) given d_out [T,1]:
+    (d_weights, d_x [T,3], d_vh [T,64]), the weight gradients summed over the jobs; `need` = (params, x, vh) selects what is computed
+    (None for the rest; nothing needed: no launch).  pc_global [J,Lg,3] with global_len (int32 device [J]: the valid rows of every
+    padded sequence; what the padding rows hold is never used), offsets: per scale [T,16,3], neighbour minus query
+    (knn_offsets_segmented; no gradient flows through the selection), x [T,3], view_harmonics [T,64], row_job (int32 device [T],
+    non-decreasing), query_sizes (host list of J: job j owns the next query_sizes[j] rows; uploaded here as the J + 1 row bounds).
+    The rows of all jobs are packed into chunks of q_chunk rows inside the entry (0 = scone_occ_backward_chunk(T)); a chunk may span
+    any number of jobs.  The fp32 network's gradient whatever the variant (mcr_scone_occ_backward_ragged: HIP kernels only,
+    deterministic; the bits may depend on q_chunk).  There is no gradient for the surface points."""
+    pc_global, x, view_harmonics = _req(pc_global, "pc_global"), _req(x, "x"), _req(view_harmonics, "view_harmonics")
+    d_out = _req(d_out, "d_out")
+    offsets = [_req(o, f"offsets[{i}]") for i, o in enumerate(offsets)]
+    global_len, row_job = _req(global_len, "global_len", torch.int32), _req(row_job, "row_job", torch.int32)
+    qs = [int(q) for q in query_sizes]
+    J, T = len(qs), x.shape[0]
+    if (x.dim() != 2 or x.shape[1] != 3 or pc_global.dim() != 3 or pc_global.shape[0] != J or pc_global.shape[2] != 3 or len(offsets) != 3
+            or any(o.shape != (T, 16, 3) for o in offsets) or view_harmonics.shape != (T, 64) or d_out.numel() != T
+            or global_len.numel() != J or row_job.numel() != T or sum(qs) != T or min(qs, default=0) < 0):
+        raise ValueError("SconeOcc ragged backward needs pc_global [J,Lg,3], global_len [J], three offsets [T,16,3], x [T,3], "
+                         "view_harmonics [T,64], row_job [T], J query_sizes summing to T and d_out [T,1]")
+    Lg = pc_global.shape[1]
+    tensors = weights[0] if isinstance(weights, tuple) else weights
+    need_w, need_x, need_v = (bool(t) for t in need)
+    if not (need_w or need_x or need_v):
+        return None, None, None
+    dev = x.device
+    job_rows = h2d(np.concatenate(([0], np.cumsum(qs))).astype(np.int64), torch.int64, dev)
+    d_w = [torch.empty(tuple(t.shape), dtype=torch.float32, device=dev) for t in tensors[:140]] if need_w else None
+    d_x = torch.empty((T, 3), dtype=torch.float32, device=dev) if need_x else None
+    d_vh = torch.empty((T, 64), dtype=torch.float32, device=dev) if need_v else None
+    L_ = lib()
+    ws = _workspace(dev, int(L_.mcr_scone_occ_backward_ragged_workspace_bytes(c_i64(J), c_i64(T), c_i64(Lg), c_i64(q_chunk))))
+    dtab = (ctypes.c_void_p * 140)(*[t.data_ptr() for t in d_w]) if need_w else None
+    offs = (ctypes.c_void_p * 3)(*[o.data_ptr() for o in offsets])
+    ptr = lambda t: _p(t) if t is not None else c_vp(None)
+    with torch.cuda.device(dev):
+        check(L_.mcr_scone_occ_backward_ragged(_p(pc_global), _p(global_len), c_i64(Lg), offs, _p(x), _p(view_harmonics), _p(row_job),
+                                               _p(job_rows), _p(d_out), c_i64(J), c_i64(T), _ptr_table(weights), c_int(_n_weights(weights)),
+                                               dtab if dtab is not None else c_vp(None), ptr(d_x), ptr(d_vh), c_i64(q_chunk), _p(ws),
+                                               c_size(ws.numel()), _stream()), "mcr_scone_occ_backward_ragged")
     return d_w, d_x, d_vh
 
 
