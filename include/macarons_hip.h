@@ -606,7 +606,10 @@ int mcr_admit_keys(const double* d, const int* key_s, const int64_t* cand, int64
  * mcr_scene_fill_begin: the device part of Scene.fill_cells for ALL cells: key[i] = cell of point i (mcr_cell_keys, box_test = 1),
  *   order = candidates grouped by cell, dmin[i] = fp64 distance of the i-th candidate IN CELL ORDER to the store of its cell
  *   (store_pts: every cell's stored points, cells in linear order; store_off [n_cells + 1] their offsets), key2 / order2 = the admitted
- *   candidates (Cell.fill :2562-2568) grouped by cell.  counts = cand [n_cells+1] | a_off [n_cells+2] | adm [n_cells+1] | adm_off [n_cells+2].
+ *   candidates (Cell.fill :2562-2568) grouped by cell.  counts [4 n_cells + 7] = cand [n_cells+1] | a_off [n_cells+2] | adm [n_cells+1] |
+ *   adm_off [n_cells+2] | n_ambiguous [1]: the number of offered in-box points that a cell OTHER than their floor cell strictly contains
+ *   (written by every call, 0 = none).  Upstream offers every in-box point to every englobing cell; for such a point the floor rule and
+ *   upstream's may part, and the caller fills upstream's way instead (Scene.fill_cells).
  * mcr_scene_fill_gather: new store row r = row g[r] of the virtual table [old store (n_store rows) | admitted candidates in cell order]
  *   (the host builds g from the cells' torch.randperm draws, :2573); features ride along (F floats per row; NULL = none).
  *

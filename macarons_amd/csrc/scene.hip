@@ -52,6 +52,11 @@ using namespace mcr;
 //   d = pts - x_min;  idx = min((d - remainder(d, step)) / step, grid - 1) truncated to an integer, clamped at 0   (utils.floor_divide)
 //   key = linear cell id if the point lies in the scene box (closed), strictly inside ITS cell's box (Cell.fill :2552-2557) and is
 //   offered (valid), else n_cells.   box_test = 0: the cell id alone (:1434 uses the lookup without the tests).
+// Upstream offers every in-box point to EVERY englobing cell, so the two rules part where `p - x_min` rounds across a face (the floor
+// rule names the neighbour, whose strict test then fails) or where the rounded boxes of two neighbours overlap.  ambig_flag[i] = 1
+// for an offered in-box point that a cell OTHER than its floor cell strictly contains, else 0 (NULL: not wanted).  The cells' bounds
+// depend on one index per axis, so a box test factorises: along each axis the members i-1, i, i+1 are tried with the rows of the
+// cell shifted along that axis only.  ambig_count (one counter, NULL: none) is zeroed here and summed by a LATER kernel of the stream.
 __device__ __forceinline__ float torch_remainder(float a, float b) {       // torch.remainder on floats: fmod, then the divisor's sign
     float m = fmodf(a, b);
     if (m != 0.f && ((b < 0.f) != (m < 0.f))) m = __fadd_rn(m, b);
@@ -59,8 +64,10 @@ __device__ __forceinline__ float torch_remainder(float a, float b) {       // to
 }
 __global__ void cell_keys_kernel(const float* __restrict__ pts, long long N, const unsigned char* __restrict__ valid,
                                  const float* __restrict__ gc, int gl, int gw, int gh, const float* __restrict__ lo_tab,
-                                 const float* __restrict__ hi_tab, int box_test, int* __restrict__ key) {
+                                 const float* __restrict__ hi_tab, int box_test, int* __restrict__ key,
+                                 int* __restrict__ ambig_flag, long long* __restrict__ ambig_count) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i == 0 && ambig_count) *ambig_count = 0;
     if (i >= N) return;
     const int g[3] = {gl, gw, gh};
     float p[3];
@@ -85,6 +92,25 @@ __global__ void cell_keys_kernel(const float* __restrict__ pts, long long N, con
         for (int a = 0; a < 3; ++a)
             ok = ok && (__fsub_rn(p[a], hi_tab[cid * 3 + a]) < 0.f) && (__fsub_rn(p[a], lo_tab[cid * 3 + a]) > 0.f);
         key[i] = ok ? cid : n_cells;
+        if (ambig_flag) {
+            const int stride[3] = {gw * gh, gh, 1};
+            bool any_all = in_scene && (!valid || valid[i]), other = false;
+#pragma unroll
+            for (int a = 0; a < 3; ++a) {
+                bool any = false;
+#pragma unroll
+                for (int s = -1; s <= 1; ++s) {
+                    const int j = idx[a] + s;
+                    if (j < 0 || j >= g[a]) continue;
+                    const int c = cid + s * stride[a];
+                    const bool in = (__fsub_rn(p[a], hi_tab[c * 3 + a]) < 0.f) && (__fsub_rn(p[a], lo_tab[c * 3 + a]) > 0.f);
+                    any = any || in;
+                    other = other || (in && s != 0);
+                }
+                any_all = any_all && any;
+            }
+            ambig_flag[i] = (any_all && other) ? 1 : 0;
+        }
     } else {
         key[i] = cid;
     }
@@ -303,8 +329,11 @@ static int group_by_key(hipStream_t s, const int* key, long long N, int nk, int*
 // admission read them through `order`.
 __global__ void admit_sorted_kernel(const double* __restrict__ d, const int* __restrict__ key, const int* __restrict__ order,
                                     const long long* __restrict__ cand, long long N, double resolution, long long n_point_min, int nk,
-                                    int* __restrict__ key2) {
+                                    int* __restrict__ key2, const int* __restrict__ ambig_flag, long long* __restrict__ ambig_count) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    // the points cell_keys_kernel flagged (any order: a count), one atomic per wave that holds some -- almost never
+    const unsigned long long flagged = __ballot(i < N && ambig_flag[i] != 0);
+    if (flagged && (threadIdx.x & 63) == 0) atomicAdd((unsigned long long*)ambig_count, (unsigned long long)__popcll(flagged));
     if (i >= N) return;
     const int k = key[order[i]];
     key2[i] = (k >= 0 && k < nk && cand[k] > n_point_min && d[i] > resolution) ? k : nk;       // Cell.fill :2562-2568 (fp64 compare)
@@ -634,7 +663,7 @@ int mcr_cell_keys(const float* pts, int64_t N, const unsigned char* valid, const
     MCR_REQUIRE(grid_l > 0 && grid_w > 0 && grid_h > 0 && (long long)grid_l * grid_w * grid_h < (1 << 30), "mcr_cell_keys: bad grid");
     MCR_REQUIRE(!box_test || (lo_tab && hi_tab), "mcr_cell_keys: the box tests need the cells' bounds");
     hipLaunchKernelGGL(cell_keys_kernel, dim3((unsigned)cdiv(N, 256)), dim3(256), 0, (hipStream_t)stream, pts, (long long)N, valid, grid_consts,
-                       grid_l, grid_w, grid_h, lo_tab, hi_tab, box_test, key);
+                       grid_l, grid_w, grid_h, lo_tab, hi_tab, box_test, key, (int*)nullptr, (long long*)nullptr);
     MCR_LAUNCH_CHECK("cell_keys_kernel");
     return 0;
 }
@@ -678,12 +707,14 @@ int mcr_scene_fill_begin(const float* pts, int64_t N, const unsigned char* valid
     MCR_REQUIRE(N > 0 && N < (1ll << 31) && grid_l > 0 && grid_w > 0 && grid_h > 0 && nk < GRP_MAXK, "mcr_scene_fill_begin: bad sizes (< 1024 cells)");
     MCR_REQUIRE(workspace && workspace_bytes >= group_ws_bytes(N, (int)nk), "mcr_scene_fill_begin: workspace too small");
     hipStream_t s = (hipStream_t)stream;
-    long long* cand = (long long*)counts;                   // cand [nk+1] | a_off [nk+2] | adm [nk+1] | adm_off [nk+2]
+    long long* cand = (long long*)counts;                   // cand [nk+1] | a_off [nk+2] | adm [nk+1] | adm_off [nk+2] | n_ambiguous [1]
     long long* a_off = cand + nk + 1;
     long long* adm = a_off + nk + 2;
     long long* adm_off = adm + nk + 1;
+    long long* n_ambig = adm_off + nk + 2;
+    int* ambig_flag = order2;                               // scratch until the last grouping writes order2: read by admit_sorted_kernel
     hipLaunchKernelGGL(cell_keys_kernel, dim3((unsigned)cdiv(N, 256)), dim3(256), 0, s, pts, (long long)N, valid, grid_consts, grid_l, grid_w,
-                       grid_h, lo_tab, hi_tab, 1, key);
+                       grid_h, lo_tab, hi_tab, 1, key, ambig_flag, n_ambig);
     MCR_LAUNCH_CHECK("cell_keys_kernel");
     if (int e = group_by_key(s, key, N, (int)nk, order, cand, a_off, (unsigned*)workspace)) return e;
     // every candidate against the store of ITS cell (fp64 nearest distance); an empty store gives +inf
@@ -691,7 +722,7 @@ int mcr_scene_fill_begin(const float* pts, int64_t N, const unsigned char* valid
                        store_pts ? store_pts : pts, (const long long*)store_off, dmin, (const int*)order);
     MCR_LAUNCH_CHECK("min_dist_seg_kernel");
     hipLaunchKernelGGL(admit_sorted_kernel, dim3((unsigned)cdiv(N, 256)), dim3(256), 0, s, dmin, key, order, (const long long*)cand,
-                       (long long)N, resolution, (long long)n_point_min, (int)nk, key2);
+                       (long long)N, resolution, (long long)n_point_min, (int)nk, key2, (const int*)ambig_flag, n_ambig);
     MCR_LAUNCH_CHECK("admit_sorted_kernel");
     return group_by_key(s, key2, N, (int)nk, order2, adm, adm_off, (unsigned*)workspace);
 }

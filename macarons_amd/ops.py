@@ -1296,7 +1296,9 @@ def group_by_key(key, nk):
 
 class PendingFill:
     """What mcr_scene_fill_begin left on the device: the candidates grouped by cell and the admitted ones among them; `counts`
-    (int64 [4 nk + 6] = cand | a_off | adm | adm_off) is what the host reads back before it draws the cells' permutations."""
+    (int64 [4 nk + 7] = cand | a_off | adm | adm_off | n_ambiguous) is what the host reads back before it draws the cells' permutations;
+    n_ambiguous > 0: some offered point lies strictly inside a cell other than its floor cell, where upstream's rule (every englobing
+    cell tests every point) and the fused one may part -- the caller fills upstream's way (Scene.fill_cells)."""
     __slots__ = ("pts", "features", "N", "nk", "key", "order", "dmin", "key2", "order2", "counts")
 
 
@@ -1312,7 +1314,7 @@ def scene_fill_begin(pts, valid, grid_consts, grid, lo_tab, hi_tab, store_pts, s
     ib = torch.empty(4 * N, dtype=torch.int32, device=dev)
     h.key, h.order, h.key2, h.order2 = ib[:N], ib[N:2 * N], ib[2 * N:3 * N], ib[3 * N:]
     h.dmin = torch.empty(N, dtype=torch.float64, device=dev)
-    h.counts = torch.empty(4 * nk + 6, dtype=torch.int64, device=dev)
+    h.counts = torch.empty(4 * nk + 7, dtype=torch.int64, device=dev)
     v = valid.to(torch.uint8).contiguous() if valid is not None else None
     L_ = lib()
     ws = _workspace(dev, max(int(L_.mcr_scene_fill_workspace_bytes(c_i64(N), c_int(nk))), 4))
@@ -1407,7 +1409,8 @@ def field_build(tables, J, n_seg, sel, proxy_points, S_all, view_states, bin_per
     n_bins = view_states.shape[1]
     with torch.cuda.device(dev):
         check(lib().mcr_field_build(c_vp(base), c_int(J), c_vp(base + 32 * J), c_int(n_seg), c_vp(base + 32 * (J + n_seg)), _p(sel.rows_order),
-                                    _p(proxy_points), _p(S_all), _p(view_states), c_int(n_bins), _p(bin_perm), _p(vh_matrix_t), c_i64(T),
+                                    _p(proxy_points), _p(S_all), _p(view_states), c_int(n_bins), _p(bin_perm) if bin_perm is not None else c_vp(0),
+                                    _p(vh_matrix_t), c_i64(T),
                                     c_i64(tot), _p(rows), _p(row_job), _p(X_world), _p(X_q), _p(vh), _p(pc_all), _stream()), "mcr_field_build")
     return rows, row_job, X_q, pc_all
 

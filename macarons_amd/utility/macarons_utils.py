@@ -250,11 +250,13 @@ def macarons_nbv_decision(params, macarons, proxy_scene, surface_scene, camera, 
     if fused:
         sel = _field_select(ps, device, True, pending=fill)
         prep = _field_prepare(params, ps, Mv_field, device, prep_ticket)   # (count-independent host work: from the worker thread)
-        nkf = 4 * fill.nk + 6
+        nkf = fill.counts.numel()
         host = torch.cat((fill.counts, sel.counts)).cpu().numpy()                                  # THE read-back of the decision's first half
         cand, adm = ps.fill_counts(host[:nkf])
         gfill = group if xch else None
-        if ps.fill_overflows(cand, adm):            # a full cell: WHICH points stay is random -> the selection has to wait for the draws
+        if ps.fill_ambiguous(host[:nkf]):           # a point strictly inside a cell other than its floor cell: upstream's rule and the fused
+            ps.fill_cells_upstream(ps.proxy_points, idx_f, 0, gfill, fov_mask)      # one may part -> upstream's way; the pass selects again
+        elif ps.fill_overflows(cand, adm):          # a full cell: WHICH points stay is random -> the selection has to wait for the draws
             ps.fill_cells_end(fill, cand, adm, 0, gfill)
         else:
             plan = {}

@@ -86,7 +86,8 @@ class Cell:
 
     def fill(self, pts, features=None, n_point_min=0, perm=None):
         """Cell.fill (:2551-2577): keep the points strictly inside the box whose fp64 distance to every stored point exceeds
-        the resolution, append, then keep a random `capacity` subset (torch.randperm on the CPU generator, or `perm`)."""
+        the resolution, append, then keep a random `capacity` subset (torch.randperm on the CPU generator, or `perm`: the permutation
+        itself, or a callable that returns it for a given length)."""
         inside = (torch.max(pts - self.x_max, dim=-1)[0] < 0.) & (torch.min(pts - self.x_min, dim=-1)[0] > 0.)
         add = pts[inside]
         if add.shape[0] <= n_point_min:                 # (the reference tests the two faces one after the other; same outcome)
@@ -97,7 +98,8 @@ class Cell:
             add = add[keep]
             fts = fts[keep] if fts is not None else None
         self.cell_pts = torch.vstack((self.cell_pts, add))
-        idx = (torch.randperm(len(self.cell_pts)) if perm is None else perm)[:self.capacity].to(self.cell_pts.device)
+        n = len(self.cell_pts)
+        idx = (torch.randperm(n) if perm is None else perm(n) if callable(perm) else perm)[:self.capacity].to(self.cell_pts.device)
         self.cell_pts = self.cell_pts[idx]
         if fts is not None:
             self.cell_features = torch.vstack((self.cell_features, fts))[idx]
@@ -263,6 +265,38 @@ class Scene:
         nk = self.grid_l * self.grid_w * self.grid_h
         return host_counts[:nk], host_counts[2 * nk + 3:3 * nk + 3]
 
+    def fill_ambiguous(self, host_counts):
+        """Number of offered points of a fill (host copy of its handle's counts) that lie strictly inside a cell OTHER than their floor
+        cell: `p - x_min` rounded across a face, or the rounded boxes of two neighbours overlap.  Upstream offers every in-box point to
+        every englobing cell, so for such a point it and the fused rule (floor cell, then that cell's box) may part: non-zero = finish
+        the fill with fill_cells_upstream instead of fill_cells_end."""
+        return int(host_counts[4 * self.grid_l * self.grid_w * self.grid_h + 6])
+
+    def fill_cells_upstream(self, pts, features=None, n_point_min=0, group=None, valid=None):
+        """Scene.fill_cells (:2727-2737) upstream's way, for the fills fill_ambiguous flags: every englobing cell of the offered in-box
+        points, in linear (= upstream's lexicographic) order, runs Cell.fill on ALL of them.  The draws and their order are upstream's by
+        construction.  `group`: rank 0's permutations reach every replica, cell by cell."""
+        from .. import dist as mdist
+        m = self.get_pts_in_bounding_box(pts)[1]
+        if valid is not None:
+            m = m & valid.bool()
+        inside = pts[m]
+        fts = features.reshape(pts.shape[0], self.feature_dim)[m] if (self.feature_dim > 0 and features is not None) else None
+        if inside.shape[0] == 0:
+            return
+        perm = None
+        if mdist.exchange_on(group):
+            rank = mdist.group_world_rank(group)[1]
+
+            def perm(n):
+                buf = (torch.randperm(n) if rank == 0 else torch.empty(n, dtype=torch.int64)).to(self.device)
+                mdist.broadcast(buf, 0, group)
+                return buf
+        cells = self._cell_table()[0]
+        self._release_store()                               # every cell owns its tensors again
+        for c in torch.unique(self.linear_cell_ids(inside)).cpu().tolist():
+            cells[c].fill(inside, fts, n_point_min, perm)
+
     def fill_overflows(self, cand, adm, n_point_min=0):
         """True when a touched cell would exceed its capacity: the subset Cell.fill keeps is then random (the draws decide WHICH points
         stay), otherwise only their order is."""
@@ -345,6 +379,8 @@ class Scene:
         cell's admission test against its own store, a second grouping compacts the admitted points, and (fill_cells_end) the host --
         after reading two integers per cell -- draws each touched cell's torch.randperm on the CPU generator in cell order (the
         reference's draws) and turns them into one gather.  A point exactly on a cell face belongs to no cell, as upstream.
+        Upstream offers every point to every englobing cell; where that can differ from the floor cell alone -- a point strictly inside
+        a cell other than its floor cell, counted by the device part -- the call is done upstream's way (fill_cells_upstream).
         `group` (a torch.distributed group whose ranks hold replicas of this scene and call together; None = a local call whatever
         process groups exist): the permutations are rank 0's, broadcast once -- every rank drawing its own would let the replicas
         diverge.
@@ -353,7 +389,10 @@ class Scene:
         if pts.shape[0] == 0:
             return
         h = self.fill_cells_begin(pts, features, n_point_min, valid)
-        cand, adm = self.fill_counts(h.counts.cpu().numpy())                                       # the one read-back
+        host = h.counts.cpu().numpy()                                                              # the one read-back
+        if self.fill_ambiguous(host):
+            return self.fill_cells_upstream(pts, features, n_point_min, group, valid)
+        cand, adm = self.fill_counts(host)
         self.fill_cells_end(h, cand, adm, n_point_min, group)
 
     def get_pt_cloud_from_cells(self, cell_indices, return_features=True):
