@@ -684,6 +684,30 @@ int mcr_macarons_gain_backward(const float* grad_gains, const float* vis, const 
                                int64_t K, int S, float* d_vis, float* d_volume /*NULL: skip*/, void* stream);
 int mcr_philox_uniform_rows(uint64_t seed, uint64_t offset, int64_t K, int S, int mapping, float* out, void* stream);
 
+/* ---- the occupancy supervision pass of the online trainer (macarons/utility/macarons_utils.py:1233-1392
+ * compute_occupancy_probability_for_supervision): selection of the supervised rows and the scatter into upstream's return value.
+ *
+ * mcr_supervision_select: prediction_mask [P] uint8 = the sampled proxy points (:1260-1278).  englobing[c] = 1 when a sampled point falls
+ *   in cell c by the floor rule (:1297, the lookup of mcr_cell_keys with box_test = 0); rows_order = for every cell in linear order the
+ *   sampled indices found in that cell's store (store_fts column 0, F floats per row, store_off [n+1]; :1325-1328), ascending, each once
+ *   per cell -- an index stored in two cells appears in both; rows_order holds rows_capacity >= n_store entries;
+ *   counts = englobing [n+1] | sel_counts [n+1] | sel_off [n+2] | n_pred [1], n = n_cells <= 1023 (entry n of the first two is 0,
+ *   sel_off[n] = sel_off[n+1] = the total); pos [P] = rank of p among the set entries of prediction_mask, -1 elsewhere.  rows_order and
+ *   sel_off are what mcr_field_build reads as rows_order and "first position in rows_order".  workspace: a bitmap of n x ceil(P/32) words
+ *   (integer atomicOr only).
+ * mcr_supervision_scatter: out[pos[rows[t]]] += occ[t] from zeros over the rows of the first J jobs (job_offsets [J+1]: job j owns rows
+ *   job_offsets[j] .. job_offsets[j+1]-1, ascending indices inside a job), summed in job order (:1371 cell after cell); out [n_out] is
+ *   written in every row that pos names.  No floating-point atomics: the bits do not depend on the number of contributions.
+ * mcr_supervision_scatter_backward: d_occ[t] = d_out[pos[rows[t]]] for t < T_scatter, 0 for T_scatter <= t < T. */
+size_t mcr_supervision_select_workspace_bytes(int64_t P, int n_cells);
+int mcr_supervision_select(const unsigned char* prediction_mask, const float* proxy_points, int64_t P, const float* grid_consts, int grid_l,
+                           int grid_w, int grid_h, const float* store_fts, int F, int64_t n_store, const int64_t* store_off, int* rows_order,
+                           int64_t rows_capacity, int64_t* counts, int* pos, void* workspace, size_t workspace_bytes, void* stream);
+int mcr_supervision_scatter(const int* rows, const float* occ, const int64_t* job_offsets, int J, const int* pos, int64_t P, float* out,
+                            int64_t n_out, void* stream);
+int mcr_supervision_scatter_backward(const int* rows, const int* pos, int64_t P, const float* d_out, int64_t n_out, int64_t T_scatter,
+                                     int64_t T, float* d_occ, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

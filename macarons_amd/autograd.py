@@ -434,3 +434,30 @@ class MacaronsGainFunction(torch.autograd.Function):
         d_vis, d_volume = ops.macarons_gain_backward(grad_gains.float().contiguous(), vis, world, inverse, n_unique, cam_world, volume,
                                                      ctx.distance_th, ctx.smooth, need_volume=ctx.needs_input_grad[5])
         return (d_vis if ctx.needs_input_grad[0] else None, None, None, None, None, d_volume, None, None)
+
+
+# ---- occupancy supervision pass: scatter into upstream's return value, HIP forward + HIP backward --------------------------------
+class SupervisionScatterFunction(torch.autograd.Function):
+    """apply(occ, rows, job_offsets, n_jobs, pos, n_out) -> [n_out,1]: forward = ops.supervision_scatter (mcr_supervision_scatter: the rows
+    of the first n_jobs jobs of occ [T,1] added in job order to zeros, the `proxy_probas[cell_X_mask] += cell_occ_probs` of
+    macarons_utils.py:1371 read at prediction_mask) without a graph; backward = ops.supervision_scatter_backward (an exact gather; the
+    rows behind the scattered jobs -- the dummy passes' -- receive zeros, so that every parameter behind occ gets a gradient tensor).
+    Differentiable once."""
+
+    @staticmethod
+    def forward(ctx, occ, rows, job_offsets, n_jobs, pos, n_out):
+        from . import ops
+        ctx.T, ctx.n_jobs = occ.shape[0], int(n_jobs)
+        ctx.T_scatter = 0 if rows is None else int(rows.numel())
+        ctx.save_for_backward(rows, pos)
+        with torch.no_grad():
+            return ops.supervision_scatter(rows, occ.detach().float().reshape(-1), job_offsets, ctx.n_jobs if ctx.T_scatter else 0, pos, int(n_out))
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        if torch.is_grad_enabled():
+            raise RuntimeError("the supervision scatter is differentiable once: its HIP backward builds no graph (create_graph is not supported)")
+        from . import ops
+        rows, pos = ctx.saved_tensors
+        d_occ = ops.supervision_scatter_backward(rows, pos, grad_out.float().contiguous(), ctx.T_scatter if ctx.n_jobs else 0, ctx.T)
+        return d_occ, None, None, None, None, None

@@ -645,6 +645,161 @@ __global__ void philox_uniform_rows_kernel(unsigned long long seed, unsigned lon
     out[gid] = v == 1.0f ? 0.0f : v;
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// Occupancy supervision pass of the online trainer (compute_occupancy_probability_for_supervision, macarons_utils.py:1233-1392): which
+// of the sampled proxy points each cell's store holds (:1325-1328), and the `proxy_probas[cell_X_mask] += cell_occ_probs` of :1371 with
+// its backward.  A proxy index may sit in several cells' stores, so the selection is a per-cell BITMAP over the proxy indices
+// (n_cells x ceil(P/32) words, set with integer atomicOr: a second store row of the same index sets the same bit); a cell's rows come
+// out in ascending index order, each once.  Integer atomics only; no result depends on the order in which threads run.
+#define SUP_THREADS 256
+
+// bitmap <- 0, englobing <- 0
+__global__ void sup_init_kernel(unsigned* __restrict__ bitmap, long long n_words, long long* __restrict__ englobing, int n_eng) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n_words) bitmap[i] = 0u;
+    if (i < n_eng) englobing[i] = 0;
+}
+
+// thread i < P: a sampled point flags its floor-rule cell (:1297; the same value from every writer);
+// thread i < n_store: a store row whose index is sampled sets its bit in its cell's bitmap
+__global__ void sup_mark_kernel(const unsigned char* __restrict__ mask, const float* __restrict__ proxy_points, long long P,
+                                const float* __restrict__ gc, int gl, int gw, int gh, const float* __restrict__ store_fts, int F,
+                                long long n_store, const long long* __restrict__ store_off, long long W, unsigned* __restrict__ bitmap,
+                                long long* __restrict__ englobing) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < P && mask[i]) englobing[cell_of_point(proxy_points + 3 * i, gc, gl, gw, gh)] = 1;
+    if (i < n_store) {
+        const long long p = (long long)store_fts[i * F];
+        if (p >= 0 && p < P && mask[p]) {
+            const int nk = gl * gw * gh;
+            const int c = upper_bound_ll(store_off, nk + 1, i) - 1;
+            if (c >= 0 && c < nk) atomicOr(&bitmap[(long long)c * W + (p >> 5)], 1u << (unsigned)(p & 31));
+        }
+    }
+}
+
+// exclusive scan of one int per thread over a block of SUP_THREADS (4 waves): shuffles inside a wave, 4 partial sums through LDS
+__device__ __forceinline__ int sup_block_exclusive(int v, int* __restrict__ s_wave, int& total) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    int inc = v;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const int n = __shfl_up(inc, o, 64);
+        if (lane >= o) inc += n;
+    }
+    __syncthreads();                                       // (s_wave may still be read from the previous round)
+    if (lane == 63) s_wave[w] = inc;
+    __syncthreads();
+    int base = 0;
+    total = 0;
+#pragma unroll
+    for (int k = 0; k < SUP_THREADS / 64; ++k) {
+        if (k < w) base += s_wave[k];
+        total += s_wave[k];
+    }
+    return base + inc - v;
+}
+
+// pos[p] = rank of p among the set entries of mask, -1 elsewhere; n_pred = their number.  ONE block: a thread counts a contiguous
+// piece, the pieces are scanned, the thread walks its piece again (P is a few 10^5 bytes).
+__global__ __launch_bounds__(SUP_THREADS) void sup_pos_kernel(const unsigned char* __restrict__ mask, long long P, int* __restrict__ pos,
+                                                               long long* __restrict__ n_pred) {
+    __shared__ int s_wave[SUP_THREADS / 64];
+    const long long piece = (P + SUP_THREADS - 1) / SUP_THREADS;
+    const long long p0 = min(P, (long long)threadIdx.x * piece), p1 = min(P, p0 + piece);
+    int n = 0;
+    for (long long p = p0; p < p1; ++p) n += mask[p] ? 1 : 0;
+    int total;
+    int r = sup_block_exclusive(n, s_wave, total);
+    for (long long p = p0; p < p1; ++p) pos[p] = mask[p] ? r++ : -1;
+    if (threadIdx.x == 0) *n_pred = total;
+}
+
+// sel_counts[c] = set bits of cell c's bitmap (block c); block nk writes the two entries behind the cells
+__global__ __launch_bounds__(SUP_THREADS) void sup_count_kernel(const unsigned* __restrict__ bitmap, long long W, int nk,
+                                                                 long long* __restrict__ sel_counts) {
+    __shared__ int s_wave[SUP_THREADS / 64];
+    const int c = blockIdx.x;
+    if (c >= nk) {
+        if (threadIdx.x == 0) sel_counts[nk] = 0;
+        return;
+    }
+    int n = 0;
+    for (long long w = threadIdx.x; w < W; w += SUP_THREADS) n += __popc(bitmap[(long long)c * W + w]);
+    int total;
+    sup_block_exclusive(n, s_wave, total);
+    if (threadIdx.x == 0) sel_counts[c] = total;
+}
+
+// block c: sel_off[c] = sum of the counts in front of it, then the cell's set bits in ascending order behind it -- per round SUP_THREADS
+// consecutive words, a scan of their popcounts, every thread writes its word's indices.  Block nk writes sel_off[nk] = sel_off[nk+1].
+__global__ __launch_bounds__(SUP_THREADS) void sup_compact_kernel(const unsigned* __restrict__ bitmap, long long W, int nk,
+                                                                   const long long* __restrict__ sel_counts, long long* __restrict__ sel_off,
+                                                                   int* __restrict__ rows_order, long long cap) {
+    __shared__ int s_wave[SUP_THREADS / 64];
+    const int c = blockIdx.x;
+    int n = 0;
+    for (int k = threadIdx.x; k < c && k < nk; k += SUP_THREADS) n += (int)sel_counts[k];
+    int first;
+    sup_block_exclusive(n, s_wave, first);
+    if (c >= nk) {
+        if (threadIdx.x == 0) sel_off[nk] = sel_off[nk + 1] = first;
+        return;
+    }
+    if (threadIdx.x == 0) sel_off[c] = first;
+    long long run = first;
+    for (long long w0 = 0; w0 < W; w0 += SUP_THREADS) {
+        const long long w = w0 + threadIdx.x;
+        unsigned bits = w < W ? bitmap[(long long)c * W + w] : 0u;
+        int total;
+        long long o = run + sup_block_exclusive(__popc(bits), s_wave, total);
+        while (bits) {
+            const int b = __ffs(bits) - 1;
+            bits &= bits - 1;
+            if (o < cap) rows_order[o] = (int)(w * 32 + b);
+            ++o;
+        }
+        run += total;
+    }
+}
+
+// out[pos[p]] = sum over the scattered jobs, IN JOB ORDER, of the occupancy of p's row in that job (:1371 cell after cell): one thread
+// per proxy point, a binary search per job (a job's rows ascend).  The sum starts from 0 like upstream's zeros_like; no atomics, so the
+// bits do not depend on how many cells hold a point.
+__global__ void sup_scatter_kernel(const int* __restrict__ rows, const float* __restrict__ occ, const long long* __restrict__ job_off, int J,
+                                   const int* __restrict__ pos, long long P, float* __restrict__ out, long long n_out) {
+    const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= P) return;
+    const long long i = pos[p];
+    if (i < 0 || i >= n_out) return;
+    float acc = 0.f;
+    for (int j = 0; j < J; ++j) {
+        long long lo = job_off[j], hi = job_off[j + 1];
+        while (lo < hi) {                                  // first t with rows[t] >= p
+            const long long mid = (lo + hi) >> 1;
+            if (rows[mid] < p) lo = mid + 1; else hi = mid;
+        }
+        if (lo < job_off[j + 1] && rows[lo] == p) acc = __fadd_rn(acc, occ[lo]);
+    }
+    out[i] = acc;
+}
+
+// d_occ[t] = d_out[pos[rows[t]]] for the T_scatter scattered rows, 0 for the rows behind them (the dummy passes')
+__global__ void sup_scatter_bwd_kernel(const int* __restrict__ rows, const int* __restrict__ pos, long long P, const float* __restrict__ d_out,
+                                       long long n_out, long long T_scatter, long long T, float* __restrict__ d_occ) {
+    const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= T) return;
+    float g = 0.f;
+    if (t < T_scatter) {
+        const long long r = rows[t];
+        const long long i = (r >= 0 && r < P) ? (long long)pos[r] : -1;
+        if (i >= 0 && i < n_out) g = d_out[i];
+    }
+    d_occ[t] = g;
+}
+
+static size_t supervision_ws_bytes(long long P, int nk) { return (size_t)nk * (size_t)((P + 31) / 32) * sizeof(unsigned); }
+
 extern "C" {
 
 int mcr_min_dist_segmented(const float* A, const int64_t* a_offsets, const float* B, const int64_t* b_offsets, int64_t n_segments,
@@ -866,6 +1021,64 @@ int mcr_philox_uniform_rows(uint64_t seed, uint64_t offset, int64_t K, int S, in
     hipLaunchKernelGGL(philox_uniform_rows_kernel, dim3((unsigned)cdiv(K * S, 256)), dim3(256), 0, (hipStream_t)stream,
                        (unsigned long long)seed, (unsigned long long)(offset / 4), (int)K, S, mapping, out);
     MCR_LAUNCH_CHECK("philox_uniform_rows_kernel");
+    return 0;
+}
+
+size_t mcr_supervision_select_workspace_bytes(int64_t P, int n_cells) { return supervision_ws_bytes(P, n_cells); }
+
+int mcr_supervision_select(const unsigned char* prediction_mask, const float* proxy_points, int64_t P, const float* grid_consts, int grid_l,
+                           int grid_w, int grid_h, const float* store_fts, int F, int64_t n_store, const int64_t* store_off, int* rows_order,
+                           int64_t rows_capacity, int64_t* counts, int* pos, void* workspace, size_t workspace_bytes, void* stream) {
+    MCR_REQUIRE(prediction_mask && proxy_points && grid_consts && store_off && rows_order && counts && pos,
+                "mcr_supervision_select: null pointer");
+    const long long nk = (long long)grid_l * grid_w * grid_h;
+    MCR_REQUIRE(P > 0 && P < (1ll << 31) && nk > 0 && nk < GRP_MAXK && F > 0 && n_store >= 0 && n_store < (1ll << 31) && rows_capacity >= 0,
+                "mcr_supervision_select: bad sizes");
+    MCR_REQUIRE(n_store == 0 || store_fts, "mcr_supervision_select: the store's features are missing");
+    MCR_REQUIRE(rows_capacity >= n_store, "mcr_supervision_select: rows_order must hold one entry per store row");
+    MCR_REQUIRE(workspace && workspace_bytes >= supervision_ws_bytes(P, (int)nk), "mcr_supervision_select: workspace too small");
+    hipStream_t s = (hipStream_t)stream;
+    const long long W = (P + 31) / 32, n_words = nk * W;
+    unsigned* bitmap = (unsigned*)workspace;
+    long long* englobing = (long long*)counts;              // englobing [nk+1] | sel_counts [nk+1] | sel_off [nk+2] | n_pred [1]
+    long long* sel_counts = englobing + nk + 1;
+    long long* sel_off = sel_counts + nk + 1;
+    long long* n_pred = sel_off + nk + 2;
+    hipLaunchKernelGGL(sup_init_kernel, dim3((unsigned)cdiv(std::max<long long>(n_words, nk + 1), 256)), dim3(256), 0, s, bitmap, n_words,
+                       englobing, (int)nk + 1);
+    MCR_LAUNCH_CHECK("sup_init_kernel");
+    hipLaunchKernelGGL(sup_mark_kernel, dim3((unsigned)cdiv(std::max<long long>(P, n_store), 256)), dim3(256), 0, s, prediction_mask,
+                       proxy_points, (long long)P, grid_consts, grid_l, grid_w, grid_h, store_fts, F, (long long)n_store,
+                       (const long long*)store_off, W, bitmap, englobing);
+    MCR_LAUNCH_CHECK("sup_mark_kernel");
+    hipLaunchKernelGGL(sup_pos_kernel, dim3(1), dim3(SUP_THREADS), 0, s, prediction_mask, (long long)P, pos, n_pred);
+    MCR_LAUNCH_CHECK("sup_pos_kernel");
+    hipLaunchKernelGGL(sup_count_kernel, dim3((unsigned)nk + 1), dim3(SUP_THREADS), 0, s, bitmap, W, (int)nk, sel_counts);
+    MCR_LAUNCH_CHECK("sup_count_kernel");
+    hipLaunchKernelGGL(sup_compact_kernel, dim3((unsigned)nk + 1), dim3(SUP_THREADS), 0, s, bitmap, W, (int)nk, sel_counts, sel_off, rows_order,
+                       (long long)rows_capacity);
+    MCR_LAUNCH_CHECK("sup_compact_kernel");
+    return 0;
+}
+
+int mcr_supervision_scatter(const int* rows, const float* occ, const int64_t* job_offsets, int J, const int* pos, int64_t P, float* out,
+                            int64_t n_out, void* stream) {
+    MCR_REQUIRE(pos && out && job_offsets && P > 0 && n_out > 0 && J >= 0, "mcr_supervision_scatter: bad arguments");
+    MCR_REQUIRE(J == 0 || (rows && occ), "mcr_supervision_scatter: null pointer");
+    hipLaunchKernelGGL(sup_scatter_kernel, dim3((unsigned)cdiv(P, 256)), dim3(256), 0, (hipStream_t)stream, rows, occ,
+                       (const long long*)job_offsets, J, pos, (long long)P, out, (long long)n_out);
+    MCR_LAUNCH_CHECK("sup_scatter_kernel");
+    return 0;
+}
+
+int mcr_supervision_scatter_backward(const int* rows, const int* pos, int64_t P, const float* d_out, int64_t n_out, int64_t T_scatter,
+                                     int64_t T, float* d_occ, void* stream) {
+    MCR_REQUIRE(pos && d_out && d_occ && P > 0 && n_out > 0 && T > 0 && T_scatter >= 0 && T_scatter <= T,
+                "mcr_supervision_scatter_backward: bad arguments");
+    MCR_REQUIRE(T_scatter == 0 || rows, "mcr_supervision_scatter_backward: null pointer");
+    hipLaunchKernelGGL(sup_scatter_bwd_kernel, dim3((unsigned)cdiv(T, 256)), dim3(256), 0, (hipStream_t)stream, rows, pos, (long long)P, d_out,
+                       (long long)n_out, (long long)T_scatter, (long long)T, d_occ);
+    MCR_LAUNCH_CHECK("sup_scatter_bwd_kernel");
     return 0;
 }
 

@@ -1438,6 +1438,65 @@ def field_finish(rows, occ, T, proxy_proba, sel, n_oof, proxy_points, X_tail, oc
                                      _stream()), "mcr_field_finish")
 
 
+class SupervisionSelection:
+    """What mcr_supervision_select left on the device; `counts` (int64 [3 nk + 5] = englobing | sel_counts | sel_off | n_pred), `pos`
+    (int32 [P]: row of every sampled point in the pass's result, -1 elsewhere), `rows_order` as FieldSelection's."""
+    __slots__ = ("P", "nk", "rows_order", "counts", "pos")
+
+
+def supervision_select(prediction_mask, proxy_points, grid_consts, grid, store_fts, n_store, store_off):
+    """Selection of the supervision pass (mcr_supervision_select): prediction_mask [P] (bool / uint8, device)."""
+    pp = _req(proxy_points, "proxy_points")
+    P, dev = pp.shape[0], pp.device
+    nk = grid[0] * grid[1] * grid[2]
+    if not (isinstance(prediction_mask, torch.Tensor) and prediction_mask.is_cuda and prediction_mask.numel() == P
+            and prediction_mask.dtype in (torch.bool, torch.uint8)):
+        raise ValueError("prediction_mask must be a bool / uint8 device tensor with one entry per proxy point")
+    m8 = prediction_mask.reshape(-1).contiguous().view(torch.uint8)
+    F = store_fts.shape[1] if (store_fts is not None and store_fts.dim() == 2) else 1
+    if n_store and (store_fts is None or store_fts.shape[0] < n_store):
+        raise ValueError("supervision_select: the store's features (the proxy indices) are missing")
+    s = SupervisionSelection()
+    s.P, s.nk = P, nk
+    ib = torch.empty(P + max(n_store, 1), dtype=torch.int32, device=dev)
+    s.pos, s.rows_order = ib[:P], ib[P:]
+    s.counts = torch.empty(3 * nk + 5, dtype=torch.int64, device=dev)
+    L_ = lib()
+    ws = _workspace(dev, max(int(L_.mcr_supervision_select_workspace_bytes(c_i64(P), c_int(nk))), 4))
+    with torch.cuda.device(dev):
+        check(L_.mcr_supervision_select(_p(m8), _p(pp), c_i64(P), _p(_req(grid_consts, "grid_consts")), c_int(grid[0]), c_int(grid[1]),
+                                        c_int(grid[2]), _p(_req(store_fts, "store_fts")) if n_store else c_vp(0), c_int(F), c_i64(n_store),
+                                        _p(_req(store_off, "store_off", torch.int64)), _p(s.rows_order), c_i64(s.rows_order.numel()),
+                                        _p(s.counts), _p(s.pos), _p(ws), c_size(ws.numel()), _stream()), "mcr_supervision_select")
+    return s
+
+
+def supervision_scatter(rows, occ, job_offsets, J, pos, n_out):
+    """out [n_out,1]: out[pos[rows[t]]] += occ[t] from zeros over the rows of the first J jobs, in job order (mcr_supervision_scatter).
+    rows int32 [>= job_offsets[J]], occ fp32 (same rows), job_offsets int64 device [>= J+1], pos int32 [P]."""
+    pos = _req(pos, "pos", torch.int32)
+    out = torch.zeros((n_out, 1), dtype=torch.float32, device=pos.device)
+    if J == 0 or n_out == 0:
+        return out
+    with torch.cuda.device(pos.device):
+        check(lib().mcr_supervision_scatter(_p(_req(rows, "rows", torch.int32)), _p(_req(occ, "occ")), _p(_req(job_offsets, "job_offsets", torch.int64)),
+                                            c_int(J), _p(pos), c_i64(pos.numel()), _p(out), c_i64(n_out), _stream()), "mcr_supervision_scatter")
+    return out
+
+
+def supervision_scatter_backward(rows, pos, d_out, T_scatter, T):
+    """d_occ [T,1] = d_out[pos[rows[t]]] for t < T_scatter, 0 behind (mcr_supervision_scatter_backward)."""
+    pos = _req(pos, "pos", torch.int32)
+    d_occ = torch.zeros((T, 1), dtype=torch.float32, device=pos.device)
+    if T == 0 or T_scatter == 0 or d_out.numel() == 0:
+        return d_occ
+    with torch.cuda.device(pos.device):
+        check(lib().mcr_supervision_scatter_backward(_p(_req(rows, "rows", torch.int32)), _p(pos), c_i64(pos.numel()), _p(_req(d_out, "d_out")),
+                                                     c_i64(d_out.numel()), c_i64(T_scatter), c_i64(T), _p(d_occ), _stream()),
+              "mcr_supervision_scatter_backward")
+    return d_occ
+
+
 def camera_boxes(sampled, n_unique, M_view, cam_world, inv_diag):
     """sampled [K,S,4], n_unique int32 [K], M_view [K,4,4], cam_world [K,3] -> (centre [K,3] of each camera's prediction box in view space,
     camera centres [K,3] in the normalised prediction space)   (mcr_camera_boxes)."""

@@ -21,7 +21,8 @@ What is swapped:
     move_view_state_to_view_space, compute_view_harmonics, compute_occupancy_probability, filter_proxy_points,
     sample_proxy_points), utils.get_knn_points, and in macarons.utility.macarons_utils the per-call occupancy chunker and the three
     distance factors -- same names, same positional arguments, same defaults (tests/test_patch_reference.py checks the signatures);
-    helpers="all" adds compute_scene_occupancy_probability_field (one batched pass over the grid cells instead of a Python loop).
+    helpers="all" adds compute_scene_occupancy_probability_field (one batched pass over the grid cells instead of a Python loop) and
+    compute_occupancy_probability_for_supervision (the trainer's occupancy supervision: one batched pass with one HIP backward).
 
 Everything else (trainers, testers, data loading, depth network, weight init walkers, checkpoint loaders) is upstream's code running
 unchanged over these classes: the weight-init walk (scone_utils.py:399-428) finds the same `nn.Linear` children by the same names, and
@@ -45,7 +46,8 @@ _HELPERS = {
                                 "get_distance_factor_smooth")),
 }
 _HELPERS_ALL = {
-    "utility.macarons_utils": ("macarons_amd.utility.macarons_utils", ("compute_scene_occupancy_probability_field",)),
+    "utility.macarons_utils": ("macarons_amd.utility.macarons_utils", ("compute_scene_occupancy_probability_field",
+                                                                        "compute_occupancy_probability_for_supervision")),
 }
 
 _STATE = {}          # package -> report of the last patch (idempotence, `unpatch_reference`)
@@ -73,7 +75,8 @@ def patch_reference(package="macarons", helpers=True, import_consumers=True):
     """Install the MI355X networks under `<package>.networks.*` and rebind the names the reference already imported.
 
     package           top-level name of the reference package (importable: on sys.path or installed)
-    helpers           True: also swap the helper functions listed in the module docstring; "all": + the batched occupancy field;
+    helpers           True: also swap the helper functions listed in the module docstring; "all": + the batched occupancy field and
+                      the batched occupancy supervision pass;
                       False: networks only
     import_consumers  import `<package>.utility.scone_utils` and `<package>.networks.Macarons` now (they need PyTorch3D like the
                       rest of the reference) so that their names are bound to the HIP classes when this returns; False leaves that

@@ -874,3 +874,170 @@ def compute_occupancy_probability(macarons, pc, X, view_harmonics, mask=None, ma
         preds.append(macarons(mode='occupancy', partial_point_cloud=pc, proxy_points=X[:, low:up].contiguous(),
                               view_harmonics=view_harmonics[:, low:up].contiguous()).view(n_clouds, up - low, -1))
     return torch.cat(preds, dim=1)
+
+
+# ---- occupancy supervision of the online trainer: the occupancy half of scone_loss as ONE batched, differentiable pass -----------
+def compute_occupancy_probability_for_supervision(params, macarons, camera, proxy_scene, proxy_mask, surface_scene,
+                                                  n_cell_per_occ_forward_pass, device, prediction_camera=None, default_value=0.,
+                                                  min_length=100, differentiable=True, record=None, chunk=20000):
+    """Occupancy probabilities of a random sample of the proxy points in `proxy_mask`, for the trainer's loss
+    (macarons_utils.py:1233-1392; called at train_macarons.py:423 and :672), as ONE batched pass with ONE graph.
+
+    Upstream samples params.n_proxy_point_for_occupancy_supervision indices of the mask (:1260), lists the cells those points fall in
+    (:1297), visits the cells in a random order (:1308) until n_cell_per_occ_forward_pass of them have been evaluated -- per cell one
+    network call on the 27-neighbourhood's surface points and the sampled points registered in the cell's store (:1320-1370), added into
+    a zero table (:1371) -- and pads with dummy passes on the first 4k+1 / k+1 raw proxy points, multiplied by 0, so that a DDP model
+    sees every parameter used (:1376-1388).  Here: one call selects the sampled rows of every cell (ops.supervision_select), the host
+    reads one count table back, draws the visiting order and lists the (cell, chunk) jobs IN VISITING ORDER, ops.field_build makes every
+    job's cloud, queries and view harmonics in its prediction space, the dummy passes become the last jobs of the same
+    SconeOcc.forward_ragged call (zero harmonics, raw points), and autograd.SupervisionScatterFunction adds the real jobs' rows, in job
+    order, into upstream's return value.  Returns (prediction_mask [P] bool, probas [n_pred,1]); when no cell ran, prediction_mask is the
+    first k+1 points and probas exact zeros (:1384-1387).  proxy_scene.proxy_proba is not touched.
+    CPU-generator draws, in upstream's order: the sampling permutation, the cell permutation, the network's hidden draws job by job
+    (a cell's chunks one after the other), the dummy passes' draws -- the generator ends where upstream's ends.
+    Host synchronisations: TWO -- the number of set entries of proxy_mask (the first draw's size), the selection's count table (the second
+    draw's size and the job list).  A prediction camera held on the device adds the read-back of its matrix, as in the field pass.
+    Gradients: with differentiable=True, gradients enabled and a parameter requiring one, probas carries a graph of two nodes --
+    autograd.SconeOccRaggedFunction over all jobs (HIP backward, weight gradients summed over the jobs) and
+    autograd.SupervisionScatterFunction; the dummy jobs' rows receive zero gradients, so every parameter gets a gradient tensor on every
+    call.  Under no_grad or with differentiable=False no graph is built; the values are the same bits.
+    `macarons`: the SCONE part or its occupancy module (needs forward_ragged); the scenes: macarons_amd.utility.scene.Scene or objects
+    with the reference Scene's attributes; `prediction_camera`: a PyTorch3D-like camera or the [4,4] world->view matrix.  `record` (dict)
+    receives what repeats the pass: `sample_perm`, `cell_perm`, `candidates`, `visited` (linear ids of the cells that ran, in order),
+    `job_cell`, `job_q`, `job_m`, `n_dummy`, `rows`, `row_job`, the job tensors `pc` / `x` / `view_harmonics`, `occ` (the network's
+    rows) and `last_ragged_perms`.  default_value and min_length are upstream's unused parameters."""
+    ps, ss = proxy_scene, surface_scene
+    occ_net = getattr(macarons, "occupancy", macarons)
+    if not hasattr(occ_net, "forward_ragged_begin"):
+        raise NotImplementedError("compute_occupancy_probability_for_supervision needs SconeOcc.forward_ragged (the batched HIP pass)")
+    if prediction_camera is None:
+        if camera is None:
+            raise NameError("Both camera and prediction_camera are equal to None.")
+        prediction_camera = camera.fov_camera_0
+    gl, gw, gh = ps.grid_l, ps.grid_w, ps.grid_h
+    n_cells = gl * gw * gh
+    if n_cells > 1023:
+        raise NotImplementedError(f"the fused supervision pass handles grids of up to 1023 cells, this one has {n_cells}")
+    nh, k = params.n_harmonics, params.k_for_knn
+    P = ps.proxy_points.shape[0]
+    cap = n_cell_per_occ_forward_pass
+    n_pass_max = max(0, int(np.ceil(cap)))                  # `while n_forward_pass < cap` from 0 in steps of 1
+    # ---- 1. sampling (:1259-1278): THE FIRST READ-BACK is the size of the mask (torch.nonzero)
+    idx = torch.nonzero(torch.as_tensor(proxy_mask, device=device).reshape(-1)).reshape(-1)
+    sample_perm = torch.randperm(idx.shape[0])[:params.n_proxy_point_for_occupancy_supervision]
+    pred8 = torch.zeros(P, dtype=torch.uint8, device=device)
+    if sample_perm.numel():                                 # (index_fill_: a scalar fill -- `pred8[...] = 1` uploads the 1 and waits for it)
+        pred8.index_fill_(0, idx.index_select(0, ops.h2d(sample_perm, torch.int64, device)), 1)
+    # ---- 2. selection: the sampled rows of every cell's store + the cells the sampled points fall in; THE SECOND READ-BACK
+    st = _store_of(ps, device)
+    if st.fts is None:
+        raise ValueError("the proxy scene's cells must carry the proxy indices as feature (feature_dim >= 1)")
+    gc, grid = _grid_consts(ps, device)
+    sel = ops.supervision_select(pred8, ps.proxy_points, gc, grid, st.fts, int(st.off[-1]), st.off_dev)
+    prep = _field_prepare(params, ps, prediction_camera, device)
+    hostc = sel.counts.cpu().numpy()
+    englobing, counts = hostc[:n_cells], hostc[n_cells + 1:2 * n_cells + 1]
+    sel_off, n_pred = hostc[2 * n_cells + 2:3 * n_cells + 4], int(hostc[3 * n_cells + 4])
+    cand = np.nonzero(englobing)[0]                          # linear order = torch.unique(dim=0)'s lexicographic order (:1297)
+    cell_perm = torch.randperm(len(cand))                   # :1308
+    # ---- 3. the walk (:1310-1373): sizes are host numbers
+    tab = prep["tab"]
+    keys, lin_of = tab["keys"], tab["lin_of"]
+    s_st = _store_of(ss, device)
+    s_keys = keys if set(ss.cells.keys()) == set(keys) else sorted(ss.cells.keys(), key=lambda k_: lin_of.get(k_, 0))
+    if len(s_keys) == n_cells:
+        s_len, s_start = np.diff(s_st.off), s_st.off[:-1]
+    else:                                                   # a surface scene on another grid: by key
+        s_len = np.zeros(n_cells, np.int64); s_start = np.zeros(n_cells, np.int64)
+        for i_, k_ in enumerate(s_keys):
+            s_len[lin_of[k_]] = s_st.off[i_ + 1] - s_st.off[i_]; s_start[lin_of[k_]] = s_st.off[i_]
+    nbm = tab["neighbour_matrix"]
+    nb_len = np.where(nbm >= 0, s_len[np.maximum(nbm, 0)], 0)
+    m_cell = nb_len.sum(1)
+    visited = []
+    for c in cand[cell_perm.numpy()]:
+        if len(visited) >= cap:
+            break
+        if m_cell[c] > 2 * 2 * k and counts[c] > 0:          # :1341
+            visited.append(int(c))
+    n_dummy = max(0, n_pass_max - len(visited))              # :1376
+    cells_run = np.asarray(visited, np.int64)
+    n_chunks = -(-counts[cells_run] // chunk) if len(visited) else np.zeros(0, np.int64)
+    job_cell = np.repeat(cells_run, n_chunks)                # one job per (cell, chunk of <= `chunk` queries): a cell is ONE pass
+    J = int(job_cell.size)
+    T = tot = 0
+    rows = row_job = X_q = pc_all = vh = None
+    if J:
+        lo = (np.arange(J) - np.repeat(np.cumsum(n_chunks) - n_chunks, n_chunks)) * chunk
+        job_q = np.minimum(chunk, counts[job_cell] - lo).astype(np.int64)
+        job_m = m_cell[job_cell].astype(np.int64)
+        q_start = np.concatenate(([0], np.cumsum(job_q)))
+        m_start = np.concatenate(([0], np.cumsum(job_m)))
+        T, tot = int(q_start[-1]), int(m_start[-1])
+        jt = np.stack((sel_off[job_cell] + lo, q_start[:-1], m_start[:-1], np.zeros(J, np.int64)), 1).astype(np.int64)
+        seg_len = nb_len[job_cell]                            # surface segments: the cell's non-empty neighbours, ascending cell order
+        keep = seg_len > 0
+        seg_l = seg_len[keep]
+        st_ = np.stack((s_start[nbm[job_cell][keep]], np.cumsum(seg_l) - seg_l, np.nonzero(keep)[0], np.zeros(seg_l.size, np.int64)),
+                       1).astype(np.int64)
+        n_seg = int(st_.shape[0])
+        xf = np.ascontiguousarray(prep["xf_all"][job_cell])
+        # ONE upload: job table | segment table | per-job transform | bin permutation | the jobs' first query rows (for the scatter)
+        raw = np.concatenate((jt.reshape(-1).view(np.uint8), st_.reshape(-1).view(np.uint8), xf.reshape(-1).view(np.uint8),
+                              prep["perm"].astype(np.int32).view(np.uint8)))
+        pad = (-raw.size) % 8
+        raw = np.concatenate((raw, np.zeros(pad, np.uint8), q_start.astype(np.int64).view(np.uint8)))
+        tables = ops.h2d(raw, torch.uint8, device)
+        n_perm = prep["perm"].size
+        o_perm = 32 * (J + n_seg) + 80 * J
+        perm_d = tables[o_perm:o_perm + 4 * n_perm].view(torch.int32)
+        job_off_d = tables[o_perm + 4 * n_perm + pad:].view(torch.int64)
+        X_world = torch.empty((T, 3), dtype=torch.float32, device=device)
+        vh = torch.empty((T + n_dummy * (k + 1), nh), dtype=torch.float32, device=device)
+        rows, row_job, X_q, pc_all = ops.field_build(tables, J, n_seg, sel, ps.proxy_points, s_st.pts, ps.view_states, perm_d,
+                                                     prep["vh_mt"], T, tot, X_world, vh)
+        sizes_m, sizes_q = job_m.tolist(), job_q.tolist()
+    else:
+        job_q = job_m = np.zeros(0, np.int64)
+        sizes_m, sizes_q = [], []
+        job_off_d = None
+        vh = torch.empty((n_dummy * (k + 1), nh), dtype=torch.float32, device=device)
+    # ---- 4. the dummy passes (:1376-1388) as the LAST jobs: raw proxy points, zero harmonics; their rows are never scattered
+    T_all = T + n_dummy * (k + 1)
+    if n_dummy:
+        d_pc, d_x = ps.proxy_points[:2 * 2 * k + 1], ps.proxy_points[:k + 1]
+        vh[T:].zero_()
+        pc_all = torch.cat(([pc_all] if J else []) + [d_pc] * n_dummy)
+        X_q = torch.cat(([X_q] if J else []) + [d_x] * n_dummy)
+        d_job = torch.arange(J, J + n_dummy, dtype=torch.int32, device=device).repeat_interleave(d_x.shape[0])
+        row_job_all = torch.cat((row_job, d_job)) if J else d_job
+        sizes_m = sizes_m + [int(d_pc.shape[0])] * n_dummy
+        sizes_q = sizes_q + [int(d_x.shape[0])] * n_dummy
+    else:
+        row_job_all = row_job
+    if J + n_dummy == 0:                                    # a cap of 0: nothing runs, upstream returns the sampled points' zeros
+        if record is not None:
+            record.update(sample_perm=sample_perm, cell_perm=cell_perm, candidates=cand, visited=visited, n_dummy=0)
+        return pred8.bool(), torch.zeros((n_pred, 1), dtype=torch.float32, device=device)
+    # ---- 5. ONE network pass over all jobs; phase 1 is queued before the hidden draws are made (job by job, the dummies' last)
+    h = occ_net.forward_ragged_begin(pc_all, sizes_m, X_q, vh, sizes_q, row_job=row_job_all)
+    occ = occ_net.forward_ragged_finish(h, differentiable=differentiable)          # [T_all,1]: no node between the network's and the scatter's
+    if occ.shape != (T_all, 1):
+        raise RuntimeError(f"forward_ragged returned {tuple(occ.shape)} for {T_all} query rows")
+    # ---- 6. the scatter (:1371 read at :1392)
+    if J:
+        prediction_mask, pos, n_out = pred8.bool(), sel.pos, n_pred
+    else:                                                   # no pass ran (:1384-1387): the first k+1 points, exact zeros
+        prediction_mask = torch.zeros(P, dtype=torch.bool, device=device)
+        prediction_mask[:k + 1] = True
+        pos, n_out = sel.pos, min(k + 1, P)
+    if occ.requires_grad:
+        probas = A.SupervisionScatterFunction.apply(occ, rows, job_off_d, J, pos, n_out)
+    else:
+        probas = ops.supervision_scatter(rows, occ.reshape(-1), job_off_d, J, pos, n_out)
+    if record is not None:
+        record.update(sample_perm=sample_perm, cell_perm=cell_perm, candidates=cand, visited=visited, job_cell=job_cell, job_q=job_q,
+                      job_m=job_m, n_dummy=n_dummy, rows=rows, row_job=row_job_all, pc=pc_all, x=X_q, view_harmonics=vh,
+                      cloud_sizes=sizes_m, query_sizes=sizes_q, occ=occ.detach(), pos=pos, job_offsets=job_off_d,
+                      last_ragged_perms=occ_net.last_ragged_perms)
+    return prediction_mask, probas
