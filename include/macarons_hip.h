@@ -576,6 +576,21 @@ int mcr_proxy_scene_update(const float* proxy_points, int64_t P, const unsigned 
                            const unsigned char* depth_mask, int H, int W, float fill, const float* X_cam, float distance_to_surface,
                            float tol, float score_threshold, int n_elev, int n_azim, float* view_states, float* n_inside,
                            float* n_behind, float* supervision_occ, float* out_of_field, float* sgn, void* stream);
+/* The online trainer's K-frame passes over the proxy points (trainers/train_macarons.py:386-415 = :616-661, and :476-487 = :719-730);
+ * 1 <= K <= 32 frames, refused otherwise before anything else is looked at.  One thread per proxy point, no atomics.
+ * mcr_supervision_frames: cameras [K,40] (mcr_points_in_fov records), depth [K,H,W], depth_mask [K,H,W] bytes or NULL, fill = K HOST
+ *   floats (1.1 zfar per frame) -> fov_bits [P] uint32 (bit k = mcr_points_in_fov of camera k), sgn [K,P] (mcr_signed_distance_to_depth
+ *   of frame k where bit k is set, 0 elsewhere), close_mask [P] bytes: `close[fov_mask_k] = |sgn_k| < surface_distance` frame after
+ *   frame (:415), i.e. the test of the LAST frame whose frustum holds the point, 0 for a point in no frustum.
+ * mcr_proxy_scene_update_frames: what K successive mcr_proxy_scene_update calls leave in the five state tensors, from fov_bits and sgn
+ *   (the depth maps are not sampled again); X_cam [K,3] device floats. */
+int mcr_supervision_frames(const float* proxy_points, int64_t P, const float* cameras, int K, const float* depth,
+                           const unsigned char* depth_mask, int H, int W, const float* fill, float surface_distance, uint32_t* fov_bits,
+                           float* sgn, unsigned char* close_mask, void* stream);
+int mcr_proxy_scene_update_frames(const float* proxy_points, int64_t P, const uint32_t* fov_bits, const float* sgn, int K,
+                                  const float* X_cam, float distance_to_surface, float tol, float score_threshold, int n_elev,
+                                  int n_azim, float* view_states, float* n_inside, float* n_behind, float* supervision_occ,
+                                  float* out_of_field, void* stream);
 int mcr_min_dist_segmented(const float* A, const int64_t* a_offsets, const float* B, const int64_t* b_offsets, int64_t n_segments,
                            int64_t max_a_per_segment, double* dmin, void* stream);
 int mcr_unproject_depth(const float* depth, int H, int W, const float* cameras, int64_t n_cam, float* world, void* stream);

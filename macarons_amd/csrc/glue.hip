@@ -317,15 +317,8 @@ __global__ __launch_bounds__(1024) void smp_gather(const long long* __restrict__
 // K2: frustum + range mask.  Row-vector convention of the reference's camera transforms:
 //   p_view = [x y z 1] * M_view (4x4 row-major),   p_ndc = ([x y z 1] * M_proj)[:3] / w
 // mask = ndc_x in [min_x,max_x] & ndc_y in [min_y,max_y] & z_view > 0 [& |p - c| < range]   (macarons_utils.py:2420-2430)
-__global__ void fov_kernel(const float* __restrict__ pts, long long P, const float* __restrict__ cam, int n_cam,
-                           unsigned char* __restrict__ mask) {
-    // cam record (40 floats): M_view[16], M_proj[16], ndc bounds {min_x,max_x,min_y,max_y}, center[3], range (<=0: none)
-    const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (gid >= P * n_cam) return;
-    const int c = (int)(gid / P);
-    const long long p = gid - (long long)c * P;
-    const float* K = cam + c * 40;
-    const float x = pts[3 * p], y = pts[3 * p + 1], z = pts[3 * p + 2];
+// cam record K (40 floats): M_view[16], M_proj[16], ndc bounds {min_x,max_x,min_y,max_y}, center[3], range (<=0: none)
+__device__ __forceinline__ bool point_in_fov(const float* __restrict__ K, float x, float y, float z) {
     const float zv = ((x * K[2] + y * K[6]) + z * K[10]) + K[14];
     const float* Mp = K + 16;
     const float px = ((x * Mp[0] + y * Mp[4]) + z * Mp[8]) + Mp[12];
@@ -337,7 +330,15 @@ __global__ void fov_kernel(const float* __restrict__ pts, long long P, const flo
         const float dx = x - K[36], dy = y - K[37], dz = z - K[38];
         m = m && sqrtf((dx * dx + dy * dy) + dz * dz) < K[39];
     }
-    mask[gid] = m ? 1 : 0;
+    return m;
+}
+__global__ void fov_kernel(const float* __restrict__ pts, long long P, const float* __restrict__ cam, int n_cam,
+                           unsigned char* __restrict__ mask) {
+    const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (gid >= P * n_cam) return;
+    const int c = (int)(gid / P);
+    const long long p = gid - (long long)c * P;
+    mask[gid] = point_in_fov(cam + c * 40, pts[3 * p], pts[3 * p + 1], pts[3 * p + 2]) ? 1 : 0;
 }
 
 
@@ -402,6 +403,74 @@ __global__ void proxy_update_kernel(const float* __restrict__ pts, long long P, 
     if (d < distance_to_surface)
         view_states[p * (long long)(n_elev * n_azim) + view_state_bin(X_cam[0] - x, X_cam[1] - y, X_cam[2] - z, n_elev, n_azim)] = 1.0f;
     const float ni = n_inside[p] + 1.f, nbh = n_behind[p] + (d >= -tol ? 1.f : 0.f);
+    n_inside[p] = ni;
+    n_behind[p] = nbh;
+    sup_occ[p] = (nbh / ni >= score_threshold) ? 1.f : 0.f;
+    out_of_field[p] = 0.f;
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// The online trainer's K-frame passes over the proxy points (train_macarons.py:386-415 / :616-661 and :476-487 / :719-730).  The
+// trainer needs the signed distances of ALL K new depth frames before it predicts and applies the state updates after, so the
+// single-frame pass above cannot serve it.  One thread per proxy point, the frames in a loop: a point's rows belong to one thread,
+// so there are no atomics and no LDS; the frame index is wave-uniform, so the camera records, fills and camera centres are
+// scalar loads.  The sgn stores are coalesced along P; the depth gathers and view-state writes are scattered by nature.
+struct FrameFills { float v[32]; };           // per-frame fill (1.1 zfar), by value: kernel arguments, no upload
+
+// fov_bits[p]: bit k = point_in_fov(cams[k]) (Camera.get_points_in_fov :392 / :648); sgn[k, p] = signed_distance to frame k where
+// the bit is set, 0 elsewhere (:399 / :655); close[p] follows the overwrite rule of :415 / :661,
+// `close[fov_mask_k] = |sgn_k| < surface_distance` frame after frame: the LAST frame whose frustum holds the point decides.
+__global__ __launch_bounds__(256) void supervision_frames_kernel(const float* __restrict__ pts, long long P, const float* __restrict__ cams,
+                                                                int K, const float* __restrict__ depth,
+                                                                const unsigned char* __restrict__ dmask, int H, int W, FrameFills fill,
+                                                                float surface_distance, unsigned* __restrict__ fov_bits,
+                                                                float* __restrict__ sgn, unsigned char* __restrict__ close) {
+    const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= P) return;
+    const float x = pts[3 * p], y = pts[3 * p + 1], z = pts[3 * p + 2];
+    const long long hw = (long long)H * W;
+    unsigned bits = 0u;
+    unsigned char cl = 0;
+    for (int k = 0; k < K; ++k) {
+        const float* cam = cams + 40 * k;
+        float d = 0.f;
+        if (point_in_fov(cam, x, y, z)) {
+            d = signed_distance(cam, depth + k * hw, dmask ? dmask + k * hw : nullptr, H, W, fill.v[k], x, y, z);
+            bits |= 1u << k;
+            cl = fabsf(d) < surface_distance ? 1 : 0;
+        }
+        sgn[(long long)k * P + p] = d;
+    }
+    fov_bits[p] = bits;
+    close[p] = cl;
+}
+
+// K successive proxy_update_kernel passes from the recorded bits and distances (the depth maps are not sampled again): per point,
+// over the frames in order, where bit k is set -- the bin towards X_cam[k] is OR'ed in if sgn_k < distance_to_surface (:2817-2877),
+// n_inside += 1, n_behind += (sgn_k >= -tol) (:2908-2912); the supervision occupancy is the last frame's quotient test (every
+// frame overwrites it); out_of_field = 0 where any bit is set (:2879-2886).  The counters add up in fp32 in frame order, as K calls do.
+__global__ __launch_bounds__(256) void proxy_update_frames_kernel(const float* __restrict__ pts, long long P,
+                                                                 const unsigned* __restrict__ fov_bits, const float* __restrict__ sgn,
+                                                                 int K, const float* __restrict__ X_cam, float distance_to_surface,
+                                                                 float tol, float score_threshold, int n_elev, int n_azim,
+                                                                 float* __restrict__ view_states, float* __restrict__ n_inside,
+                                                                 float* __restrict__ n_behind, float* __restrict__ sup_occ,
+                                                                 float* __restrict__ out_of_field) {
+    const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= P) return;
+    const unsigned bits = fov_bits[p];
+    if (!bits) return;
+    const float x = pts[3 * p], y = pts[3 * p + 1], z = pts[3 * p + 2];
+    const long long n_bins = (long long)n_elev * n_azim;
+    float ni = n_inside[p], nbh = n_behind[p];
+    for (int k = 0; k < K; ++k) {
+        if (!((bits >> k) & 1u)) continue;
+        const float d = sgn[(long long)k * P + p];
+        if (d < distance_to_surface)
+            view_states[p * n_bins + view_state_bin(X_cam[3 * k] - x, X_cam[3 * k + 1] - y, X_cam[3 * k + 2] - z, n_elev, n_azim)] = 1.0f;
+        ni = ni + 1.f;
+        nbh = nbh + (d >= -tol ? 1.f : 0.f);
+    }
     n_inside[p] = ni;
     n_behind[p] = nbh;
     sup_occ[p] = (nbh / ni >= score_threshold) ? 1.f : 0.f;
@@ -801,6 +870,35 @@ int mcr_proxy_scene_update(const float* proxy_points, int64_t P, const unsigned 
                        fov_mask, camera, depth, depth_mask, H, W, fill, X_cam, distance_to_surface, tol,
                        score_threshold, n_elev, n_azim, view_states, n_inside, n_behind, supervision_occ, out_of_field, sgn);
     MCR_LAUNCH_CHECK("proxy_update_kernel");
+    return 0;
+}
+
+int mcr_supervision_frames(const float* proxy_points, int64_t P, const float* cameras, int K, const float* depth,
+                           const unsigned char* depth_mask, int H, int W, const float* fill, float surface_distance, uint32_t* fov_bits,
+                           float* sgn, unsigned char* close_mask, void* stream) {
+    MCR_REQUIRE(K >= 1 && K <= 32, "mcr_supervision_frames: between 1 and 32 frames (one bit of fov_bits each)");
+    MCR_REQUIRE(proxy_points && cameras && depth && fill && fov_bits && sgn && close_mask, "mcr_supervision_frames: null pointer");
+    MCR_REQUIRE(P > 0 && H > 0 && W > 0, "mcr_supervision_frames: bad sizes");
+    FrameFills f;
+    for (int k = 0; k < 32; ++k) f.v[k] = k < K ? fill[k] : 0.f;          // fill: K HOST floats
+    hipLaunchKernelGGL(supervision_frames_kernel, dim3((unsigned)cdiv(P, 256)), dim3(256), 0, (hipStream_t)stream, proxy_points,
+                       (long long)P, cameras, K, depth, depth_mask, H, W, f, surface_distance, fov_bits, sgn, close_mask);
+    MCR_LAUNCH_CHECK("supervision_frames_kernel");
+    return 0;
+}
+
+int mcr_proxy_scene_update_frames(const float* proxy_points, int64_t P, const uint32_t* fov_bits, const float* sgn, int K,
+                                  const float* X_cam, float distance_to_surface, float tol, float score_threshold, int n_elev,
+                                  int n_azim, float* view_states, float* n_inside, float* n_behind, float* supervision_occ,
+                                  float* out_of_field, void* stream) {
+    MCR_REQUIRE(K >= 1 && K <= 32, "mcr_proxy_scene_update_frames: between 1 and 32 frames (one bit of fov_bits each)");
+    MCR_REQUIRE(proxy_points && fov_bits && sgn && X_cam && view_states && n_inside && n_behind && supervision_occ && out_of_field,
+                "mcr_proxy_scene_update_frames: null pointer");
+    MCR_REQUIRE(P > 0 && n_elev > 0 && n_azim > 0, "mcr_proxy_scene_update_frames: bad sizes");
+    hipLaunchKernelGGL(proxy_update_frames_kernel, dim3((unsigned)cdiv(P, 256)), dim3(256), 0, (hipStream_t)stream, proxy_points,
+                       (long long)P, fov_bits, sgn, K, X_cam, distance_to_surface, tol, score_threshold, n_elev, n_azim, view_states,
+                       n_inside, n_behind, supervision_occ, out_of_field);
+    MCR_LAUNCH_CHECK("proxy_update_frames_kernel");
     return 0;
 }
 

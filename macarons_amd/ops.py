@@ -1232,6 +1232,68 @@ def proxy_scene_update_(proxy_points, fov_mask, camera, depth, depth_mask, fill,
     return sgn
 
 
+def _check_n_frames(K, what):
+    if not 1 <= K <= 32:
+        raise ValueError(f"{what}: between 1 and 32 frames (one bit of fov_bits each), got {K}")
+
+
+def supervision_frames(proxy_points, cameras, depth, depth_mask, fill, surface_distance):
+    """The supervision signal of K new depth frames over the proxy points (train_macarons.py:386-415) in one pass
+    (mcr_supervision_frames): proxy_points [P,3], cameras [K,40], depth [K,H,W], depth_mask [K,H,W] bool/uint8 or None, fill: K host
+    numbers (1.1 zfar) -> fov_bits [P] int32 (bit k = in frustum k), sgn [K,P] (0 where the bit is clear), close [P] bool (upstream's
+    overwrite rule: the last frame whose frustum holds the point decides)."""
+    K = int(cameras.shape[0])
+    _check_n_frames(K, "supervision_frames")
+    pp, cams, depth = _req(proxy_points, "proxy_points"), _req(cameras, "cameras"), _req(depth, "depth")
+    if cams.shape[1] != 40 or pp.shape[1] != 3:
+        raise ValueError("cameras must be [K,40] and proxy_points [P,3]")
+    P, H, W = pp.shape[0], depth.shape[-2], depth.shape[-1]
+    if depth.numel() != K * H * W:
+        raise ValueError(f"depth must hold K = {K} maps, got {tuple(depth.shape)}")
+    dm = None
+    if depth_mask is not None:
+        dm = depth_mask.to(torch.uint8).contiguous()
+        if dm.numel() != K * H * W:
+            raise ValueError(f"depth_mask must hold K = {K} maps, got {tuple(depth_mask.shape)}")
+    fills = (ctypes.c_float * K)(*[float(f) for f in fill])
+    bits = torch.empty(P, dtype=torch.int32, device=pp.device)
+    sgn = torch.empty((K, P), dtype=torch.float32, device=pp.device)
+    close = torch.empty(P, dtype=torch.uint8, device=pp.device)
+    if P == 0:
+        return bits, sgn, close.bool()
+    with torch.cuda.device(pp.device):
+        check(lib().mcr_supervision_frames(_p(pp), c_i64(P), _p(cams), c_int(K), _p(depth), _p(dm) if dm is not None else c_vp(0),
+                                           c_int(H), c_int(W), fills, c_f32(float(surface_distance)), _p(bits), _p(sgn), _p(close),
+                                           _stream()), "mcr_supervision_frames")
+    return bits, sgn, close.bool()
+
+
+def proxy_scene_update_frames_(proxy_points, fov_bits, sgn, X_cam, distance_to_surface, tol, score_threshold, n_elev, n_azim,
+                               view_states, n_inside, n_behind, supervision_occ, out_of_field):
+    """K successive proxy_scene_update_ calls from the bits and distances of supervision_frames, in place on the state tensors
+    (mcr_proxy_scene_update_frames; train_macarons.py:476-487).  sgn [K,P], X_cam [K,3]."""
+    K = int(sgn.shape[0])
+    _check_n_frames(K, "proxy_scene_update_frames_")
+    pp, sgn, xc = _req(proxy_points, "proxy_points"), _req(sgn, "sgn"), _req(X_cam, "X_cam")
+    bits = _req(fov_bits, "fov_bits", torch.int32)
+    P = pp.shape[0]
+    if sgn.shape[1] != P or bits.numel() != P or xc.numel() != 3 * K:
+        raise ValueError("fov_bits must be [P], sgn [K,P] and X_cam [K,3]")
+    for name, t in (("view_states", view_states), ("n_inside", n_inside), ("n_behind", n_behind), ("supervision_occ", supervision_occ),
+                    ("out_of_field", out_of_field)):
+        if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
+            raise ValueError(f"{name} must be a contiguous fp32 device tensor (updated in place)")
+    if view_states.numel() != P * n_elev * n_azim or any(t.numel() != P for t in (n_inside, n_behind, supervision_occ, out_of_field)):
+        raise ValueError("the state tensors must hold one row per proxy point")
+    if P == 0:
+        return
+    with torch.cuda.device(pp.device):
+        check(lib().mcr_proxy_scene_update_frames(_p(pp), c_i64(P), _p(bits), _p(sgn), c_int(K), _p(xc), c_f32(float(distance_to_surface)),
+                                                  c_f32(float(tol)), c_f32(float(score_threshold)), c_int(n_elev), c_int(n_azim),
+                                                  _p(view_states), _p(n_inside), _p(n_behind), _p(supervision_occ), _p(out_of_field),
+                                                  _stream()), "mcr_proxy_scene_update_frames")
+
+
 # ---- scene-grid bookkeeping, fused (Scene.fill_cells / the cell lookup of the occupancy field) -----------------------------------------
 def cell_keys(pts, grid_consts, grid, lo_tab=None, hi_tab=None, valid=None):
     """pts [N,3] -> int32 [N]: linear id of the cell each point falls in (upstream's floor rule); with the cells' bounds lo_tab / hi_tab

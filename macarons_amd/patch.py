@@ -22,7 +22,9 @@ What is swapped:
     sample_proxy_points), utils.get_knn_points, and in macarons.utility.macarons_utils the per-call occupancy chunker and the three
     distance factors -- same names, same positional arguments, same defaults (tests/test_patch_reference.py checks the signatures);
     helpers="all" adds compute_scene_occupancy_probability_field (one batched pass over the grid cells instead of a Python loop) and
-    compute_occupancy_probability_for_supervision (the trainer's occupancy supervision: one batched pass with one HIP backward).
+    compute_occupancy_probability_for_supervision (the trainer's occupancy supervision: one batched pass with one HIP backward),
+    get_occ_loss_fn / get_cov_loss_fn, and ADDS scone_supervision_step (the trainer's scone_loss of one step from K depth frames) and
+    compute_partial_point_clouds, which upstream writes inline.
 
 Everything else (trainers, testers, data loading, depth network, weight init walkers, checkpoint loaders) is upstream's code running
 unchanged over these classes: the weight-init walk (scone_utils.py:399-428) finds the same `nn.Linear` children by the same names, and
@@ -47,7 +49,12 @@ _HELPERS = {
 }
 _HELPERS_ALL = {
     "utility.macarons_utils": ("macarons_amd.utility.macarons_utils", ("compute_scene_occupancy_probability_field",
-                                                                        "compute_occupancy_probability_for_supervision")),
+                                                                        "compute_occupancy_probability_for_supervision",
+                                                                        "get_occ_loss_fn", "get_cov_loss_fn")),
+}
+# names upstream does not have (its trainer writes these bodies inline): added to the reference module by helpers="all"
+_ADDITIONS_ALL = {
+    "utility.macarons_utils": ("macarons_amd.utility.macarons_utils", ("scone_supervision_step", "compute_partial_point_clouds")),
 }
 
 _STATE = {}          # package -> report of the last patch (idempotence, `unpatch_reference`)
@@ -140,6 +147,20 @@ def patch_reference(package="macarons", helpers=True, import_consumers=True):
                 setattr(ref_mod, name, new)
                 report["helpers"].append((full, name))
 
+    if helpers == "all":
+        for rel, (new_name, names) in _ADDITIONS_ALL.items():
+            ref_mod = sys.modules.get(f"{package}.{rel}")
+            if ref_mod is None:
+                continue
+            new_mod = importlib.import_module(new_name)
+            for name in names:
+                if getattr(ref_mod, name, None) is not getattr(new_mod, name):
+                    report["originals"].setdefault(f"{package}.{rel}.{name}", getattr(ref_mod, name, None))
+                    setattr(ref_mod, name, getattr(new_mod, name))
+                else:                                          # a second call: still ours to take away again
+                    report["originals"].setdefault(f"{package}.{rel}.{name}", None)
+                report["helpers"].append((f"{package}.{rel}", name))
+
     # 4. sweep: every module of the reference package that already holds one of the replaced objects gets the replacement
     ours = {id(importlib.import_module("macarons_amd.networks." + s)) for s in _NETWORK_MODULES}
     for mod_name, mod in list(sys.modules.items()):
@@ -191,6 +212,8 @@ def unpatch_reference(package="macarons"):
         old = rep["originals"].get(f"{full}.{name}")
         if old is not None and full in sys.modules:
             setattr(sys.modules[full], name, old)
+        elif f"{full}.{name}" in rep["originals"] and full in sys.modules and hasattr(sys.modules[full], name):
+            delattr(sys.modules[full], name)                  # an addition: upstream has no such name
     mac_mod = sys.modules.get(f"{package}.networks.Macarons")
     if mac_mod is not None and hasattr(mac_mod, "Macarons"):
         orig = vars(mac_mod.Macarons).get("_mcr_original_compute_visibility_gains")

@@ -388,6 +388,46 @@ def compute_partial_point_cloud(depth, mask, camera, gathering_factor, fov_range
     return world[idx.to(world.device)]
 
 
+def _kept_rows(mask, n):
+    """Indices of the n set entries of a flat bool mask, ascending, when the host already knows n: what torch.nonzero returns without
+    the read-back of its size (the j-th set entry is where the running count first reaches j + 1)."""
+    cs = torch.cumsum(mask.reshape(-1).to(torch.int32), 0, dtype=torch.int32)
+    return torch.searchsorted(cs, torch.arange(1, n + 1, dtype=torch.int32, device=mask.device))
+
+
+def compute_partial_point_clouds(depths, masks, cameras18, gathering_factor, fov_range=None):
+    """K compute_partial_point_cloud calls (the trainer's K new frames, train_macarons.py:392 / :639) as one pass: depths [K,H,W(,1)]
+    (or K maps), masks alike, cameras18 [K,18] (depth_camera_record) -> list of K clouds.  One ops.unproject_depth launch over the
+    K frames, ONE read-back (the K keep counts), then the K torch.randperm draws on the CPU generator in frame order; the kept pixels
+    are found from the counts (no per-frame compaction), the K subsets leave in one gather.  Clouds and final generator state equal the
+    K single calls'."""
+    if not torch.is_tensor(depths):
+        depths = torch.stack([d.reshape(d.shape[-3], d.shape[-2]) if d.shape[-1] == 1 and d.dim() > 2 else d.reshape(d.shape[-2], d.shape[-1])
+                              for d in depths])
+    K = depths.shape[0]
+    H, W = (depths.shape[1], depths.shape[2])
+    dev = depths.device
+    if not torch.is_tensor(masks):
+        masks = torch.stack([m.reshape(H, W) for m in masks])
+    if not torch.is_tensor(cameras18):
+        cameras18 = torch.stack([c.reshape(18) for c in cameras18])
+    d = depths.reshape(K, H, W).contiguous().float()
+    pts = ops.unproject_depth(d, ops.h2d(cameras18.reshape(K, 18), torch.float32, dev)).view(K * H * W, 3)
+    keep = masks.reshape(K, H * W).bool()
+    if fov_range is not None:
+        keep = keep & (d.reshape(K, H * W) < fov_range)
+    counts = keep.sum(1).cpu().tolist()                                                     # THE read-back
+    kept = _kept_rows(keep, sum(counts))
+    sel, sizes, first = [], [], 0
+    for n in counts:
+        n_points = int(n * gathering_factor)
+        sel.append(torch.randperm(n)[:n_points] + first)
+        sizes.append(n_points)
+        first += n
+    world = pts.index_select(0, kept.index_select(0, ops.h2d(torch.cat(sel), torch.int64, dev)))
+    return list(torch.split(world, sizes))
+
+
 def project_depth_back_to_3D(depth, cameras):
     """utils.project_depth_back_to_3D (utils.py:1458-1487): depth [n_cam,H,W,1], cameras [n_cam,18] (depth_camera_record) ->
     world points of the pixels with depth > -1, camera-major."""
@@ -424,16 +464,17 @@ def cell_fill_mask(pts_to_add, cell_pts, resolution, a_offsets=None, b_offsets=N
     return ops.min_dist_segmented(pts_to_add, a_offsets, cell_pts, b_offsets) > resolution
 
 
-def covered_mask(surface_pts, seen_pts, epsilon, a_offsets=None, b_offsets=None, fp32_compare=False):
+def covered_mask(surface_pts, seen_pts, epsilon, a_offsets=None, b_offsets=None, fp32_compare=False, max_a=None):
     """heaviside(epsilon - min cdist, 0) of camera_coverage_gain / scene_coverage (macarons_utils.py:3022-3024,
     3049-3051): a surface point is covered iff some seen point lies strictly within epsilon.  The nearest distance is fp64;
     scene_coverage compares it in fp64, camera_coverage_gain rounds it to fp32 first (`.float()`, :3022) and subtracts it from
-    epsilon in fp32 (fp32_compare=True)."""
+    epsilon in fp32 (fp32_compare=True).  max_a: an upper bound of the largest surface segment, when the caller knows one (it sizes the
+    grid; without it the offsets are read back)."""
     dev = surface_pts.device
     if a_offsets is None:
         a_offsets = torch.tensor([0, surface_pts.shape[0]], dtype=torch.int64, device=dev)
         b_offsets = torch.tensor([0, seen_pts.shape[0]], dtype=torch.int64, device=dev)
-    d = ops.min_dist_segmented(surface_pts, a_offsets, seen_pts, b_offsets)
+    d = ops.min_dist_segmented(surface_pts, a_offsets, seen_pts, b_offsets, max_a=max_a)
     if fp32_compare:
         return (epsilon - d.float()) > 0.
     return (epsilon - d) > 0.
@@ -1041,3 +1082,162 @@ def compute_occupancy_probability_for_supervision(params, macarons, camera, prox
                       cloud_sizes=sizes_m, query_sizes=sizes_q, occ=occ.detach(), pos=pos, job_offsets=job_off_d,
                       last_ragged_perms=occ_net.last_ragged_perms)
     return prediction_mask, probas
+
+
+# ---- the online trainer's SCONE step: scone_loss of K new depth frames -----------------------------------------------------------
+def get_occ_loss_fn(params):
+    """macarons_utils.py:1566-1573."""
+    if params.occ_loss_fn == "mse":
+        return torch.nn.MSELoss(size_average=None, reduce=None, reduction='mean')
+    raise NameError("Invalid training loss function."
+                    "Please choose a valid loss like 'mse'.")
+
+
+def get_cov_loss_fn(params):
+    """macarons_utils.py:1791-1805: the three loss classes of networks/SconeVis.py."""
+    from ..networks.SconeVis import KLDivCE, L1_loss, Uncentered_L1_loss
+    if params.cov_loss_fn == "kl_divergence":
+        return KLDivCE()
+    if params.cov_loss_fn == "l1":
+        return L1_loss()
+    if params.cov_loss_fn == "uncentered_l1":
+        return Uncentered_L1_loss()
+    raise NameError("Invalid training loss function."
+                    "Please choose a valid loss between 'kl_divergence', 'l1' or 'uncentered_l1.")
+
+
+def _frame_fields(f):
+    if isinstance(f, dict):
+        return f["depth"], f["mask"], f.get("error_mask"), f["camera"], f["depth_camera"]
+    return f
+
+
+def scone_supervision_step(params, macarons, proxy_scene, surface_scene, frames, X_world, view_harmonics, occ_probs, surface_distance,
+                           n_cell_per_occ_forward_pass, occ_loss_fn, cov_loss_fn, device, prediction_camera=None,
+                           pseudo_gt_proxy_proba=None, supervise_with_online_field=True, predict=True, record=None, samples=None):
+    """scone_loss of one step of the online trainer from K new depth frames: the body upstream has twice, train_macarons.py:375-513
+    (`loop`) and :605-756 (`memory_scene_loop`), everything between the depth maps and `scone_loss = occ_loss + cov_loss`.
+    `frames`: K items (depth, mask, error_mask, camera, depth_camera) -- tuples in that order or dicts with those keys: depth and masks
+    [H,W] (+ singleton dims; error_mask may be None), a SceneCamera (record with the sensor range, X_cam, zfar) and the 18 floats of
+    depth_camera_record.  X_world, view_harmonics, occ_probs: the occupancy field the trainer computed under no_grad (:283 / :598).
+    `macarons`: the SCONE part (.occupancy / .visibility).  prediction_camera: a PyTorch3D-like camera or its [4,4] world->view matrix
+    (upstream's camera.fov_camera_0 / memory prediction camera); needed when predict.  Order of work:
+      1. the K partial clouds (compute_partial_point_clouds; mask * error_mask, :392-396);
+      2. frustum bits, signed distances and the close mask of all K frames in one pass (ops.supervision_frames, :402-415);
+      3. close mask AND out_of_field < 1 (:422);
+      4. compute_occupancy_probability_for_supervision(..., differentiable=True) (:423);
+      5. predict_coverage_gain_for_cameras(..., differentiable=True) for the K frame cameras (:433-444);
+      6. surface fill_cells, feature 1 for frame 0's points and 0 for the rest (:451-454);
+      7. Scene.camera_coverage_gains (:460-465);  8. set_all_features_to_value(1.) (:468);
+      9. proxy fill_cells of the points in any frustum, their index as feature (:472-474);
+      10. view states, counters, supervision occupancy and out-of-field flags of the K frames in one pass
+          (ops.proxy_scene_update_frames_, :476-487);
+      11. occ_loss = occ_loss_fn(predicted, supervision) * n_pred / n_proxy_point_for_occupancy_supervision (supervision: the proxy
+          scene's supervision occupancy AFTER step 10, or pseudo_gt_proxy_proba with supervise_with_online_field=False) and
+          cov_loss = cov_loss_fn on [1,K,1] views (:495-513).
+    predict=False (upstream's `freeze` / not online_learning): steps 4, 5 and 11 are skipped, the losses are zeros without a graph.
+    Returns dict(scone_loss (with its graph), occ_loss, cov_loss (detached), prediction_mask, predicted_occs, predicted_coverage_gains
+    [K,1], supervision_coverage_gains [K,1], part_pcs (list of K), fov_bits [P] int32, sgn [K,P], close_mask [P] bool).
+    Draws, in upstream's order: CPU generator -- the K partial clouds' permutations, the supervision pass's (sampling, cell order, the
+    network's hidden draws), the surface fill's, the proxy fill's; device generator -- the K cameras' sampling uniforms in one launch
+    (`samples` [K,S] replaces them).  Upstream draws no uniforms for a frame whose frustum holds no sampled point; the batched call
+    draws K rows always (as macarons_nbv_decision does).
+    Host synchronisations: SEVEN with predict, FOUR without (counted with torch.cuda.set_sync_debug_mode, tools/time_scone_step.py) --
+      a. the K keep counts of the partial clouds                      [K] int64
+      b. the number of set entries of the close mask (step 4)          torch.nonzero's size
+      c. the supervision selection's count table (step 4)              [3 n_cells + 5] int64
+      d. SconeVis' range flag (step 5, range_guard="sync", its default) [1] int32
+      e. the surface fill's count table                                [4 n_cells + 7] int64
+      f. the (frame, cell) point counts of camera_coverage_gains       [K, n_cells] int32
+      g. the proxy fill's count table                                  [4 n_cells + 7] int64
+    (a fill that finds an ambiguous point runs upstream's per-cell loop instead, with its own read-backs).  Once per scene object, on
+    its first step: the grid tables of the field pass (two read-backs) and the box diagonal (one), kept on the scene.  A prediction
+    camera or camera records held on the device add their read-backs / copies; hand poses over as host tensors.  The K supervision
+    gains and the losses stay on the device.
+    Gradients: scone_loss.backward() runs autograd.SconeOccRaggedFunction + SupervisionScatterFunction (occupancy) and
+    MacaronsGainFunction + the scorer's and SconeVis' backward (coverage) -- HIP end to end; every parameter of both networks receives a
+    gradient tensor on every call, also when a frame's frustum is empty."""
+    ps, ss = proxy_scene, surface_scene
+    K = len(frames)
+    if not 1 <= K <= 32:
+        raise ValueError(f"scone_supervision_step: between 1 and 32 frames, got {K}")
+    H, W = params.image_height, params.image_width
+    fr = [_frame_fields(f) for f in frames]
+    depths = torch.stack([f[0].reshape(H, W) for f in fr]).to(device=device, dtype=torch.float32).contiguous()
+    masks = torch.stack([f[1].reshape(H, W).bool() for f in fr]).to(device)
+    cloud_masks = masks if all(f[2] is None for f in fr) else \
+        masks & torch.stack([(torch.ones(H, W, dtype=torch.bool) if f[2] is None else f[2].reshape(H, W).bool()) for f in fr]).to(device)
+    cams = [f[3] for f in fr]
+    if all(c.record.device.type == "cpu" and c.X_cam.device.type == "cpu" for c in cams):     # poses are host data: one upload
+        both = ops.h2d(torch.stack([torch.cat((c.record.reshape(40), c.X_cam.reshape(3))) for c in cams]), torch.float32, device)
+        recs, xc = both[:, :40].contiguous(), both[:, 40:].contiguous()
+    else:
+        recs = torch.stack([c.record.reshape(40).to(device) for c in cams]).contiguous()
+        xc = torch.stack([c.X_cam.reshape(3).to(device) for c in cams]).contiguous()
+    P = ps.proxy_points.shape[0]
+    # 1 ---- partial clouds
+    part_pcs = compute_partial_point_clouds(depths, cloud_masks, torch.stack([f[4].reshape(18) for f in fr]), params.gathering_factor,
+                                            params.sensor_range)
+    # 2, 3 ---- supervision signal of the K frames
+    fov_bits, sgn, close = ops.supervision_frames(ps.proxy_points, recs, depths, masks, [1.1 * c.zfar for c in cams], surface_distance)
+    close_mask = close & (ps.out_of_field[..., 0] < 1.)
+    # 4, 5 ---- predictions, with their graphs
+    prediction_mask = predicted_occs = predicted_gains = None
+    if predict:
+        if prediction_camera is None:
+            raise NameError("Both camera and prediction_camera are equal to None.")
+        prediction_mask, predicted_occs = compute_occupancy_probability_for_supervision(
+            params, macarons, None, ps, close_mask, ss, n_cell_per_occ_forward_pass, device, prediction_camera=prediction_camera,
+            differentiable=True, record=record)
+        th = params.distance_factor_th
+        smooth = th == 'smooth'
+        if th is None or smooth:
+            th = sensor_distance_threshold(params, cams[0], ss.cell_resolution)
+        diag = getattr(ps, "_mcr_box_diag", None)       # a constant of the scene: read back once, not once per step
+        if diag is None:
+            diag = torch.linalg.norm(ps.x_max - ps.x_min).item()
+            try:
+                ps._mcr_box_diag = diag
+            except Exception:
+                pass
+        Mv = prediction_camera if torch.is_tensor(prediction_camera) else _world_to_view_matrix(prediction_camera)
+        Mv = ops.h2d(Mv.reshape(1, 4, 4), torch.float32, device).expand(K, -1, -1)
+        predicted_gains = predict_coverage_gain_for_cameras(macarons.visibility, X_world, view_harmonics, occ_probs, recs, xc, Mv, diag,
+                                                            seq_len=params.seq_len, min_occ=params.min_occ_for_proxy_points,
+                                                            distance_th=float(th), samples=samples, smooth=smooth, record=record,
+                                                            differentiable=True).view(K, 1)
+    # 6 - 8 ---- surface scene
+    sizes = [int(p_.shape[0]) for p_ in part_pcs]
+    complete = torch.cat(part_pcs)
+    features = torch.zeros(len(complete), 1, device=device)
+    features[:sizes[0]] = 1.
+    ss.fill_cells(complete, features=features)
+    supervision_gains = ss.camera_coverage_gains(part_pcs, surface_epsilon=None,
+                                                 surface_epsilon_factor=params.surface_epsilon_factor).view(K, 1)
+    ss.set_all_features_to_value(value=1.)
+    # 9, 10 ---- proxy scene
+    idx_f = getattr(ps, "_mcr_index_feature", None)
+    if idx_f is None or idx_f.shape[0] != P or idx_f.device != ps.proxy_points.device:
+        idx_f = torch.arange(P, device=device, dtype=torch.float32).view(-1, 1)
+        try:
+            ps._mcr_index_feature = idx_f
+        except Exception:
+            pass
+    ps.fill_cells(ps.proxy_points, features=idx_f, valid=fov_bits != 0)
+    ops.proxy_scene_update_frames_(ps.proxy_points, fov_bits, sgn, xc, 3 * ps.distance_between_proxy_points, params.carving_tolerance,
+                                   ps.score_threshold, ps.view_state_n_elev, ps.view_state_n_azim, ps.view_states, ps.proxy_n_inside_fov,
+                                   ps.proxy_n_behind_depth, ps.proxy_supervision_occ, ps.out_of_field)
+    # 11 ---- losses
+    zero = torch.zeros(1, device=device)[0]
+    occ_loss, cov_loss = zero, zero
+    if predict:
+        n_pred = int(predicted_occs.shape[0])
+        if n_pred > 0:
+            target = ps.proxy_supervision_occ if supervise_with_online_field else pseudo_gt_proxy_proba
+            supervision_occs = target.reshape(P, 1).index_select(0, _kept_rows(prediction_mask, n_pred))
+            occ_loss = occ_loss_fn(predicted_occs, supervision_occs) * n_pred / params.n_proxy_point_for_occupancy_supervision
+        cov_loss = cov_loss_fn(predicted_gains.view(1, -1, 1), supervision_gains.view(1, -1, 1))
+    return {"scone_loss": occ_loss + cov_loss, "occ_loss": occ_loss.detach(), "cov_loss": cov_loss.detach(),
+            "prediction_mask": prediction_mask, "predicted_occs": predicted_occs, "predicted_coverage_gains": predicted_gains,
+            "supervision_coverage_gains": supervision_gains, "part_pcs": part_pcs, "fov_bits": fov_bits, "sgn": sgn,
+            "close_mask": close_mask}

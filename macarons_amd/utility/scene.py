@@ -512,3 +512,49 @@ class Scene:
         seen = torch.cat([c.cell_features.view(-1) for c in cells])
         covered = mu.covered_mask(A, inside.contiguous(), epsilon, fp32_compare=True)
         return (covered.float() * (1. - seen)).sum()
+
+    def camera_coverage_gains(self, part_pcs, surface_epsilon=None, surface_epsilon_factor=None):
+        """camera_coverage_gain of K partial clouds against the SAME store (the trainer measures its K new frames after one fill,
+        train_macarons.py:460-465 / :704-708) -> [K] fp32.  The K calls are independent, so they are the K segments of ONE
+        covered_mask launch: frame k's surface segment = the stored points of the non-empty cells its in-box points touch, its seen
+        segment = those in-box points.  ONE read-back for all frames (the [K, n_cells] table of in-box points per cell, which lists the
+        cells and sizes the segments).  The values are sums of zeros and ones: equal to K camera_coverage_gain calls exactly."""
+        from .. import ops
+        epsilon = self.cell_resolution if surface_epsilon is None else surface_epsilon
+        if surface_epsilon_factor is not None:
+            epsilon = epsilon * surface_epsilon_factor
+        K, dev = len(part_pcs), self.device
+        sizes = [int(p.shape[0]) for p in part_pcs]
+        N = sum(sizes)
+        if K == 0 or N == 0:
+            return torch.zeros(K, device=dev)
+        if self.feature_dim != 1:
+            raise ValueError("camera_coverage_gains reads the cells' one feature (seen / not seen): feature_dim must be 1")
+        n_cells = self.grid_l * self.grid_w * self.grid_h
+        c = self._consts(dev)
+        pts = torch.cat(list(part_pcs)).contiguous()
+        frame = torch.repeat_interleave(torch.arange(K, device=dev), ops.h2d(sizes, torch.int64, dev), output_size=N)
+        inbox = ((pts >= c["x_min"]) & (pts <= c["x_max"])).all(dim=-1)
+        slot = frame * n_cells + self.linear_cell_ids(pts).long()
+        table = torch.zeros(K * n_cells, dtype=torch.int32, device=dev).index_add_(0, slot, inbox.to(torch.int32))
+        table = table.cpu().numpy().reshape(K, n_cells)                                     # THE read-back
+        st = self.flat_store()
+        off = st.off
+        rows, a_off = [], [0]
+        for k in range(K):
+            for cell in np.nonzero(table[k])[0]:
+                if off[cell + 1] > off[cell]:
+                    rows.append(np.arange(off[cell], off[cell + 1], dtype=np.int64))
+            a_off.append(sum(len(r) for r in rows))
+        a_off = np.asarray(a_off, np.int64)
+        if a_off[-1] == 0:
+            return torch.zeros(K, device=dev)
+        b_off = np.concatenate(([0], np.cumsum(table.sum(1, dtype=np.int64)))).astype(np.int64)
+        up = ops.h2d(np.concatenate(rows + [a_off, b_off]), torch.int64, dev)
+        a_idx, a_off_d, b_off_d = up[:a_off[-1]], up[a_off[-1]:a_off[-1] + K + 1], up[a_off[-1] + K + 1:]
+        A = st.pts.index_select(0, a_idx)
+        seen = st.fts.reshape(-1).index_select(0, a_idx)
+        B = pts.index_select(0, mu._kept_rows(inbox, int(b_off[-1])))
+        covered = mu.covered_mask(A, B, epsilon, a_off_d, b_off_d, fp32_compare=True, max_a=int(np.diff(a_off).max()))
+        cs = torch.cat((torch.zeros(1, device=dev), torch.cumsum(covered.float() * (1. - seen), 0)))
+        return cs.index_select(0, a_off_d[1:]) - cs.index_select(0, a_off_d[:-1])
