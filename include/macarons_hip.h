@@ -723,6 +723,27 @@ int mcr_supervision_scatter(const int* rows, const float* occ, const int64_t* jo
 int mcr_supervision_scatter_backward(const int* rows, const int* pos, int64_t P, const float* d_out, int64_t n_out, int64_t T_scatter,
                                      int64_t T, float* d_occ, void* stream);
 
+/* ---- the plane sweep of the depth module (macarons/networks/ManyDepth.py:207-305 CostVolumeBuilder.forward, up to and without the
+ * torch.cat / conv_reduce at :299-300), fused (cost_volume.hip).
+ *
+ * mcr_cost_volume: out[b, k, i, j] = (1/C) sum_c | mean_a warped[b, k, a, c, i, j] - x[b, c, i, j] |, replacing: the B*D and B*D*A
+ *   FoVPerspectiveCameras (:233-254), reproject_depth_map of D constant depth maps (:257-261 -> :111-144, unproject_points with
+ *   scaled_depth_input=False), warp (:264-282 -> :146-205: transform_points(eps=1e-8) of the full projection transform, the
+ *   -min(w,h)/w, -min(w,h)/h factors, F.interpolate(mode='bicubic') of the H x W coordinate images to Hf x Wf, F.grid_sample(bilinear,
+ *   zeros, align_corners=False) of D contiguous copies of the source maps), torch.mean over the sources (:288) and the L1 norm over the
+ *   channels / C (:291-297).
+ *   x [B,C,Hf,Wf] target features, x_alpha [B,A,C,Hf,Wf] source features, depth_bins [D], cams [B,1+A,12]: row 0 the target camera, rows
+ *   1..A the sources, each PyTorch3D's R (9 floats, row-major, row-vector convention view = world @ R + T) then T (3 floats).  H x W is
+ *   the image size whose pixel grid is unprojected, Hf <= H, Wf <= W, H, W >= 2.  fov_scale = 1 / tan(fov / 2) (upstream: fov = 60
+ *   degrees; znear and zfar drop out).  out: batch b starts at out + b * out_batch_stride floats and holds [D,Hf,Wf] contiguous, so out
+ *   may be channel C of a [B,C+D,Hf,Wf] buffer (out_batch_stride = (C+D)*Hf*Wf): upstream's cat.  C must be 64.  A resized coordinate that
+ *   is not finite or lies a pixel or more outside the source map contributes zero and indexes nothing.  No atomics, fixed summation order:
+ *   bit-reproducible.  workspace (16-byte aligned): a channels-last copy of x_alpha. */
+size_t mcr_cost_volume_workspace_bytes(int64_t B, int64_t A, int64_t C, int64_t Hf, int64_t Wf);
+int mcr_cost_volume(const float* x, const float* x_alpha, const float* cams, const float* depth_bins, float* out,
+                    int64_t out_batch_stride, int64_t B, int A, int C, int H, int W, int Hf, int Wf, int D, float fov_scale,
+                    void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

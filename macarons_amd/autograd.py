@@ -13,7 +13,8 @@ MCR_SCONE_OCC_BWD=hip: no recomputation in torch at all -- SconeOccFunction belo
 x-embedding, head, global transformer) to one entry, mcr_scone_occ_backward, for the parameters, x and the view harmonics; a gradient
 for the surface points pc is not computed there, so a forward whose pc requires one takes the pct route.  The MACARONS-regime gain
 (ops.macarons_gain_indexed / macarons_gain_) is HIP both ways as well: MacaronsGainFunction below, backward mcr_macarons_gain_backward, with
-gradients for the per-point visibility gains and the volumes and for nothing else.  The composites
+gradients for the per-point visibility gains and the volumes and for nothing else.  The depth module's plane sweep (ops.cost_volume)
+has a HIP forward and, for now, a composite backward (CostVolumeFunction below; networks.ManyDepth.cost_volume_planes).  The composites
 are ordinary differentiable torch code, so they are also what the parity tests differentiate numerically (tests/test_autograd.py:
 fp64 finite differences on CPU; on the GPU the composite forward must reproduce the HIP forward to 1e-4, which makes its gradient
 the gradient of the kernels' function) and the second reference of the HIP backward's tests.
@@ -461,3 +462,50 @@ class SupervisionScatterFunction(torch.autograd.Function):
         rows, pos = ctx.saved_tensors
         d_occ = ops.supervision_scatter_backward(rows, pos, grad_out.float().contiguous(), ctx.T_scatter if ctx.n_jobs else 0, ctx.T)
         return d_occ, None, None, None, None, None
+
+
+# ---- depth module, the plane sweep: HIP forward + composite backward -------------------------------------------------------------
+class CostVolumeFunction(torch.autograd.Function):
+    """apply(x, x_alpha, cams, depth_bins, H, W, fov_scale, concat) -> the cost volume [B,D,Hf,Wf] of ops.cost_volume (mcr_cost_volume)
+    without a graph, or with concat the buffer [B,C+D,Hf,Wf] = cat(x, cost volume) of ManyDepth.py:299, the volume written in place
+    by the kernel.  backward = autograd through networks.ManyDepth.cost_volume_planes (plain torch on the same device, recomputed
+    PLANE_CHUNK planes at a time so that its intermediates stay bounded), for x and x_alpha; the cameras and the bins are constants of
+    the graph.  Differentiable once.  (A HIP backward is open: the x_alpha gradient is a scatter.)"""
+
+    PLANE_CHUNK = 8
+
+    @staticmethod
+    def forward(ctx, x, x_alpha, cams, depth_bins, H, W, fov_scale, concat):
+        from . import ops
+        ctx.H, ctx.W, ctx.fov_scale, ctx.concat = int(H), int(W), float(fov_scale), bool(concat)
+        ctx.save_for_backward(x, x_alpha, cams, depth_bins)
+        with torch.no_grad():
+            if not concat:
+                return ops.cost_volume(x, x_alpha, cams, depth_bins, H, W, fov_scale)
+            B, C, Hf, Wf = x.shape
+            buf = torch.empty((B, C + depth_bins.numel(), Hf, Wf), dtype=torch.float32, device=x.device)
+            buf[:, :C].copy_(x)
+            ops.cost_volume(x, x_alpha, cams, depth_bins, H, W, fov_scale, out=buf[:, C:])
+            return buf
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        if torch.is_grad_enabled():
+            raise RuntimeError("the cost volume is differentiable once: its backward recomputes without a graph (create_graph is not supported)")
+        from .networks.ManyDepth import cost_volume_planes
+        x, x_alpha, cams, depth_bins = ctx.saved_tensors
+        C = x.shape[1]
+        g_cv = grad_out[:, C:] if ctx.concat else grad_out
+        need = ctx.needs_input_grad[:2]
+        grads = [None, None]
+        with torch.enable_grad():
+            ins = [t.detach().requires_grad_(n) for t, n in zip((x, x_alpha), need)]
+            wrt = [i for i in (0, 1) if need[i]]
+            for k in range(0, depth_bins.numel(), CostVolumeFunction.PLANE_CHUNK) if wrt else ():
+                sl = slice(k, k + CostVolumeFunction.PLANE_CHUNK)
+                cv = cost_volume_planes(ins[0], ins[1], cams, depth_bins[sl], ctx.H, ctx.W, ctx.fov_scale)
+                for i, g in zip(wrt, torch.autograd.grad(cv, [ins[i] for i in wrt], g_cv[:, sl])):
+                    grads[i] = g if grads[i] is None else grads[i] + g
+        if ctx.concat and need[0]:
+            grads[0] = grads[0] + grad_out[:, :C]
+        return (grads[0], grads[1], None, None, None, None, None, None)

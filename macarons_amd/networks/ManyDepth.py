@@ -1,0 +1,147 @@
+"""The plane sweep of the depth module on HIP: a mirror of upstream's `CostVolumeBuilder` (macarons/networks/ManyDepth.py:80-305) whose
+forward builds the cost volume with one fused entry (ops.cost_volume -> mcr_cost_volume, csrc/cost_volume.hip) instead of upstream's
+cameras / unprojection / projection / bicubic resize / 96-fold feature copy / grid_sample / mean / norm sequence, and the seam that puts
+an existing upstream instance on that path (`adopt_cost_volume_builder`).  The rest of the depth network -- the ResNet encoder and
+decoder, the pose decoder, `apply_depth_model`, the reconstruction loss with its own calls of `reproject_depth_map` / `warp` -- is
+convolutions the vendor library serves and stays upstream's.
+
+Needs neither PyTorch3D nor torchvision: a camera is its R, T (PyTorch3D's row-vector convention, view = world @ R + T) and the default
+60 degree field of view upstream never overrides; znear and zfar drop out of the sweep (they only shape the z the projection returns,
+which upstream discards, and the scaled depth the unprojection immediately inverts).
+
+`cost_volume_composite` is the same mathematics in plain differentiable torch, chunked over the planes: what CostVolumeFunction
+differentiates (autograd.py) and what the tests hold against an independent fp64 model.
+"""
+import torch
+import torch.nn.functional as F
+from torch import nn
+
+from .. import ops
+from ..ops import COST_VOLUME_FOV_SCALE
+
+__all__ = ["CostVolumeBuilder", "adopt_cost_volume_builder"]
+
+
+def pack_cameras(R, T, R_alpha, T_alpha):
+    """R [B,3,3], T [B,3], R_alpha [B,A,3,3], T_alpha [B,A,3] -> cams [B,1+A,12] float32 (row 0 the target; R row-major, then T)."""
+    B, A = R_alpha.shape[0], R_alpha.shape[1]
+    tgt = torch.cat((R.reshape(B, 1, 9), T.reshape(B, 1, 3)), -1)
+    src = torch.cat((R_alpha.reshape(B, A, 9), T_alpha.reshape(B, A, 3)), -1)
+    return torch.cat((tgt, src), 1).float().contiguous()
+
+
+def cost_volume_planes(x, x_alpha, cams, depth_bins, H, W, fov_scale=COST_VOLUME_FOV_SCALE):
+    """The cost volume [B,len(depth_bins),Hf,Wf] of the given planes in torch ops, in x's dtype, all planes at once."""
+    B, A, C, Hf, Wf = x_alpha.shape
+    dt, dev, s = x.dtype, x.device, float(fov_scale)
+    Dc = depth_bins.numel()
+    cams = cams.to(dt)
+    R, T = cams[:, 0, :9].reshape(B, 3, 3), cams[:, 0, 9:]
+    Ra, Ta = cams[:, 1:, :9].reshape(B, A, 3, 3), cams[:, 1:, 9:]
+    m, mf = min(H, W), min(Hf, Wf)
+    # the ray of full-resolution pixel (p, q) in the target view, per unit depth (reproject_depth_map, ManyDepth.py:128-137)
+    nx = (W / m - 2.0 * torch.arange(W, dtype=dt, device=dev) / (m - 1)) / s
+    ny = (H / m - 2.0 * torch.arange(H, dtype=dt, device=dev) / (m - 1)) / s
+    n = torch.stack((nx[None, :].expand(H, W), ny[:, None].expand(H, W), torch.ones(H, W, dtype=dt, device=dev)), -1)
+    # target view -> world -> source view is affine: v_a = v (R^T R_a) + (T_a - T R^T R_a), hence affine in the depth along a ray
+    M = torch.einsum("bij,baik->bajk", R, Ra)
+    u = torch.einsum("hwj,bajk->bahwk", n, M)
+    t = Ta - torch.einsum("bj,bajk->bak", T, M)
+    v = depth_bins.to(dt).view(1, 1, Dc, 1, 1, 1) * u[:, :, None] + t[:, :, None, None, None, :]          # [B,A,Dc,H,W,3]
+    w = v[..., 2]
+    w = torch.where(w < 0, -torch.ones_like(w), torch.ones_like(w)) * w.abs().clamp(min=1e-8)             # transform_points(eps=1e-8)
+    g = torch.cat(((-(mf / Wf) * s) * v[..., 0] / w, (-(mf / Hf) * s) * v[..., 1] / w), 2)                # warp, :176-178
+    g = F.interpolate(g.reshape(B * A, 2 * Dc, H, W), size=(Hf, Wf), mode="bicubic", align_corners=False)
+    grid = torch.stack((g[:, :Dc], g[:, Dc:]), -1).reshape(B * A, Dc * Hf, Wf, 2)
+    # a coordinate that is not finite, or absurdly far out, samples nothing: sent well outside the map before grid_sample converts it
+    bad = ~(torch.isfinite(grid) & (grid.abs() < 1e6))
+    grid = torch.where(bad, torch.full_like(grid, -3.0), grid)
+    smp = F.grid_sample(x_alpha.reshape(B * A, C, Hf, Wf), grid, mode="bilinear", padding_mode="zeros", align_corners=False)
+    smp = smp.reshape(B, A, C, Dc, Hf, Wf).mean(1)
+    return (smp - x[:, :, None]).abs().sum(1) / C
+
+
+def cost_volume_composite(x, x_alpha, cams, depth_bins, H, W, fov_scale=COST_VOLUME_FOV_SCALE, plane_chunk=8):
+    """ops.cost_volume in plain torch (any device, differentiable in x and x_alpha), `plane_chunk` planes at a time: the largest
+    intermediates are the [B,A,plane_chunk,H,W,3] source-view points and the [B,A,C,plane_chunk,Hf,Wf] samples."""
+    D = depth_bins.numel()
+    return torch.cat([cost_volume_planes(x, x_alpha, cams, depth_bins[k:k + plane_chunk], H, W, fov_scale)
+                      for k in range(0, D, plane_chunk)], 1)
+
+
+def _forward(self, x, R, T, zfar, x_alpha, R_alpha, T_alpha, zfar_alpha, device=None, return_cost_volume=False):
+    """CostVolumeBuilder.forward (ManyDepth.py:207-305), same signature: x [B,C,Hf,Wf], R [B,3,3], T [B,3], x_alpha [B,A,C,Hf,Wf],
+    R_alpha [B,A,3,3], T_alpha [B,A,3] -> relu(conv_reduce(cat(x, cost volume))) [B,output_channels,Hf,Wf] (and the cost volume
+    [B,n_depth,Hf,Wf]).  zfar, zfar_alpha and device are accepted and unused: the far planes drop out, the tensors name the device.
+    The sweep writes the volume where the cat would put it; with gradients required for x or x_alpha it goes through CostVolumeFunction."""
+    from ..autograd import CostVolumeFunction
+    # upstream's forward is also where its plain tensor attributes reach the device (ManyDepth.py:225-228; they are no buffers, .to()
+    # leaves them behind): depth_bins, and on an adopted upstream instance the pixel tables x_tab / y_tab its reproject_depth_map reads
+    for name in ("depth_bins", "x_tab", "y_tab"):
+        t = getattr(self, name, None)
+        if torch.is_tensor(t) and t.device != x.device:
+            setattr(self, name, t.to(x.device))
+    B, C, Hf, Wf = x.shape
+    cams = pack_cameras(R, T, R_alpha, T_alpha)
+    if torch.is_grad_enabled() and (x.requires_grad or x_alpha.requires_grad):
+        buf = CostVolumeFunction.apply(x, x_alpha, cams, self.depth_bins, self.height, self.width, COST_VOLUME_FOV_SCALE, True)
+    else:
+        with torch.no_grad():
+            buf = torch.empty((B, C + self.n_depth, Hf, Wf), dtype=torch.float32, device=x.device)
+            buf[:, :C].copy_(x)
+            ops.cost_volume(x, x_alpha, cams, self.depth_bins, self.height, self.width, out=buf[:, C:])
+    res = F.relu(self.conv_reduce(buf))
+    if return_cost_volume:
+        return res, buf[:, C:]
+    return res
+
+
+class CostVolumeBuilder(nn.Module):
+    """Mirror of upstream's CostVolumeBuilder: the same constructor arguments, attributes and parameter names (`conv_reduce.weight`,
+    `conv_reduce.bias`: upstream state dicts load), the forward on HIP.  `reproject_depth_map` and `warp` are not offered here; a caller
+    that needs them (upstream's reconstruction loss) keeps its upstream instance and adopts it (adopt_cost_volume_builder)."""
+
+    def __init__(self, height, width, feature_height, feature_width, feature_channels, n_alpha, d_min, d_max, n_depth, output_channels,
+                 kernel_size=3, stride=1, padding=1):
+        super().__init__()
+        self.height, self.width = height, width
+        self.feature_height, self.feature_width, self.feature_channels = feature_height, feature_width, feature_channels
+        self.n_alpha = n_alpha
+        self.d_min, self.d_max, self.n_depth = d_min, d_max, n_depth
+        self.depth_bins = torch.linspace(d_min, d_max, n_depth)
+        self.conv_reduce = nn.Conv2d(in_channels=feature_channels + n_depth, out_channels=output_channels, kernel_size=kernel_size,
+                                     stride=stride, padding=padding)
+        self.relu = nn.ReLU()
+
+    forward = _forward
+
+
+_ADOPT_ATTRIBUTES = ("height", "width", "feature_height", "feature_width", "feature_channels", "n_alpha", "d_min", "d_max", "n_depth",
+                     "depth_bins", "conv_reduce")
+
+
+class _AdoptedForward:
+    """The `forward` of an adopted instance: a module-level callable holding the instance, so that the instance still pickles
+    (torch.save(model)) and deep-copies -- a bound method of a function that upstream's class does not have would not."""
+
+    def __init__(self, builder):
+        self.builder = builder
+
+    def __call__(self, *args, **kwargs):
+        return _forward(self.builder, *args, **kwargs)
+
+
+def adopt_cost_volume_builder(builder):
+    """Put an existing upstream CostVolumeBuilder instance on the HIP sweep: its `forward` is rebound (on the instance) to the forward
+    above, which reads only height, width, feature_*, n_alpha, d_min, d_max, n_depth, depth_bins and conv_reduce, and like upstream's
+    moves depth_bins, x_tab and y_tab to the input's device; `reproject_depth_map` and `warp` stay as they are, upstream's
+    reconstruction loss calls them.  Returns the instance; adopting twice changes nothing.  Loading a pickled adopted model needs this
+    package importable.
+
+        adopt_cost_volume_builder(macarons.depth.depth_decoder.cost_volume_builder)"""
+    missing = [a for a in _ADOPT_ATTRIBUTES if not hasattr(builder, a)]
+    if missing:
+        raise TypeError(f"adopt_cost_volume_builder: not a CostVolumeBuilder, it lacks {missing}")
+    if not isinstance(vars(builder).get("forward"), _AdoptedForward):
+        object.__setattr__(builder, "forward", _AdoptedForward(builder))     # a plain instance attribute, whatever the class's __setattr__ does
+    return builder

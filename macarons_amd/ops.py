@@ -1637,3 +1637,37 @@ def uniform_rows(K, S, device, generator=None):
                                             c_int(_PHILOX_MAPPING), _p(out), _stream()), "mcr_philox_uniform_rows")
     gen.set_offset(off + 4 * K)
     return out
+
+
+# ---- depth module: the plane sweep ---------------------------------------------------------------------------------------------
+COST_VOLUME_FOV_SCALE = 1.0 / float(np.tan(np.deg2rad(60.0) / 2))    # FoVPerspectiveCameras' default fov, which upstream never overrides
+
+
+def cost_volume(x, x_alpha, cams, depth_bins, H, W, fov_scale=COST_VOLUME_FOV_SCALE, out=None):
+    """cost volume [B,D,Hf,Wf] of CostVolumeBuilder.forward (ManyDepth.py:207-297) in one entry (mcr_cost_volume): x [B,64,Hf,Wf] target
+    features, x_alpha [B,A,64,Hf,Wf] source features, cams [B,1+A,12] (row 0 the target, then the sources; R row-major then T, PyTorch3D's
+    row-vector convention), depth_bins [D], H x W the image size whose pixel grid is unprojected.  out: None, or a [B,D,Hf,Wf] float32
+    view whose batches may be strided -- channels C.. of a [B,C+D,Hf,Wf] buffer, where upstream's torch.cat puts the volume."""
+    x, x_alpha, cams, depth_bins = _req(x, "x"), _req(x_alpha, "x_alpha"), _req(cams, "cams"), _req(depth_bins, "depth_bins")
+    if x.dim() != 4 or x_alpha.dim() != 5:
+        raise ValueError(f"x must be [B,C,Hf,Wf] and x_alpha [B,A,C,Hf,Wf]; got {tuple(x.shape)}, {tuple(x_alpha.shape)}")
+    B, C, Hf, Wf = x.shape
+    A, D = x_alpha.shape[1], depth_bins.numel()
+    if tuple(x_alpha.shape) != (B, A, C, Hf, Wf):
+        raise ValueError(f"x_alpha must be [B,A,C,Hf,Wf] = {(B, A, C, Hf, Wf)}, got {tuple(x_alpha.shape)}")
+    if tuple(cams.shape) != (B, 1 + A, 12):
+        raise ValueError(f"cams must be [B,1+A,12] = {(B, 1 + A, 12)}, got {tuple(cams.shape)}")
+    if out is None:
+        out = torch.empty((B, D, Hf, Wf), dtype=torch.float32, device=x.device)
+    else:
+        if not isinstance(out, torch.Tensor) or not out.is_cuda or out.device != x.device or out.dtype != torch.float32:
+            raise MacaronsHipError("out must be a float32 tensor on x's HIP device")
+        if tuple(out.shape) != (B, D, Hf, Wf) or (B * D * Hf * Wf and out[0].stride() != (Hf * Wf, Wf, 1)):
+            raise ValueError(f"out must be [B,D,Hf,Wf] = {(B, D, Hf, Wf)} with contiguous batches, got {tuple(out.shape)} strides {out.stride()}")
+    L = lib()
+    ws = _workspace(x.device, max(int(L.mcr_cost_volume_workspace_bytes(c_i64(B), c_i64(A), c_i64(C), c_i64(Hf), c_i64(Wf))), 4))
+    with torch.cuda.device(x.device):
+        check(L.mcr_cost_volume(_p(x), _p(x_alpha), _p(cams), _p(depth_bins), _p(out), c_i64(out.stride(0) if B > 1 else D * Hf * Wf),
+                                c_i64(B), c_int(A), c_int(C), c_int(int(H)), c_int(int(W)), c_int(Hf), c_int(Wf), c_int(D),
+                                c_f32(float(fov_scale)), _p(ws), c_size(ws.numel()), _stream()), "mcr_cost_volume")
+    return out

@@ -1,0 +1,179 @@
+"""The depth module's plane sweep without a GPU: the fp64 model (tests/_cost_volume_model.py) against the reference's own forward
+(tests/golden/cost_volume.npz), the product's torch composite against the model, values and gradients, and the host-side classes.
+
+Distances measured (max |difference| / max |reference value|; the bound is the project's 1e-4 everywhere):
+  reference forward vs model     cost volume  a 3.7e-07  b 7.5e-07  c 3.8e-07     res  a 2.5e-07  b 3.7e-07  c 2.7e-07
+  composite (fp32) vs model      cost volume  a 3.5e-07  b 4.7e-07  c 2.8e-07
+  composite gradients vs model   x 2.0e-07 / 1.4e-07, x_alpha 1.0e-06 / 1.5e-06, conv_reduce.weight 2.2e-07 / 2.6e-07,
+                                 conv_reduce.bias 2.0e-07 / 6.6e-08   (cases a / c)
+"""
+import os
+import sys
+
+import pytest
+import torch
+import torch.nn.functional as F
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import _cost_volume_model as model                                     # noqa: E402
+from _cost_volume_model import load_case, rel                          # noqa: E402
+
+from macarons_amd.networks import ManyDepth                            # noqa: E402
+
+TOL = 1e-4
+CASES = ("a", "b", "c")
+
+
+@pytest.fixture(scope="module")
+def cases():
+    return {t: load_case(t) for t in CASES}
+
+
+@pytest.fixture(scope="module")
+def modelled(cases):
+    """(res, cost volume) of the fp64 model per case, computed once."""
+    out = {}
+    for t, c in cases.items():
+        with torch.no_grad():
+            out[t] = model.forward(c["x"], c["R"], c["T"], c["x_alpha"], c["R_alpha"], c["T_alpha"], c["depth_bins"], c["H"], c["W"],
+                                   c["conv_reduce_weight"], c["conv_reduce_bias"])
+    return out
+
+
+def _cams(c):
+    return ManyDepth.pack_cameras(c["R"], c["T"], c["R_alpha"], c["T_alpha"])
+
+
+@pytest.mark.parametrize("tag", CASES)
+def test_model_reproduces_reference(cases, modelled, tag):
+    c, (res, cv) = cases[tag], modelled[tag]
+    e_cv, e_res = rel(c["cost_volume"], cv), rel(c["res"], res)
+    print(f"case {tag}: reference vs model: cost volume {e_cv:.2e}, res {e_res:.2e}")
+    assert e_cv < TOL and e_res < TOL
+
+
+@pytest.mark.parametrize("tag", CASES)
+def test_composite_matches_model(cases, modelled, tag):
+    c = cases[tag]
+    with torch.no_grad():
+        cv = ManyDepth.cost_volume_composite(c["x"], c["x_alpha"], _cams(c), c["depth_bins"], c["H"], c["W"], plane_chunk=4)
+    assert cv.dtype == torch.float32 and tuple(cv.shape) == tuple(c["cost_volume"].shape)
+    e = rel(cv, modelled[tag][1])
+    print(f"case {tag}: composite (fp32, CPU) vs model: {e:.2e}; vs reference {rel(cv, c['cost_volume']):.2e}")
+    assert e < TOL
+
+
+@pytest.mark.parametrize("tag", ("a", "c"))
+def test_composite_gradients(cases, tag):
+    """d loss / d (x, x_alpha, conv_reduce.weight, conv_reduce.bias), loss = a fixed random weighting of res: the fp32 composite under
+    autograd against fp64 autograd through the model."""
+    c = cases[tag]
+    x, xa = c["x"].clone().requires_grad_(True), c["x_alpha"].clone().requires_grad_(True)
+    w, b = c["conv_reduce_weight"].clone().requires_grad_(True), c["conv_reduce_bias"].clone().requires_grad_(True)
+    lw = torch.randn(c["res"].shape, generator=torch.Generator().manual_seed(5))
+    cv = ManyDepth.cost_volume_composite(x, xa, _cams(c), c["depth_bins"], c["H"], c["W"], plane_chunk=2)
+    res = F.relu(F.conv2d(torch.cat((x, cv), 1), w, b, padding=1))
+    got = torch.autograd.grad((res * lw).sum(), (x, xa, w, b))
+    x6, xa6, w6, b6 = (t.detach().double().requires_grad_(True) for t in (x, xa, w, b))
+    res6, _ = model.forward(x6, c["R"], c["T"], xa6, c["R_alpha"], c["T_alpha"], c["depth_bins"], c["H"], c["W"], w6, b6)
+    want = torch.autograd.grad((res6 * lw.double()).sum(), (x6, xa6, w6, b6))
+    for name, g, r in zip(("x", "x_alpha", "conv_reduce.weight", "conv_reduce.bias"), got, want):
+        e = rel(g, r)
+        print(f"case {tag}: gradient of {name}: {e:.2e}")
+        assert e < TOL, name
+
+
+@pytest.mark.parametrize("tag", CASES)
+def test_mirror_class_state_dict(cases, tag):
+    c = cases[tag]
+    Hf, Wf = c["x"].shape[-2:]
+    m = ManyDepth.CostVolumeBuilder(c["H"], c["W"], Hf, Wf, 64, c["x_alpha"].shape[1], float(c["d_range"][0]), float(c["d_range"][1]),
+                                    c["D"], c["out_ch"])
+    sd = m.state_dict()
+    assert list(sd.keys()) == c["state_keys"]
+    assert [tuple(v.shape) for v in sd.values()] == c["state_shapes"]
+    m.load_state_dict({"conv_reduce.weight": c["conv_reduce_weight"], "conv_reduce.bias": c["conv_reduce_bias"]})
+    assert m.depth_bins.dtype == torch.float32 and torch.equal(m.depth_bins, c["depth_bins"])
+    assert (m.height, m.width, m.feature_height, m.feature_width, m.feature_channels, m.n_alpha, m.n_depth) == \
+        (c["H"], c["W"], Hf, Wf, 64, c["x_alpha"].shape[1], c["D"])
+    assert not hasattr(m, "warp") and not hasattr(m, "reproject_depth_map")
+
+
+class _StandIn:
+    """What adopt_cost_volume_builder reads of an upstream instance, and what it must leave working: `warp`, and a
+    `reproject_depth_map` that, like upstream's, reads the plain CPU-built tensor attributes x_tab / y_tab (row and column index of every
+    pixel; no buffers, so .to(device) does not move them -- upstream's forward does)."""
+
+    def __init__(self):
+        self.height, self.width, self.feature_height, self.feature_width, self.feature_channels = 26, 42, 6, 10, 64
+        self.n_alpha, self.d_min, self.d_max, self.n_depth = 2, 0.5, 12.0, 5
+        self.depth_bins = torch.linspace(0.5, 12.0, 5)
+        self.x_tab = torch.arange(26.0)[:, None].expand(26, 42).contiguous()
+        self.y_tab = torch.arange(42.0)[None, :].expand(26, 42).contiguous()
+        self.conv_reduce = torch.nn.Conv2d(69, 8, 3, padding=1)
+
+    def warp(self):
+        return "upstream warp"
+
+    def reproject_depth_map(self, depth):
+        """[n,H,W,1] -> [n,H*W,3]: (row, column, depth) of every pixel; mixing devices raises, as upstream's torch.cat does."""
+        n = depth.shape[0]
+        return torch.cat((self.x_tab.view(1, -1, 1).expand(n, -1, -1), self.y_tab.view(1, -1, 1).expand(n, -1, -1), depth.view(n, -1, 1)), -1)
+
+    def forward(self):
+        return "upstream forward"
+
+
+def test_adopt_keeps_warp_and_is_idempotent():
+    s = _StandIn()
+    assert ManyDepth.adopt_cost_volume_builder(s) is s
+    assert s.warp() == "upstream warp" and tuple(s.reproject_depth_map(torch.ones(2, 26, 42, 1)).shape) == (2, 26 * 42, 3)
+    f = s.forward
+    assert isinstance(f, ManyDepth._AdoptedForward) and f.builder is s
+    assert ManyDepth.adopt_cost_volume_builder(s) is s and s.forward is f
+    assert "forward" not in vars(_StandIn()) and _StandIn().forward() == "upstream forward"       # the class is untouched
+    with pytest.raises(TypeError):
+        ManyDepth.adopt_cost_volume_builder(object())
+
+
+def _adopted_module():
+    m = torch.nn.Module()
+    for k, v in vars(_StandIn()).items():
+        setattr(m, k, v)
+    return ManyDepth.adopt_cost_volume_builder(m)
+
+
+def test_adopt_on_a_module_instance():
+    m = _adopted_module()
+    assert isinstance(m.forward, ManyDepth._AdoptedForward) and m.forward.builder is m
+    assert list(m.state_dict().keys()) == ["conv_reduce.weight", "conv_reduce.bias"]
+
+
+def test_adopted_module_pickles_and_copies():
+    """torch.save(model) of a whole model pickles its modules: the adopted forward must survive and point at the loaded instance."""
+    import copy
+    import io
+    m = _adopted_module()
+    buf = io.BytesIO()
+    torch.save(m, buf)
+    buf.seek(0)
+    for n in (torch.load(buf, weights_only=False), copy.deepcopy(m)):
+        assert n is not m and isinstance(vars(n)["forward"], ManyDepth._AdoptedForward) and n.forward.builder is n
+        assert torch.equal(n.conv_reduce.weight, m.conv_reduce.weight) and torch.equal(n.x_tab, m.x_tab)
+        assert ManyDepth.adopt_cost_volume_builder(n).forward.builder is n
+
+
+def test_source_looking_away_costs_the_target_norm(cases):
+    """With the one source whose samples all fall outside its map, the warped features are exactly zero: cost = sum_c |x| / C."""
+    c = cases["a"]
+    b, a = c["away"]
+    x, xa = c["x"][b:b + 1], c["x_alpha"][b:b + 1, a:a + 1]
+    cams = ManyDepth.pack_cameras(c["R"][b:b + 1], c["T"][b:b + 1], c["R_alpha"][b:b + 1, a:a + 1], c["T_alpha"][b:b + 1, a:a + 1])
+    with torch.no_grad():
+        cv = ManyDepth.cost_volume_composite(x, xa, cams, c["depth_bins"], c["H"], c["W"])
+        cv6 = model.cost_volume(x, c["R"][b:b + 1], c["T"][b:b + 1], xa, c["R_alpha"][b:b + 1, a:a + 1], c["T_alpha"][b:b + 1, a:a + 1],
+                                c["depth_bins"], c["H"], c["W"])
+    # nothing but the rounding of a 64-term sum in another order may differ: at most 64 ulp-halves, relative (all terms positive)
+    want6 = (x.double().abs().sum(1) / 64)[:, None].expand(-1, c["D"], -1, -1)
+    assert float(((cv.double() - want6).abs() / want6).max()) <= 64 * 2.0 ** -24
+    assert float(((cv6 - want6).abs() / want6).max()) <= 64 * 2.0 ** -53
