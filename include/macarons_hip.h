@@ -744,6 +744,28 @@ int mcr_cost_volume(const float* x, const float* x_alpha, const float* cams, con
                     int64_t out_batch_stride, int64_t B, int A, int C, int H, int W, int Hf, int Wf, int D, float fov_scale,
                     void* workspace, size_t workspace_bytes, void* stream);
 
+/* mcr_cost_volume_backward (cost_volume_bwd.hip): the gradients of mcr_cost_volume's x and x_alpha for d_out = d loss / d out; the cameras
+ *   and the bins are constants.  With m_c = mean over the sources of the warped channel c and s_c = sign(m_c - x_c), one of -1, 0, +1
+ *   (0 where the difference is exactly 0, as torch's abs backward has it: ReLU'd features meet there):
+ *     d_x[b,c,p]           = -(1/C)  sum_k d_out[b,k,p] s_c(k,p)
+ *     d_x_alpha[b,a,c,y,x] = 1/(A C) sum over the (k, p, corner) whose bilinear corner is pixel (y,x) of  w_corner d_out[b,k,p] s_c(k,p)
+ *   x, x_alpha, cams, depth_bins, the sizes and fov_scale as in mcr_cost_volume; the coordinates are computed by the forward's own code.
+ *   d_out: batch b starts at d_out + b * d_out_batch_stride floats and holds [D,Hf,Wf] contiguous (channels C.. of the gradient of a
+ *   [B,C+D,Hf,Wf] buffer: d_out_batch_stride = (C+D)*Hf*Wf).  d_x [B,C,Hf,Wf] or NULL, d_x_alpha [B,A,C,Hf,Wf] or NULL: a NULL output is
+ *   not computed, and its passes do not run (d_x_alpha is the expensive half); both NULL is refused.  A sample that the forward's inside
+ *   test rejects has weight 0 here too.  The refusals of mcr_cost_volume, and one more: 4*B*A*D*Hf*Wf (the corner contributions) must not
+ *   exceed 2^31 - 1.  No floating-point atomics: d_x sums the planes in ascending order; d_x_alpha is summed per destination pixel from an
+ *   inverted index (integer atomics count and place the entries) in 64-bit fixed point, q = llrint(w d_out 2^32 / max|d_out|) per entry,
+ *   which no order of the entries changes -- two calls give the same bits.  max|d_out| = 0 gives zero gradients; a d_out with a NaN or an
+ *   infinity gives gradients of NaN throughout.  workspace (16-byte aligned): the channels-last copy of x_alpha (reused for its gradient),
+ *   the sign states (16 bytes per (b,k,p): nothing here has a channel axis per source, plane and position), the sampled coordinate of every
+ *   (b,a,k,p) and the index (8 bytes per corner contribution); mcr_cost_volume_backward_workspace_bytes is 0 for sizes that are not
+ *   positive or that the entry refuses. */
+size_t mcr_cost_volume_backward_workspace_bytes(int64_t B, int64_t A, int64_t C, int64_t Hf, int64_t Wf, int64_t D);
+int mcr_cost_volume_backward(const float* x, const float* x_alpha, const float* cams, const float* depth_bins, const float* d_out,
+                             int64_t d_out_batch_stride, float* d_x, float* d_x_alpha, int64_t B, int A, int C, int H, int W, int Hf, int Wf,
+                             int D, float fov_scale, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -14,7 +14,8 @@ x-embedding, head, global transformer) to one entry, mcr_scone_occ_backward, for
 for the surface points pc is not computed there, so a forward whose pc requires one takes the pct route.  The MACARONS-regime gain
 (ops.macarons_gain_indexed / macarons_gain_) is HIP both ways as well: MacaronsGainFunction below, backward mcr_macarons_gain_backward, with
 gradients for the per-point visibility gains and the volumes and for nothing else.  The depth module's plane sweep (ops.cost_volume)
-has a HIP forward and, for now, a composite backward (CostVolumeFunction below; networks.ManyDepth.cost_volume_planes).  The composites
+is HIP both ways too (CostVolumeFunction below: mcr_cost_volume_backward; env MCR_COST_VOLUME_BWD=composite puts it back on the
+recomputation through networks.ManyDepth.cost_volume_planes, A/B).  The composites
 are ordinary differentiable torch code, so they are also what the parity tests differentiate numerically (tests/test_autograd.py:
 fp64 finite differences on CPU; on the GPU the composite forward must reproduce the HIP forward to 1e-4, which makes its gradient
 the gradient of the kernels' function) and the second reference of the HIP backward's tests.
@@ -464,13 +465,20 @@ class SupervisionScatterFunction(torch.autograd.Function):
         return d_occ, None, None, None, None, None
 
 
-# ---- depth module, the plane sweep: HIP forward + composite backward -------------------------------------------------------------
+# ---- depth module, the plane sweep: HIP forward + HIP backward --------------------------------------------------------------------
+def cost_volume_backward_mode():
+    """'hip' (default) or 'composite' (env MCR_COST_VOLUME_BWD=composite: the recomputing torch backward, for A/B comparisons)."""
+    return "composite" if os.environ.get("MCR_COST_VOLUME_BWD", "").lower() == "composite" else "hip"
+
+
 class CostVolumeFunction(torch.autograd.Function):
     """apply(x, x_alpha, cams, depth_bins, H, W, fov_scale, concat) -> the cost volume [B,D,Hf,Wf] of ops.cost_volume (mcr_cost_volume)
     without a graph, or with concat the buffer [B,C+D,Hf,Wf] = cat(x, cost volume) of ManyDepth.py:299, the volume written in place
-    by the kernel.  backward = autograd through networks.ManyDepth.cost_volume_planes (plain torch on the same device, recomputed
-    PLANE_CHUNK planes at a time so that its intermediates stay bounded), for x and x_alpha; the cameras and the bins are constants of
-    the graph.  Differentiable once.  (A HIP backward is open: the x_alpha gradient is a scatter.)"""
+    by the kernel.  backward = ops.cost_volume_backward (mcr_cost_volume_backward, cost_volume_bwd.hip: no floating-point atomics, the
+    same bits on every run) for x and x_alpha, each computed only if its input needs it; the cameras and the bins are constants of
+    the graph.  With cost_volume_backward_mode() == 'composite' the backward is autograd through networks.ManyDepth.cost_volume_planes
+    instead (plain torch on the same device, recomputed PLANE_CHUNK planes at a time so that its intermediates stay bounded).
+    Differentiable once."""
 
     PLANE_CHUNK = 8
 
@@ -492,11 +500,18 @@ class CostVolumeFunction(torch.autograd.Function):
     def backward(ctx, grad_out):
         if torch.is_grad_enabled():
             raise RuntimeError("the cost volume is differentiable once: its backward recomputes without a graph (create_graph is not supported)")
-        from .networks.ManyDepth import cost_volume_planes
         x, x_alpha, cams, depth_bins = ctx.saved_tensors
         C = x.shape[1]
         g_cv = grad_out[:, C:] if ctx.concat else grad_out
         need = ctx.needs_input_grad[:2]
+        if cost_volume_backward_mode() == "hip":
+            from . import ops
+            d_x, d_xa = (None, None) if not any(need) else ops.cost_volume_backward(
+                x, x_alpha, cams, depth_bins, g_cv.float(), ctx.H, ctx.W, ctx.fov_scale, need_x=need[0], need_x_alpha=need[1])
+            if ctx.concat and need[0]:
+                d_x += grad_out[:, :C]
+            return (d_x, d_xa, None, None, None, None, None, None)
+        from .networks.ManyDepth import cost_volume_planes
         grads = [None, None]
         with torch.enable_grad():
             ins = [t.detach().requires_grad_(n) for t, n in zip((x, x_alpha), need)]

@@ -16,31 +16,9 @@
 //     the 4 chains are independent (branch-free: outside corners are read at a clamped address with weight 0) and hide each other's
 //     latency.
 // No atomics; every sum has a fixed order (sources ascending, corners nw ne sw se, the row butterflies), so two runs give the same bits.
-#include "common.h"
-#include <math.h>
+#include "cost_volume.h"
 
 namespace mcr {
-
-constexpr int CV_C = 64;                             // feature channels: 16 lanes x float4
-constexpr int CV_PLANES = 4;                         // depth planes per workgroup (126 VGPRs: four waves per SIMD; 8 planes need 231)
-constexpr int CV_POS = 16;                           // output positions per workgroup (256 threads)
-
-// Sum over the 16 lanes of a DPP row, the total in EVERY lane of the row with the same bits (each step adds the same two numbers in both
-// partners): xor 1, xor 2 inside the quads, then the quads of a half mirrored, then the halves mirrored.
-__device__ __forceinline__ float row16_sum_all(float v) {
-    v += dpp_mov0<0xB1>(v);                          // quad_perm:[1,0,3,2]
-    v += dpp_mov0<0x4E>(v);                          // quad_perm:[2,3,0,1]
-    v += dpp_mov0<0x141>(v);                         // row_half_mirror
-    v += dpp_mov0<0x140>(v);                         // row_mirror
-    return v;
-}
-
-// Cubic convolution weight of tap r (0..3) at fraction t, A = -0.75 (upsample_bicubic2d's get_cubic_upsample_coefficients).
-__device__ __forceinline__ double cubic_weight(double t, int r) {
-    const double A = -0.75;
-    const double x = r == 0 ? t + 1.0 : r == 1 ? t : r == 2 ? 1.0 - t : 2.0 - t;
-    return (r == 0 || r == 3) ? ((A * x - 5.0 * A) * x + 8.0 * A) * x - 4.0 * A : ((A + 2.0) * x - (A + 3.0)) * x * x + 1.0;
-}
 
 // [img, 64, P] -> [img, P, 64] through a 64 x 64 LDS tile (padded: the transposed read is conflict-free).  The first workgroup of an
 // image (b, a) also writes its pose, 12 doubles: M = R^T R_a (row-major) and t = T_a - T M, so that the source-view point of the target-view
@@ -86,68 +64,8 @@ __global__ __launch_bounds__(256) void cv_sweep_kernel(const float* __restrict__
     const int pos = valid ? pos_raw : P - 1;          // a row past the end repeats the last position (every lane stays in the butterflies)
     const int b = blockIdx.z;
     const int k0 = blockIdx.y * CV_PLANES;
-    const int i = pos / Wf, j = pos - i * Wf;
-
-    // ---- this lane's bicubic tap: full-resolution pixel (p, q), weight wy[r] * wx[c] (align_corners = False, indices clamped) ----
-    const int r = lane >> 2, c = lane & 3;
-    const double sy = (i + 0.5) * ((double)H / Hf) - 0.5, sx = (j + 0.5) * ((double)W / Wf) - 0.5;
-    const double fy = floor(sy), fx = floor(sx);
-    const int p = min(max((int)fy - 1 + r, 0), H - 1), q = min(max((int)fx - 1 + c, 0), W - 1);
-    const float wgt = (float)(cubic_weight(sy - fy, r) * cubic_weight(sx - fx, c));
-    const int m = min(H, W), mf = min(Hf, Wf);
-    const double s = (double)fov_scale;
-    const double nx = ((double)W / m - 2.0 * q / (m - 1)) / s, ny = ((double)H / m - 2.0 * p / (m - 1)) / s;
-    const float cx = (float)(-((double)mf / Wf) * s), cy = (float)(-((double)mf / Hf) * s);
-
-    float dk[CV_PLANES];
-#pragma unroll
-    for (int kk = 0; kk < CV_PLANES; ++kk) dk[kk] = bins[min(k0 + kk, D - 1)];   // planes past the end repeat the last one; not stored
-
     float4 acc[CV_PLANES];
-#pragma unroll
-    for (int kk = 0; kk < CV_PLANES; ++kk) acc[kk] = make_float4(0.f, 0.f, 0.f, 0.f);
-
-    const float fWf = (float)Wf, fHf = (float)Hf;
-    for (int a = 0; a < A; ++a) {
-        const double* ps = pose + ((size_t)b * A + a) * 12;          // wave-uniform
-        float u[3], t[3];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            u[k] = (float)(nx * ps[k] + ny * ps[3 + k] + ps[6 + k]);
-            t[k] = (float)ps[9 + k];
-        }
-        const float* base = xa_cl + ((size_t)b * A + a) * (size_t)P * CV_C + lane * 4;
-#pragma unroll
-        for (int kk = 0; kk < CV_PLANES; ++kk) {
-            const float d = dk[kk];
-            const float vx = fmaf(d, u[0], t[0]), vy = fmaf(d, u[1], t[1]), vz = fmaf(d, u[2], t[2]);
-            const float aw = fmaxf(fabsf(vz), 1e-8f);
-            const float w = vz < 0.f ? -aw : aw;     // sign(w) * max(|w|, eps), sign(0) taken as +1
-            const float gx = row16_sum_all(wgt * ((cx * vx) / w));
-            const float gy = row16_sum_all(wgt * ((cy * vy) / w));
-            float px = ((gx + 1.f) * fWf - 1.f) * 0.5f, py = ((gy + 1.f) * fHf - 1.f) * 0.5f;
-            // decided in floating point, before any conversion: NaN, infinities and anything whose four corners all lie outside fail
-            // this test and contribute zero (weights 0, address of pixel (0, 0))
-            const bool in = px > -1.f && px < fWf && py > -1.f && py < fHf;
-            px = in ? px : 0.f;
-            py = in ? py : 0.f;
-            const float flx = floorf(px), fly = floorf(py);
-            const int x0 = (int)flx, y0 = (int)fly;   // in [-1, size - 1]
-            const float wx1 = px - flx, wx0 = (flx + 1.f) - px, wy1 = py - fly, wy0 = (fly + 1.f) - py;
-            const bool x0in = in && x0 >= 0, x1in = in && x0 + 1 < Wf, y0in = y0 >= 0, y1in = y0 + 1 < Hf;
-            const int x0c = max(x0, 0), x1c = min(x0 + 1, Wf - 1), y0c = max(y0, 0), y1c = min(y0 + 1, Hf - 1);
-            const float w00 = (x0in && y0in) ? wx0 * wy0 : 0.f, w01 = (x1in && y0in) ? wx1 * wy0 : 0.f;
-            const float w10 = (x0in && y1in) ? wx0 * wy1 : 0.f, w11 = (x1in && y1in) ? wx1 * wy1 : 0.f;
-            const float4 f00 = *(const float4*)(base + ((size_t)y0c * Wf + x0c) * CV_C);
-            const float4 f01 = *(const float4*)(base + ((size_t)y0c * Wf + x1c) * CV_C);
-            const float4 f10 = *(const float4*)(base + ((size_t)y1c * Wf + x0c) * CV_C);
-            const float4 f11 = *(const float4*)(base + ((size_t)y1c * Wf + x1c) * CV_C);
-            acc[kk].x += ((f00.x * w00 + f01.x * w01) + f10.x * w10) + f11.x * w11;
-            acc[kk].y += ((f00.y * w00 + f01.y * w01) + f10.y * w10) + f11.y * w11;
-            acc[kk].z += ((f00.z * w00 + f01.z * w01) + f10.z * w10) + f11.z * w11;
-            acc[kk].w += ((f00.w * w00 + f01.w * w01) + f10.w * w10) + f11.w * w11;
-        }
-    }
+    cv_sweep_row<false>(xa_cl, pose, bins, nullptr, b, k0, pos, valid, lane, A, H, W, Hf, Wf, D, fov_scale, acc);
 
     // ---- mean over the sources, L1 distance to the target features over the 64 channels ----
     const float* xt = x + ((size_t)b * CV_C + lane * 4) * (size_t)P + pos;
@@ -160,6 +78,11 @@ __global__ __launch_bounds__(256) void cv_sweep_kernel(const float* __restrict__
         const float tot = row16_sum_all(part);
         if (lane == 0 && valid && k0 + kk < D) out[(size_t)b * out_batch_stride + (size_t)(k0 + kk) * P + pos] = tot * (1.f / CV_C);
     }
+}
+
+void cv_launch_channels_last(const float* x_alpha, float* xa_cl, int P, const float* cams, int64_t B, int A, double* pose, hipStream_t stream) {
+    hipLaunchKernelGGL(cv_channels_last_kernel, dim3((unsigned)cdiv(P, 64), (unsigned)(B * A)), dim3(256), 0, stream, x_alpha, xa_cl, P, cams, A,
+                       pose);
 }
 
 }  // namespace mcr
@@ -193,8 +116,7 @@ extern "C" int mcr_cost_volume(const float* x, const float* x_alpha, const float
     const int P = Hf * Wf;
     float* xa_cl = (float*)workspace;
     double* pose = (double*)(xa_cl + (size_t)B * A * CV_C * P);       // 256-byte multiple from an aligned base
-    hipLaunchKernelGGL(cv_channels_last_kernel, dim3((unsigned)cdiv(P, 64), (unsigned)(B * A)), dim3(256), 0, (hipStream_t)stream, x_alpha, xa_cl,
-                       P, cams, A, pose);
+    cv_launch_channels_last(x_alpha, xa_cl, P, cams, B, A, pose, (hipStream_t)stream);
     MCR_LAUNCH_CHECK("cv_channels_last_kernel");
     hipLaunchKernelGGL(cv_sweep_kernel, dim3((unsigned)cdiv(P, CV_POS), (unsigned)cdiv(D, CV_PLANES), (unsigned)B), dim3(256), 0,
                        (hipStream_t)stream, x, xa_cl, pose, depth_bins, out, out_batch_stride, A, H, W, Hf, Wf, D, fov_scale);

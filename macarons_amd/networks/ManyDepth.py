@@ -9,8 +9,9 @@ Needs neither PyTorch3D nor torchvision: a camera is its R, T (PyTorch3D's row-v
 60 degree field of view upstream never overrides; znear and zfar drop out of the sweep (they only shape the z the projection returns,
 which upstream discards, and the scaled depth the unprojection immediately inverts).
 
+The backward is HIP as well (ops.cost_volume_backward -> mcr_cost_volume_backward, csrc/cost_volume_bwd.hip, behind CostVolumeFunction).
 `cost_volume_composite` is the same mathematics in plain differentiable torch, chunked over the planes: what CostVolumeFunction
-differentiates (autograd.py) and what the tests hold against an independent fp64 model.
+differentiates instead under MCR_COST_VOLUME_BWD=composite (autograd.py) and what the tests hold against an independent fp64 model.
 """
 import torch
 import torch.nn.functional as F

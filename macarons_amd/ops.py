@@ -1671,3 +1671,39 @@ def cost_volume(x, x_alpha, cams, depth_bins, H, W, fov_scale=COST_VOLUME_FOV_SC
                                 c_i64(B), c_int(A), c_int(C), c_int(int(H)), c_int(int(W)), c_int(Hf), c_int(Wf), c_int(D),
                                 c_f32(float(fov_scale)), _p(ws), c_size(ws.numel()), _stream()), "mcr_cost_volume")
     return out
+
+
+def cost_volume_backward(x, x_alpha, cams, depth_bins, d_out, H, W, fov_scale=COST_VOLUME_FOV_SCALE, need_x=True, need_x_alpha=True):
+    """(d_x [B,64,Hf,Wf] | None, d_x_alpha [B,A,64,Hf,Wf] | None): the gradients of cost_volume's x and x_alpha for the upstream gradient
+    d_out [B,D,Hf,Wf], in one entry (mcr_cost_volume_backward, csrc/cost_volume_bwd.hip); the cameras and the bins are constants.  d_out's
+    batches may be strided -- channels C.. of the gradient of a [B,C+D,Hf,Wf] buffer.  A gradient that is not needed is not computed
+    (the x_alpha half is the expensive one).  No floating-point atomics: two calls give the same bits.  A d_out that is not finite gives
+    gradients of NaN."""
+    x, x_alpha, cams, depth_bins = _req(x, "x"), _req(x_alpha, "x_alpha"), _req(cams, "cams"), _req(depth_bins, "depth_bins")
+    if x.dim() != 4 or x_alpha.dim() != 5:
+        raise ValueError(f"x must be [B,C,Hf,Wf] and x_alpha [B,A,C,Hf,Wf]; got {tuple(x.shape)}, {tuple(x_alpha.shape)}")
+    B, C, Hf, Wf = x.shape
+    A, D = x_alpha.shape[1], depth_bins.numel()
+    if tuple(x_alpha.shape) != (B, A, C, Hf, Wf):
+        raise ValueError(f"x_alpha must be [B,A,C,Hf,Wf] = {(B, A, C, Hf, Wf)}, got {tuple(x_alpha.shape)}")
+    if tuple(cams.shape) != (B, 1 + A, 12):
+        raise ValueError(f"cams must be [B,1+A,12] = {(B, 1 + A, 12)}, got {tuple(cams.shape)}")
+    if not isinstance(d_out, torch.Tensor) or not d_out.is_cuda or d_out.device != x.device or d_out.dtype != torch.float32:
+        raise MacaronsHipError("d_out must be a float32 tensor on x's HIP device")
+    if tuple(d_out.shape) != (B, D, Hf, Wf):
+        raise ValueError(f"d_out must be [B,D,Hf,Wf] = {(B, D, Hf, Wf)}, got {tuple(d_out.shape)}")
+    if not need_x and not need_x_alpha:
+        raise ValueError("cost_volume_backward: nothing to do, neither gradient is needed")
+    if B * D * Hf * Wf and (d_out[0].stride() != (Hf * Wf, Wf, 1) or (B > 1 and d_out.stride(0) < D * Hf * Wf)):
+        d_out = d_out.contiguous()
+    d_x = torch.empty_like(x) if need_x else None
+    d_xa = torch.empty_like(x_alpha) if need_x_alpha else None
+    L = lib()
+    ws = _workspace(x.device, max(int(L.mcr_cost_volume_backward_workspace_bytes(c_i64(B), c_i64(A), c_i64(C), c_i64(Hf), c_i64(Wf), c_i64(D))), 4))
+    with torch.cuda.device(x.device):
+        check(L.mcr_cost_volume_backward(_p(x), _p(x_alpha), _p(cams), _p(depth_bins), _p(d_out),
+                                         c_i64(d_out.stride(0) if B > 1 else D * Hf * Wf), _p(d_x) if need_x else None,
+                                         _p(d_xa) if need_x_alpha else None, c_i64(B), c_int(A), c_int(C), c_int(int(H)), c_int(int(W)),
+                                         c_int(Hf), c_int(Wf), c_int(D), c_f32(float(fov_scale)), _p(ws), c_size(ws.numel()), _stream()),
+              "mcr_cost_volume_backward")
+    return d_x, d_xa
