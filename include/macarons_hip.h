@@ -766,6 +766,43 @@ int mcr_cost_volume_backward(const float* x, const float* x_alpha, const float* 
                              int64_t d_out_batch_stride, float* d_x, float* d_x_alpha, int64_t B, int A, int C, int H, int W, int Hf, int Wf,
                              int D, float fov_scale, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- the photometric reconstruction loss of the depth module (macarons/utility/macarons_utils.py:1091-1187 get_reconstruction_loss_fn,
+ * with reproject_depth_map / warp of macarons/networks/ManyDepth.py:111-205 and SSIM of :809-842), fused (reconstruction_loss.hip).
+ *
+ * mcr_reconstruction_loss: loss[s] of S depth maps in one call, replacing per scale: the unprojection and projection, F.grid_sample, the
+ *   transpositions, the five average pools over reflection-padded copies, the elementwise chain, the min over the sources and the
+ *   masked sum.  images [B,H,W,3], alpha_images [B,A,H,W,3], mask [B,H,W] bytes (non-zero = inside) or NULL, cams [B,1+A,12] as for
+ *   mcr_cost_volume, depth [S,B,H,W].  Per pixel (p,q): d = mask ? depth : zfar (a masked-out pixel still warps, at zfar, and still
+ *   feeds its neighbours' windows); ray per unit depth ((W/m - 2q/(m-1))/fov_scale, (H/m - 2p/(m-1))/fov_scale, 1), m = min(H,W);
+ *   source-view point v, w = sign(v_z) max(|v_z|, 1e-8), grid (-(m/W) fov_scale v_x/w, -(m/H) fov_scale v_y/w); bilinear sample,
+ *   align_corners = False, padding_mode 0 = zeros or 1 = border; l1_a = mean_c |I - Iw_a|; ssim_a = mean_c clamp((1 - n/d)/2, 0, 1)
+ *   over 3x3 windows of the reflection-padded images (C1 = 1e-4, C2 = 9e-4), the window statistics computed centred on the window's
+ *   means; loss_a = ssim_factor ssim_a + (1 - ssim_factor) l1_a (ssim_factor = 0 skips the SSIM part); the min over a, the lowest index
+ *   on a tie.  With a mask loss[s] = sum_b sum_p sel mask / (sum_p mask + 1e-7) -- the per-image means SUMMED over the batch, as
+ *   upstream has it -- and without one the mean over B H W.  loss_map [S,B,H,W] (the selected loss of every pixel) and argmin
+ *   [S,B,H,W] bytes (its source) are written when not NULL.  The pixel coordinate is computed in double (an fp32 coordinate near 456
+ *   is spaced 3e-5 apart, which the SSIM gradient magnifies to 1e-3), the samples and the loss in fp32.  A pixel coordinate that is not
+ *   finite AS AN FP32 VALUE samples nothing in either padding mode (value 0, no address formed from it; torch leaves the clamp of a NaN
+ *   unspecified) -- a finite grid coordinate whose pixel coordinate overflows fp32 included.  Refused before any launch: A outside
+ *   1..8, H or W below 2, another padding mode, a workspace that is short or not 16-byte aligned, sizes whose products overflow an
+ *   index (S, B <= 65535).  No floating-point atomics: every workgroup stores one partial, a second launch of one workgroup adds them
+ *   in a fixed order.  workspace: the partials.
+ * mcr_reconstruction_loss_backward: d_depth [S,B,H,W] = d (sum_s d_loss[s] loss[s]) / d depth; images, cameras and mask are constants.
+ *   A gather per pixel that recomputes coordinates, samples and selection with the forward's device code (the same bits), no atomics:
+ *   two calls give the same bits.  A masked-out pixel's d_depth is exactly 0; the gradient of |x - y| at 0 is 0; a coordinate held by
+ *   border's clamp, and the w held by the 1e-8 clamp, pass no gradient.  Same refusals.  workspace: the mask counts of every image.
+ * The size functions return 0 for sizes that the entries refuse. */
+size_t mcr_reconstruction_loss_workspace_bytes(int64_t S, int64_t B, int64_t A, int64_t H, int64_t W);
+int mcr_reconstruction_loss(const float* images, const float* alpha_images, const unsigned char* mask, const float* cams,
+                            const float* depth, float* loss, float* loss_map, unsigned char* argmin, int64_t S, int64_t B, int A, int H,
+                            int W, float fov_scale, float zfar, float ssim_factor, int padding_mode, void* workspace,
+                            size_t workspace_bytes, void* stream);
+size_t mcr_reconstruction_loss_backward_workspace_bytes(int64_t S, int64_t B, int64_t A, int64_t H, int64_t W);
+int mcr_reconstruction_loss_backward(const float* images, const float* alpha_images, const unsigned char* mask, const float* cams,
+                                     const float* depth, const float* d_loss, float* d_depth, int64_t S, int64_t B, int A, int H, int W,
+                                     float fov_scale, float zfar, float ssim_factor, int padding_mode, void* workspace,
+                                     size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

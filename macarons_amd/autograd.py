@@ -15,7 +15,8 @@ for the surface points pc is not computed there, so a forward whose pc requires 
 (ops.macarons_gain_indexed / macarons_gain_) is HIP both ways as well: MacaronsGainFunction below, backward mcr_macarons_gain_backward, with
 gradients for the per-point visibility gains and the volumes and for nothing else.  The depth module's plane sweep (ops.cost_volume)
 is HIP both ways too (CostVolumeFunction below: mcr_cost_volume_backward; env MCR_COST_VOLUME_BWD=composite puts it back on the
-recomputation through networks.ManyDepth.cost_volume_planes, A/B).  The composites
+recomputation through networks.ManyDepth.cost_volume_planes, A/B), and so is the depth module's photometric reconstruction loss
+(ReconstructionLossFunction: mcr_reconstruction_loss_backward, for the depth alone; env MCR_RECONSTRUCTION_LOSS_BWD=composite).  The composites
 are ordinary differentiable torch code, so they are also what the parity tests differentiate numerically (tests/test_autograd.py:
 fp64 finite differences on CPU; on the GPU the composite forward must reproduce the HIP forward to 1e-4, which makes its gradient
 the gradient of the kernels' function) and the second reference of the HIP backward's tests.
@@ -524,3 +525,46 @@ class CostVolumeFunction(torch.autograd.Function):
         if ctx.concat and need[0]:
             grads[0] = grads[0] + grad_out[:, :C]
         return (grads[0], grads[1], None, None, None, None, None, None)
+
+
+# ---- depth module, the photometric reconstruction loss: HIP forward + HIP backward --------------------------------------------------
+def reconstruction_loss_backward_mode():
+    """'hip' (default) or 'composite' (env MCR_RECONSTRUCTION_LOSS_BWD=composite: the recomputing torch backward, for A/B comparisons)."""
+    return "composite" if os.environ.get("MCR_RECONSTRUCTION_LOSS_BWD", "").lower() == "composite" else "hip"
+
+
+class ReconstructionLossFunction(torch.autograd.Function):
+    """apply(depth, images, alpha_images, mask, cams, zfar, ssim_factor, padding_mode, fov_scale) -> loss [S] of ops.reconstruction_loss
+    (mcr_reconstruction_loss).  backward = ops.reconstruction_loss_backward (mcr_reconstruction_loss_backward: a gather per pixel, no
+    atomics, the same bits on every run) for depth [S,B,H,W] and for nothing else: the images, the mask and the cameras are constants of
+    the graph.  With reconstruction_loss_backward_mode() == 'composite' the backward is autograd through
+    networks.ManyDepth.reconstruction_loss_composite instead (plain torch on the same device).  Differentiable once."""
+
+    @staticmethod
+    def forward(ctx, depth, images, alpha_images, mask, cams, zfar, ssim_factor, padding_mode, fov_scale):
+        from . import ops
+        ctx.zfar, ctx.ssim_factor, ctx.padding_mode, ctx.fov_scale = float(zfar), float(ssim_factor), padding_mode, float(fov_scale)
+        ctx.has_mask = mask is not None
+        ctx.save_for_backward(depth, images, alpha_images, cams, *((mask,) if mask is not None else ()))
+        with torch.no_grad():
+            return ops.reconstruction_loss(images, alpha_images, mask, cams, depth, zfar, ssim_factor, padding_mode, fov_scale)
+
+    @staticmethod
+    def backward(ctx, grad_loss):
+        if torch.is_grad_enabled():
+            raise RuntimeError("the reconstruction loss is differentiable once: its backward recomputes without a graph "
+                               "(create_graph is not supported)")
+        depth, images, alpha_images, cams = ctx.saved_tensors[:4]
+        mask = ctx.saved_tensors[4] if ctx.has_mask else None
+        none = (None,) * 8
+        if not ctx.needs_input_grad[0]:
+            return (None,) + none
+        if reconstruction_loss_backward_mode() == "hip":
+            from . import ops
+            return (ops.reconstruction_loss_backward(images, alpha_images, mask, cams, depth, grad_loss.float().contiguous(), ctx.zfar,
+                                                     ctx.ssim_factor, ctx.padding_mode, ctx.fov_scale),) + none
+        from .networks.ManyDepth import reconstruction_loss_composite
+        with torch.enable_grad():
+            d = depth.detach().requires_grad_(True)
+            loss = reconstruction_loss_composite(images, alpha_images, mask, cams, d, ctx.zfar, ctx.ssim_factor, ctx.padding_mode, ctx.fov_scale)
+            return tuple(torch.autograd.grad(loss, (d,), grad_loss)) + none

@@ -2,8 +2,10 @@
 forward builds the cost volume with one fused entry (ops.cost_volume -> mcr_cost_volume, csrc/cost_volume.hip) instead of upstream's
 cameras / unprojection / projection / bicubic resize / 96-fold feature copy / grid_sample / mean / norm sequence, and the seam that puts
 an existing upstream instance on that path (`adopt_cost_volume_builder`).  The rest of the depth network -- the ResNet encoder and
-decoder, the pose decoder, `apply_depth_model`, the reconstruction loss with its own calls of `reproject_depth_map` / `warp` -- is
-convolutions the vendor library serves and stays upstream's.
+decoder, the pose decoder, `apply_depth_model` -- is convolutions the vendor library serves and stays upstream's.  The photometric
+reconstruction loss is fused on HIP as well (ops.reconstruction_loss -> mcr_reconstruction_loss, csrc/reconstruction_loss.hip, behind
+utility.macarons_utils.get_reconstruction_loss_fn); `reconstruction_loss_composite` below is the same mathematics in plain
+differentiable torch, for the cases the entry does not take and for the tests.
 
 Needs neither PyTorch3D nor torchvision: a camera is its R, T (PyTorch3D's row-vector convention, view = world @ R + T) and the default
 60 degree field of view upstream never overrides; znear and zfar drop out of the sweep (they only shape the z the projection returns,
@@ -68,6 +70,76 @@ def cost_volume_composite(x, x_alpha, cams, depth_bins, H, W, fov_scale=COST_VOL
     D = depth_bins.numel()
     return torch.cat([cost_volume_planes(x, x_alpha, cams, depth_bins[k:k + plane_chunk], H, W, fov_scale)
                       for k in range(0, D, plane_chunk)], 1)
+
+
+def _window_moments(x, y):
+    """x, y [N,C,H,W] -> (mu_x, mu_y, sigma_x, sigma_y, sigma_xy) over the 3x3 windows of the reflection-padded images, the second
+    moments centred on the window's means (upstream's E[y^2] - mu^2 cancels in flat regions, where sigma is small next to C2)."""
+    px = F.pad(x, (1, 1, 1, 1), mode="reflect").unfold(2, 3, 1).unfold(3, 3, 1)                            # [N,C,H,W,3,3] views
+    py = F.pad(y, (1, 1, 1, 1), mode="reflect").unfold(2, 3, 1).unfold(3, 3, 1)
+    mu_x, mu_y = px.mean((-1, -2)), py.mean((-1, -2))
+    dx, dy = px - mu_x[..., None, None], py - mu_y[..., None, None]
+    return mu_x, mu_y, (dx * dx).mean((-1, -2)), (dy * dy).mean((-1, -2)), (dx * dy).mean((-1, -2))
+
+
+def ssim_loss(x, y):
+    """upstream's SSIM.forward (ManyDepth.py:828-842) of x, y [N,C,H,W], with centred window moments."""
+    C1, C2 = 0.01 ** 2, 0.03 ** 2
+    mu_x, mu_y, s_x, s_y, s_xy = _window_moments(x, y)
+    n = (2 * mu_x * mu_y + C1) * (2 * s_xy + C2)
+    d = (mu_x ** 2 + mu_y ** 2 + C1) * (s_x + s_y + C2)
+    return torch.clamp((1 - n / d) / 2, 0, 1)
+
+
+def reconstruction_loss_composite(images, alpha_images, mask, cams, depth, zfar, ssim_factor, padding_mode="border",
+                                  fov_scale=COST_VOLUME_FOV_SCALE, return_map=False, ssim_loss_fn=None):
+    """ops.reconstruction_loss in plain torch (any device, depth's dtype; differentiable in depth and in the cameras): upstream's
+    reconstruction_loss_fn (macarons_utils.py:1120-1185) for S depth maps.  images [B,H,W,3], alpha_images [B,A,H,W,3], mask [B,H,W]
+    bool or None, cams [B,1+A,12], depth [S,B,H,W] -> loss [S] (return_map: also the selected per-pixel loss [S,B,H,W] and its source
+    index).  Also what serves the cases the entry does not take: padding_mode 'reflection', cameras that require a gradient, another
+    field of view than upstream's default (through fov_scale), an ssim_loss_fn(x, y) of the caller's (None: `ssim_loss` above)."""
+    S, B, H, W = depth.shape
+    A = alpha_images.shape[1]
+    dt, dev, s, f = depth.dtype, depth.device, float(fov_scale), float(ssim_factor)
+    cams = cams.to(dt)
+    R, T = cams[:, 0, :9].reshape(B, 3, 3), cams[:, 0, 9:]
+    Ra, Ta = cams[:, 1:, :9].reshape(B, A, 3, 3), cams[:, 1:, 9:]
+    m = min(H, W)
+    nx = (W / m - 2.0 * torch.arange(W, dtype=dt, device=dev) / (m - 1)) / s
+    ny = (H / m - 2.0 * torch.arange(H, dtype=dt, device=dev) / (m - 1)) / s
+    n = torch.stack((nx[None, :].expand(H, W), ny[:, None].expand(H, W), torch.ones(H, W, dtype=dt, device=dev)), -1)
+    M = torch.einsum("bij,baik->bajk", R, Ra)
+    u = torch.einsum("hwj,bajk->bahwk", n, M)
+    t = Ta - torch.einsum("bj,bajk->bak", T, M)
+    d = depth if mask is None else torch.where(mask[None], depth, torch.full_like(depth, float(zfar)))
+    x = images.to(dt).permute(0, 3, 1, 2)[:, None].expand(B, A, 3, H, W).reshape(B * A, 3, H, W)
+    src = alpha_images.to(dt).reshape(B * A, H, W, 3).permute(0, 3, 1, 2)
+    losses, maps, idxs = [], [], []
+    for k in range(S):
+        v = d[k][:, None, :, :, None] * u + t[:, :, None, None, :]                                         # [B,A,H,W,3]
+        w = v[..., 2]
+        w = torch.where(w < 0, -torch.ones_like(w), torch.ones_like(w)) * w.abs().clamp(min=1e-8)
+        g = torch.stack(((-(m / W) * s) * v[..., 0] / w, (-(m / H) * s) * v[..., 1] / w), -1).reshape(B * A, H, W, 2)
+        # a PIXEL coordinate that is not finite samples nothing -- decided where the entry decides it, on the coordinate rounded to this
+        # dtype, so a finite grid coordinate whose pixel coordinate overflows counts as not finite in both; a distant finite one is brought to where
+        # grid_sample converts it safely (border: still the border pixel, zeros: still nothing)
+        ok = torch.isfinite((((g.double() + 1) * g.new_tensor([W, H], dtype=torch.float64) - 1) / 2).to(dt)).all(-1)
+        g = torch.where(ok[..., None], g, torch.zeros_like(g))
+        g = torch.where(g.abs() < 1e6, g, torch.full_like(g, -3.0) if padding_mode == "zeros" else g.detach().clamp(-1e6, 1e6))
+        y = F.grid_sample(src, g, mode="bilinear", padding_mode=padding_mode, align_corners=False) * ok[:, None].to(dt)
+        loss = (x - y).abs().mean(1)
+        if f > 0:
+            loss = f * (ssim_loss if ssim_loss_fn is None else ssim_loss_fn)(x, y).mean(1) + (1 - f) * loss
+        sel, idx = torch.min(loss.reshape(B, A, H, W), dim=1)
+        if mask is not None:
+            mk = mask.to(dt)
+            losses.append((sel * mk / (mk.sum((1, 2), keepdim=True) + 1e-7)).sum())
+        else:
+            losses.append(sel.mean())
+        maps.append(sel), idxs.append(idx)
+    if return_map:
+        return torch.stack(losses), torch.stack(maps), torch.stack(idxs)
+    return torch.stack(losses)
 
 
 def _forward(self, x, R, T, zfar, x_alpha, R_alpha, T_alpha, zfar_alpha, device=None, return_cost_volume=False):

@@ -1707,3 +1707,69 @@ def cost_volume_backward(x, x_alpha, cams, depth_bins, d_out, H, W, fov_scale=CO
                                          c_int(Hf), c_int(Wf), c_int(D), c_f32(float(fov_scale)), _p(ws), c_size(ws.numel()), _stream()),
               "mcr_cost_volume_backward")
     return d_x, d_xa
+
+
+# ---- depth module: the photometric reconstruction loss ------------------------------------------------------------------------------
+RECONSTRUCTION_PADDING_MODES = {"zeros": 0, "border": 1}
+
+
+def _reconstruction_args(images, alpha_images, mask, cams, depth, padding_mode):
+    images, alpha_images, cams, depth = _req(images, "images"), _req(alpha_images, "alpha_images"), _req(cams, "cams"), _req(depth, "depth")
+    if images.dim() != 4 or images.shape[-1] != 3 or alpha_images.dim() != 5 or depth.dim() != 4:
+        raise ValueError(f"images must be [B,H,W,3], alpha_images [B,A,H,W,3] and depth [S,B,H,W]; got {tuple(images.shape)}, "
+                         f"{tuple(alpha_images.shape)}, {tuple(depth.shape)}")
+    B, H, W, _ = images.shape
+    A, S = alpha_images.shape[1], depth.shape[0]
+    if tuple(alpha_images.shape) != (B, A, H, W, 3):
+        raise ValueError(f"alpha_images must be [B,A,H,W,3] = {(B, A, H, W, 3)}, got {tuple(alpha_images.shape)}")
+    if tuple(depth.shape) != (S, B, H, W):
+        raise ValueError(f"depth must be [S,B,H,W] = {(S, B, H, W)}, got {tuple(depth.shape)}")
+    if tuple(cams.shape) != (B, 1 + A, 12):
+        raise ValueError(f"cams must be [B,1+A,12] = {(B, 1 + A, 12)}, got {tuple(cams.shape)}")
+    if mask is not None:
+        mask = _req(mask, "mask", torch.bool)
+        if tuple(mask.shape) != (B, H, W):
+            raise ValueError(f"mask must be [B,H,W] = {(B, H, W)}, got {tuple(mask.shape)}")
+    if padding_mode not in RECONSTRUCTION_PADDING_MODES:
+        raise ValueError(f"padding_mode must be one of {sorted(RECONSTRUCTION_PADDING_MODES)} here, got {padding_mode!r} "
+                         "(networks.ManyDepth.reconstruction_loss_composite takes 'reflection')")
+    return images, alpha_images, mask, cams, depth, (S, B, A, H, W), RECONSTRUCTION_PADDING_MODES[padding_mode]
+
+
+def reconstruction_loss(images, alpha_images, mask, cams, depth, zfar, ssim_factor, padding_mode="border", fov_scale=COST_VOLUME_FOV_SCALE,
+                        return_map=False):
+    """loss [S] of upstream's reconstruction_loss_fn (macarons_utils.py:1120-1185) for S depth maps in one entry (mcr_reconstruction_loss):
+    images [B,H,W,3], alpha_images [B,A,H,W,3], mask [B,H,W] bool or None (None = params.use_depth_mask False), cams [B,1+A,12]
+    (networks.ManyDepth.pack_cameras), depth [S,B,H,W]; padding_mode 'zeros' or 'border'.  return_map: (loss, loss_map [S,B,H,W] the
+    selected per-pixel loss, argmin [S,B,H,W] uint8 its source)."""
+    images, alpha_images, mask, cams, depth, (S, B, A, H, W), mode = _reconstruction_args(images, alpha_images, mask, cams, depth, padding_mode)
+    loss = torch.empty((S,), dtype=torch.float32, device=images.device)
+    lmap = torch.empty((S, B, H, W), dtype=torch.float32, device=images.device) if return_map else None
+    amin = torch.empty((S, B, H, W), dtype=torch.uint8, device=images.device) if return_map else None
+    L = lib()
+    ws = _workspace(images.device, max(int(L.mcr_reconstruction_loss_workspace_bytes(c_i64(S), c_i64(B), c_i64(A), c_i64(H), c_i64(W))), 4))
+    with torch.cuda.device(images.device):
+        check(L.mcr_reconstruction_loss(_p(images), _p(alpha_images), _p(mask) if mask is not None else None, _p(cams), _p(depth), _p(loss),
+                                        _p(lmap) if return_map else None, _p(amin) if return_map else None, c_i64(S), c_i64(B), c_int(A),
+                                        c_int(H), c_int(W), c_f32(float(fov_scale)), c_f32(float(zfar)), c_f32(float(ssim_factor)),
+                                        c_int(mode), _p(ws), c_size(ws.numel()), _stream()), "mcr_reconstruction_loss")
+    return (loss, lmap, amin) if return_map else loss
+
+
+def reconstruction_loss_backward(images, alpha_images, mask, cams, depth, d_loss, zfar, ssim_factor, padding_mode="border",
+                                 fov_scale=COST_VOLUME_FOV_SCALE):
+    """d_depth [S,B,H,W]: the gradient of sum_s d_loss[s] * reconstruction_loss(...)[s] for depth, in one entry
+    (mcr_reconstruction_loss_backward); the images, the cameras and the mask are constants.  No atomics: two calls give the same bits."""
+    images, alpha_images, mask, cams, depth, (S, B, A, H, W), mode = _reconstruction_args(images, alpha_images, mask, cams, depth, padding_mode)
+    d_loss = _req(d_loss, "d_loss")
+    if tuple(d_loss.shape) != (S,):
+        raise ValueError(f"d_loss must be [S] = {(S,)}, got {tuple(d_loss.shape)}")
+    d_depth = torch.empty((S, B, H, W), dtype=torch.float32, device=images.device)
+    L = lib()
+    ws = _workspace(images.device, max(int(L.mcr_reconstruction_loss_backward_workspace_bytes(c_i64(S), c_i64(B), c_i64(A), c_i64(H), c_i64(W))), 4))
+    with torch.cuda.device(images.device):
+        check(L.mcr_reconstruction_loss_backward(_p(images), _p(alpha_images), _p(mask) if mask is not None else None, _p(cams), _p(depth),
+                                                 _p(d_loss), _p(d_depth), c_i64(S), c_i64(B), c_int(A), c_int(H), c_int(W),
+                                                 c_f32(float(fov_scale)), c_f32(float(zfar)), c_f32(float(ssim_factor)), c_int(mode), _p(ws),
+                                                 c_size(ws.numel()), _stream()), "mcr_reconstruction_loss_backward")
+    return d_depth

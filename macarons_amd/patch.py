@@ -23,7 +23,8 @@ What is swapped:
     distance factors -- same names, same positional arguments, same defaults (tests/test_patch_reference.py checks the signatures);
     helpers="all" adds compute_scene_occupancy_probability_field (one batched pass over the grid cells instead of a Python loop) and
     compute_occupancy_probability_for_supervision (the trainer's occupancy supervision: one batched pass with one HIP backward),
-    get_occ_loss_fn / get_cov_loss_fn, and ADDS scone_supervision_step (the trainer's scone_loss of one step from K depth frames) and
+    get_occ_loss_fn / get_cov_loss_fn, get_reconstruction_loss_fn (the depth module's photometric loss, fused on HIP both ways; the
+    variant in depth_model_utils.py is not touched), and ADDS scone_supervision_step (the trainer's scone_loss of one step from K depth frames) and
     compute_partial_point_clouds, which upstream writes inline.
 
 Everything else (trainers, testers, data loading, depth network, weight init walkers, checkpoint loaders) is upstream's code running
@@ -50,7 +51,8 @@ _HELPERS = {
 _HELPERS_ALL = {
     "utility.macarons_utils": ("macarons_amd.utility.macarons_utils", ("compute_scene_occupancy_probability_field",
                                                                         "compute_occupancy_probability_for_supervision",
-                                                                        "get_occ_loss_fn", "get_cov_loss_fn")),
+                                                                        "get_occ_loss_fn", "get_cov_loss_fn",
+                                                                        "get_reconstruction_loss_fn")),
 }
 # names upstream does not have (its trainer writes these bodies inline): added to the reference module by helpers="all"
 _ADDITIONS_ALL = {

@@ -1106,6 +1106,80 @@ def get_cov_loss_fn(params):
                     "Please choose a valid loss between 'kl_divergence', 'l1' or 'uncentered_l1.")
 
 
+# ---- the depth module's photometric reconstruction loss --------------------------------------------------------------------------
+def _is_upstream_ssim(ssim_loss_fn):
+    """None, or an instance of upstream's SSIM layer (ManyDepth.py:809-842) with its constants: what the fused entry computes."""
+    if ssim_loss_fn is None:
+        return True
+    return (type(ssim_loss_fn).__name__ == "SSIM" and getattr(ssim_loss_fn, "C1", None) == 0.01 ** 2
+            and getattr(ssim_loss_fn, "C2", None) == 0.03 ** 2 and isinstance(getattr(ssim_loss_fn, "mu_x_pool", None), torch.nn.AvgPool2d))
+
+
+def _fov_scale_of(*cameras):
+    """(fov_scale, default): 1 / tan(fov / 2) of the cameras' `fov` attribute in degrees (absent: upstream's default 60); the warp has
+    one scale, so every camera of every object must carry the same field of view."""
+    fovs = set()
+    for c in cameras:
+        fov = getattr(c, "fov", None)
+        fovs.update([60.0] if fov is None else torch.as_tensor(fov, dtype=torch.float64).reshape(-1).tolist())
+    if len(fovs) > 1:
+        raise ValueError(f"the reconstruction loss takes one field of view for all cameras, got {sorted(fovs)} degrees")
+    fov = fovs.pop() if fovs else 60.0
+    if fov == 60.0:
+        return ops.COST_VOLUME_FOV_SCALE, True
+    return 1.0 / float(np.tan(np.deg2rad(fov) / 2)), False
+
+
+def reconstruction_losses(params, images, alpha_images, mask, cameras, alpha_cameras, depths, padding_mode="border", ssim_loss_fn=None):
+    """The reconstruction losses of S depth maps in ONE entry call, [S]: what apply_depth_model (macarons_utils.py:1042-1065) computes
+    with four calls of its depth_loss_fn, all at full resolution with the same images, cameras and mask.  images [B,H,W,3],
+    alpha_images [B,A,H,W,3], mask [B,H,W] or [B,H,W,1] bool (read when params.use_depth_mask), cameras / alpha_cameras: objects with
+    .R [B,3,3] / [B*A,3,3] and .T [B,3] / [B*A,3], depths [S,B,H,W].  Differentiable in depths (ReconstructionLossFunction: HIP both
+    ways).  The composite (networks.ManyDepth.reconstruction_loss_composite, plain torch) serves what the entry does not take:
+    padding_mode 'reflection', cameras that require a gradient, a field of view other than 60 degrees, an ssim_loss_fn that is not
+    upstream's SSIM."""
+    from ..networks.ManyDepth import pack_cameras, reconstruction_loss_composite
+    B, H, W = images.shape[0], images.shape[1], images.shape[2]
+    n_alpha = alpha_images.shape[1]
+    R, T, Ra, Ta = cameras.R, cameras.T, alpha_cameras.R, alpha_cameras.T
+    cams_grad = torch.is_grad_enabled() and any(t.requires_grad for t in (R, T, Ra, Ta))
+    cams = pack_cameras(R, T, Ra.reshape(B, n_alpha, 3, 3), Ta.reshape(B, n_alpha, 3))        # differentiable
+    mk = mask.reshape(B, H, W).bool() if params.use_depth_mask else None
+    fov_scale, default_fov = _fov_scale_of(cameras, alpha_cameras)
+    upstream_ssim = _is_upstream_ssim(ssim_loss_fn)
+    if padding_mode not in ops.RECONSTRUCTION_PADDING_MODES or cams_grad or not default_fov or not upstream_ssim:
+        return reconstruction_loss_composite(images.float(), alpha_images.float(), mk, cams, depths.float(), params.zfar, params.ssim_factor,
+                                             padding_mode, fov_scale, ssim_loss_fn=None if upstream_ssim else ssim_loss_fn)
+    images, alpha_images, depths = images.float().contiguous(), alpha_images.float().contiguous(), depths.float().contiguous()
+    if torch.is_grad_enabled() and depths.requires_grad:
+        return A.ReconstructionLossFunction.apply(depths, images, alpha_images, mk, cams, params.zfar, params.ssim_factor, padding_mode, fov_scale)
+    return ops.reconstruction_loss(images, alpha_images, mk, cams, depths, params.zfar, params.ssim_factor, padding_mode, fov_scale)
+
+
+def get_reconstruction_loss_fn(params):
+    """macarons_utils.py:1091-1187: returns the loss function with upstream's parameter list; its body is one call of
+    `reconstruction_losses` with S = 1 (the warp, the SSIM windows, the min over the sources and the masked sum fused on HIP)."""
+    def reconstruction_loss_fn(params,
+                               input_images, input_alpha_images, mask,
+                               cameras, alpha_cameras,
+                               predicted_depth,
+                               macarons,
+                               ssim_loss_fn,
+                               channel_is_at_the_end=True,
+                               padding_mode='border'):
+        """input_images [B,H,W,3] and input_alpha_images [B,A,H,W,3] (channel_is_at_the_end) or [B,3,H,W] and [B,A,3,H,W];
+        mask [B,H,W,1] bool; predicted_depth [B,H,W,1]; macarons is not read (its cost_volume_builder only served the warp)."""
+        if channel_is_at_the_end:
+            images, alpha_images = input_images, input_alpha_images
+        else:
+            images, alpha_images = input_images.permute(0, 2, 3, 1), input_alpha_images.permute(0, 1, 3, 4, 2)
+        B, H, W = images.shape[0], images.shape[1], images.shape[2]
+        return reconstruction_losses(params, images, alpha_images, mask, cameras, alpha_cameras, predicted_depth.reshape(1, B, H, W),
+                                     padding_mode=padding_mode, ssim_loss_fn=ssim_loss_fn)[0]
+
+    return reconstruction_loss_fn
+
+
 def _frame_fields(f):
     if isinstance(f, dict):
         return f["depth"], f["mask"], f.get("error_mask"), f["camera"], f["depth_camera"]
