@@ -803,6 +803,54 @@ int mcr_reconstruction_loss_backward(const float* images, const float* alpha_ima
                                      float fov_scale, float zfar, float ssim_factor, int padding_mode, void* workspace,
                                      size_t workspace_bytes, void* stream);
 
+/* ---- between the depth network's disparity maps and its losses (macarons/utility/macarons_utils.py:959-1031 apply_depth_model, with
+ * get_regularity_loss_fn / regularity_tab of depth_model_utils.py:522-562), fused (disparity_scales.hip).
+ *
+ * mcr_disparity_scales: the depth of S disparity maps at full resolution, their S edge-aware regularity values and the error mask of scale
+ *   0 in one call, replacing the S disparity-to-depth conversions, the nearest upsamplings, the depth-to-disparity round trips, the
+ *   per-image mean normalisations, the mask zeroings, the S regularity losses and the table of the error mask with its threshold.
+ *   disps: a HOST array of S device pointers, disps[s] [B,Hs[s],Ws[s]]; Hs, Ws: HOST arrays of S ints with H = r_s Hs[s] and
+ *   W = r_s Ws[s], r_s one of 1, 2, 4, 8, 16 and the same on both axes (for these ratios torch's `nearest` reads source pixel dst / r_s);
+ *   all three arrays are read before the entry returns.  images [B,H,W,3], mask [B,H,W] bytes (non-zero = inside) or NULL (nothing is
+ *   zeroed).  With a = 1/znear - 1/zfar and b = 1/zfar, per scale, image and full-resolution pixel p = (y,x):
+ *     depth[s,b,p] = 1 / (a disp_s[b, y / r_s, x / r_s] + b), [S,B,H,W] as mcr_reconstruction_loss reads it;
+ *     D = disp_s[b, y / r_s, x / r_s] -- the entry READS THE DISPARITY DIRECTLY where upstream recomputes it from the depth as
+ *       (1/depth - b)/a (the identity to 6e-8 in fp32, derivative 1), so the pixels of an upsampled block compare exactly equal;
+ *     n = D / (mu + 1e-7), mu the mean of D over the image, and n = 0 where the mask is zero, BY SELECTION where upstream multiplies by 0:
+ *       the two differ only for a disparity that is not finite (0 here, NaN upstream);
+ *     reg[s] = mean over B H (W-1) of |n[y,x] - n[y,x+1]| exp(-mean_c |I[y,x] - I[y,x+1]|) + mean over B (H-1) W of the same downwards:
+ *       the raw value, the scale weights (1, 1/2, 1/4, 1/8) and params.regularity_factor stay with the caller.
+ *   From scale 0 alone, with P(i,j) = n[reflect(i-1), reflect(j-1)] and I_P the image likewise (upstream's table on reflection-padded
+ *   copies, with its one-pixel shift up and left): tab[i,j] = |P(i,j) - P(i,j+1)| exp(-mean_c |I_P(i,j) - I_P(i,j+1)|) + the same
+ *   downwards; thr[b] = mean(tab_b) + std(tab_b), the std unbiased (N - 1); error_mask [B,H,W] bytes = tab < thr.  The mean and the
+ *   variance are formed from per-tile sums of t and of t^2 held and added in double (the square of an fp32 value is exact in double),
+ *   never from an fp32 E[t^2] - mean^2.  tab [B,H,W] and thr [B] are written when not NULL.  Refused before any launch: S outside 1..8,
+ *   H or W below 2, a scale whose ratio is not in the set or differs between the axes (Hs[s] r_s != H or Ws[s] r_s != W), znear or zfar
+ *   not positive and finite, a workspace that is short or not 16-byte aligned, sizes whose products overflow an index (B <= 65535).
+ *   Four launches (the S B sums at each scale's own resolution; one 16 x 16 tile of one image for all scales per workgroup; one
+ *   workgroup that adds the partials in a fixed order; tab < thr), no floating-point atomics: two calls give the same bits.
+ *   workspace: the partials, and the table and thresholds when the caller does not take them.
+ * mcr_disparity_scales_backward: d_disps[s] [B,Hs[s],Ws[s]] (a HOST array of S device pointers) = d (sum_p d_depth . depth + sum_s
+ *   d_reg[s] reg[s]) / d disp_s, each at its own resolution; images and mask are constants, the error mask has no gradient.
+ *   d_depth [S,B,H,W] or NULL, d_reg [S] or NULL: a NULL half is not computed (without d_reg: one launch), both NULL is refused.  With
+ *   G[p] = d_reg[s] d reg[s] / d n[p] and m the mask,
+ *     d_disp_s[j] = sum over the pixels p of block j of (-a depth[p]^2 d_depth[s,b,p] + m[p] G[p] / (mu + eps))
+ *                   - sum over the image of m[p] G[p] D[p] / ((mu + eps)^2 Hs Ws)        (the derivative through the mean: every pixel
+ *   of the image receives it, the masked-out ones too, as in upstream where the mean is taken before the mask).  The gradient of |x| at 0
+ *   is 0, so the interior of an upsampled block contributes nothing, as in torch; a masked-out pixel's own term is exactly 0.  n is
+ *   formed by the forward's device code from the same sums: both directions see the same signs.  Same refusals.  No floating-point
+ *   atomics, every sum in a fixed order (a block is summed row by row; 16 is a multiple of every ratio, so no block straddles a tile): two
+ *   calls give the same bits.  workspace: the partials.
+ * The size functions return 0 for sizes that the entries refuse. */
+size_t mcr_disparity_scales_workspace_bytes(int64_t S, int64_t B, int64_t H, int64_t W);
+int mcr_disparity_scales(const float* const* disps, const int* Hs, const int* Ws, const float* images, const unsigned char* mask,
+                         float* depth, float* reg, unsigned char* error_mask, float* tab, float* thr, int S, int64_t B, int H, int W,
+                         float znear, float zfar, void* workspace, size_t workspace_bytes, void* stream);
+size_t mcr_disparity_scales_backward_workspace_bytes(int64_t S, int64_t B, int64_t H, int64_t W);
+int mcr_disparity_scales_backward(const float* const* disps, const int* Hs, const int* Ws, const float* images, const unsigned char* mask,
+                                  const float* d_depth, const float* d_reg, float* const* d_disps, int S, int64_t B, int H, int W,
+                                  float znear, float zfar, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

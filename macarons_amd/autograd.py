@@ -16,7 +16,9 @@ for the surface points pc is not computed there, so a forward whose pc requires 
 gradients for the per-point visibility gains and the volumes and for nothing else.  The depth module's plane sweep (ops.cost_volume)
 is HIP both ways too (CostVolumeFunction below: mcr_cost_volume_backward; env MCR_COST_VOLUME_BWD=composite puts it back on the
 recomputation through networks.ManyDepth.cost_volume_planes, A/B), and so is the depth module's photometric reconstruction loss
-(ReconstructionLossFunction: mcr_reconstruction_loss_backward, for the depth alone; env MCR_RECONSTRUCTION_LOSS_BWD=composite).  The composites
+(ReconstructionLossFunction: mcr_reconstruction_loss_backward, for the depth alone; env MCR_RECONSTRUCTION_LOSS_BWD=composite) and the step
+in front of it, from the network's disparity maps to the depths, regularity values and error mask (DisparityScalesFunction:
+mcr_disparity_scales_backward, for the disparities alone; env MCR_DISPARITY_SCALES_BWD=composite).  The composites
 are ordinary differentiable torch code, so they are also what the parity tests differentiate numerically (tests/test_autograd.py:
 fp64 finite differences on CPU; on the GPU the composite forward must reproduce the HIP forward to 1e-4, which makes its gradient
 the gradient of the kernels' function) and the second reference of the HIP backward's tests.
@@ -568,3 +570,53 @@ class ReconstructionLossFunction(torch.autograd.Function):
             d = depth.detach().requires_grad_(True)
             loss = reconstruction_loss_composite(images, alpha_images, mask, cams, d, ctx.zfar, ctx.ssim_factor, ctx.padding_mode, ctx.fov_scale)
             return tuple(torch.autograd.grad(loss, (d,), grad_loss)) + none
+
+
+# ---- depth module, disparity scales / regularity values / error mask: HIP forward + HIP backward ---------------------------------------
+def disparity_scales_backward_mode():
+    """'hip' (default) or 'composite' (env MCR_DISPARITY_SCALES_BWD=composite: the recomputing torch backward, for A/B comparisons)."""
+    return "composite" if os.environ.get("MCR_DISPARITY_SCALES_BWD", "").lower() == "composite" else "hip"
+
+
+class DisparityScalesFunction(torch.autograd.Function):
+    """apply(images, mask, znear, zfar, *disps) -> (depth [S,B,H,W], reg [S], error_mask [B,H,W] bool) of ops.disparity_scales
+    (mcr_disparity_scales).  Differentiable in the disparities only, through depth and reg; error_mask is marked non-differentiable.
+    backward = ops.disparity_scales_backward (mcr_disparity_scales_backward: no atomics, the same bits on every run); a half whose
+    gradient is absent or not needed is not computed.  With disparity_scales_backward_mode() == 'composite' the backward is autograd
+    through networks.ManyDepth.disparity_scales_composite instead (plain torch on the same device).  Differentiable once."""
+
+    @staticmethod
+    def forward(ctx, images, mask, znear, zfar, *disps):
+        from . import ops
+        ctx.znear, ctx.zfar, ctx.has_mask = float(znear), float(zfar), mask is not None
+        ctx.save_for_backward(images, *((mask,) if mask is not None else ()), *disps)
+        with torch.no_grad():
+            depth, reg, error_mask = ops.disparity_scales(disps, images, mask, znear, zfar)
+        ctx.mark_non_differentiable(error_mask)
+        ctx.set_materialize_grads(False)
+        return depth, reg, error_mask
+
+    @staticmethod
+    def backward(ctx, grad_depth, grad_reg, _grad_error_mask):
+        if torch.is_grad_enabled():
+            raise RuntimeError("the disparity scales are differentiable once: their backward recomputes without a graph "
+                               "(create_graph is not supported)")
+        images = ctx.saved_tensors[0]
+        mask = ctx.saved_tensors[1] if ctx.has_mask else None
+        disps = ctx.saved_tensors[2 if ctx.has_mask else 1:]
+        none = (None,) * 4
+        if not any(ctx.needs_input_grad[4:]) or (grad_depth is None and grad_reg is None):
+            return none + (None,) * len(disps)
+        if disparity_scales_backward_mode() == "hip":
+            from . import ops
+            grads = ops.disparity_scales_backward(disps, images, mask, ctx.znear, ctx.zfar,
+                                                  None if grad_depth is None else grad_depth.float().contiguous(),
+                                                  None if grad_reg is None else grad_reg.float().contiguous())
+            return none + tuple(g.reshape(d.shape) if n else None for g, d, n in zip(grads, disps, ctx.needs_input_grad[4:]))
+        from .networks.ManyDepth import disparity_scales_composite
+        with torch.enable_grad():
+            leaves = [d.detach().requires_grad_(True) for d in disps]
+            depth, reg, _ = disparity_scales_composite(leaves, images, mask, ctx.znear, ctx.zfar)
+            outs, gouts = zip(*[(o, g) for o, g in ((depth, grad_depth), (reg, grad_reg)) if g is not None])
+            grads = torch.autograd.grad(outs, leaves, gouts)
+        return none + tuple(g if n else None for g, n in zip(grads, ctx.needs_input_grad[4:]))

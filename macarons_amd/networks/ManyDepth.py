@@ -5,7 +5,9 @@ an existing upstream instance on that path (`adopt_cost_volume_builder`).  The r
 decoder, the pose decoder, `apply_depth_model` -- is convolutions the vendor library serves and stays upstream's.  The photometric
 reconstruction loss is fused on HIP as well (ops.reconstruction_loss -> mcr_reconstruction_loss, csrc/reconstruction_loss.hip, behind
 utility.macarons_utils.get_reconstruction_loss_fn); `reconstruction_loss_composite` below is the same mathematics in plain
-differentiable torch, for the cases the entry does not take and for the tests.
+differentiable torch, for the cases the entry does not take and for the tests.  So is the step between the network's disparity maps
+and that loss (ops.disparity_scales -> mcr_disparity_scales, csrc/disparity_scales.hip, behind utility.macarons_utils.depth_scale_losses):
+`disparity_scales_composite` below is its plain-torch form.
 
 Needs neither PyTorch3D nor torchvision: a camera is its R, T (PyTorch3D's row-vector convention, view = world @ R + T) and the default
 60 degree field of view upstream never overrides; znear and zfar drop out of the sweep (they only shape the z the projection returns,
@@ -140,6 +142,48 @@ def reconstruction_loss_composite(images, alpha_images, mask, cams, depth, zfar,
     if return_map:
         return torch.stack(losses), torch.stack(maps), torch.stack(idxs)
     return torch.stack(losses)
+
+
+def edge_aware_gradients(disp, img):
+    """disp [N,1,H,W], img [N,C,H,W] -> (|disp[.., x] - disp[.., x+1]| exp(-mean_c |img[.., x] - img[.., x+1]|) [N,1,H,W-1], the same
+    downwards [N,1,H-1,W]): the two weighted difference maps both of upstream's regularity functions are made of
+    (depth_model_utils.py:533-540, :553-560)."""
+    gx = (disp[..., :, :-1] - disp[..., :, 1:]).abs() * torch.exp(-(img[..., :, :-1] - img[..., :, 1:]).abs().mean(1, keepdim=True))
+    gy = (disp[..., :-1, :] - disp[..., 1:, :]).abs() * torch.exp(-(img[..., :-1, :] - img[..., 1:, :]).abs().mean(1, keepdim=True))
+    return gx, gy
+
+
+def disparity_scales_composite(disps, images, mask, znear, zfar, return_tab=False):
+    """ops.disparity_scales in plain torch (any device, the disparities' dtype; differentiable in the disparities): what upstream's
+    apply_depth_model does between the depth network and its losses (macarons_utils.py:959-1031).  disps: a sequence of [B,1,H_s,W_s]
+    or [B,H_s,W_s] maps of ANY size (F.interpolate, mode 'nearest', brings each to the images' size: this also serves the ratios and
+    sizes the entry refuses); images [B,H,W,3]; mask [B,H,W] bool or None.  Returns (depth [S,B,H,W], reg [S], error_mask [B,H,W] bool),
+    with return_tab also (tab [B,H,W], thr [B]).  Like the entry it upsamples the disparity itself where upstream upsamples the depth and
+    converts back (the identity), and zeroes the masked-out pixels by selection."""
+    B, H, W, _ = images.shape
+    dt = disps[0].dtype
+    a, b = 1.0 / float(znear) - 1.0 / float(zfar), 1.0 / float(zfar)
+    img = images.to(dt).permute(0, 3, 1, 2)
+    depths, regs, n0 = [], [], None
+    for d in disps:
+        d = d.reshape(B, 1, d.shape[-2], d.shape[-1])
+        if tuple(d.shape[-2:]) != (H, W):
+            d = F.interpolate(d, size=(H, W), mode="nearest")
+        depths.append(1.0 / (a * d[:, 0] + b))
+        n = d / (d.mean((2, 3), keepdim=True) + 1e-7)
+        if mask is not None:
+            n = torch.where(mask[:, None], n, torch.zeros_like(n))
+        gx, gy = edge_aware_gradients(n, img)
+        regs.append(gx.mean() + gy.mean())
+        if n0 is None:
+            n0 = n.detach()
+    with torch.no_grad():                                   # the error mask of scale 0 (:984-993): the table of the reflection-padded copies
+        gx, gy = edge_aware_gradients(F.pad(n0, (1, 1, 1, 1), mode="reflect"), F.pad(img, (1, 1, 1, 1), mode="reflect"))
+        tab = (gx[:, 0, :H, :W] + gy[:, 0, :H, :W])
+        thr = tab.reshape(B, -1).mean(-1) + tab.reshape(B, -1).std(-1)
+        error_mask = tab < thr.view(B, 1, 1)
+    out = (torch.stack(depths), torch.stack(regs), error_mask)
+    return out + (tab, thr) if return_tab else out
 
 
 def _forward(self, x, R, T, zfar, x_alpha, R_alpha, T_alpha, zfar_alpha, device=None, return_cost_volume=False):

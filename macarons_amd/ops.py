@@ -1773,3 +1773,95 @@ def reconstruction_loss_backward(images, alpha_images, mask, cams, depth, d_loss
                                                  c_f32(float(fov_scale)), c_f32(float(zfar)), c_f32(float(ssim_factor)), c_int(mode), _p(ws),
                                                  c_size(ws.numel()), _stream()), "mcr_reconstruction_loss_backward")
     return d_depth
+
+
+# ---- depth module: disparity scales, regularity values and the error mask -------------------------------------------------------------
+DISPARITY_SCALE_RATIOS = (1, 2, 4, 8, 16)
+DISPARITY_MAX_SCALES = 8
+
+
+def _disparity_args(disps, images, mask):
+    """The shapes first (ValueError, on any device), then the operands themselves (HIP, float32, contiguous)."""
+    if isinstance(disps, torch.Tensor) or not len(disps):
+        raise ValueError("disps must be a non-empty sequence of [B,1,H_s,W_s] or [B,H_s,W_s] tensors, one per scale")
+    if not 1 <= len(disps) <= DISPARITY_MAX_SCALES:
+        raise ValueError(f"between 1 and {DISPARITY_MAX_SCALES} scales are supported, got {len(disps)}")
+    if not isinstance(images, torch.Tensor) or images.dim() != 4 or images.shape[-1] != 3:
+        raise ValueError(f"images must be [B,H,W,3], got {tuple(getattr(images, 'shape', ()))}")
+    B, H, W, _ = images.shape
+    if H < 2 or W < 2:
+        raise ValueError(f"the image is {H} x {W}, H and W must be at least 2")
+    maps, sizes = [], []
+    for s, d in enumerate(disps):
+        if not isinstance(d, torch.Tensor):
+            raise TypeError(f"disps[{s}] must be a torch.Tensor")
+        if d.dim() == 4 and d.shape[1] == 1:
+            d = d[:, 0]
+        if d.dim() != 3 or d.shape[0] != B or d.shape[1] < 1 or d.shape[2] < 1:
+            raise ValueError(f"disps[{s}] must be [B,1,H_s,W_s] or [B,H_s,W_s] with B = {B}, got {tuple(disps[s].shape)}")
+        Hs, Ws = int(d.shape[1]), int(d.shape[2])
+        r = H // Hs
+        if r not in DISPARITY_SCALE_RATIOS or Hs * r != H or Ws * r != W:
+            raise ValueError(f"disps[{s}] is {Hs} x {Ws} for an image of {H} x {W}: the ratio must be one of {DISPARITY_SCALE_RATIOS}, the "
+                             "same on both axes (networks.ManyDepth.disparity_scales_composite takes other sizes)")
+        maps.append(d), sizes.append((Hs, Ws))
+    if mask is not None and (not isinstance(mask, torch.Tensor) or tuple(mask.shape) != (B, H, W)):
+        raise ValueError(f"mask must be [B,H,W] = {(B, H, W)}, got {tuple(getattr(mask, 'shape', ()))}")
+    images = _req(images, "images")
+    maps = [_req(d, f"disps[{s}]") for s, d in enumerate(maps)]
+    if mask is not None:
+        mask = _req(mask, "mask", torch.bool)
+    S = len(maps)
+    ptrs = (ctypes.c_void_p * S)(*[d.data_ptr() for d in maps])
+    hs, wss = (ctypes.c_int * S)(*[h for h, _ in sizes]), (ctypes.c_int * S)(*[w for _, w in sizes])
+    return maps, images, mask, (S, B, H, W), (ptrs, hs, wss)
+
+
+def disparity_scales(disps, images, mask, znear, zfar, return_tab=False):
+    """(depth [S,B,H,W], reg [S], error_mask [B,H,W] bool) of S disparity maps in one entry (mcr_disparity_scales): what upstream's
+    apply_depth_model does between the depth network and its losses (macarons_utils.py:959-1031).  disps: a sequence of [B,1,H_s,W_s] or
+    [B,H_s,W_s] float32 maps, each 1, 2, 4, 8 or 16 times smaller than the images on both axes (they are not concatenated: the kernels
+    take the S pointers); images [B,H,W,3]; mask [B,H,W] bool or None.  depth is the layout ops.reconstruction_loss reads; reg[s] is the
+    raw regularity value of scale s (the scale weights and params.regularity_factor stay with the caller); error_mask is upstream's
+    `error_tab < mean + std` of scale 0.  return_tab: also tab [B,H,W] and thr [B]."""
+    maps, images, mask, (S, B, H, W), (ptrs, hs, wss) = _disparity_args(disps, images, mask)
+    dev = images.device
+    depth = torch.empty((S, B, H, W), dtype=torch.float32, device=dev)
+    reg = torch.empty((S,), dtype=torch.float32, device=dev)
+    em = torch.empty((B, H, W), dtype=torch.bool, device=dev)
+    tab = torch.empty((B, H, W), dtype=torch.float32, device=dev) if return_tab else None
+    thr = torch.empty((B,), dtype=torch.float32, device=dev) if return_tab else None
+    L = lib()
+    ws = _workspace(dev, max(int(L.mcr_disparity_scales_workspace_bytes(c_i64(S), c_i64(B), c_i64(H), c_i64(W))), 4))
+    with torch.cuda.device(dev):
+        check(L.mcr_disparity_scales(ptrs, hs, wss, _p(images), _p(mask) if mask is not None else None, _p(depth), _p(reg), _p(em),
+                                     _p(tab) if return_tab else None, _p(thr) if return_tab else None, c_int(S), c_i64(B), c_int(H), c_int(W),
+                                     c_f32(float(znear)), c_f32(float(zfar)), _p(ws), c_size(ws.numel()), _stream()), "mcr_disparity_scales")
+    return (depth, reg, em, tab, thr) if return_tab else (depth, reg, em)
+
+
+def disparity_scales_backward(disps, images, mask, znear, zfar, d_depth, d_reg):
+    """The S gradients [B,H_s,W_s] of sum(d_depth * depth) + sum(d_reg * reg) of disparity_scales for the disparities, each at its own
+    resolution, in one entry (mcr_disparity_scales_backward).  d_depth [S,B,H,W] or None, d_reg [S] or None: a half that is None is not
+    computed, both None is refused.  No atomics: two calls give the same bits."""
+    if d_depth is None and d_reg is None:
+        raise ValueError("disparity_scales_backward: nothing to do, d_depth and d_reg are both None")
+    maps, images, mask, (S, B, H, W), (ptrs, hs, wss) = _disparity_args(disps, images, mask)
+    if d_depth is not None:
+        if not isinstance(d_depth, torch.Tensor) or tuple(d_depth.shape) != (S, B, H, W):
+            raise ValueError(f"d_depth must be [S,B,H,W] = {(S, B, H, W)}, got {tuple(getattr(d_depth, 'shape', ()))}")
+        d_depth = _req(d_depth, "d_depth")
+    if d_reg is not None:
+        if not isinstance(d_reg, torch.Tensor) or tuple(d_reg.shape) != (S,):
+            raise ValueError(f"d_reg must be [S] = {(S,)}, got {tuple(getattr(d_reg, 'shape', ()))}")
+        d_reg = _req(d_reg, "d_reg")
+    grads = [torch.empty_like(d) for d in maps]
+    gptrs = (ctypes.c_void_p * S)(*[g.data_ptr() for g in grads])
+    L = lib()
+    ws = _workspace(images.device, max(int(L.mcr_disparity_scales_backward_workspace_bytes(c_i64(S), c_i64(B), c_i64(H), c_i64(W))), 4))
+    with torch.cuda.device(images.device):
+        check(L.mcr_disparity_scales_backward(ptrs, hs, wss, _p(images), _p(mask) if mask is not None else None,
+                                              _p(d_depth) if d_depth is not None else None, _p(d_reg) if d_reg is not None else None, gptrs,
+                                              c_int(S), c_i64(B), c_int(H), c_int(W), c_f32(float(znear)), c_f32(float(zfar)), _p(ws),
+                                              c_size(ws.numel()), _stream()), "mcr_disparity_scales_backward")
+    return grads

@@ -24,8 +24,10 @@ What is swapped:
     helpers="all" adds compute_scene_occupancy_probability_field (one batched pass over the grid cells instead of a Python loop) and
     compute_occupancy_probability_for_supervision (the trainer's occupancy supervision: one batched pass with one HIP backward),
     get_occ_loss_fn / get_cov_loss_fn, get_reconstruction_loss_fn (the depth module's photometric loss, fused on HIP both ways; the
-    variant in depth_model_utils.py is not touched), and ADDS scone_supervision_step (the trainer's scone_loss of one step from K depth frames) and
-    compute_partial_point_clouds, which upstream writes inline.
+    variant in depth_model_utils.py is not touched), get_regularity_loss_fn / regularity_tab (macarons_utils' bindings of them; the
+    definitions in depth_model_utils.py are not touched), and ADDS scone_supervision_step (the trainer's scone_loss of one step from K
+    depth frames), compute_partial_point_clouds and depth_scale_losses (a depth step from the network's disparity maps to its depth and
+    regularity losses: one fused HIP entry each for the scales and for the reconstruction losses), which upstream writes inline.
 
 Everything else (trainers, testers, data loading, depth network, weight init walkers, checkpoint loaders) is upstream's code running
 unchanged over these classes: the weight-init walk (scone_utils.py:399-428) finds the same `nn.Linear` children by the same names, and
@@ -52,11 +54,13 @@ _HELPERS_ALL = {
     "utility.macarons_utils": ("macarons_amd.utility.macarons_utils", ("compute_scene_occupancy_probability_field",
                                                                         "compute_occupancy_probability_for_supervision",
                                                                         "get_occ_loss_fn", "get_cov_loss_fn",
-                                                                        "get_reconstruction_loss_fn")),
+                                                                        "get_reconstruction_loss_fn", "get_regularity_loss_fn",
+                                                                        "regularity_tab")),
 }
 # names upstream does not have (its trainer writes these bodies inline): added to the reference module by helpers="all"
 _ADDITIONS_ALL = {
-    "utility.macarons_utils": ("macarons_amd.utility.macarons_utils", ("scone_supervision_step", "compute_partial_point_clouds")),
+    "utility.macarons_utils": ("macarons_amd.utility.macarons_utils", ("scone_supervision_step", "compute_partial_point_clouds",
+                                                                        "depth_scale_losses")),
 }
 
 _STATE = {}          # package -> report of the last patch (idempotence, `unpatch_reference`)
@@ -145,6 +149,8 @@ def patch_reference(package="macarons", helpers=True, import_consumers=True):
                         raise TypeError(f"{new_name}.{name}{inspect.signature(new)} cannot be called like "
                                         f"{full}.{name}{inspect.signature(old)}")
                     swap[id(old)] = (new, old)
+                    report["originals"][f"{full}.{name}"] = old
+                else:                                          # a name the module imported (regularity_tab): this binding alone
                     report["originals"][f"{full}.{name}"] = old
                 setattr(ref_mod, name, new)
                 report["helpers"].append((full, name))

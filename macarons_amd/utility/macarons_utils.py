@@ -1180,6 +1180,83 @@ def get_reconstruction_loss_fn(params):
     return reconstruction_loss_fn
 
 
+# ---- the depth module between the network's disparity maps and its losses --------------------------------------------------------
+def compute_depth_from_disparity(params, disp):
+    """depth_model_utils.py:844-848."""
+    return 1.0 / ((1.0 / params.znear - 1.0 / params.zfar) * disp + 1.0 / params.zfar)
+
+
+def compute_disparity_from_depth(params, depth):
+    """depth_model_utils.py:851-855."""
+    return (1.0 / depth - 1.0 / params.zfar) / (1.0 / params.znear - 1.0 / params.zfar)
+
+
+def regularity_tab(disp, img):
+    """depth_model_utils.py:547-562: the per-pixel edge-aware smoothness of disp [N,1,h,w] with img [N,C,h,w], [N,1,h-2,w-2] (upstream
+    calls it on reflection-padded copies).  Plain torch; the fused entry computes the same table of scale 0 (ops.disparity_scales)."""
+    from ..networks.ManyDepth import edge_aware_gradients
+    h, w = disp.shape[-2], disp.shape[-1]
+    gx, gy = edge_aware_gradients(disp, img)
+    return gx[:, :, :h - 2, :w - 2] + gy[:, :, :h - 2, :w - 2]
+
+
+def get_regularity_loss_fn(params):
+    """depth_model_utils.py:522-544: returns the edge-aware smoothness loss of one disparity map, with upstream's parameter list.  Plain
+    torch; a depth step takes all its scales through `depth_scale_losses` instead (one fused entry)."""
+    def regularity_loss_fn(disp, img):
+        from ..networks.ManyDepth import edge_aware_gradients
+        gx, gy = edge_aware_gradients(disp, img)
+        return gx.mean() + gy.mean()
+
+    return regularity_loss_fn
+
+
+_scale_weights = {}
+
+
+def depth_scale_losses(params, disps, images, alpha_images, mask, cameras, alpha_cameras, padding_mode, ssim_loss_fn=None, compute_loss=True):
+    """What apply_depth_model (macarons_utils.py:959-1065) writes inline between the depth network and `loss = pose_loss + depth_loss +
+    regularity_loss`: ONE DisparityScalesFunction call (the S depths at full resolution, the S regularity values and the error mask,
+    mcr_disparity_scales) and ONE `reconstruction_losses` call on its depth (mcr_reconstruction_loss) -- no torch op between the two.
+    disps: the network's S disparity maps [B,1,H_s,W_s], finest first; images [B,H,W,3], alpha_images [B,A,H,W,3], mask [B,H,W] or
+    [B,H,W,1] bool (read when params.use_depth_mask), cameras / alpha_cameras as for `reconstruction_losses`.  Returns
+      depth_loss       the sum of the S reconstruction losses,
+      regularity_loss  params.regularity_factor * sum_s 2^-s reg[s]; 0. when params.regularity_loss is false or the factor is 0 (the
+                       backward then skips that half),
+      depth            [B,H,W,1] of scale 0, detached,
+      mask             [B,H,W,1] bool (None without params.use_depth_mask),
+      error_mask       [B,H,W,1] bool.
+    compute_loss=False: the forward alone without a graph, both losses 0.  Maps whose ratio to the images the entry does not take (not
+    1, 2, 4, 8 or 16, or different on the two axes) go through networks.ManyDepth.disparity_scales_composite."""
+    from ..networks.ManyDepth import disparity_scales_composite
+    B, H, W = images.shape[0], images.shape[1], images.shape[2]
+    mk = mask.reshape(B, H, W).bool() if params.use_depth_mask else None
+    images = images.float().contiguous()
+    disps = [d.float() for d in disps]
+    fused = all(H // d.shape[-2] in ops.DISPARITY_SCALE_RATIOS and d.shape[-2] * (H // d.shape[-2]) == H
+                and d.shape[-1] * (H // d.shape[-2]) == W for d in disps) and len(disps) <= ops.DISPARITY_MAX_SCALES
+    out_mask = None if mk is None else mk.reshape(B, H, W, 1)
+    if not compute_loss:
+        with torch.no_grad():
+            depth, _, error_mask = (ops.disparity_scales if fused else disparity_scales_composite)(disps, images, mk, params.znear, params.zfar)
+        return 0., 0., depth[0].reshape(B, H, W, 1), out_mask, error_mask.reshape(B, H, W, 1)
+    if not fused:
+        depth, reg, error_mask = disparity_scales_composite(disps, images, mk, params.znear, params.zfar)
+    elif torch.is_grad_enabled() and any(d.requires_grad for d in disps):
+        depth, reg, error_mask = A.DisparityScalesFunction.apply(images, mk, params.znear, params.zfar, *disps)
+    else:
+        depth, reg, error_mask = ops.disparity_scales(disps, images, mk, params.znear, params.zfar)
+    depth_loss = reconstruction_losses(params, images, alpha_images, mask, cameras, alpha_cameras, depth, padding_mode=padding_mode,
+                                       ssim_loss_fn=ssim_loss_fn).sum()
+    regularity_loss = 0.
+    if params.regularity_loss and params.regularity_factor > 0.:
+        key = (reg.device, reg.shape[0])
+        if key not in _scale_weights:                          # 2^-s, uploaded once per device
+            _scale_weights[key] = torch.tensor([0.5 ** s for s in range(reg.shape[0])], dtype=torch.float32).to(reg.device)
+        regularity_loss = params.regularity_factor * (reg * _scale_weights[key]).sum()
+    return depth_loss, regularity_loss, depth[0].detach().reshape(B, H, W, 1), out_mask, error_mask.reshape(B, H, W, 1)
+
+
 def _frame_fields(f):
     if isinstance(f, dict):
         return f["depth"], f["mask"], f.get("error_mask"), f["camera"], f["depth_camera"]
