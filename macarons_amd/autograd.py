@@ -162,12 +162,18 @@ def pc_transformer(pct, x):
     return torch.cat((x.max(dim=1)[0], x.mean(dim=1)), dim=-1)
 
 
+def _env_mode(value, allowed, default):
+    """`value` (what the environment holds for a *_BWD variable; read at the call, where the name stands next to os.environ for the scan of
+    tests/test_knobs_cpu.py) lower-cased if it is one of `allowed`, else `default`."""
+    mode = value.lower()
+    return mode if mode in allowed else default
+
+
 def scone_occ_backward_mode():
     """'composite' (default), 'pct' (env MCR_SCONE_OCC_BWD=pct: the four PCTransformers of the recomputation on the HIP backward) or
     'hip' (MCR_SCONE_OCC_BWD=hip: the whole network's backward behind one entry, SconeOccFunction; with a gradient wanted for the surface
     points, the 'pct' route).  Anything else: 'composite'."""
-    mode = os.environ.get("MCR_SCONE_OCC_BWD", "").lower()
-    return mode if mode in ("pct", "hip") else "composite"
+    return _env_mode(os.environ.get("MCR_SCONE_OCC_BWD", ""), ("pct", "hip"), "composite")
 
 
 def scone_occ(model, pc_global, scales, x, view_harmonics, knn_idx):
@@ -259,10 +265,30 @@ def with_torch_backward(hip_fn, torch_fn, inputs, module=None):
     return _HipForwardTorchBackward.apply(hip_fn, torch_fn, len(inputs), *inputs, *params)
 
 
+# ---- what the HIP-backward Functions share ---------------------------------------------------------------------------------------
+def _once(what, why="its HIP backward builds no graph"):
+    """The guard of every Function below: `what` (subject and verb, 'the cost volume is') can be differentiated once."""
+    if torch.is_grad_enabled():
+        raise RuntimeError(f"{what} differentiable once: {why} (create_graph is not supported)")
+
+
+def _slot_grads(ctx, d_w, first, dtypes=None):
+    """The gradients of a network Function's parameters from the weight-gradient table d_w: ctx.slots[j] = (table index, row slice or
+    None) of parameter j, whose needs_input_grad is number first + j; None where no gradient is needed.  dtypes: cast to dtypes[j]."""
+    grads = []
+    for j, (i, rows) in enumerate(ctx.slots):
+        if not ctx.needs_input_grad[first + j]:
+            grads.append(None)
+            continue
+        g = d_w[i] if rows is None else d_w[i][rows[0]:rows[1]]
+        grads.append(g if dtypes is None else g.to(dtypes[j]))
+    return grads
+
+
 # ---- SconeVis: HIP forward + HIP backward ----------------------------------------------------------------------------------------
 def scone_vis_backward_mode():
     """'hip' (default) or 'composite' (env MCR_SCONE_VIS_BWD=composite: the recomputing torch backward above, for A/B comparisons)."""
-    return "composite" if os.environ.get("MCR_SCONE_VIS_BWD", "").lower() == "composite" else "hip"
+    return _env_mode(os.environ.get("MCR_SCONE_VIS_BWD", ""), ("composite",), "hip")
 
 
 class SconeVisFunction(torch.autograd.Function):
@@ -280,22 +306,15 @@ class SconeVisFunction(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_out):
-        if torch.is_grad_enabled():
-            raise RuntimeError("SconeVis.forward is differentiable once: its HIP backward builds no graph (create_graph is not supported)")
+        _once("SconeVis.forward is")
         from . import ops
         pts, vh = ctx.saved_tensors
         need_p, need_v = ctx.needs_input_grad[4], ctx.needs_input_grad[5]
         need_w = any(ctx.needs_input_grad[6:])
         d_w, d_pts, d_vh = ops.scone_vis_backward(pts, vh, grad_out, ctx.table_fn(), ctx.lengths, need=(need_w, need_p, need_v))
-        grads = []
-        for j, (idx, rows) in enumerate(ctx.slots):
-            if not ctx.needs_input_grad[6 + j]:
-                grads.append(None)
-                continue
-            g = d_w[idx] if rows is None else d_w[idx][rows[0]:rows[1]]
-            grads.append(g)
+        # NOT cast to the parameters' dtypes, unlike the three Functions below: SconeVis hands out the table's fp32 gradients as they are
         return (None, None, None, None, d_pts.to(pts.dtype) if d_pts is not None else None,
-                d_vh.to(vh.dtype) if d_vh is not None else None, *grads)
+                d_vh.to(vh.dtype) if d_vh is not None else None, *_slot_grads(ctx, d_w, 6))
 
 
 # ---- PCTransformer: HIP forward + HIP backward -----------------------------------------------------------------------------------
@@ -315,20 +334,12 @@ class PCTransformerFunction(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_out):
-        if torch.is_grad_enabled():
-            raise RuntimeError("PCTransformer.forward is differentiable once: its HIP backward builds no graph (create_graph is not supported)")
+        _once("PCTransformer.forward is")
         from . import ops
         pc, = ctx.saved_tensors
         need_p, need_w = ctx.needs_input_grad[4], any(ctx.needs_input_grad[5:])
         d_w, d_pc = ops.pc_transformer_backward(pc, grad_out, ctx.table_fn(), ctx.feature_dim, need=(need_w, need_p))
-        grads = []
-        for j, (idx, rows) in enumerate(ctx.slots):
-            if not ctx.needs_input_grad[5 + j]:
-                grads.append(None)
-                continue
-            g = d_w[idx] if rows is None else d_w[idx][rows[0]:rows[1]]
-            grads.append(g.to(ctx.param_dtypes[j]))
-        return (None, None, None, None, d_pc.to(pc.dtype) if d_pc is not None else None, *grads)
+        return (None, None, None, None, d_pc.to(pc.dtype) if d_pc is not None else None, *_slot_grads(ctx, d_w, 5, ctx.param_dtypes))
 
 
 # ---- SconeOcc: HIP forward + HIP backward ----------------------------------------------------------------------------------------
@@ -350,8 +361,7 @@ class SconeOccFunction(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_out):
-        if torch.is_grad_enabled():
-            raise RuntimeError("SconeOcc.forward is differentiable once: its HIP backward builds no graph (create_graph is not supported)")
+        _once("SconeOcc.forward is")
         from . import ops
         pc_global, x, vh, *scales = ctx.saved_tensors
         need_x, need_v = ctx.needs_input_grad[6], ctx.needs_input_grad[7]
@@ -361,15 +371,8 @@ class SconeOccFunction(torch.autograd.Function):
         idx = [ops.knn_points(xq, s_, ctx.k)[2] for s_ in sc]
         d_w, d_x, d_vh = ops.scone_occ_backward(pc_global.detach().float(), sc, xq, vh.detach().float(), idx, grad_out.float(),
                                                 ctx.table_fn(), need=(need_w, need_x, need_v))
-        grads = []
-        for j, (i, rows) in enumerate(ctx.slots):
-            if not ctx.needs_input_grad[8 + j]:
-                grads.append(None)
-                continue
-            g = d_w[i] if rows is None else d_w[i][rows[0]:rows[1]]
-            grads.append(g.to(ctx.param_dtypes[j]))
         return (None, None, None, None, None, None, d_x.to(x.dtype) if d_x is not None else None,
-                d_vh.to(vh.dtype) if d_vh is not None else None, *grads)
+                d_vh.to(vh.dtype) if d_vh is not None else None, *_slot_grads(ctx, d_w, 8, ctx.param_dtypes))
 
 
 class SconeOccRaggedFunction(torch.autograd.Function):
@@ -390,9 +393,7 @@ class SconeOccRaggedFunction(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_out):
-        if torch.is_grad_enabled():
-            raise RuntimeError("SconeOcc.forward_ragged is differentiable once: its HIP backward builds no graph (create_graph is not "
-                               "supported)")
+        _once("SconeOcc.forward_ragged is")
         from . import ops
         pc_global, global_len, row_job, x, vh, *clouds = ctx.saved_tensors
         need_x, need_v = ctx.needs_input_grad[9], ctx.needs_input_grad[10]
@@ -402,14 +403,8 @@ class SconeOccRaggedFunction(torch.autograd.Function):
                    for c_, sizes in zip(clouds, ctx.scale_sizes)]
         d_w, d_x, d_vh = ops.scone_occ_backward_ragged(pc_global.detach().float(), global_len, offsets, xq, vh.detach().float(), row_job,
                                                        ctx.query_sizes, grad_out.float(), ctx.table_fn(), need=(need_w, need_x, need_v))
-        grads = []
-        for j, (i, rows) in enumerate(ctx.slots):
-            if not ctx.needs_input_grad[11 + j]:
-                grads.append(None)
-                continue
-            g = d_w[i] if rows is None else d_w[i][rows[0]:rows[1]]
-            grads.append(g.to(ctx.param_dtypes[j]))
-        return (None,) * 9 + (d_x.to(x.dtype) if d_x is not None else None, d_vh.to(vh.dtype) if d_vh is not None else None, *grads)
+        return (None,) * 9 + (d_x.to(x.dtype) if d_x is not None else None, d_vh.to(vh.dtype) if d_vh is not None else None,
+                              *_slot_grads(ctx, d_w, 11, ctx.param_dtypes))
 
 
 # ---- MACARONS-regime gain: HIP forward + HIP backward ----------------------------------------------------------------------------
@@ -432,8 +427,7 @@ class MacaronsGainFunction(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_gains):
-        if torch.is_grad_enabled():
-            raise RuntimeError("the MACARONS gain is differentiable once: its HIP backward builds no graph (create_graph is not supported)")
+        _once("the MACARONS gain is")
         from . import ops
         vis, world, inverse, n_unique, cam_world, volume = ctx.saved_tensors
         d_vis, d_volume = ops.macarons_gain_backward(grad_gains.float().contiguous(), vis, world, inverse, n_unique, cam_world, volume,
@@ -460,8 +454,7 @@ class SupervisionScatterFunction(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_out):
-        if torch.is_grad_enabled():
-            raise RuntimeError("the supervision scatter is differentiable once: its HIP backward builds no graph (create_graph is not supported)")
+        _once("the supervision scatter is")
         from . import ops
         rows, pos = ctx.saved_tensors
         d_occ = ops.supervision_scatter_backward(rows, pos, grad_out.float().contiguous(), ctx.T_scatter if ctx.n_jobs else 0, ctx.T)
@@ -471,7 +464,7 @@ class SupervisionScatterFunction(torch.autograd.Function):
 # ---- depth module, the plane sweep: HIP forward + HIP backward --------------------------------------------------------------------
 def cost_volume_backward_mode():
     """'hip' (default) or 'composite' (env MCR_COST_VOLUME_BWD=composite: the recomputing torch backward, for A/B comparisons)."""
-    return "composite" if os.environ.get("MCR_COST_VOLUME_BWD", "").lower() == "composite" else "hip"
+    return _env_mode(os.environ.get("MCR_COST_VOLUME_BWD", ""), ("composite",), "hip")
 
 
 class CostVolumeFunction(torch.autograd.Function):
@@ -501,8 +494,7 @@ class CostVolumeFunction(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_out):
-        if torch.is_grad_enabled():
-            raise RuntimeError("the cost volume is differentiable once: its backward recomputes without a graph (create_graph is not supported)")
+        _once("the cost volume is", "its backward recomputes without a graph")
         x, x_alpha, cams, depth_bins = ctx.saved_tensors
         C = x.shape[1]
         g_cv = grad_out[:, C:] if ctx.concat else grad_out
@@ -532,7 +524,7 @@ class CostVolumeFunction(torch.autograd.Function):
 # ---- depth module, the photometric reconstruction loss: HIP forward + HIP backward --------------------------------------------------
 def reconstruction_loss_backward_mode():
     """'hip' (default) or 'composite' (env MCR_RECONSTRUCTION_LOSS_BWD=composite: the recomputing torch backward, for A/B comparisons)."""
-    return "composite" if os.environ.get("MCR_RECONSTRUCTION_LOSS_BWD", "").lower() == "composite" else "hip"
+    return _env_mode(os.environ.get("MCR_RECONSTRUCTION_LOSS_BWD", ""), ("composite",), "hip")
 
 
 class ReconstructionLossFunction(torch.autograd.Function):
@@ -553,9 +545,7 @@ class ReconstructionLossFunction(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_loss):
-        if torch.is_grad_enabled():
-            raise RuntimeError("the reconstruction loss is differentiable once: its backward recomputes without a graph "
-                               "(create_graph is not supported)")
+        _once("the reconstruction loss is", "its backward recomputes without a graph")
         depth, images, alpha_images, cams = ctx.saved_tensors[:4]
         mask = ctx.saved_tensors[4] if ctx.has_mask else None
         none = (None,) * 8
@@ -575,7 +565,7 @@ class ReconstructionLossFunction(torch.autograd.Function):
 # ---- depth module, disparity scales / regularity values / error mask: HIP forward + HIP backward ---------------------------------------
 def disparity_scales_backward_mode():
     """'hip' (default) or 'composite' (env MCR_DISPARITY_SCALES_BWD=composite: the recomputing torch backward, for A/B comparisons)."""
-    return "composite" if os.environ.get("MCR_DISPARITY_SCALES_BWD", "").lower() == "composite" else "hip"
+    return _env_mode(os.environ.get("MCR_DISPARITY_SCALES_BWD", ""), ("composite",), "hip")
 
 
 class DisparityScalesFunction(torch.autograd.Function):
@@ -598,9 +588,7 @@ class DisparityScalesFunction(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_depth, grad_reg, _grad_error_mask):
-        if torch.is_grad_enabled():
-            raise RuntimeError("the disparity scales are differentiable once: their backward recomputes without a graph "
-                               "(create_graph is not supported)")
+        _once("the disparity scales are", "their backward recomputes without a graph")
         images = ctx.saved_tensors[0]
         mask = ctx.saved_tensors[1] if ctx.has_mask else None
         disps = ctx.saved_tensors[2 if ctx.has_mask else 1:]

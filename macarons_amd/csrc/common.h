@@ -27,7 +27,13 @@ int check_hip(hipError_t e, const char* what);
         if (int _e = ::mcr::check_hip(hipGetLastError(), name)) return _e; \
     } while (0)
 
-static inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
+__host__ __device__ static inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
+
+// Chunk c of `chunks` equal chunks of [0, n): [i0, i1), empty past the end.
+__device__ __forceinline__ void chunk_range(int64_t n, int chunks, int c, int64_t& i0, int64_t& i1) {
+    const int64_t per = cdiv(n, chunks);
+    i0 = c * per, i1 = min(n, i0 + per);
+}
 
 // ---- wave64 DPP reductions ---------------------------------------------------------------------------
 // After wave_sum_to_last(), lane 63 holds the sum of all 64 lanes (other lanes hold partial garbage).
@@ -83,10 +89,26 @@ __device__ __forceinline__ float wave_max_all(float v) {
     return v;
 }
 
-__device__ __forceinline__ float wave_sum_all(float v) {
+template <typename T>                                  // float, double, int, long long
+__device__ __forceinline__ T wave_sum_all(T v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;
+}
+
+// The four wave totals of a 256-thread workgroup, `stride` apart, added in the one fixed association.
+template <typename T>
+__device__ __forceinline__ T four_wave_sum(const T* red, int stride = 1) {
+    return (red[0] + red[stride]) + (red[2 * stride] + red[3 * stride]);
+}
+
+// Sum of v over the workgroup's 256 threads in a fixed order, through red[4] in LDS; every thread gets it after the barrier inside.
+template <typename T>
+__device__ __forceinline__ T block_sum_256(T v, T* red) {
+    v = wave_sum_all(v);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return four_wave_sum(red);
 }
 
 }  // namespace mcr

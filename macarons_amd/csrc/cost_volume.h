@@ -2,7 +2,8 @@
 // butterfly, the bicubic tap of a lane, the pose of a source, the projection of a tap onto a plane and the bilinear corners of the
 // resized coordinate.  Both directions run the sweep below, so both compute a coordinate with the same instructions.
 #pragma once
-#include "common.h"
+#include "depth_geom.h"
+#include "workspace.h"
 #include <math.h>
 
 namespace mcr {
@@ -70,9 +71,10 @@ __device__ __forceinline__ void cv_sweep_row(const float* __restrict__ xa_cl, co
     const double fy = floor(sy), fx = floor(sx);
     const int p = min(max((int)fy - 1 + r, 0), H - 1), q = min(max((int)fx - 1 + c, 0), W - 1);
     const float wgt = (float)(cubic_weight(sy - fy, r) * cubic_weight(sx - fx, c));
-    const int m = min(H, W), mf = min(Hf, Wf);
+    const int mf = min(Hf, Wf);
     const double s = (double)fov_scale;
-    const double nx = ((double)W / m - 2.0 * q / (m - 1)) / s, ny = ((double)H / m - 2.0 * p / (m - 1)) / s;
+    double nx, ny;
+    pixel_ray(H, W, fov_scale, p, q, nx, ny);
     const float cx = (float)(-((double)mf / Wf) * s), cy = (float)(-((double)mf / Hf) * s);
 
     float dk[CV_PLANES];
@@ -123,5 +125,22 @@ __device__ __forceinline__ void cv_sweep_row(const float* __restrict__ xa_cl, co
 
 // The layout pass of cost_volume.hip: x_alpha [B*A,64,P] -> xa_cl [B*A,P,64] and the pose of every source (12 doubles each).
 void cv_launch_channels_last(const float* x_alpha, float* xa_cl, int P, const float* cams, int64_t B, int A, double* pose, hipStream_t stream);
+
+// The checks both entries share; `io` is the forward's out or the backward's d_out, `stride_name` what its batch stride is called.
+inline int cv_check(const char* who, const void* x, const void* x_alpha, const void* cams, const void* depth_bins, const void* io,
+                    const char* stride_name, int64_t batch_stride, int64_t B, int A, int C, int H, int W, int Hf, int Wf, int D, float fov_scale) {
+    MCR_REQUIRE(x && x_alpha && cams && depth_bins && io, "%s: NULL operand", who);
+    MCR_REQUIRE(C == CV_C, "%s: C = %d feature channels, only %d (ResNet layer1, upstream's feature extractor) is supported", who, C, CV_C);
+    MCR_REQUIRE(B >= 1 && A >= 1 && D >= 1, "%s: B = %lld, A = %d, D = %d must all be at least 1", who, (long long)B, A, D);
+    MCR_REQUIRE(Hf >= 1 && Wf >= 1 && Hf <= H && Wf <= W && H >= 2 && W >= 2,
+                "%s: need 1 <= Hf <= H, 1 <= Wf <= W and H, W >= 2 (got image %d x %d, features %d x %d)", who, H, W, Hf, Wf);
+    MCR_REQUIRE((int64_t)Hf * Wf <= 0x7fffffffll - CV_POS && (int64_t)H * W <= 0x7fffffffll, "%s: image too large for int pixel indices", who);
+    MCR_REQUIRE(B <= 65535 && B * A <= 65535 && cdiv(D, CV_PLANES) <= 65535, "%s: B, B*A and D/%d are limited to 65535 (grid dimensions)", who,
+                CV_PLANES);
+    MCR_REQUIRE(batch_stride >= (int64_t)D * Hf * Wf, "%s: %s = %lld is less than D*Hf*Wf = %lld", who, stride_name, (long long)batch_stride,
+                (long long)D * Hf * Wf);
+    MCR_REQUIRE(fov_scale > 0.f && fov_scale < INFINITY, "%s: fov_scale = 1/tan(fov/2) must be positive and finite", who);
+    return 0;
+}
 
 }  // namespace mcr

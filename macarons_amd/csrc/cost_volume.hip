@@ -21,24 +21,14 @@
 namespace mcr {
 
 // [img, 64, P] -> [img, P, 64] through a 64 x 64 LDS tile (padded: the transposed read is conflict-free).  The first workgroup of an
-// image (b, a) also writes its pose, 12 doubles: M = R^T R_a (row-major) and t = T_a - T M, so that the source-view point of the target-view
-// point v is v M + t.
+// image (b, a) also writes its pose, 12 doubles (pose_column, depth_geom.h).
 __global__ __launch_bounds__(256) void cv_channels_last_kernel(const float* __restrict__ src, float* __restrict__ dst, int P,
                                                                const float* __restrict__ cams, int A, double* __restrict__ pose) {
     __shared__ float tile[CV_C][CV_C + 1];
     const int64_t img = blockIdx.y;
     if (blockIdx.x == 0 && threadIdx.x < 3) {
-        const int k = threadIdx.x;
         const float* cam0 = cams + (img / A) * (1 + A) * 12;
-        const float* cama = cam0 + (1 + img % A) * 12;
-        double tk = (double)cama[9 + k];
-        for (int jj = 0; jj < 3; ++jj) {
-            const double mjk = (double)cam0[jj] * (double)cama[k] + (double)cam0[3 + jj] * (double)cama[3 + k] +
-                               (double)cam0[6 + jj] * (double)cama[6 + k];
-            pose[img * 12 + 3 * jj + k] = mjk;
-            tk -= (double)cam0[9 + jj] * mjk;
-        }
-        pose[img * 12 + 9 + k] = tk;
+        pose_column(cam0, cam0 + (1 + img % A) * 12, threadIdx.x, pose + img * 12);
     }
     const int p0 = blockIdx.x * 64;
     const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
@@ -89,37 +79,33 @@ void cv_launch_channels_last(const float* x_alpha, float* xa_cl, int P, const fl
 
 using namespace mcr;
 
+// channels-last copy of the source maps | poses
+struct CvScratch { float* xa_cl; double* pose; };
+static CvScratch carve_cv(Arena& a, int64_t B, int64_t A, int64_t C, int64_t P) {
+    CvScratch w;
+    w.xa_cl = a.f((size_t)B * A * C * P);
+    w.pose = (double*)a.bytes((size_t)B * A * 12 * sizeof(double));
+    return w;
+}
+
 extern "C" size_t mcr_cost_volume_workspace_bytes(int64_t B, int64_t A, int64_t C, int64_t Hf, int64_t Wf) {
     if (B <= 0 || A <= 0 || C <= 0 || Hf <= 0 || Wf <= 0) return 0;
-    return (size_t)B * A * (C * Hf * Wf * sizeof(float) + 12 * sizeof(double));   // channels-last copy of the source maps | poses
+    return measure(carve_cv, B, A, C, Hf * Wf);
 }
 
 extern "C" int mcr_cost_volume(const float* x, const float* x_alpha, const float* cams, const float* depth_bins, float* out,
                                int64_t out_batch_stride, int64_t B, int A, int C, int H, int W, int Hf, int Wf, int D, float fov_scale,
                                void* workspace, size_t workspace_bytes, void* stream) {
-    MCR_REQUIRE(x && x_alpha && cams && depth_bins && out, "mcr_cost_volume: NULL operand");
-    MCR_REQUIRE(C == CV_C, "mcr_cost_volume: C = %d feature channels, only %d (ResNet layer1, upstream's feature extractor) is supported", C,
-                CV_C);
-    MCR_REQUIRE(B >= 1 && A >= 1 && D >= 1, "mcr_cost_volume: B = %lld, A = %d, D = %d must all be at least 1", (long long)B, A, D);
-    MCR_REQUIRE(Hf >= 1 && Wf >= 1 && Hf <= H && Wf <= W && H >= 2 && W >= 2,
-                "mcr_cost_volume: need 1 <= Hf <= H, 1 <= Wf <= W and H, W >= 2 (got image %d x %d, features %d x %d)", H, W, Hf, Wf);
-    MCR_REQUIRE((int64_t)Hf * Wf <= 0x7fffffffll - CV_POS && (int64_t)H * W <= 0x7fffffffll, "mcr_cost_volume: image too large for int pixel indices");
-    MCR_REQUIRE(B <= 65535 && B * A <= 65535 && cdiv(D, CV_PLANES) <= 65535, "mcr_cost_volume: B, B*A and D/%d are limited to 65535 (grid dimensions)",
-                CV_PLANES);
-    MCR_REQUIRE(out_batch_stride >= (int64_t)D * Hf * Wf, "mcr_cost_volume: out_batch_stride = %lld is less than D*Hf*Wf = %lld",
-                (long long)out_batch_stride, (long long)D * Hf * Wf);
-    MCR_REQUIRE(fov_scale > 0.f && fov_scale < INFINITY, "mcr_cost_volume: fov_scale = 1/tan(fov/2) must be positive and finite");
-    const size_t need = mcr_cost_volume_workspace_bytes(B, A, C, Hf, Wf);
-    MCR_REQUIRE(workspace && workspace_bytes >= need, "mcr_cost_volume: workspace of %zu bytes, %zu needed", workspace ? workspace_bytes : (size_t)0,
-                need);
-    MCR_REQUIRE(((uintptr_t)workspace & 15) == 0, "mcr_cost_volume: the workspace must be 16-byte aligned");
+    const char* who = "mcr_cost_volume";
+    if (int e = cv_check(who, x, x_alpha, cams, depth_bins, out, "out_batch_stride", out_batch_stride, B, A, C, H, W, Hf, Wf, D, fov_scale)) return e;
+    if (int e = check_workspace(who, workspace, workspace_bytes, mcr_cost_volume_workspace_bytes(B, A, C, Hf, Wf))) return e;
     const int P = Hf * Wf;
-    float* xa_cl = (float*)workspace;
-    double* pose = (double*)(xa_cl + (size_t)B * A * CV_C * P);       // 256-byte multiple from an aligned base
-    cv_launch_channels_last(x_alpha, xa_cl, P, cams, B, A, pose, (hipStream_t)stream);
+    Arena arena{(char*)workspace, workspace_bytes};
+    const CvScratch ws = carve_cv(arena, B, A, C, P);
+    cv_launch_channels_last(x_alpha, ws.xa_cl, P, cams, B, A, ws.pose, (hipStream_t)stream);
     MCR_LAUNCH_CHECK("cv_channels_last_kernel");
     hipLaunchKernelGGL(cv_sweep_kernel, dim3((unsigned)cdiv(P, CV_POS), (unsigned)cdiv(D, CV_PLANES), (unsigned)B), dim3(256), 0,
-                       (hipStream_t)stream, x, xa_cl, pose, depth_bins, out, out_batch_stride, A, H, W, Hf, Wf, D, fov_scale);
+                       (hipStream_t)stream, x, ws.xa_cl, ws.pose, depth_bins, out, out_batch_stride, A, H, W, Hf, Wf, D, fov_scale);
     MCR_LAUNCH_CHECK("cv_sweep_kernel");
     return 0;
 }

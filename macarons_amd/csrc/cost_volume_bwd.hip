@@ -205,27 +205,28 @@ __global__ __launch_bounds__(256) void cv_from_channels_last_kernel(const float*
     }
 }
 
-// The workspace, every part a multiple of 256 bytes from an aligned base.
-struct CvBwdLayout {
-    size_t xa_cl, pose, masks, samples, counts, cursor, maxbits, entries, total;
+// The workspace.  counts and maxbits stay adjacent: the entry zeroes them with one memset.
+struct CvBwdScratch {
+    float* xa_cl;                                    // the source maps channels-last, later their gradient
+    double* pose;
+    unsigned char* masks;                            // the sign states
+    float2* samples;
+    unsigned *counts, *maxbits, *cursor;             // counts [n_dest + 1], then offsets
+    int2* entries;                                   // room for four corners of every sample
 };
 
-static size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
-
-static CvBwdLayout cv_bwd_layout(int64_t B, int64_t A, int64_t Hf, int64_t Wf, int64_t D) {
+static CvBwdScratch carve_cv_bwd(Arena& a, int64_t B, int64_t A, int64_t Hf, int64_t Wf, int64_t D) {
     const size_t P = (size_t)Hf * Wf, n_dest = (size_t)B * A * P, n_samples = n_dest * D;
-    CvBwdLayout L;
-    size_t o = 0;
-    L.xa_cl = o, o += up256(n_dest * CV_C * sizeof(float));               // the source maps channels-last, later their gradient
-    L.pose = o, o += up256((size_t)B * A * 12 * sizeof(double));
-    L.masks = o, o += up256((size_t)B * D * P * 16);                      // the sign states
-    L.samples = o, o += up256(n_samples * sizeof(float2));
-    L.counts = o, o += up256((n_dest + 1) * sizeof(unsigned));            // counts, then offsets; zeroed together with maxbits
-    L.maxbits = o, o += 256;
-    L.cursor = o, o += up256(n_dest * sizeof(unsigned));
-    L.entries = o, o += up256(4 * n_samples * sizeof(int2));              // room for four corners of every sample
-    L.total = o;
-    return L;
+    CvBwdScratch w;
+    w.xa_cl = a.f(n_dest * CV_C);
+    w.pose = (double*)a.bytes((size_t)B * A * 12 * sizeof(double));
+    w.masks = (unsigned char*)a.bytes((size_t)B * D * P * 16);
+    w.samples = (float2*)a.bytes(n_samples * sizeof(float2));
+    w.counts = (unsigned*)a.bytes((n_dest + 1) * sizeof(unsigned));
+    w.maxbits = (unsigned*)a.bytes(sizeof(unsigned));
+    w.cursor = (unsigned*)a.bytes(n_dest * sizeof(unsigned));
+    w.entries = (int2*)a.bytes(4 * n_samples * sizeof(int2));
+    return w;
 }
 
 }  // namespace mcr
@@ -235,76 +236,58 @@ using namespace mcr;
 extern "C" size_t mcr_cost_volume_backward_workspace_bytes(int64_t B, int64_t A, int64_t C, int64_t Hf, int64_t Wf, int64_t D) {
     if (B <= 0 || A <= 0 || C <= 0 || Hf <= 0 || Wf <= 0 || D <= 0) return 0;
     if (4.0 * (double)B * (double)A * (double)D * (double)Hf * (double)Wf > 2147483647.0) return 0;   // refused by the entry
-    return cv_bwd_layout(B, A, Hf, Wf, D).total;
+    return measure(carve_cv_bwd, B, A, Hf, Wf, D);
 }
 
 extern "C" int mcr_cost_volume_backward(const float* x, const float* x_alpha, const float* cams, const float* depth_bins, const float* d_out,
                                         int64_t d_out_batch_stride, float* d_x, float* d_x_alpha, int64_t B, int A, int C, int H, int W, int Hf,
                                         int Wf, int D, float fov_scale, void* workspace, size_t workspace_bytes, void* stream) {
-    MCR_REQUIRE(x && x_alpha && cams && depth_bins && d_out, "mcr_cost_volume_backward: NULL operand");
-    MCR_REQUIRE(d_x || d_x_alpha, "mcr_cost_volume_backward: nothing to do, d_x and d_x_alpha are both NULL");
-    MCR_REQUIRE(C == CV_C, "mcr_cost_volume_backward: C = %d feature channels, only %d (ResNet layer1, upstream's feature extractor) is supported",
-                C, CV_C);
-    MCR_REQUIRE(B >= 1 && A >= 1 && D >= 1, "mcr_cost_volume_backward: B = %lld, A = %d, D = %d must all be at least 1", (long long)B, A, D);
-    MCR_REQUIRE(Hf >= 1 && Wf >= 1 && Hf <= H && Wf <= W && H >= 2 && W >= 2,
-                "mcr_cost_volume_backward: need 1 <= Hf <= H, 1 <= Wf <= W and H, W >= 2 (got image %d x %d, features %d x %d)", H, W, Hf, Wf);
-    MCR_REQUIRE((int64_t)Hf * Wf <= 0x7fffffffll - CV_POS && (int64_t)H * W <= 0x7fffffffll,
-                "mcr_cost_volume_backward: image too large for int pixel indices");
-    MCR_REQUIRE(B <= 65535 && B * A <= 65535 && cdiv(D, CV_PLANES) <= 65535,
-                "mcr_cost_volume_backward: B, B*A and D/%d are limited to 65535 (grid dimensions)", CV_PLANES);
+    const char* who = "mcr_cost_volume_backward";
+    if (int e = cv_check(who, x, x_alpha, cams, depth_bins, d_out, "d_out_batch_stride", d_out_batch_stride, B, A, C, H, W, Hf, Wf, D, fov_scale))
+        return e;
+    MCR_REQUIRE(d_x || d_x_alpha, "%s: nothing to do, d_x and d_x_alpha are both NULL", who);
     MCR_REQUIRE(4.0 * (double)B * A * D * Hf * Wf <= 2147483647.0,
-                "mcr_cost_volume_backward: 4*B*A*D*Hf*Wf = %.0f corner contributions exceed the 2^31 - 1 that the lists index",
-                4.0 * (double)B * A * D * Hf * Wf);
-    MCR_REQUIRE(d_out_batch_stride >= (int64_t)D * Hf * Wf, "mcr_cost_volume_backward: d_out_batch_stride = %lld is less than D*Hf*Wf = %lld",
-                (long long)d_out_batch_stride, (long long)D * Hf * Wf);
-    MCR_REQUIRE(fov_scale > 0.f && fov_scale < INFINITY, "mcr_cost_volume_backward: fov_scale = 1/tan(fov/2) must be positive and finite");
-    const size_t need = mcr_cost_volume_backward_workspace_bytes(B, A, C, Hf, Wf, D);
-    MCR_REQUIRE(workspace && workspace_bytes >= need, "mcr_cost_volume_backward: workspace of %zu bytes, %zu needed",
-                workspace ? workspace_bytes : (size_t)0, need);
-    MCR_REQUIRE(((uintptr_t)workspace & 15) == 0, "mcr_cost_volume_backward: the workspace must be 16-byte aligned");
+                "%s: 4*B*A*D*Hf*Wf = %.0f corner contributions exceed the 2^31 - 1 that the lists index", who, 4.0 * (double)B * A * D * Hf * Wf);
+    if (int e = check_workspace(who, workspace, workspace_bytes, mcr_cost_volume_backward_workspace_bytes(B, A, C, Hf, Wf, D))) return e;
 
     const hipStream_t st = (hipStream_t)stream;
     const int P = Hf * Wf;
-    const CvBwdLayout L = cv_bwd_layout(B, A, Hf, Wf, D);
-    char* ws = (char*)workspace;
-    float* xa_cl = (float*)(ws + L.xa_cl);
-    double* pose = (double*)(ws + L.pose);
-    unsigned char* masks = (unsigned char*)(ws + L.masks);
-    float2* samples = d_x_alpha ? (float2*)(ws + L.samples) : nullptr;
-    unsigned* counts = (unsigned*)(ws + L.counts);
-    unsigned* maxbits = (unsigned*)(ws + L.maxbits);
-    unsigned* cursor = (unsigned*)(ws + L.cursor);
-    int2* entries = (int2*)(ws + L.entries);
+    Arena arena{(char*)workspace, workspace_bytes};
+    const CvBwdScratch ws = carve_cv_bwd(arena, B, A, Hf, Wf, D);
+    float2* samples = d_x_alpha ? ws.samples : nullptr;
     const int64_t n_dest = B * A * P, n_samples = n_dest * D, per_batch = (int64_t)D * P;
 
-    if (int e = check_hip(hipMemsetAsync(counts, 0, L.cursor - L.counts, st), "hipMemsetAsync(counts, maxbits)")) return e;
+    // one memset for counts and maxbits: the carve hands them out back to back, so the span is the distance between the carved pointers
+    // (whatever the rounding), not a sum of sizes written a second time
+    if (int e = check_hip(hipMemsetAsync(ws.counts, 0, (char*)ws.cursor - (char*)ws.counts, st), "hipMemsetAsync(counts, maxbits)"))
+        return e;
     hipLaunchKernelGGL(cv_maxabs_kernel, dim3((unsigned)min((int64_t)256, cdiv(per_batch, 256)), (unsigned)B), dim3(256), 0, st, d_out,
-                       d_out_batch_stride, per_batch, maxbits);
+                       d_out_batch_stride, per_batch, ws.maxbits);
     MCR_LAUNCH_CHECK("cv_maxabs_kernel");
-    cv_launch_channels_last(x_alpha, xa_cl, P, cams, B, A, pose, st);
+    cv_launch_channels_last(x_alpha, ws.xa_cl, P, cams, B, A, ws.pose, st);
     MCR_LAUNCH_CHECK("cv_channels_last_kernel");
-    hipLaunchKernelGGL(cv_sign_sweep_kernel, dim3((unsigned)cdiv(P, CV_POS), (unsigned)cdiv(D, CV_PLANES), (unsigned)B), dim3(256), 0, st, x, xa_cl,
-                       pose, depth_bins, masks, samples, A, H, W, Hf, Wf, D, fov_scale);
+    hipLaunchKernelGGL(cv_sign_sweep_kernel, dim3((unsigned)cdiv(P, CV_POS), (unsigned)cdiv(D, CV_PLANES), (unsigned)B), dim3(256), 0, st, x,
+                       ws.xa_cl, ws.pose, depth_bins, ws.masks, samples, A, H, W, Hf, Wf, D, fov_scale);
     MCR_LAUNCH_CHECK("cv_sign_sweep_kernel");
     if (d_x) {
-        hipLaunchKernelGGL(cv_dx_kernel, dim3((unsigned)cdiv(P, CV_POS), (unsigned)B), dim3(256), 0, st, d_out, d_out_batch_stride, masks, maxbits,
-                           d_x, P, D);
+        hipLaunchKernelGGL(cv_dx_kernel, dim3((unsigned)cdiv(P, CV_POS), (unsigned)B), dim3(256), 0, st, d_out, d_out_batch_stride, ws.masks,
+                           ws.maxbits, d_x, P, D);
         MCR_LAUNCH_CHECK("cv_dx_kernel");
     }
     if (d_x_alpha) {
         const dim3 sg((unsigned)cdiv(n_samples, 256));
-        hipLaunchKernelGGL(cv_scatter_kernel<false>, sg, dim3(256), 0, st, samples, d_out, d_out_batch_stride, counts, counts, entries, n_samples,
-                           A, Hf, Wf, D);
+        hipLaunchKernelGGL(cv_scatter_kernel<false>, sg, dim3(256), 0, st, samples, d_out, d_out_batch_stride, ws.counts, ws.counts, ws.entries,
+                           n_samples, A, Hf, Wf, D);
         MCR_LAUNCH_CHECK("cv_scatter_kernel<count>");
-        hipLaunchKernelGGL(cv_scan_kernel, dim3(1), dim3(CV_SCAN_THREADS), 0, st, counts, cursor, n_dest);
+        hipLaunchKernelGGL(cv_scan_kernel, dim3(1), dim3(CV_SCAN_THREADS), 0, st, ws.counts, ws.cursor, n_dest);
         MCR_LAUNCH_CHECK("cv_scan_kernel");
-        hipLaunchKernelGGL(cv_scatter_kernel<true>, sg, dim3(256), 0, st, samples, d_out, d_out_batch_stride, cursor, counts, entries, n_samples, A,
-                           Hf, Wf, D);
+        hipLaunchKernelGGL(cv_scatter_kernel<true>, sg, dim3(256), 0, st, samples, d_out, d_out_batch_stride, ws.cursor, ws.counts, ws.entries,
+                           n_samples, A, Hf, Wf, D);
         MCR_LAUNCH_CHECK("cv_scatter_kernel<fill>");
-        hipLaunchKernelGGL(cv_dest_sum_kernel, dim3((unsigned)cdiv(n_dest, CV_DEST_PER_WG)), dim3(256), 0, st, counts, entries, masks, maxbits, xa_cl,
-                           n_dest, A, P, D);
+        hipLaunchKernelGGL(cv_dest_sum_kernel, dim3((unsigned)cdiv(n_dest, CV_DEST_PER_WG)), dim3(256), 0, st, ws.counts, ws.entries, ws.masks,
+                           ws.maxbits, ws.xa_cl, n_dest, A, P, D);
         MCR_LAUNCH_CHECK("cv_dest_sum_kernel");
-        hipLaunchKernelGGL(cv_from_channels_last_kernel, dim3((unsigned)cdiv(P, 64), (unsigned)(B * A)), dim3(256), 0, st, xa_cl, d_x_alpha, P);
+        hipLaunchKernelGGL(cv_from_channels_last_kernel, dim3((unsigned)cdiv(P, 64), (unsigned)(B * A)), dim3(256), 0, st, ws.xa_cl, d_x_alpha, P);
         MCR_LAUNCH_CHECK("cv_from_channels_last_kernel");
     }
     return 0;

@@ -27,7 +27,7 @@
 // d_disp_s, plus the tile's partial of sum m G D); ds_backward_mean_kernel (adds an image's partials in a fixed order and subtracts
 // sum m G D / ((mu + eps)^2 H_s W_s), the derivative through the mean, from every pixel of d_disp_s[b]).  Both directions form n with the
 // same operations from the same partials, so they agree on every sign bit for bit.
-#include "common.h"
+#include "workspace.h"
 #include <math.h>
 
 namespace mcr {
@@ -51,14 +51,6 @@ struct DsArgs {
 // The by-value argument struct is indexed with compile-time constants only (a run-time index would copy it to scratch).
 #define DS_FOR_SCALES(s) _Pragma("unroll") for (int s = 0; s < DS_MAX_S; ++s) if (s < g.S)
 
-__device__ __forceinline__ int64_t ds_cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
-
-__device__ __forceinline__ double ds_wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 // part[((s B) + b) DS_CHUNKS + c] = the sum of chunk c of disp_s[b], in double.  grid (DS_CHUNKS, B, S).
 __global__ __launch_bounds__(256) void ds_mean_kernel(DsArgs g, double* __restrict__ part) {
     __shared__ double red[4];
@@ -68,13 +60,12 @@ __global__ __launch_bounds__(256) void ds_mean_kernel(DsArgs g, double* __restri
     DS_FOR_SCALES(s) if (s == sc) src = g.disp[s], sh = g.shift[s];
     const int64_t n = (int64_t)(g.H >> sh) * (g.W >> sh);
     src += (size_t)b * n;
-    const int64_t per = ds_cdiv(n, DS_CHUNKS), i0 = c * per, i1 = min(n, i0 + per);
+    int64_t i0, i1;
+    chunk_range(n, DS_CHUNKS, c, i0, i1);
     double acc = 0.0;
     for (int64_t i = i0 + threadIdx.x; i < i1; i += 256) acc += (double)src[i];
-    acc = ds_wave_sum(acc);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) part[((size_t)sc * g.B + b) * DS_CHUNKS + c] = (red[0] + red[1]) + (red[2] + red[3]);
+    acc = block_sum_256(acc, red);
+    if (threadIdx.x == 0) part[((size_t)sc * g.B + b) * DS_CHUNKS + c] = acc;
 }
 
 // den[s] = mu_{s,b} + 1e-7 in fp32, from the chunk sums in ascending order: thread s of the workgroup.
@@ -173,17 +164,17 @@ __global__ __launch_bounds__(DS_T* DS_T) void ds_forward_kernel(DsArgs g, const 
         const float vx = wave_sum_all(sx[s]), vy = wave_sum_all(sy[s]);
         if (lane == 0) redf[wave][s] = vx, redf[wave][g.S + s] = vy;
     }
-    t1 = ds_wave_sum(t1), t2 = ds_wave_sum(t2);
+    t1 = wave_sum_all(t1), t2 = wave_sum_all(t2);
     if (lane == 0) redd[wave][0] = t1, redd[wave][1] = t2;
     __syncthreads();
     const size_t slot = (size_t)b * gridDim.x + tile;
     if ((int)threadIdx.x < 2 * g.S) {
         const int k = threadIdx.x;
-        part_reg[slot * 2 * g.S + k] = (redf[0][k] + redf[1][k]) + (redf[2][k] + redf[3][k]);
+        part_reg[slot * 2 * g.S + k] = four_wave_sum(&redf[0][k], 2 * DS_MAX_S);
     }
     if (threadIdx.x < 2) {
         const int k = threadIdx.x;
-        part_tab[slot * 2 + k] = (redd[0][k] + redd[1][k]) + (redd[2][k] + redd[3][k]);
+        part_tab[slot * 2 + k] = four_wave_sum(&redd[0][k], 2);
     }
 }
 
@@ -203,7 +194,7 @@ __global__ __launch_bounds__(256) void ds_finish_kernel(const float* __restrict_
             const int64_t j = i - n_reg, b = j >> 1, k = j & 1;
             for (int t = lane; t < n_tiles; t += 64) acc += part_tab[(b * n_tiles + t) * 2 + k];
         }
-        acc = ds_wave_sum(acc);
+        acc = wave_sum_all(acc);
         if (lane == 0) sb[i] = acc;
     }
     __syncthreads();
@@ -285,14 +276,14 @@ __global__ __launch_bounds__(DS_T* DS_T) void ds_backward_kernel(DsArgs g, const
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     if (d_reg) {
         DS_FOR_SCALES(s) {
-            const double v = ds_wave_sum(mgd[s]);
+            const double v = wave_sum_all(mgd[s]);
             if (lane == 0) redd[wave][s] = v;
         }
     }
     __syncthreads();
     if (d_reg && (int)threadIdx.x < g.S) {
         const int s = threadIdx.x;
-        part[((size_t)b * gridDim.x + tile) * g.S + s] = (redd[0][s] + redd[1][s]) + (redd[2][s] + redd[3][s]);
+        part[((size_t)b * gridDim.x + tile) * g.S + s] = four_wave_sum(&redd[0][s], DS_MAX_S);
     }
     // the r x r blocks of the tile, each summed row-major by one thread
     DS_FOR_SCALES(s) {
@@ -321,17 +312,16 @@ __global__ __launch_bounds__(256) void ds_backward_mean_kernel(DsArgs g, const d
     ds_means(g, mean_part, b, den);
     double acc = 0.0;
     for (int t = threadIdx.x; t < n_tiles; t += 256) acc += part[((size_t)b * n_tiles + t) * g.S + sc];
-    acc = ds_wave_sum(acc);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-    __syncthreads();
+    acc = block_sum_256(acc, red);
     float* dst = nullptr;
     int sh = 0;
     DS_FOR_SCALES(s) if (s == sc) dst = g.d_disp[s], sh = g.shift[s];
     const int64_t n = (int64_t)(g.H >> sh) * (g.W >> sh);
     const double dn = (double)den[sc];
-    const float sub = (float)(((red[0] + red[1]) + (red[2] + red[3])) / (dn * dn * (double)n));
+    const float sub = (float)(acc / (dn * dn * (double)n));
     dst += (size_t)b * n;
-    const int64_t per = ds_cdiv(n, DS_CHUNKS), i0 = c * per, i1 = min(n, i0 + per);
+    int64_t i0, i1;
+    chunk_range(n, DS_CHUNKS, c, i0, i1);
     for (int64_t i = i0 + threadIdx.x; i < i1; i += 256) dst[i] -= sub;
 }
 
@@ -343,38 +333,32 @@ static bool ds_sizes_ok(int64_t S, int64_t B, int64_t H, int64_t W) {
     return true;
 }
 
-static size_t ds_up256(size_t v) { return (v + 255) & ~(size_t)255; }
-
-struct DsFwdLayout {
-    size_t mean, reg, tabp, sb, tab, thr, total;
+// The forward's workspace.  tab and thr are the caller's outputs when it asks for them; the scratch copies are carved either way.
+struct DsFwdScratch {
+    double* mean_part;                               // [S,B,DS_CHUNKS]
+    float* part_reg;                                 // [B,tiles,2S]
+    double *part_tab, *sb;                           // [B,tiles,2]; 2 S B + 2 B sums
+    float *tab, *thr;                                // [B,H,W]; [B]
 };
-
-static DsFwdLayout ds_fwd_layout(int64_t S, int64_t B, int64_t H, int64_t W) {
+static DsFwdScratch carve_ds_fwd(Arena& a, int64_t S, int64_t B, int64_t H, int64_t W) {
     const size_t tiles = (size_t)(cdiv(H, DS_T) * cdiv(W, DS_T));
-    DsFwdLayout L;
-    size_t o = 0;
-    L.mean = o, o += ds_up256((size_t)S * B * DS_CHUNKS * sizeof(double));
-    L.reg = o, o += ds_up256((size_t)B * tiles * 2 * S * sizeof(float));
-    L.tabp = o, o += ds_up256((size_t)B * tiles * 2 * sizeof(double));
-    L.sb = o, o += ds_up256(((size_t)B * 2 * S + 2 * (size_t)B) * sizeof(double));
-    L.tab = o, o += ds_up256((size_t)B * H * W * sizeof(float));
-    L.thr = o, o += ds_up256((size_t)B * sizeof(float));
-    L.total = o;
-    return L;
+    DsFwdScratch w;
+    w.mean_part = (double*)a.bytes((size_t)S * B * DS_CHUNKS * sizeof(double));
+    w.part_reg = a.f((size_t)B * tiles * 2 * S);
+    w.part_tab = (double*)a.bytes((size_t)B * tiles * 2 * sizeof(double));
+    w.sb = (double*)a.bytes(((size_t)B * 2 * S + 2 * (size_t)B) * sizeof(double));
+    w.tab = a.f((size_t)B * H * W);
+    w.thr = a.f((size_t)B);
+    return w;
 }
 
-struct DsBwdLayout {
-    size_t mean, part, total;
-};
-
-static DsBwdLayout ds_bwd_layout(int64_t S, int64_t B, int64_t H, int64_t W) {
+struct DsBwdScratch { double *mean_part, *part; };   // [S,B,DS_CHUNKS]; [B,tiles,S]
+static DsBwdScratch carve_ds_bwd(Arena& a, int64_t S, int64_t B, int64_t H, int64_t W) {
     const size_t tiles = (size_t)(cdiv(H, DS_T) * cdiv(W, DS_T));
-    DsBwdLayout L;
-    size_t o = 0;
-    L.mean = o, o += ds_up256((size_t)S * B * DS_CHUNKS * sizeof(double));
-    L.part = o, o += ds_up256((size_t)B * tiles * S * sizeof(double));
-    L.total = o;
-    return L;
+    DsBwdScratch w;
+    w.mean_part = (double*)a.bytes((size_t)S * B * DS_CHUNKS * sizeof(double));
+    w.part = (double*)a.bytes((size_t)B * tiles * S * sizeof(double));
+    return w;
 }
 
 // The checks both entries share, and the argument struct (d_disps may be NULL: the forward).
@@ -411,7 +395,7 @@ using namespace mcr;
 
 extern "C" size_t mcr_disparity_scales_workspace_bytes(int64_t S, int64_t B, int64_t H, int64_t W) {
     if (!ds_sizes_ok(S, B, H, W)) return 0;
-    return ds_fwd_layout(S, B, H, W).total;
+    return measure(carve_ds_fwd, S, B, H, W);
 }
 
 extern "C" int mcr_disparity_scales(const float* const* disps, const int* Hs, const int* Ws, const float* images, const unsigned char* mask,
@@ -421,26 +405,20 @@ extern "C" int mcr_disparity_scales(const float* const* disps, const int* Hs, co
     DsArgs g;
     if (int e = ds_prepare(who, disps, nullptr, Hs, Ws, images, mask, S, B, H, W, znear, zfar, g)) return e;
     MCR_REQUIRE(depth && reg && error_mask, "%s: NULL depth, reg or error_mask", who);
-    const size_t need = mcr_disparity_scales_workspace_bytes(S, B, H, W);
-    MCR_REQUIRE(workspace && workspace_bytes >= need, "%s: workspace of %zu bytes, %zu needed", who, workspace ? workspace_bytes : (size_t)0, need);
-    MCR_REQUIRE(((uintptr_t)workspace & 15) == 0, "%s: the workspace must be 16-byte aligned", who);
+    if (int e = check_workspace(who, workspace, workspace_bytes, mcr_disparity_scales_workspace_bytes(S, B, H, W))) return e;
 
     const hipStream_t st = (hipStream_t)stream;
-    const DsFwdLayout L = ds_fwd_layout(S, B, H, W);
-    char* ws = (char*)workspace;
-    double* mean_part = (double*)(ws + L.mean);
-    float* part_reg = (float*)(ws + L.reg);
-    double* part_tab = (double*)(ws + L.tabp);
-    double* sb = (double*)(ws + L.sb);
-    float* tab_out = tab ? tab : (float*)(ws + L.tab);
-    float* thr_out = thr ? thr : (float*)(ws + L.thr);
+    Arena arena{(char*)workspace, workspace_bytes};
+    const DsFwdScratch ws = carve_ds_fwd(arena, S, B, H, W);
+    float* tab_out = tab ? tab : ws.tab;
+    float* thr_out = thr ? thr : ws.thr;
     const int n_tiles = (int)(cdiv(H, DS_T) * cdiv(W, DS_T));
-    hipLaunchKernelGGL(ds_mean_kernel, dim3(DS_CHUNKS, (unsigned)B, (unsigned)S), dim3(256), 0, st, g, mean_part);
+    hipLaunchKernelGGL(ds_mean_kernel, dim3(DS_CHUNKS, (unsigned)B, (unsigned)S), dim3(256), 0, st, g, ws.mean_part);
     MCR_LAUNCH_CHECK("ds_mean_kernel");
-    hipLaunchKernelGGL(ds_forward_kernel, dim3((unsigned)n_tiles, (unsigned)B), dim3(DS_T * DS_T), 0, st, g, mean_part, depth, tab_out, part_reg,
-                       part_tab);
+    hipLaunchKernelGGL(ds_forward_kernel, dim3((unsigned)n_tiles, (unsigned)B), dim3(DS_T * DS_T), 0, st, g, ws.mean_part, depth, tab_out, ws.part_reg,
+                       ws.part_tab);
     MCR_LAUNCH_CHECK("ds_forward_kernel");
-    hipLaunchKernelGGL(ds_finish_kernel, dim3(1), dim3(256), 0, st, part_reg, part_tab, sb, reg, thr_out, S, (int)B, H, W, n_tiles);
+    hipLaunchKernelGGL(ds_finish_kernel, dim3(1), dim3(256), 0, st, ws.part_reg, ws.part_tab, ws.sb, reg, thr_out, S, (int)B, H, W, n_tiles);
     MCR_LAUNCH_CHECK("ds_finish_kernel");
     const int64_t n_pix = (int64_t)H * W;
     hipLaunchKernelGGL(ds_mask_kernel, dim3((unsigned)cdiv(n_pix, 256), (unsigned)B), dim3(256), 0, st, tab_out, thr_out, error_mask, n_pix);
@@ -450,7 +428,7 @@ extern "C" int mcr_disparity_scales(const float* const* disps, const int* Hs, co
 
 extern "C" size_t mcr_disparity_scales_backward_workspace_bytes(int64_t S, int64_t B, int64_t H, int64_t W) {
     if (!ds_sizes_ok(S, B, H, W)) return 0;
-    return ds_bwd_layout(S, B, H, W).total;
+    return measure(carve_ds_bwd, S, B, H, W);
 }
 
 extern "C" int mcr_disparity_scales_backward(const float* const* disps, const int* Hs, const int* Ws, const float* images,
@@ -462,24 +440,20 @@ extern "C" int mcr_disparity_scales_backward(const float* const* disps, const in
     DsArgs g;
     if (int e = ds_prepare(who, disps, d_disps, Hs, Ws, images, mask, S, B, H, W, znear, zfar, g)) return e;
     MCR_REQUIRE(d_depth || d_reg, "%s: d_depth and d_reg are both NULL, nothing to do", who);
-    const size_t need = mcr_disparity_scales_backward_workspace_bytes(S, B, H, W);
-    MCR_REQUIRE(workspace && workspace_bytes >= need, "%s: workspace of %zu bytes, %zu needed", who, workspace ? workspace_bytes : (size_t)0, need);
-    MCR_REQUIRE(((uintptr_t)workspace & 15) == 0, "%s: the workspace must be 16-byte aligned", who);
+    if (int e = check_workspace(who, workspace, workspace_bytes, mcr_disparity_scales_backward_workspace_bytes(S, B, H, W))) return e;
 
     const hipStream_t st = (hipStream_t)stream;
-    const DsBwdLayout L = ds_bwd_layout(S, B, H, W);
-    char* ws = (char*)workspace;
-    double* mean_part = (double*)(ws + L.mean);
-    double* part = (double*)(ws + L.part);
+    Arena arena{(char*)workspace, workspace_bytes};
+    const DsBwdScratch ws = carve_ds_bwd(arena, S, B, H, W);
     const int n_tiles = (int)(cdiv(H, DS_T) * cdiv(W, DS_T));
     if (d_reg) {
-        hipLaunchKernelGGL(ds_mean_kernel, dim3(DS_CHUNKS, (unsigned)B, (unsigned)S), dim3(256), 0, st, g, mean_part);
+        hipLaunchKernelGGL(ds_mean_kernel, dim3(DS_CHUNKS, (unsigned)B, (unsigned)S), dim3(256), 0, st, g, ws.mean_part);
         MCR_LAUNCH_CHECK("ds_mean_kernel");
     }
-    hipLaunchKernelGGL(ds_backward_kernel, dim3((unsigned)n_tiles, (unsigned)B), dim3(DS_T * DS_T), 0, st, g, mean_part, d_depth, d_reg, part);
+    hipLaunchKernelGGL(ds_backward_kernel, dim3((unsigned)n_tiles, (unsigned)B), dim3(DS_T * DS_T), 0, st, g, ws.mean_part, d_depth, d_reg, ws.part);
     MCR_LAUNCH_CHECK("ds_backward_kernel");
     if (d_reg) {
-        hipLaunchKernelGGL(ds_backward_mean_kernel, dim3(DS_CHUNKS, (unsigned)B, (unsigned)S), dim3(256), 0, st, g, mean_part, part, n_tiles);
+        hipLaunchKernelGGL(ds_backward_mean_kernel, dim3(DS_CHUNKS, (unsigned)B, (unsigned)S), dim3(256), 0, st, g, ws.mean_part, ws.part, n_tiles);
         MCR_LAUNCH_CHECK("ds_backward_mean_kernel");
     }
     return 0;

@@ -2,11 +2,12 @@
 //   1. The weight tables (arrays of device pointers; order documented in include/macarons_hip.h, produced by networks/packing.py):
 //      slot names, table lengths, the structs the entries work on, ONE reader per struct and ONE validation.  No table index is
 //      written as an integer anywhere else.
-//   2. The caller's workspace: ONE bump allocator with the one rounding rule.  Every entry describes its scratch as a struct of
-//      pointers with one carve function next to the code that uses it; its *_workspace_bytes runs that same function on a
-//      measuring arena, so the stated size and the layout cannot drift apart, and every carve is checked against the capacity.
+//   2. The caller's workspace: the bump allocator, its one rounding rule and `measure` live in workspace.h (the depth module carves its
+//      workspaces with them too) and come in through this header.  Every entry describes its scratch as a struct of pointers with one carve
+//      function next to the code that uses it; its *_workspace_bytes runs that same function on a measuring arena, so the stated size and
+//      the layout cannot drift apart, and every carve is checked against the capacity.
 #pragma once
-#include "common.h"
+#include "workspace.h"
 
 namespace mcr {
 
@@ -111,31 +112,6 @@ inline OccW read_occ_table(const float* const* weights, int n_weights) {
     const float* const* lin = weights + OCC_LIN;
     w.lin1 = read_lin(lin); w.lin2 = read_lin(lin + LIN_NW); w.lin3 = read_lin(lin + 2 * LIN_NW);
     return w;
-}
-
-// ---- workspace -------------------------------------------------------------------------------------------------------------------
-inline size_t align256(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
-
-// Bump allocator over the caller's workspace (256-B aligned blocks).  Without a base it only measures: the carve functions run
-// on it unchanged, hand out NULLs, and `off` is what they need.  ok(): nothing carved so far lies beyond the capacity.
-struct Arena {
-    char* base = nullptr; size_t cap = ~(size_t)0, off = 0;            // (as constructed by default: a measuring arena)
-    void* bytes(size_t n) {
-        char* p = base ? base + off : nullptr;
-        off += align256(n);
-        return p;
-    }
-    float* f(size_t n_floats) { return reinterpret_cast<float*>(bytes(n_floats * sizeof(float))); }
-    bool ok() const { return off <= cap; }
-    // what is left behind the carved part, as an arena of its own (a region alternatives reuse: each carves a copy of it)
-    Arena rest() const { return Arena{base ? base + off : nullptr, off <= cap ? cap - off : 0}; }
-};
-// bytes `carve(arena, args...)` consumes
-template <class Carve, class... A>
-inline size_t measure(Carve carve, A... args) {
-    Arena a;
-    carve(a, args...);
-    return a.off;
 }
 
 }  // namespace mcr

@@ -25,7 +25,8 @@
 // three coefficients of its selected source times the window's gate (mask_n / mask_factor_b) d_loss[s] f/3, a second pass sums per pixel
 // over every (window n, offset) whose reflected position is that pixel -- an edge pixel enters a window more than once -- and
 //   d_depth[p] = sum_a sum_c dL/dIw[a,c,p] (dIw/dpx dpx/dd + dIw/dpy dpy/dd).
-#include "common.h"
+#include "depth_geom.h"
+#include "workspace.h"
 #include <math.h>
 
 namespace mcr {
@@ -47,24 +48,14 @@ struct RlArgs {
     int border;                                      // padding mode: 0 zeros, 1 border
 };
 
-__device__ __forceinline__ int64_t cdiv_dev(int64_t a, int64_t b) { return (a + b - 1) / b; }
-
 __device__ __forceinline__ int rl_reflect(int c, int n) { return c < 0 ? -c : (c >= n ? 2 * n - 2 - c : c); }
 
-// The poses of image b's sources into LDS, 12 doubles each: M = R^T R_a row-major, then t = T_a - T M (cost_volume.hip's).
+// The poses of image b's sources into LDS, 12 doubles each (pose_column, depth_geom.h: the plane sweep's).
 __device__ __forceinline__ void rl_pose(const float* __restrict__ cams, int b, int A, double* pose) {
     for (int i = threadIdx.x; i < 3 * A; i += blockDim.x) {
         const int a = i / 3, k = i - 3 * a;
         const float* cam0 = cams + (size_t)b * (1 + A) * 12;
-        const float* cama = cam0 + (size_t)(1 + a) * 12;
-        double tk = (double)cama[9 + k];
-        for (int jj = 0; jj < 3; ++jj) {
-            const double mjk = (double)cam0[jj] * (double)cama[k] + (double)cam0[3 + jj] * (double)cama[3 + k] +
-                               (double)cam0[6 + jj] * (double)cama[6 + k];
-            pose[a * 12 + 3 * jj + k] = mjk;
-            tk -= (double)cam0[9 + jj] * mjk;
-        }
-        pose[a * 12 + 9 + k] = tk;
+        pose_column(cam0, cam0 + (size_t)(1 + a) * 12, k, pose + a * 12);
     }
 }
 
@@ -137,12 +128,6 @@ __device__ __forceinline__ float rl_depth(const RlArgs& g, int s, int b, int p, 
     return (g.mask && !g.mask[pix]) ? g.zfar : d;
 }
 
-__device__ __forceinline__ void rl_ray(const RlArgs& g, int p, int q, double& nx, double& ny) {
-    const int m = min(g.H, g.W);
-    const double s = (double)g.fov_scale;
-    nx = ((double)g.W / m - 2.0 * q / (m - 1)) / s, ny = ((double)g.H / m - 2.0 * p / (m - 1)) / s;
-}
-
 // Fills the region of a tile: padded coordinates [y0 - HALO, y0 + RL_T + HALO) x [x0 - HALO, ...), row-major, RW = RL_T + 2 HALO wide.
 // tgt[c * R + r] the target, wrp[(a * 3 + c) * R + r] the warped sources, at the REFLECTED pixel of r; a padded coordinate outside
 // [-1, size] belongs to no window and holds 0.
@@ -168,7 +153,7 @@ __device__ __forceinline__ void rl_warp_region(const RlArgs& g, int s, int b, in
         for (int c = 0; c < 3; ++c) tgt[c * R + r] = ip[c];
         const float d = rl_depth(g, s, b, p, q);
         double nx, ny;
-        rl_ray(g, p, q, nx, ny);
+        pixel_ray(g.H, g.W, g.fov_scale, p, q, nx, ny);
         for (int a = 0; a < A; ++a) {
             float val[3], dval[3];
             rl_sample<false>(g, g.alpha + ((size_t)b * A + a) * (size_t)H * W * 3, pose + a * 12, nx, ny, d, val, dval);
@@ -234,14 +219,6 @@ __device__ __forceinline__ float rl_select(const float* tgt, const float* wrp, i
     return best;
 }
 
-// Sum of v over the workgroup's 256 threads in a fixed order, returned in thread 0.
-__device__ __forceinline__ float rl_block_sum(float v, float* red) {
-    v = wave_sum_all(v);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return (red[0] + red[1]) + (red[2] + red[3]);
-}
-
 __global__ __launch_bounds__(RL_T* RL_T) void rl_forward_kernel(RlArgs g, float* __restrict__ loss_map, unsigned char* __restrict__ argmin,
                                                                float* __restrict__ part_sum, int* __restrict__ part_cnt) {
     constexpr int HALO = 1, RW = RL_T + 2 * HALO, R = RW * RW;
@@ -270,14 +247,11 @@ __global__ __launch_bounds__(RL_T* RL_T) void rl_forward_kernel(RlArgs g, float*
         const bool on = !g.mask || g.mask[pix];
         contrib = on ? l : 0.f, cnt = on ? 1 : 0;
     }
-    const float tot = rl_block_sum(contrib, red);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o, 64);
-    if ((threadIdx.x & 63) == 0) redc[threadIdx.x >> 6] = cnt;
-    __syncthreads();
+    const float tot = block_sum_256(contrib, red);
+    cnt = block_sum_256(cnt, redc);
     if (threadIdx.x == 0) {
         const size_t i = ((size_t)s * g.B + b) * gridDim.x + tile;
-        part_sum[i] = tot, part_cnt[i] = redc[0] + redc[1] + redc[2] + redc[3];
+        part_sum[i] = tot, part_cnt[i] = cnt;
     }
 }
 
@@ -290,8 +264,7 @@ __global__ __launch_bounds__(256) void rl_finish_kernel(const float* __restrict_
         double acc = 0.0;
         long long c = 0;
         for (int t = lane; t < n_tiles; t += 64) acc += (double)part_sum[i * n_tiles + t], c += part_cnt[i * n_tiles + t];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64), c += __shfl_xor(c, o, 64);
+        acc = wave_sum_all(acc), c = wave_sum_all(c);
         if (lane == 0) sb[i] = masked ? acc / (double)((float)c + 1e-7f) : acc;
     }
     __syncthreads();
@@ -307,14 +280,12 @@ __global__ __launch_bounds__(256) void rl_finish_kernel(const float* __restrict_
 __global__ __launch_bounds__(256) void rl_mask_count_kernel(const unsigned char* __restrict__ mask, int64_t n_pix, int* __restrict__ cnt) {
     __shared__ int red[4];
     const unsigned char* mb = mask + (size_t)blockIdx.y * n_pix;
-    const int64_t per = cdiv_dev(n_pix, RL_CNT_CHUNKS), i0 = blockIdx.x * per, i1 = min(n_pix, i0 + per);
+    int64_t i0, i1;
+    chunk_range(n_pix, RL_CNT_CHUNKS, blockIdx.x, i0, i1);
     int c = 0;
     for (int64_t i = i0 + threadIdx.x; i < i1; i += 256) c += mb[i] ? 1 : 0;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) cnt[blockIdx.y * RL_CNT_CHUNKS + blockIdx.x] = red[0] + red[1] + red[2] + red[3];
+    c = block_sum_256(c, red);
+    if (threadIdx.x == 0) cnt[blockIdx.y * RL_CNT_CHUNKS + blockIdx.x] = c;
 }
 
 __global__ __launch_bounds__(RL_T* RL_T) void rl_backward_kernel(RlArgs g, const float* __restrict__ d_loss, const int* __restrict__ mask_cnt,
@@ -384,7 +355,7 @@ __global__ __launch_bounds__(RL_T* RL_T) void rl_backward_kernel(RlArgs g, const
     const int rc = (ty + HALO) * RW + tx + HALO, nc = (ty + 1) * NW + tx + 1;
     const float d = g.depth[o];
     double nx, ny;
-    rl_ray(g, p, q, nx, ny);
+    pixel_ray(H, W, g.fov_scale, p, q, nx, ny);
     float acc = 0.f;
     for (int a = 0; a < A; ++a) {
         float ca[3] = {0.f, 0.f, 0.f}, cb[3] = {0.f, 0.f, 0.f}, cg[3] = {0.f, 0.f, 0.f};
@@ -431,22 +402,20 @@ static bool rl_sizes_ok(int64_t S, int64_t B, int64_t A, int64_t H, int64_t W) {
     return true;
 }
 
-static size_t rl_up256(size_t v) { return (v + 255) & ~(size_t)255; }
-
-struct RlFwdLayout {
-    size_t sum, cnt, sb, total;
-};
-
-static RlFwdLayout rl_fwd_layout(int64_t S, int64_t B, int64_t H, int64_t W) {
+// The forward's workspace: a partial sum and a mask count per (s, b, tile), a double per (s, b).
+struct RlFwdScratch { float* part_sum; int* part_cnt; double* sb; };
+static RlFwdScratch carve_rl_fwd(Arena& a, int64_t S, int64_t B, int64_t H, int64_t W) {
     const size_t n = (size_t)S * B * (size_t)(cdiv(H, RL_T) * cdiv(W, RL_T));
-    RlFwdLayout L;
-    size_t o = 0;
-    L.sum = o, o += rl_up256(n * sizeof(float));
-    L.cnt = o, o += rl_up256(n * sizeof(int));
-    L.sb = o, o += rl_up256((size_t)S * B * sizeof(double));
-    L.total = o;
-    return L;
+    RlFwdScratch w;
+    w.part_sum = a.f(n);
+    w.part_cnt = (int*)a.bytes(n * sizeof(int));
+    w.sb = (double*)a.bytes((size_t)S * B * sizeof(double));
+    return w;
 }
+
+// The backward's: the mask counts of every image, by chunk.
+struct RlBwdScratch { int* mask_cnt; };
+static RlBwdScratch carve_rl_bwd(Arena& a, int64_t B) { return {(int*)a.bytes((size_t)B * RL_CNT_CHUNKS * sizeof(int))}; }
 
 static int rl_check(const char* who, const void* images, const void* alpha, const void* cams, const void* depth, int64_t S, int64_t B, int A,
                     int H, int W, float fov_scale, float zfar, float ssim_factor, int padding_mode) {
@@ -478,7 +447,7 @@ using namespace mcr;
 
 extern "C" size_t mcr_reconstruction_loss_workspace_bytes(int64_t S, int64_t B, int64_t A, int64_t H, int64_t W) {
     if (!rl_sizes_ok(S, B, A, H, W)) return 0;
-    return rl_fwd_layout(S, B, H, W).total;
+    return measure(carve_rl_fwd, S, B, H, W);
 }
 
 extern "C" int mcr_reconstruction_loss(const float* images, const float* alpha_images, const unsigned char* mask, const float* cams,
@@ -488,24 +457,19 @@ extern "C" int mcr_reconstruction_loss(const float* images, const float* alpha_i
     const char* who = "mcr_reconstruction_loss";
     if (int e = rl_check(who, images, alpha_images, cams, depth, S, B, A, H, W, fov_scale, zfar, ssim_factor, padding_mode)) return e;
     MCR_REQUIRE(loss, "%s: NULL loss", who);
-    const size_t need = mcr_reconstruction_loss_workspace_bytes(S, B, A, H, W);
-    MCR_REQUIRE(workspace && workspace_bytes >= need, "%s: workspace of %zu bytes, %zu needed", who, workspace ? workspace_bytes : (size_t)0, need);
-    MCR_REQUIRE(((uintptr_t)workspace & 15) == 0, "%s: the workspace must be 16-byte aligned", who);
+    if (int e = check_workspace(who, workspace, workspace_bytes, mcr_reconstruction_loss_workspace_bytes(S, B, A, H, W))) return e;
 
     const hipStream_t st = (hipStream_t)stream;
-    const RlFwdLayout L = rl_fwd_layout(S, B, H, W);
-    char* ws = (char*)workspace;
-    float* part_sum = (float*)(ws + L.sum);
-    int* part_cnt = (int*)(ws + L.cnt);
-    double* sb = (double*)(ws + L.sb);
+    Arena arena{(char*)workspace, workspace_bytes};
+    const RlFwdScratch ws = carve_rl_fwd(arena, S, B, H, W);
     const RlArgs g = rl_args(images, alpha_images, mask, cams, depth, B, A, H, W, fov_scale, zfar, ssim_factor, padding_mode);
     const int n_tiles = (int)(cdiv(H, RL_T) * cdiv(W, RL_T));
     constexpr int R = (RL_T + 2) * (RL_T + 2);
     const size_t lds = (size_t)A * 12 * sizeof(double) + (size_t)(3 + 3 * A) * R * sizeof(float);
     hipLaunchKernelGGL(rl_forward_kernel, dim3((unsigned)n_tiles, (unsigned)B, (unsigned)S), dim3(RL_T * RL_T), lds, st, g, loss_map, argmin,
-                       part_sum, part_cnt);
+                       ws.part_sum, ws.part_cnt);
     MCR_LAUNCH_CHECK("rl_forward_kernel");
-    hipLaunchKernelGGL(rl_finish_kernel, dim3(1), dim3(256), 0, st, part_sum, part_cnt, sb, loss, (int)S, (int)B, n_tiles, mask ? 1 : 0,
+    hipLaunchKernelGGL(rl_finish_kernel, dim3(1), dim3(256), 0, st, ws.part_sum, ws.part_cnt, ws.sb, loss, (int)S, (int)B, n_tiles, mask ? 1 : 0,
                        (double)B * H * W);
     MCR_LAUNCH_CHECK("rl_finish_kernel");
     return 0;
@@ -513,7 +477,7 @@ extern "C" int mcr_reconstruction_loss(const float* images, const float* alpha_i
 
 extern "C" size_t mcr_reconstruction_loss_backward_workspace_bytes(int64_t S, int64_t B, int64_t A, int64_t H, int64_t W) {
     if (!rl_sizes_ok(S, B, A, H, W)) return 0;
-    return rl_up256((size_t)B * RL_CNT_CHUNKS * sizeof(int));                            // the mask counts of every image, by chunk
+    return measure(carve_rl_bwd, B);
 }
 
 extern "C" int mcr_reconstruction_loss_backward(const float* images, const float* alpha_images, const unsigned char* mask, const float* cams,
@@ -523,12 +487,11 @@ extern "C" int mcr_reconstruction_loss_backward(const float* images, const float
     const char* who = "mcr_reconstruction_loss_backward";
     if (int e = rl_check(who, images, alpha_images, cams, depth, S, B, A, H, W, fov_scale, zfar, ssim_factor, padding_mode)) return e;
     MCR_REQUIRE(d_loss && d_depth, "%s: NULL d_loss or d_depth", who);
-    const size_t need = mcr_reconstruction_loss_backward_workspace_bytes(S, B, A, H, W);
-    MCR_REQUIRE(workspace && workspace_bytes >= need, "%s: workspace of %zu bytes, %zu needed", who, workspace ? workspace_bytes : (size_t)0, need);
-    MCR_REQUIRE(((uintptr_t)workspace & 15) == 0, "%s: the workspace must be 16-byte aligned", who);
+    if (int e = check_workspace(who, workspace, workspace_bytes, mcr_reconstruction_loss_backward_workspace_bytes(S, B, A, H, W))) return e;
 
     const hipStream_t st = (hipStream_t)stream;
-    int* mask_cnt = (int*)workspace;
+    Arena arena{(char*)workspace, workspace_bytes};
+    int* mask_cnt = carve_rl_bwd(arena, B).mask_cnt;
     const RlArgs g = rl_args(images, alpha_images, mask, cams, depth, B, A, H, W, fov_scale, zfar, ssim_factor, padding_mode);
     if (mask) {
         hipLaunchKernelGGL(rl_mask_count_kernel, dim3(RL_CNT_CHUNKS, (unsigned)B), dim3(256), 0, st, mask, (int64_t)H * W, mask_cnt);

@@ -35,23 +35,31 @@ def pack_cameras(R, T, R_alpha, T_alpha):
     return torch.cat((tgt, src), 1).float().contiguous()
 
 
-def cost_volume_planes(x, x_alpha, cams, depth_bins, H, W, fov_scale=COST_VOLUME_FOV_SCALE):
-    """The cost volume [B,len(depth_bins),Hf,Wf] of the given planes in torch ops, in x's dtype, all planes at once."""
-    B, A, C, Hf, Wf = x_alpha.shape
-    dt, dev, s = x.dtype, x.device, float(fov_scale)
-    Dc = depth_bins.numel()
-    cams = cams.to(dt)
+def _source_rays(cams, H, W, fov_scale, dtype, device):
+    """cams [B,1+A,12] -> (u [B,A,H,W,3], t [B,A,3]): the source-view point of full-resolution pixel (p, q) at depth d is
+    d * u[b,a,p,q] + t[b,a], for every source a of image b."""
+    B, A = cams.shape[0], cams.shape[1] - 1
+    cams = cams.to(dtype)
     R, T = cams[:, 0, :9].reshape(B, 3, 3), cams[:, 0, 9:]
     Ra, Ta = cams[:, 1:, :9].reshape(B, A, 3, 3), cams[:, 1:, 9:]
-    m, mf = min(H, W), min(Hf, Wf)
+    m = min(H, W)
     # the ray of full-resolution pixel (p, q) in the target view, per unit depth (reproject_depth_map, ManyDepth.py:128-137)
-    nx = (W / m - 2.0 * torch.arange(W, dtype=dt, device=dev) / (m - 1)) / s
-    ny = (H / m - 2.0 * torch.arange(H, dtype=dt, device=dev) / (m - 1)) / s
-    n = torch.stack((nx[None, :].expand(H, W), ny[:, None].expand(H, W), torch.ones(H, W, dtype=dt, device=dev)), -1)
+    nx = (W / m - 2.0 * torch.arange(W, dtype=dtype, device=device) / (m - 1)) / fov_scale
+    ny = (H / m - 2.0 * torch.arange(H, dtype=dtype, device=device) / (m - 1)) / fov_scale
+    n = torch.stack((nx[None, :].expand(H, W), ny[:, None].expand(H, W), torch.ones(H, W, dtype=dtype, device=device)), -1)
     # target view -> world -> source view is affine: v_a = v (R^T R_a) + (T_a - T R^T R_a), hence affine in the depth along a ray
     M = torch.einsum("bij,baik->bajk", R, Ra)
     u = torch.einsum("hwj,bajk->bahwk", n, M)
-    t = Ta - torch.einsum("bj,bajk->bak", T, M)
+    return u, Ta - torch.einsum("bj,bajk->bak", T, M)
+
+
+def cost_volume_planes(x, x_alpha, cams, depth_bins, H, W, fov_scale=COST_VOLUME_FOV_SCALE):
+    """The cost volume [B,len(depth_bins),Hf,Wf] of the given planes in torch ops, in x's dtype, all planes at once."""
+    B, A, C, Hf, Wf = x_alpha.shape
+    dt, s = x.dtype, float(fov_scale)
+    Dc = depth_bins.numel()
+    mf = min(Hf, Wf)
+    u, t = _source_rays(cams, H, W, s, dt, x.device)
     v = depth_bins.to(dt).view(1, 1, Dc, 1, 1, 1) * u[:, :, None] + t[:, :, None, None, None, :]          # [B,A,Dc,H,W,3]
     w = v[..., 2]
     w = torch.where(w < 0, -torch.ones_like(w), torch.ones_like(w)) * w.abs().clamp(min=1e-8)             # transform_points(eps=1e-8)
@@ -102,17 +110,9 @@ def reconstruction_loss_composite(images, alpha_images, mask, cams, depth, zfar,
     field of view than upstream's default (through fov_scale), an ssim_loss_fn(x, y) of the caller's (None: `ssim_loss` above)."""
     S, B, H, W = depth.shape
     A = alpha_images.shape[1]
-    dt, dev, s, f = depth.dtype, depth.device, float(fov_scale), float(ssim_factor)
-    cams = cams.to(dt)
-    R, T = cams[:, 0, :9].reshape(B, 3, 3), cams[:, 0, 9:]
-    Ra, Ta = cams[:, 1:, :9].reshape(B, A, 3, 3), cams[:, 1:, 9:]
+    dt, s, f = depth.dtype, float(fov_scale), float(ssim_factor)
     m = min(H, W)
-    nx = (W / m - 2.0 * torch.arange(W, dtype=dt, device=dev) / (m - 1)) / s
-    ny = (H / m - 2.0 * torch.arange(H, dtype=dt, device=dev) / (m - 1)) / s
-    n = torch.stack((nx[None, :].expand(H, W), ny[:, None].expand(H, W), torch.ones(H, W, dtype=dt, device=dev)), -1)
-    M = torch.einsum("bij,baik->bajk", R, Ra)
-    u = torch.einsum("hwj,bajk->bahwk", n, M)
-    t = Ta - torch.einsum("bj,bajk->bak", T, M)
+    u, t = _source_rays(cams, H, W, s, dt, depth.device)
     d = depth if mask is None else torch.where(mask[None], depth, torch.full_like(depth, float(zfar)))
     x = images.to(dt).permute(0, 3, 1, 2)[:, None].expand(B, A, 3, H, W).reshape(B * A, 3, H, W)
     src = alpha_images.to(dt).reshape(B * A, H, W, 3).permute(0, 3, 1, 2)

@@ -113,7 +113,7 @@ def sh_coverage_gain_partials(pts, harmonics, cams, use_sigmoid=True, waves_per_
     bench.py time the dominant kernel alone with HIP events.  Returns nothing."""
     pts, harmonics, cams, B, N, P, C = _scorer_args(pts, harmonics, cams)
     L = lib()
-    ws = _workspace(pts.device, max(L.mcr_sh_coverage_gain_workspace_bytes(c_i64(B), c_i64(N), c_i64(C)), 4))
+    ws = _entry_workspace(pts.device, L.mcr_sh_coverage_gain_workspace_bytes, c_i64(B), c_i64(N), c_i64(C))
     with torch.cuda.device(pts.device):
         check(L.mcr_sh_coverage_gain_partials(_p(pts), c_int(P), _p(harmonics), _p(cams), c_i64(B), c_i64(N), c_i64(C),
                                               c_int(int(bool(use_sigmoid))), c_int(waves_per_simd), _p(ws), c_size(ws.numel()),
@@ -150,7 +150,7 @@ def sh_scorer_backward(pts, harmonics, cams, grad, per_pair, use_sigmoid=True, n
     d_pts = torch.empty((B, N, P), dtype=torch.float32, device=pts.device) if need_p else None
     d_cams = torch.empty((B, C, 3), dtype=torch.float32, device=pts.device) if need_c else None
     L = lib()
-    ws = _workspace(pts.device, max(int(L.mcr_sh_scorer_backward_workspace_bytes(c_i64(B), c_i64(N), c_i64(C))), 4))
+    ws = _entry_workspace(pts.device, L.mcr_sh_scorer_backward_workspace_bytes, c_i64(B), c_i64(N), c_i64(C))
     ptr = lambda t: _p(t) if t is not None else c_vp(None)
     with torch.cuda.device(pts.device):
         check(L.mcr_sh_scorer_backward(_p(pts), c_int(P), _p(harmonics), _p(cams), _p(grad), c_int(int(bool(per_pair))),
@@ -198,7 +198,7 @@ def knn_offsets_segmented(X, pc, cloud_sizes, query_sizes, split=True):
     d_blocks = h2d(np.asarray(blocks, np.int32).reshape(-1, 4), torch.int32, X.device)
     out = torch.empty((T, 16, 3), dtype=torch.float32, device=X.device)
     with torch.cuda.device(X.device):
-        ws = _workspace(X.device, max(int(L.mcr_knn_offsets_segmented_workspace_bytes(c_i64(T))), 4)) if split else None
+        ws = _entry_workspace(X.device, L.mcr_knn_offsets_segmented_workspace_bytes, c_i64(T)) if split else None
         check(L.mcr_knn_offsets_segmented(_p(X), _p(pc), _p(d_off), _p(d_blocks), c_i64(len(blocks)), c_i64(T), _p(out),
                                           _p(ws) if ws is not None else c_vp(0), c_size(ws.numel() * ws.element_size() if ws is not None else 0),
                                           _stream()), "mcr_knn_offsets_segmented")
@@ -375,6 +375,11 @@ def _workspace(device, nbytes, tag=None):
         buf.record_stream(stream)
         _ws_cache[key] = buf
     return buf
+
+
+def _entry_workspace(device, size_fn, *sizes):
+    """The arena, large enough for what the entry's own `size_fn(*sizes)` asks (never empty: an entry refuses a NULL workspace)."""
+    return _workspace(device, max(int(size_fn(*sizes)), 4))
 
 
 _ws_epoch = {}
@@ -1349,7 +1354,7 @@ def group_by_key(key, nk):
     order = torch.empty(N, dtype=torch.int32, device=dev)
     co = torch.empty(2 * nk + 3, dtype=torch.int64, device=dev)
     L_ = lib()
-    ws = _workspace(dev, max(int(L_.mcr_group_by_key_workspace_bytes(c_i64(N), c_int(nk))), 4))
+    ws = _entry_workspace(dev, L_.mcr_group_by_key_workspace_bytes, c_i64(N), c_int(nk))
     with torch.cuda.device(dev):
         check(L_.mcr_group_by_key(_p(key), c_i64(N), c_int(nk), _p(order), _p(co), c_vp(co.data_ptr() + 8 * (nk + 1)), _p(ws),
                                   c_size(ws.numel()), _stream()), "mcr_group_by_key")
@@ -1379,7 +1384,7 @@ def scene_fill_begin(pts, valid, grid_consts, grid, lo_tab, hi_tab, store_pts, s
     h.counts = torch.empty(4 * nk + 7, dtype=torch.int64, device=dev)
     v = valid.to(torch.uint8).contiguous() if valid is not None else None
     L_ = lib()
-    ws = _workspace(dev, max(int(L_.mcr_scene_fill_workspace_bytes(c_i64(N), c_int(nk))), 4))
+    ws = _entry_workspace(dev, L_.mcr_scene_fill_workspace_bytes, c_i64(N), c_int(nk))
     with torch.cuda.device(dev):
         check(L_.mcr_scene_fill_begin(_p(pts), c_i64(N), _p(v) if v is not None else c_vp(0), _p(gc), c_int(grid[0]), c_int(grid[1]),
                                       c_int(grid[2]), _p(_req(lo_tab, "lo_tab")), _p(_req(hi_tab, "hi_tab")),
@@ -1444,7 +1449,7 @@ def field_select(proxy_points, supervision_occ, out_of_field, proxy_proba, store
     s.stored_cell, key_sel, key_oof, s.rows_order, s.oof_order = (ib[k * P:(k + 1) * P] for k in range(5))
     s.counts = torch.empty(3 * nk + 9, dtype=torch.int64, device=dev)
     L_ = lib()
-    ws = _workspace(dev, max(int(L_.mcr_field_select_workspace_bytes(c_i64(P), c_int(nk))), 4))
+    ws = _entry_workspace(dev, L_.mcr_field_select_workspace_bytes, c_i64(P), c_int(nk))
     pe = pending
     with torch.cuda.device(dev):
         check(L_.mcr_field_select(_p(pp), c_i64(P), _p(supervision_occ), _p(out_of_field), _p(proxy_proba),
@@ -1524,7 +1529,7 @@ def supervision_select(prediction_mask, proxy_points, grid_consts, grid, store_f
     s.pos, s.rows_order = ib[:P], ib[P:]
     s.counts = torch.empty(3 * nk + 5, dtype=torch.int64, device=dev)
     L_ = lib()
-    ws = _workspace(dev, max(int(L_.mcr_supervision_select_workspace_bytes(c_i64(P), c_int(nk))), 4))
+    ws = _entry_workspace(dev, L_.mcr_supervision_select_workspace_bytes, c_i64(P), c_int(nk))
     with torch.cuda.device(dev):
         check(L_.mcr_supervision_select(_p(m8), _p(pp), c_i64(P), _p(_req(grid_consts, "grid_consts")), c_int(grid[0]), c_int(grid[1]),
                                         c_int(grid[2]), _p(_req(store_fts, "store_fts")) if n_store else c_vp(0), c_int(F), c_i64(n_store),
@@ -1643,11 +1648,7 @@ def uniform_rows(K, S, device, generator=None):
 COST_VOLUME_FOV_SCALE = 1.0 / float(np.tan(np.deg2rad(60.0) / 2))    # FoVPerspectiveCameras' default fov, which upstream never overrides
 
 
-def cost_volume(x, x_alpha, cams, depth_bins, H, W, fov_scale=COST_VOLUME_FOV_SCALE, out=None):
-    """cost volume [B,D,Hf,Wf] of CostVolumeBuilder.forward (ManyDepth.py:207-297) in one entry (mcr_cost_volume): x [B,64,Hf,Wf] target
-    features, x_alpha [B,A,64,Hf,Wf] source features, cams [B,1+A,12] (row 0 the target, then the sources; R row-major then T, PyTorch3D's
-    row-vector convention), depth_bins [D], H x W the image size whose pixel grid is unprojected.  out: None, or a [B,D,Hf,Wf] float32
-    view whose batches may be strided -- channels C.. of a [B,C+D,Hf,Wf] buffer, where upstream's torch.cat puts the volume."""
+def _cost_volume_args(x, x_alpha, cams, depth_bins):
     x, x_alpha, cams, depth_bins = _req(x, "x"), _req(x_alpha, "x_alpha"), _req(cams, "cams"), _req(depth_bins, "depth_bins")
     if x.dim() != 4 or x_alpha.dim() != 5:
         raise ValueError(f"x must be [B,C,Hf,Wf] and x_alpha [B,A,C,Hf,Wf]; got {tuple(x.shape)}, {tuple(x_alpha.shape)}")
@@ -1657,6 +1658,15 @@ def cost_volume(x, x_alpha, cams, depth_bins, H, W, fov_scale=COST_VOLUME_FOV_SC
         raise ValueError(f"x_alpha must be [B,A,C,Hf,Wf] = {(B, A, C, Hf, Wf)}, got {tuple(x_alpha.shape)}")
     if tuple(cams.shape) != (B, 1 + A, 12):
         raise ValueError(f"cams must be [B,1+A,12] = {(B, 1 + A, 12)}, got {tuple(cams.shape)}")
+    return x, x_alpha, cams, depth_bins, B, A, C, Hf, Wf, D
+
+
+def cost_volume(x, x_alpha, cams, depth_bins, H, W, fov_scale=COST_VOLUME_FOV_SCALE, out=None):
+    """cost volume [B,D,Hf,Wf] of CostVolumeBuilder.forward (ManyDepth.py:207-297) in one entry (mcr_cost_volume): x [B,64,Hf,Wf] target
+    features, x_alpha [B,A,64,Hf,Wf] source features, cams [B,1+A,12] (row 0 the target, then the sources; R row-major then T, PyTorch3D's
+    row-vector convention), depth_bins [D], H x W the image size whose pixel grid is unprojected.  out: None, or a [B,D,Hf,Wf] float32
+    view whose batches may be strided -- channels C.. of a [B,C+D,Hf,Wf] buffer, where upstream's torch.cat puts the volume."""
+    x, x_alpha, cams, depth_bins, B, A, C, Hf, Wf, D = _cost_volume_args(x, x_alpha, cams, depth_bins)
     if out is None:
         out = torch.empty((B, D, Hf, Wf), dtype=torch.float32, device=x.device)
     else:
@@ -1665,7 +1675,7 @@ def cost_volume(x, x_alpha, cams, depth_bins, H, W, fov_scale=COST_VOLUME_FOV_SC
         if tuple(out.shape) != (B, D, Hf, Wf) or (B * D * Hf * Wf and out[0].stride() != (Hf * Wf, Wf, 1)):
             raise ValueError(f"out must be [B,D,Hf,Wf] = {(B, D, Hf, Wf)} with contiguous batches, got {tuple(out.shape)} strides {out.stride()}")
     L = lib()
-    ws = _workspace(x.device, max(int(L.mcr_cost_volume_workspace_bytes(c_i64(B), c_i64(A), c_i64(C), c_i64(Hf), c_i64(Wf))), 4))
+    ws = _entry_workspace(x.device, L.mcr_cost_volume_workspace_bytes, c_i64(B), c_i64(A), c_i64(C), c_i64(Hf), c_i64(Wf))
     with torch.cuda.device(x.device):
         check(L.mcr_cost_volume(_p(x), _p(x_alpha), _p(cams), _p(depth_bins), _p(out), c_i64(out.stride(0) if B > 1 else D * Hf * Wf),
                                 c_i64(B), c_int(A), c_int(C), c_int(int(H)), c_int(int(W)), c_int(Hf), c_int(Wf), c_int(D),
@@ -1679,15 +1689,7 @@ def cost_volume_backward(x, x_alpha, cams, depth_bins, d_out, H, W, fov_scale=CO
     batches may be strided -- channels C.. of the gradient of a [B,C+D,Hf,Wf] buffer.  A gradient that is not needed is not computed
     (the x_alpha half is the expensive one).  No floating-point atomics: two calls give the same bits.  A d_out that is not finite gives
     gradients of NaN."""
-    x, x_alpha, cams, depth_bins = _req(x, "x"), _req(x_alpha, "x_alpha"), _req(cams, "cams"), _req(depth_bins, "depth_bins")
-    if x.dim() != 4 or x_alpha.dim() != 5:
-        raise ValueError(f"x must be [B,C,Hf,Wf] and x_alpha [B,A,C,Hf,Wf]; got {tuple(x.shape)}, {tuple(x_alpha.shape)}")
-    B, C, Hf, Wf = x.shape
-    A, D = x_alpha.shape[1], depth_bins.numel()
-    if tuple(x_alpha.shape) != (B, A, C, Hf, Wf):
-        raise ValueError(f"x_alpha must be [B,A,C,Hf,Wf] = {(B, A, C, Hf, Wf)}, got {tuple(x_alpha.shape)}")
-    if tuple(cams.shape) != (B, 1 + A, 12):
-        raise ValueError(f"cams must be [B,1+A,12] = {(B, 1 + A, 12)}, got {tuple(cams.shape)}")
+    x, x_alpha, cams, depth_bins, B, A, C, Hf, Wf, D = _cost_volume_args(x, x_alpha, cams, depth_bins)
     if not isinstance(d_out, torch.Tensor) or not d_out.is_cuda or d_out.device != x.device or d_out.dtype != torch.float32:
         raise MacaronsHipError("d_out must be a float32 tensor on x's HIP device")
     if tuple(d_out.shape) != (B, D, Hf, Wf):
@@ -1699,7 +1701,7 @@ def cost_volume_backward(x, x_alpha, cams, depth_bins, d_out, H, W, fov_scale=CO
     d_x = torch.empty_like(x) if need_x else None
     d_xa = torch.empty_like(x_alpha) if need_x_alpha else None
     L = lib()
-    ws = _workspace(x.device, max(int(L.mcr_cost_volume_backward_workspace_bytes(c_i64(B), c_i64(A), c_i64(C), c_i64(Hf), c_i64(Wf), c_i64(D))), 4))
+    ws = _entry_workspace(x.device, L.mcr_cost_volume_backward_workspace_bytes, c_i64(B), c_i64(A), c_i64(C), c_i64(Hf), c_i64(Wf), c_i64(D))
     with torch.cuda.device(x.device):
         check(L.mcr_cost_volume_backward(_p(x), _p(x_alpha), _p(cams), _p(depth_bins), _p(d_out),
                                          c_i64(d_out.stride(0) if B > 1 else D * Hf * Wf), _p(d_x) if need_x else None,
@@ -1747,7 +1749,7 @@ def reconstruction_loss(images, alpha_images, mask, cams, depth, zfar, ssim_fact
     lmap = torch.empty((S, B, H, W), dtype=torch.float32, device=images.device) if return_map else None
     amin = torch.empty((S, B, H, W), dtype=torch.uint8, device=images.device) if return_map else None
     L = lib()
-    ws = _workspace(images.device, max(int(L.mcr_reconstruction_loss_workspace_bytes(c_i64(S), c_i64(B), c_i64(A), c_i64(H), c_i64(W))), 4))
+    ws = _entry_workspace(images.device, L.mcr_reconstruction_loss_workspace_bytes, c_i64(S), c_i64(B), c_i64(A), c_i64(H), c_i64(W))
     with torch.cuda.device(images.device):
         check(L.mcr_reconstruction_loss(_p(images), _p(alpha_images), _p(mask) if mask is not None else None, _p(cams), _p(depth), _p(loss),
                                         _p(lmap) if return_map else None, _p(amin) if return_map else None, c_i64(S), c_i64(B), c_int(A),
@@ -1766,7 +1768,7 @@ def reconstruction_loss_backward(images, alpha_images, mask, cams, depth, d_loss
         raise ValueError(f"d_loss must be [S] = {(S,)}, got {tuple(d_loss.shape)}")
     d_depth = torch.empty((S, B, H, W), dtype=torch.float32, device=images.device)
     L = lib()
-    ws = _workspace(images.device, max(int(L.mcr_reconstruction_loss_backward_workspace_bytes(c_i64(S), c_i64(B), c_i64(A), c_i64(H), c_i64(W))), 4))
+    ws = _entry_workspace(images.device, L.mcr_reconstruction_loss_backward_workspace_bytes, c_i64(S), c_i64(B), c_i64(A), c_i64(H), c_i64(W))
     with torch.cuda.device(images.device):
         check(L.mcr_reconstruction_loss_backward(_p(images), _p(alpha_images), _p(mask) if mask is not None else None, _p(cams), _p(depth),
                                                  _p(d_loss), _p(d_depth), c_i64(S), c_i64(B), c_int(A), c_int(H), c_int(W),
@@ -1832,7 +1834,7 @@ def disparity_scales(disps, images, mask, znear, zfar, return_tab=False):
     tab = torch.empty((B, H, W), dtype=torch.float32, device=dev) if return_tab else None
     thr = torch.empty((B,), dtype=torch.float32, device=dev) if return_tab else None
     L = lib()
-    ws = _workspace(dev, max(int(L.mcr_disparity_scales_workspace_bytes(c_i64(S), c_i64(B), c_i64(H), c_i64(W))), 4))
+    ws = _entry_workspace(dev, L.mcr_disparity_scales_workspace_bytes, c_i64(S), c_i64(B), c_i64(H), c_i64(W))
     with torch.cuda.device(dev):
         check(L.mcr_disparity_scales(ptrs, hs, wss, _p(images), _p(mask) if mask is not None else None, _p(depth), _p(reg), _p(em),
                                      _p(tab) if return_tab else None, _p(thr) if return_tab else None, c_int(S), c_i64(B), c_int(H), c_int(W),
@@ -1858,7 +1860,7 @@ def disparity_scales_backward(disps, images, mask, znear, zfar, d_depth, d_reg):
     grads = [torch.empty_like(d) for d in maps]
     gptrs = (ctypes.c_void_p * S)(*[g.data_ptr() for g in grads])
     L = lib()
-    ws = _workspace(images.device, max(int(L.mcr_disparity_scales_backward_workspace_bytes(c_i64(S), c_i64(B), c_i64(H), c_i64(W))), 4))
+    ws = _entry_workspace(images.device, L.mcr_disparity_scales_backward_workspace_bytes, c_i64(S), c_i64(B), c_i64(H), c_i64(W))
     with torch.cuda.device(images.device):
         check(L.mcr_disparity_scales_backward(ptrs, hs, wss, _p(images), _p(mask) if mask is not None else None,
                                               _p(d_depth) if d_depth is not None else None, _p(d_reg) if d_reg is not None else None, gptrs,
