@@ -190,8 +190,12 @@ def test_scene_side_kernels(dev):
     depth = rng.uniform(2, 50, (1, H, W)).astype(np.float32)
     cam = np.concatenate([Minv.reshape(-1), [K[2, 2], K[3, 2]]]).astype(np.float32)[None]
     w = ops.unproject_depth(T(depth, dev), T(cam, dev)).cpu().numpy()[0]
-    ref = S.unproject_depth(depth[0], cam[0, :16].reshape(4, 4), cam[0, 16], cam[0, 17])
-    assert np.abs(w - ref).max() < 2e-3 * np.abs(ref).max()
+    # the same formula in fp64 on the fp32 inputs; the bar is four times the error of its fp32 restatement in the kernel's order (fp32
+    # rounding that depends on contraction and on the divide), measured here: 1.9e-4 -> 7.5e-4 on |world| up to 60 (it was 2e-3 |world|)
+    import _glue_model as G
+    ref = G.unproject_depth(depth[0], cam[0], np.float64)
+    bar = 4 * np.abs(G.unproject_depth(depth[0], cam[0], np.float32).astype(np.float64) - ref).max()
+    assert np.abs(w - ref).max() <= bar < 1e-3
     # and the geometry closes: re-projecting the world points gives back the pixel ndc and the depth
     ph = np.concatenate([w.astype(np.float64), np.ones((H * W, 1))], 1)
     view = ph @ Mv
