@@ -186,7 +186,7 @@ int mcr_linear_planes_dot(const void* Xh, const void* Xl, int64_t ldx, const voi
                           int64_t M, int K, int gelu, float wscale_inv, const float* v, const float* c, int gelu2, float* out,
                           int n_planes, void* stream);
 
-/* ---- backward building blocks (scone_vis_bwd.hip): fp32, deterministic (no float atomics; fixed-order sums) ----------------------
+/* ---- backward building blocks (bwd_blocks.hip, attention_bwd.hip): fp32, deterministic (no float atomics; fixed-order sums) ----------------------
  * mcr_attention_backward: gradient of mcr_attention's output (with lens as mcr_attention_planes: keys of sequence s = its first
  *   min(L, max(1, lens[s])) rows; lens may be NULL) with respect to the packed rows: d_qkv [S*L, ld_dqkv] <- [dq | dk | dv] given
  *   d_out [S*L, ld_dout].  Per-head widths 16 (q, k) and 64 (v) only.  The forward is recomputed (O and the log-sum-exp of every

@@ -3,7 +3,7 @@ macarons/trainers/pretrain_scone_vis.py:224, through SconeOcc.forward at pretrai
 
 The forward passes stay on the hand-written HIP kernels.  SconeVis.forward's backward is HIP too (SconeVisFunction below:
 mcr_scone_vis_backward, scone_vis_bwd.hip), as is the scorer's (the Autograd kernels of torch.ops.macarons.sh_coverage_gain /
-sh_visibilities) and that of PCTransformer.forward called on its own (PCTransformerFunction below: mcr_pc_transformer_backward).
+sh_visibilities) and that of PCTransformer.forward called on its own (PCTransformerFunction below: mcr_pc_transformer_backward, pct_bwd.hip).
 SconeOcc's entry point is still wrapped in a torch.autograd.Function whose backward RECOMPUTES the same
 mathematics with plain torch ops on the same device (composite functions below, written against the modules' own parameters) under
 autograd and back-propagates through that; env MCR_SCONE_VIS_BWD=composite puts SconeVis back on that path (A/B).  Opt-in, env

@@ -1,4 +1,5 @@
-// Host-only: the two data formats the network entry points (networks.hip, scone_vis_bwd.hip) share with their callers.
+// Host-only: the two data formats the network entry points (networks.hip; the backwards: scone_vis_bwd.hip, pct_bwd.hip,
+// scone_occ_bwd.hip) share with their callers.
 //   1. The weight tables (arrays of device pointers; order documented in include/macarons_hip.h, produced by networks/packing.py):
 //      slot names, table lengths, the structs the entries work on, ONE reader per struct and ONE validation.  No table index is
 //      written as an integer anywhere else.
@@ -42,8 +43,44 @@ inline int check_table(const char* who, const TableSpec& t, const float* const* 
     for (int i = 0; i < n_required; ++i) MCR_REQUIRE(weights[i], "%s: weight %d is null", who, i);
     return 0;
 }
+// ... and of a backward's table of gradient destinations: optional as a whole, complete when given
+inline int check_d_weights(const char* who, float* const* d_weights, int n) {
+    if (d_weights)
+        for (int i = 0; i < n; ++i) MCR_REQUIRE(d_weights[i], "%s: d_weights[%d] is null", who, i);
+    return 0;
+}
 inline bool has_planes(const TableSpec& t, int n_weights) { return n_weights >= t.n + t.planes; }
 inline bool has_end_planes(const TableSpec& t, int n_weights) { return n_weights == t.n + t.planes + t.ends; }
+
+// nn.Linear as the table holds it: weight [N, K] (N outputs of K inputs), bias [N].  ONE shape per layer: the backwards' forward and
+// backward helpers (bwd_kernels.h: lin_fwd / lin_bwd) and the sizes of the table's entries (the staging areas) all read it.
+struct LinShape { int N, K; };
+constexpr int lin_slot_floats(LinShape l, int slot) { return slot == LIN_W ? l.N * l.K : l.N; }     // slot: LIN_W or LIN_B
+// the layers of an encoder of width E: packed q | k | v (q, k of E / 4 channels, v of E), out, ff1, ff2
+constexpr LinShape enc_qkv(int E) { return {E / 2 + E, E}; }
+constexpr LinShape enc_out(int E) { return {E, E}; }
+constexpr LinShape enc_ff1(int E) { return {2 * E, E}; }
+constexpr LinShape enc_ff2(int E) { return {E, 2 * E}; }
+// floats of the encoder's table entry `slot` (< ENC_NW): its four layers, else a LayerNorm's gamma or beta
+constexpr int enc_slot_floats(int slot, int E) {
+    return slot >= ENC_FF2 ? lin_slot_floats(enc_ff2(E), slot - ENC_FF2) : slot >= ENC_FF1 ? lin_slot_floats(enc_ff1(E), slot - ENC_FF1)
+           : slot >= ENC_N2G ? E : slot >= ENC_OUT ? lin_slot_floats(enc_out(E), slot - ENC_OUT)
+           : slot >= ENC_QKV ? lin_slot_floats(enc_qkv(E), slot - ENC_QKV) : E;
+}
+// the PCTransformer (E = 128): its embedding, its tail (half = feature_dim / 2); floats of its table entry `slot`, and of the whole table
+constexpr int PB_E = 128, PB_F = 125, PB_W3 = 2 * 32 + PB_E;        // PB_F: the embedding's inner width (E - 3: the raw points fill the row)
+constexpr LinShape PB_L1{PB_F, 3}, PB_L2{PB_F, PB_F};
+constexpr LinShape pb_lin0(int half) { return {half, PB_E}; }
+static_assert(enc_qkv(PB_E).N == PB_W3, "packed q | k | v width");
+constexpr int pb_slot_floats(int slot, int half) {
+    return slot >= PCT_LIN0 ? lin_slot_floats(pb_lin0(half), slot - PCT_LIN0) : slot >= PCT_NG ? PB_E                        // (the final norm)
+           : slot >= PCT_ENC ? enc_slot_floats((slot - PCT_ENC) % ENC_NW, PB_E) : lin_slot_floats(slot >= PCT_L2 ? PB_L2 : PB_L1, slot % LIN_NW);
+}
+inline size_t pb_stage_floats(int half) {
+    size_t n = 0;
+    for (int i = 0; i < PCT_NW; ++i) n += pb_slot_floats(i, half);
+    return n;
+}
 
 struct LinW { const float* w; const float* b; };
 struct EncW {

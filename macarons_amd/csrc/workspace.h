@@ -37,5 +37,11 @@ inline int check_workspace(const char* who, const void* workspace, size_t worksp
     MCR_REQUIRE(((uintptr_t)workspace & 15) == 0, "%s: the workspace must be 16-byte aligned", who);
     return 0;
 }
+// ... and of the networks' backward entries (their *_workspace_bytes includes a slack; their messages are matched by the tests as they are)
+inline int check_bwd_workspace(const char* who, const void* workspace, size_t workspace_bytes, size_t need) {
+    MCR_REQUIRE(workspace && workspace_bytes >= need, "%s: workspace too small", who);
+    MCR_REQUIRE((uintptr_t)workspace % 16 == 0, "%s: workspace must be 16-byte aligned", who);
+    return 0;
+}
 
 }  // namespace mcr

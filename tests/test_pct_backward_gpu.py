@@ -1,4 +1,4 @@
-"""PCTransformer HIP backward (scone_vis_bwd.hip: mcr_pc_transformer_backward, mcr_attention_backward_pct, mcr_pool_max_avg_backward)
+"""PCTransformer HIP backward (pct_bwd.hip: mcr_pc_transformer_backward; attention_bwd.hip: mcr_attention_backward_pct; bwd_blocks.hip: mcr_pool_max_avg_backward)
 against fp64 torch autograd on the GPU, the fp64 composite (autograd.pc_transformer) and the reference's own fp64 gradients
 (pct_grad.npz, make_golden_pct_grad.py).  Errors are max |got - ref| / max |ref| per tensor; parameter denominators are floored at
 1e-4 x the largest parameter gradient.  mhsa.w_k.bias has a mathematically zero gradient: it is bounded absolutely, at 2e-6 x the

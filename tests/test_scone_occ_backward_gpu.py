@@ -1,4 +1,4 @@
-"""SconeOcc HIP backward (scone_vis_bwd.hip: mcr_scone_occ_backward; autograd.SconeOccFunction, env MCR_SCONE_OCC_BWD=hip) against the
+"""SconeOcc HIP backward (scone_occ_bwd.hip: mcr_scone_occ_backward; autograd.SconeOccFunction, env MCR_SCONE_OCC_BWD=hip) against the
 fp64 torch composite (autograd.scone_occ on a float64 copy of the module), in the metric and on the bounds of
 tests/test_pct_backward_gpu.py: max |got - ref| / max |ref| per tensor < NET_TOL = 1e-4, parameter denominators floored at 1e-4 x the
 largest parameter gradient; the mathematically zero mhsa.w_k.bias gradients are bounded absolutely, at ZERO_TOL x the largest parameter

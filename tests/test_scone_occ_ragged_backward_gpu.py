@@ -1,4 +1,4 @@
-"""Ragged SconeOcc HIP backward (scone_vis_bwd.hip: mcr_scone_occ_backward_ragged; ops.scone_occ_backward_ragged,
+"""Ragged SconeOcc HIP backward (scone_occ_bwd.hip: mcr_scone_occ_backward_ragged; ops.scone_occ_backward_ragged,
 autograd.SconeOccRaggedFunction, SconeOcc.forward_ragged(..., differentiable=True)) against the fp64 torch composite
 (autograd.scone_occ_ragged on a float64 copy of the module; tests/test_scone_occ_ragged_grad_cpu.py ties that composite to J separate
 calls), in the metric and on the bounds of tests/test_pct_backward_gpu.py: max |got - ref| / max |ref| per tensor < NET_TOL = 1e-4,

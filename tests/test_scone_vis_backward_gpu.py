@@ -1,4 +1,4 @@
-"""SconeVis HIP backward (scone_vis_bwd.hip: mcr_scone_vis_backward and its building blocks) against fp64 torch autograd on the GPU,
+"""SconeVis HIP backward (scone_vis_bwd.hip: mcr_scone_vis_backward; its building blocks: bwd_blocks.hip, attention_bwd.hip) against fp64 torch autograd on the GPU,
 the fp64 composite (autograd.scone_vis) and the reference's own fp64 gradients (scone_vis_grad*.npz, make_golden_scone_vis_grad.py).
 Errors are max |got - ref| / max |ref| per tensor; parameter denominators are floored at 1e-4 x the largest parameter gradient
 (w_k.bias has a mathematically zero gradient).  Measured errors are printed with an ERR prefix."""

@@ -1,4 +1,5 @@
-"""The *_workspace_bytes functions of networks.hip / scone_vis_bwd.hip, one library against another (plain host code: no GPU).
+"""The *_workspace_bytes functions of networks.hip and of the backward sources (bwd_blocks.hip, attention_bwd.hip, pct_bwd.hip,
+scone_vis_bwd.hip, scone_occ_bwd.hip), one library against another (plain host code: no GPU).
 
     python tools/compare_workspace_sizes.py OLD/libmacarons_hip.so NEW/libmacarons_hip.so
 
@@ -25,6 +26,16 @@ ENTRIES = {
     "mcr_linear_backward_workspace_bytes": ((I64, CI, CI), [(m, n, k) for m in (1, 16, 777, 61440, 83968) for (n, k) in
                                                             ((126, 4), (384, 256), (512, 256), (256, 512), (64, 128), (7, 5))], 3),
     "mcr_layernorm_backward_workspace_bytes": ((I64, CI), [(m, e) for m in (1, 16, 4097, 61440, 83968) for e in (64, 128, 256, 512)], 1),
+    "mcr_attention_backward_pct_workspace_bytes": ((I64, I64), SL + [(2, 17), (2, 2049), (65535, 16)], 4),
+    # (S, L): L == 16 on both sides of the 2048-sequence chunk, long sequences with S on both sides of the attention's split
+    "mcr_pc_transformer_backward_workspace_bytes": ((I64, I64), SL + [(2047, 16), (2048, 16), (2049, 16), (2, 2049), (3, 2047), (1, 17)], 24),
+    # (B, Q, Lg, q_chunk): Q on both sides of the default chunk, q_chunk 0 (the default) and 16 and a larger one
+    "mcr_scone_occ_backward_workspace_bytes": ((I64, I64, I64, I64), [(b, q, lg, qc) for (b, q) in ((1, 16), (1, 300), (2, 48), (1, 2047),
+                                                                                                     (1, 2048), (3, 2049), (8, 4096), (41, 777))
+                                                                    for lg in (2048, 16, 1000) for qc in (0, 16, 1024)], 63),
+    # (J, T, Lg, q_chunk): one job and a few dozen, T on both sides of the default chunk
+    "mcr_scone_occ_backward_ragged_workspace_bytes": ((I64, I64, I64, I64), list(itertools.product((1, 3, 27, 41), (16, 1000, 2047, 2049, 40000),
+                                                                                                   (2048, 512, 17), (0, 16, 1024))), 63),
     "mcr_attention_planes_workspace_bytes": ((I64, I64, CI, CI, CI), [(s, l, 4, qk, v) for (s, l) in ((1, 2048), (30, 2048), (41, 2048), (2, 700),
                                                                                                      (3, 333), (1, 16)) for (qk, v) in ((32, 128), (64, 256))], 2),
 }

@@ -1,6 +1,6 @@
 """sha256 of the device-only assembly of every macarons_amd/csrc/*.hip: the check of a host-only change.
 
-    python tools/device_asm_hash.py [--per-kernel] [--json OUT] [--against OTHER.json]
+    python tools/device_asm_hash.py [--per-kernel [--ignore-file]] [--json OUT] [--against OTHER.json]
 
 Each source is compiled with the library's own flags (build.FLAGS minus -shared -fPIC, plus the file's MCR_HIPCC_FLAGS line), device side
 only, to assembly (--cuda-device-only -S); -fuse-cuid=none keeps the hash of the source text out of the symbol names, so two trees whose
@@ -11,6 +11,9 @@ deleted one gets another ordinal, so the file's bytes differ although no survivi
 `.globl SYM` to its `.Lfunc_endN:` (the .amdhsa_kernel block lies in between); comments (`;` to the end of the line) and trailing
 blanks are dropped and the function's ordinal in `BB<N>_` and `.Lfunc_begin<N>` / `.Lfunc_end<N>` is replaced before hashing.  Against
 another --per-kernel file, symbols that are gone are listed; a symbol that differs or is new exits 1.
+
+--ignore-file (with --per-kernel --against): compare by symbol alone, for a change that moves kernels between files (a moved kernel
+would else show as gone plus new); a symbol that occurs in two files of either tree is an error.
 """
 import argparse
 import hashlib
@@ -57,6 +60,7 @@ def main():
     ap.add_argument("--json")
     ap.add_argument("--against")
     ap.add_argument("--per-kernel", action="store_true")
+    ap.add_argument("--ignore-file", action="store_true")
     a = ap.parse_args()
     srcs = b.sources()
     with ThreadPoolExecutor(8) as ex:
@@ -71,6 +75,13 @@ def main():
             other = json.load(f)
         if a.per_kernel:
             flat = lambda d: {(k, sym): h for k, v in d.items() for sym, h in v.items()}
+            if a.ignore_file:                       # by symbol alone: a kernel may have moved to another file, but must not exist twice
+                for d in (out, other):
+                    syms = [sym for v in d.values() for sym in v]
+                    twice = sorted({s for s in syms if syms.count(s) > 1})
+                    if twice:
+                        sys.exit("--ignore-file: in two files: " + ", ".join(twice))
+                flat = lambda d: {("*", sym): h for v in d.values() for sym, h in v.items()}
             mine, theirs = flat(out), flat(other)
             gone = sorted(set(theirs) - set(mine))
             bad = sorted(k for k in mine if mine[k] != theirs.get(k))
