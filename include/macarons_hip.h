@@ -851,6 +851,32 @@ int mcr_disparity_scales_backward(const float* const* disps, const int* Hs, cons
                                   const float* d_depth, const float* d_reg, float* const* d_disps, int S, int64_t B, int H, int W,
                                   float znear, float zfar, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- the disparity heads of the depth decoder (macarons/networks/ManyDepth.py:366-384 DisparityLayer, disp1..disp4 of :442-472): a
+ * reflection pad, a 3x3 convolution to one output channel and a sigmoid, fused (disparity_head.hip).
+ *
+ * mcr_disparity_head: x [B,C,Hs,Ws], weight [C,3,3] (upstream's conv.weight [1,C,3,3]), bias [1] -> y [B,Hs,Ws], all contiguous fp32:
+ *     z[b,i,j] = bias + sum_c sum_{di,dj in -1..1} weight[c,di+1,dj+1] x[b,c,r(i+di,Hs),r(j+dj,Ws)],   y = 1 / (1 + exp(-z)),
+ *   r torch's `reflect` for padding 1 (-1 -> 1, n -> n-2), an index computation: no padded copy exists.  z [B,Hs,Ws], the
+ *   pre-activation, is written when not NULL.  One launch: a workgroup owns a tile of one image for all channels (32 x 8 pixels, or 16 x 4
+ *   where that would leave compute units idle), stages the tile and its one-pixel ring in LDS 8 (or 24) channels at a time -- every feature is
+ *   read from memory once, apart from the ring, along W -- and adds the products in a fixed order (c ascending, the taps row-major, from
+ *   the bias): two calls give the same bits.  The weights are read wave-uniformly (scalar loads), never per thread.
+ * mcr_disparity_head_backward: with g = d_y y (1 - y) -- y [B,Hs,Ws] is an input, what the forward returned -- and d_y [B,Hs,Ws],
+ *     d_bias [1] = sum g;   d_weight [C,3,3]: d_weight[c,t] = sum_{b,i,j} g[b,i,j] x[b,c,r(i+di),r(j+dj)];
+ *     d_x [B,C,Hs,Ws]: d_x[b,c,i,j] = the sum of weight[c,t] g[b,q] over every (output pixel q, tap t) whose reflected source is (i,j):
+ *   row 1 also receives what padded row -1 would, row Hs-2 what padded row Hs would, the columns likewise, both at the corners; on a
+ *   two-pixel axis the two mirrors land on different pixels.  A NULL output is not computed (d_x alone: x may be NULL and is not read;
+ *   without d_x weight may be NULL), all three NULL is refused.  d_x is a gather (one launch, x not read); d_weight and d_bias take
+ *   two launches: every workgroup stores one partial per sum into the workspace, a second launch adds the partials of each output in a
+ *   fixed order, in double.  No floating-point atomics: two calls give the same bits.  workspace: the partials.
+ * Both refuse before any launch: Hs or Ws below 2, C outside 1..512, B below 1, B C Hs Ws beyond a 32-bit index, and the backward a
+ * workspace that is short or not 16-byte aligned.  The size function returns 0 for sizes that the entries refuse. */
+int mcr_disparity_head(const float* x, const float* weight, const float* bias, float* y, float* z, int64_t B, int C, int Hs, int Ws,
+                       void* stream);
+size_t mcr_disparity_head_backward_workspace_bytes(int64_t B, int64_t C, int64_t Hs, int64_t Ws);
+int mcr_disparity_head_backward(const float* x, const float* weight, const float* y, const float* d_y, float* d_x, float* d_weight,
+                                float* d_bias, int64_t B, int C, int Hs, int Ws, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

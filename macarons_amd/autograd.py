@@ -608,3 +608,45 @@ class DisparityScalesFunction(torch.autograd.Function):
             outs, gouts = zip(*[(o, g) for o, g in ((depth, grad_depth), (reg, grad_reg)) if g is not None])
             grads = torch.autograd.grad(outs, leaves, gouts)
         return none + tuple(g if n else None for g, n in zip(grads, ctx.needs_input_grad[4:]))
+
+
+# ---- depth module, the disparity heads: HIP forward + HIP backward -------------------------------------------------------------------------
+def disparity_head_backward_mode():
+    """'composite' (default) or 'hip' (env MCR_DISPARITY_HEAD_BWD=hip: the HIP backward mcr_disparity_head_backward).  The default is the
+    torch composite because profiles/disparity_head_times.json does not show a forward-and-backward step through the Function faster
+    with the intervals apart at every shape (nine rows of ten; not at [4,128,32,57]): a step of one head is bound by the host either
+    way, not by the kernels (NOTES.md)."""
+    return _env_mode(os.environ.get("MCR_DISPARITY_HEAD_BWD", ""), ("hip",), "composite")
+
+
+class DisparityHeadFunction(torch.autograd.Function):
+    """apply(x, weight, bias) -> y [B,1,Hs,Ws] of ops.disparity_head (mcr_disparity_head): x [B,C,Hs,Ws], weight [1,C,3,3], bias [1].
+    Saves x, weight and y (and the bias, which only the composite route reads).  backward = ops.disparity_head_backward (mcr_disparity_head_backward: no atomics, the same bits on every
+    run) with disparity_head_backward_mode() == 'hip'; the d_x half and the d_weight / d_bias half each run only if an input needs them.
+    With the mode 'composite' (the default) the backward is autograd through networks.ManyDepth.disparity_head_composite instead (plain
+    torch on the same device, recomputed; for A/B runs -- the module's forward does not come here in that mode, it runs the composite
+    under autograd directly).  Differentiable once."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias):
+        from . import ops
+        with torch.no_grad():
+            y = ops.disparity_head(x, weight, bias)
+        ctx.save_for_backward(x, weight, bias, y)
+        return y
+
+    @staticmethod
+    def backward(ctx, grad_y):
+        _once("the disparity head is", "its backward runs without a graph")
+        x, weight, bias, y = ctx.saved_tensors
+        need = tuple(ctx.needs_input_grad)
+        if not any(need):
+            return None, None, None
+        if disparity_head_backward_mode() == "hip":
+            from . import ops
+            return ops.disparity_head_backward(x, weight, y, grad_y.float().contiguous(), need=need)
+        from .networks.ManyDepth import disparity_head_composite
+        with torch.enable_grad():
+            ins = [t.detach().requires_grad_(n) for t, n in zip((x, weight, bias), need)]
+            grads = iter(torch.autograd.grad(disparity_head_composite(*ins), [t for t, n in zip(ins, need) if n], grad_y))
+        return tuple(next(grads) if n else None for n in need)

@@ -7,7 +7,9 @@ reconstruction loss is fused on HIP as well (ops.reconstruction_loss -> mcr_reco
 utility.macarons_utils.get_reconstruction_loss_fn); `reconstruction_loss_composite` below is the same mathematics in plain
 differentiable torch, for the cases the entry does not take and for the tests.  So is the step between the network's disparity maps
 and that loss (ops.disparity_scales -> mcr_disparity_scales, csrc/disparity_scales.hip, behind utility.macarons_utils.depth_scale_losses):
-`disparity_scales_composite` below is its plain-torch form.
+`disparity_scales_composite` below is its plain-torch form.  And so are the decoder's four disparity heads, the last link upstream of those
+maps (ops.disparity_head -> mcr_disparity_head, csrc/disparity_head.hip): `DisparityLayer` mirrors upstream's class (ManyDepth.py:366-384),
+`adopt_disparity_layer` / `adopt_depth_decoder` put existing upstream instances on it, `disparity_head_composite` is its plain-torch form.
 
 Needs neither PyTorch3D nor torchvision: a camera is its R, T (PyTorch3D's row-vector convention, view = world @ R + T) and the default
 60 degree field of view upstream never overrides; znear and zfar drop out of the sweep (they only shape the z the projection returns,
@@ -24,7 +26,7 @@ from torch import nn
 from .. import ops
 from ..ops import COST_VOLUME_FOV_SCALE
 
-__all__ = ["CostVolumeBuilder", "adopt_cost_volume_builder"]
+__all__ = ["CostVolumeBuilder", "adopt_cost_volume_builder", "DisparityLayer", "adopt_disparity_layer", "adopt_depth_decoder"]
 
 
 def pack_cameras(R, T, R_alpha, T_alpha):
@@ -262,3 +264,94 @@ def adopt_cost_volume_builder(builder):
     if not isinstance(vars(builder).get("forward"), _AdoptedForward):
         object.__setattr__(builder, "forward", _AdoptedForward(builder))     # a plain instance attribute, whatever the class's __setattr__ does
     return builder
+
+
+# ---- the disparity heads ---------------------------------------------------------------------------------------------------------------------
+def disparity_head_composite(x, weight, bias):
+    """ops.disparity_head in plain torch (any device and dtype, differentiable): upstream's DisparityLayer.forward as the three ops
+    torch runs it as -- the reflection-padded copy, the convolution, the sigmoid.  x [B,C,Hs,Ws], weight [1,C,3,3], bias [1] ->
+    [B,1,Hs,Ws]."""
+    return torch.sigmoid(F.conv2d(F.pad(x, (1, 1, 1, 1), mode="reflect"), weight, bias))
+
+
+def _head_forward(self, x):
+    """DisparityLayer.forward (ManyDepth.py:383-384), same signature: x [B,C,Hs,Ws] -> sigmoid(conv(x)) [B,1,Hs,Ws].  Without a gradient
+    to record, contiguous float32 HIP tensors outside autocast go to the fused entry (profiles/disparity_head_times.json: faster than
+    upstream's op sequence at all four of upstream's shapes, the intervals apart at B 1 and B 4); anything else (CPU, another dtype,
+    autocast, a strided input) is served by the composite.  With a gradient required the route follows
+    autograd.disparity_head_backward_mode(): 'hip' (MCR_DISPARITY_HEAD_BWD=hip) goes through DisparityHeadFunction, the default
+    'composite' runs the composite under autograd -- upstream's own sequence: the same file shows the step through the Function faster
+    with the intervals apart at nine rows of ten, not at all of them, which is what the project's rule asks of a default."""
+    w, b = self.conv.weight, self.conv.bias
+    fused = (x.is_cuda and x.dtype == torch.float32 and w.dtype == torch.float32 and w.device == x.device and x.dim() == 4
+             and x.is_contiguous() and w.is_contiguous() and not torch.is_autocast_enabled()
+             and x.shape[1] <= ops.DISPARITY_HEAD_MAX_CHANNELS and min(x.shape[2:]) >= 2 and x.numel() < 2 ** 31)
+    if fused and torch.is_grad_enabled() and (x.requires_grad or w.requires_grad or b.requires_grad):
+        from ..autograd import DisparityHeadFunction, disparity_head_backward_mode
+        if disparity_head_backward_mode() == "hip":
+            return DisparityHeadFunction.apply(x, w, b)
+        fused = False
+    return ops.disparity_head(x, w, b) if fused else disparity_head_composite(x, w, b)
+
+
+class DisparityLayer(nn.Module):
+    """Mirror of upstream's DisparityLayer: the same constructor argument, attributes and parameter names (`conv.weight` [1,C,3,3],
+    `conv.bias` [1]: upstream state dicts load).  The forward is the HIP entry wherever no gradient is recorded; with a gradient
+    required it is the torch composite under autograd by default and the HIP function with MCR_DISPARITY_HEAD_BWD=hip (_head_forward)."""
+
+    def __init__(self, input_channels):
+        super().__init__()
+        self.channels = input_channels
+        self.conv = nn.Conv2d(in_channels=input_channels, out_channels=1, kernel_size=3, stride=1, padding=1, padding_mode="reflect")
+        self.sigmoid = nn.Sigmoid()
+
+    forward = _head_forward
+
+
+class _AdoptedHeadForward:
+    """The `forward` of an adopted DisparityLayer: a module-level callable holding the instance (see _AdoptedForward)."""
+
+    def __init__(self, layer):
+        self.layer = layer
+
+    def __call__(self, x):
+        return _head_forward(self.layer, x)
+
+
+def _pair(v):
+    return tuple(v) if isinstance(v, (tuple, list)) else (v, v)
+
+
+def adopt_disparity_layer(layer):
+    """Put an existing upstream DisparityLayer instance on the HIP head: its `forward` is rebound (on the instance) to the forward above,
+    which reads only `conv.weight` and `conv.bias`.  TypeError unless `conv` is what the entry computes: a 3 x 3, stride 1, padding 1,
+    `reflect`, one-output-channel, ungrouped, undilated convolution with a bias.  Returns the instance; adopting twice changes nothing.
+    Loading a pickled adopted model needs this package importable."""
+    conv = getattr(layer, "conv", None)
+    facts = None if conv is None else [
+        ("kernel_size", (3, 3)), ("stride", (1, 1)), ("padding", (1, 1)), ("dilation", (1, 1)), ("padding_mode", "reflect"),
+        ("out_channels", 1), ("groups", 1)]
+    if facts is None or not all(hasattr(conv, k) for k, _ in facts) or getattr(conv, "bias", None) is None:
+        raise TypeError("adopt_disparity_layer: not a DisparityLayer, it has no `conv` with a bias and a convolution's attributes")
+    wrong = [f"{k} = {getattr(conv, k)!r}" for k, v in facts if (_pair(getattr(conv, k)) if isinstance(v, tuple) else getattr(conv, k)) != v]
+    if wrong:
+        raise TypeError("adopt_disparity_layer: the head is a 3 x 3, stride 1, padding 1, reflect, one-output-channel convolution; this "
+                        f"one has {', '.join(wrong)}")
+    if not isinstance(vars(layer).get("forward"), _AdoptedHeadForward):
+        object.__setattr__(layer, "forward", _AdoptedHeadForward(layer))
+    return layer
+
+
+def adopt_depth_decoder(decoder):
+    """adopt_cost_volume_builder(decoder.cost_volume_builder) and adopt_disparity_layer on decoder.disp1 .. disp4 (upstream's
+    DepthDecoder, ManyDepth.py:387-529).  Returns the decoder.
+
+        adopt_depth_decoder(macarons.depth.depth_decoder)"""
+    names = ("cost_volume_builder", "disp1", "disp2", "disp3", "disp4")
+    missing = [a for a in names if not hasattr(decoder, a)]
+    if missing:
+        raise TypeError(f"adopt_depth_decoder: not a DepthDecoder, it lacks {missing}")
+    adopt_cost_volume_builder(decoder.cost_volume_builder)
+    for name in names[1:]:
+        adopt_disparity_layer(getattr(decoder, name))
+    return decoder

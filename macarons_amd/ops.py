@@ -1867,3 +1867,66 @@ def disparity_scales_backward(disps, images, mask, znear, zfar, d_depth, d_reg):
                                               c_int(S), c_i64(B), c_int(H), c_int(W), c_f32(float(znear)), c_f32(float(zfar)), _p(ws),
                                               c_size(ws.numel()), _stream()), "mcr_disparity_scales_backward")
     return grads
+
+
+# ---- depth module: the disparity heads (reflect 3x3 convolution to one channel + sigmoid) -------------------------------------------------
+DISPARITY_HEAD_MAX_CHANNELS = 512
+
+
+def _disparity_head_args(x, weight, bias=None, maps=()):
+    """The shapes first (ValueError, on any device), then the operands themselves (HIP, float32, contiguous).  weight: upstream's
+    conv.weight [1,C,3,3] or [C,3,3]; bias [1] (None: not needed, the backward); maps: (name, [B,1,Hs,Ws] or [B,Hs,Ws]) pairs."""
+    if not isinstance(x, torch.Tensor) or x.dim() != 4:
+        raise ValueError(f"x must be [B,C,Hs,Ws], got {tuple(getattr(x, 'shape', ()))}")
+    B, C, Hs, Ws = (int(v) for v in x.shape)
+    if B < 1 or not 1 <= C <= DISPARITY_HEAD_MAX_CHANNELS:
+        raise ValueError(f"x is {tuple(x.shape)}: B must be at least 1 and C between 1 and {DISPARITY_HEAD_MAX_CHANNELS}")
+    if Hs < 2 or Ws < 2:
+        raise ValueError(f"the map is {Hs} x {Ws}, Hs and Ws must be at least 2 (the reflection padding)")
+    if B * C * Hs * Ws > 2 ** 31 - 1:
+        raise ValueError(f"x is {tuple(x.shape)}: its size overflows a 32-bit index")
+    if not isinstance(weight, torch.Tensor) or tuple(weight.shape) not in ((1, C, 3, 3), (C, 3, 3)):
+        raise ValueError(f"weight must be [1,C,3,3] or [C,3,3] with C = {C}, got {tuple(getattr(weight, 'shape', ()))}")
+    if bias is not None and (not isinstance(bias, torch.Tensor) or bias.numel() != 1):
+        raise ValueError(f"bias must hold one value, got {tuple(getattr(bias, 'shape', ()))}")
+    for name, m in maps:
+        if not isinstance(m, torch.Tensor) or tuple(m.shape) not in ((B, 1, Hs, Ws), (B, Hs, Ws)):
+            raise ValueError(f"{name} must be [B,1,Hs,Ws] or [B,Hs,Ws] = {(B, Hs, Ws)}, got {tuple(getattr(m, 'shape', ()))}")
+    x, weight = _req(x, "x"), _req(weight, "weight")
+    if bias is not None:
+        bias = _req(bias, "bias")
+    return x, weight, bias, (B, C, Hs, Ws), [_req(m, name) for name, m in maps]
+
+
+def disparity_head(x, weight, bias, return_z=False):
+    """y [B,1,Hs,Ws] = sigmoid(conv3x3(reflection_pad(x), weight) + bias) in one entry (mcr_disparity_head): upstream's DisparityLayer
+    (ManyDepth.py:366-384).  x [B,C,Hs,Ws], weight [1,C,3,3] or [C,3,3], bias [1], float32.  return_z: also the pre-activation z
+    [B,1,Hs,Ws].  The same bits on every call."""
+    x, weight, bias, (B, C, Hs, Ws), _ = _disparity_head_args(x, weight, bias)
+    y = torch.empty((B, 1, Hs, Ws), dtype=torch.float32, device=x.device)
+    z = torch.empty_like(y) if return_z else None
+    with torch.cuda.device(x.device):
+        check(lib().mcr_disparity_head(_p(x), _p(weight), _p(bias), _p(y), _p(z) if return_z else None, c_i64(B), c_int(C), c_int(Hs),
+                                       c_int(Ws), _stream()), "mcr_disparity_head")
+    return (y, z) if return_z else y
+
+
+def disparity_head_backward(x, weight, y, d_y, need=(True, True, True)):
+    """(d_x [B,C,Hs,Ws], d_weight in weight's shape, d_bias [1]) of sum(d_y * y) for y = disparity_head(x, weight, bias), in one entry
+    (mcr_disparity_head_backward); y and d_y [B,1,Hs,Ws] or [B,Hs,Ws].  need: which of the three are computed, the others are None
+    (d_x alone does not read x); all False is refused.  No atomics: two calls give the same bits."""
+    need = tuple(bool(n) for n in need)
+    if len(need) != 3 or not any(need):
+        raise ValueError("disparity_head_backward: need must name at least one of (d_x, d_weight, d_bias)")
+    x, weight, _, (B, C, Hs, Ws), (y, d_y) = _disparity_head_args(x, weight, maps=(("y", y), ("d_y", d_y)))
+    dev = x.device
+    d_x = torch.empty_like(x) if need[0] else None
+    d_w = torch.empty_like(weight) if need[1] else None
+    d_b = torch.empty((1,), dtype=torch.float32, device=dev) if need[2] else None
+    L = lib()
+    ws = _entry_workspace(dev, L.mcr_disparity_head_backward_workspace_bytes, c_i64(B), c_i64(C), c_i64(Hs), c_i64(Ws))
+    with torch.cuda.device(dev):
+        check(L.mcr_disparity_head_backward(_p(x), _p(weight), _p(y), _p(d_y), _p(d_x) if need[0] else None, _p(d_w) if need[1] else None,
+                                            _p(d_b) if need[2] else None, c_i64(B), c_int(C), c_int(Hs), c_int(Ws), _p(ws),
+                                            c_size(ws.numel()), _stream()), "mcr_disparity_head_backward")
+    return d_x, d_w, d_b
