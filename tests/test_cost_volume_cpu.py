@@ -6,6 +6,10 @@ Distances measured (max |difference| / max |reference value|; the bound is the p
   composite (fp32) vs model      cost volume  a 3.5e-07  b 4.7e-07  c 2.8e-07
   composite gradients vs model   x 2.0e-07 / 1.4e-07, x_alpha 1.0e-06 / 1.5e-06, conv_reduce.weight 2.2e-07 / 2.6e-07,
                                  conv_reduce.bias 2.0e-07 / 6.6e-08   (cases a / c)
+
+The seeded cases of tests/_cost_volume_cases.py (sizes the goldens do not have: Hf = 1, Wf = 1, Hf = H, a portrait image, A = 8, B = 3,
+D = 1, ragged layout tiles, scan chunks of two) are pinned here too: their input conditions, and the model against the composite in
+float64, values and gradients, to 1e-10 (measured: at most 7.7e-15).
 """
 import os
 import sys
@@ -15,6 +19,7 @@ import torch
 import torch.nn.functional as F
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import _cost_volume_cases as edge                                      # noqa: E402
 import _cost_volume_model as model                                     # noqa: E402
 from _cost_volume_model import load_case, rel                          # noqa: E402
 
@@ -177,3 +182,66 @@ def test_source_looking_away_costs_the_target_norm(cases):
     want6 = (x.double().abs().sum(1) / 64)[:, None].expand(-1, c["D"], -1, -1)
     assert float(((cv.double() - want6).abs() / want6).max()) <= 64 * 2.0 ** -24
     assert float(((cv6 - want6).abs() / want6).max()) <= 64 * 2.0 ** -53
+
+
+# ---- the seeded cases at the kernels' edges (tests/_cost_volume_cases.py): the reference pinned before any kernel is asked ---------------
+@pytest.fixture(scope="module")
+def edge_cases():
+    """tag -> (case, conditions), built once; "maxabs" is the D = 4 sub-problem of the maximum's stride-loop case."""
+    out = {t: edge.build_case(*edge.SHAPES[t]) for t in edge.TAGS}
+    _, sub, cond = edge.maxabs_case()
+    out["maxabs"] = (sub, cond)
+    return out
+
+
+EDGE_TAGS = edge.TAGS + ("maxabs",)
+
+
+@pytest.mark.parametrize("tag", EDGE_TAGS)
+def test_edge_case_conditions(edge_cases, tag):
+    """Conditions on the inputs: no bicubic tap near w = 0, most samples inside their source map, at most 1 % of the positions dropped
+    for a sign that fp32 and fp64 could read differently."""
+    c, cond = edge_cases[tag]
+    print(f"case {tag}: min |w| {cond['min_abs_w']:.3f}, inside share {cond['inside_share']:.3f}, good share {cond['good_share']:.4f}")
+    assert cond["min_abs_w"] >= edge.MIN_ABS_W
+    assert cond["inside_share"] >= edge.MIN_INSIDE
+    assert cond["good_share"] >= edge.MIN_GOOD
+    assert edge.holds(cond)
+    assert tuple(cond["good"].shape) == tuple(cond["lw"].shape) == (c["x"].shape[0], c["D"]) + tuple(c["x"].shape[-2:])
+
+
+def test_edge_case_shapes_are_the_ones_meant():
+    """The arithmetic the shapes were chosen for."""
+    def dims(tag):
+        _, B, A, H, W, Hf, Wf, D = edge.SHAPES[tag]
+        return B, A, H, W, Hf, Wf, D, Hf * Wf, B * A * Hf * Wf
+
+    assert dims("min")[:7] == (1, 1, 2, 2, 1, 1, 1)
+    assert dims("row")[4] == 1 and dims("col")[5] == 1 and dims("col")[2] > dims("col")[3]
+    assert dims("full")[2:4] == dims("full")[4:6] and dims("full2")[2:4] == dims("full2")[4:6] and dims("full2")[7] == 15 * 64
+    assert dims("tile1")[7] == 64 + 1 == 4 * 16 + 1 and dims("tile1")[6] == 2 * 4 + 1 and dims("tile1")[0] == 3
+    assert dims("wide")[1] == 8
+    B, A, _, _, _, _, _, P, n_dest = dims("scan")
+    per = -(-n_dest // 1024)                                             # cv_scan_kernel's chunk
+    assert n_dest == 1377 and per == 2 and n_dest - 688 * per == 1 and P == 2 * 64 + 25
+    _, B, A, H, W, Hf, Wf, D = edge.MAXABS_SHAPE
+    assert D * Hf * Wf == 66048 > 256 * 256 and (D - 1) * Hf * Wf == 65664 >= 256 * 256 and B == 2
+    assert edge.MAXABS_SUB == (D - 4, D) and (D - 4) % 4 == 0            # the same plane quadruple, the same place inside it
+
+
+@pytest.mark.parametrize("tag", EDGE_TAGS)
+def test_edge_case_model_matches_composite_fp64(edge_cases, tag):
+    """The model against the product's composite, both in float64: values, and gradients of sum(cv * lw * good) under autograd."""
+    c, cond = edge_cases[tag]
+    weight = (cond["lw"] * cond["good"]).double()
+    x6, xa6 = c["x"].double().requires_grad_(True), c["x_alpha"].double().requires_grad_(True)
+    cv = ManyDepth.cost_volume_composite(x6, xa6, _cams(c), c["depth_bins"], c["H"], c["W"])
+    assert cv.dtype == torch.float64
+    got = torch.autograd.grad((cv * weight).sum(), (x6, xa6))
+    with torch.no_grad():
+        cv6 = model.cost_volume(c["x"], c["R"], c["T"], c["x_alpha"], c["R_alpha"], c["T_alpha"], c["depth_bins"], c["H"], c["W"])
+    want = edge.reference_gradients(c, weight)
+    e = (rel(cv, cv6), rel(got[0], want[0]), rel(got[1], want[1]))
+    print(f"case {tag}: composite vs model in fp64: cost volume {e[0]:.1e}, d_x {e[1]:.1e}, d_x_alpha {e[2]:.1e}")
+    assert float(want[0].abs().max()) > 0 and float(want[1].abs().max()) > 0
+    assert max(e) < 1e-10
