@@ -9,6 +9,10 @@ The error mask must equal the model's at every pixel that is not undecided (|tab
 
 Distances measured, composite fp32 vs model, worst case: depth 9.3e-08 reg 1.3e-07 tab 2.8e-06 thr 1.6e-07 d_disp 2.0e-07;
 composite fp64 vs golden (that is, the golden's own fp32 rounding): depth 9.3e-08 reg 1.3e-07 tab 3.7e-06 thr 2.5e-07 d_disp 2.0e-07.
+
+The last section holds the cases at the kernels' edges (tests/_depth_loss_cases.py), for which there is no golden: what each reaches in
+the kernels' own numbers, the golden generator's conditions on their inputs from the model alone, and the composite in fp64 against the
+model (1e-9; measured 1.8e-15 at most).
 """
 import ctypes
 import inspect
@@ -273,3 +277,70 @@ def test_patch_lists_the_new_names():
     for name in ("get_regularity_loss_fn", "regularity_tab"):
         assert name in patch._HELPERS_ALL["utility.macarons_utils"][1] and name not in patch._HELPERS["utility.macarons_utils"][1]
     assert "depth_scale_losses" in patch._ADDITIONS_ALL["utility.macarons_utils"][1]
+
+
+# ---- the cases at the kernels' edges (tests/_depth_loss_cases.py): what they reach, their conditions, and the reference itself -------------
+import _depth_loss_cases as edge                                       # noqa: E402
+
+
+def test_edge_cases_reach_what_they_are_for():
+    """The sizes in the kernels' own numbers, so that a later change of DS_T, DS_MAX_S or the ratios cannot silently empty a case."""
+    D = edge.DISPARITY
+    assert len(D["s8"]["ratios"]) == ops.DISPARITY_MAX_SCALES == 8 and D["s8"]["ratios"].count(16) == 2 and D["s8"]["ratios"].count(1) == 2
+    assert max(ops.DISPARITY_SCALE_RATIOS) == 16 and edge.n_tiles(D["s8"]["H"], D["s8"]["W"]) == 6 and D["s8"]["B"] == 2
+    assert D["r16row"]["H"] // max(D["r16row"]["ratios"]) == 1                                # H_s = 1
+    assert D["coarse0"]["ratios"][0] == 16 and 1 in D["coarse0"]["ratios"][1:]
+    H, W = D["tiles65"]["H"], D["tiles65"]["W"]
+    assert edge.cdiv(H, 16) * edge.cdiv(W, 16) > 64 and edge.n_tiles(H, W) > edge.FINISH_LANES and D["tiles65"]["B"] > 1
+    assert 16 in D["tiles65"]["ratios"] and 16 in D["flat"]["ratios"]
+    for tag in edge.DISPARITY_TAGS:                                      # every case is one the entry takes
+        inp = edge.disparity_inputs(tag)
+        assert len(inp["disps"]) <= ops.DISPARITY_MAX_SCALES
+        assert all(D[tag]["H"] // d.shape[1] in ops.DISPARITY_SCALE_RATIOS and d.shape[1] * r == D[tag]["H"] and d.shape[2] * r == D[tag]["W"]
+                   for d, r in zip(inp["disps"], D[tag]["ratios"]))
+    s8 = edge.disparity_inputs("s8")["disps"]
+    assert not np.array_equal(s8[0], s8[1]) and not np.array_equal(s8[2], s8[3]) and not np.array_equal(s8[6], s8[7])
+    flat = edge.disparity_inputs("flat")["disps"]
+    assert all(bool((d[0] == np.float32(edge.FLAT_VALUE)).all()) and bool((d[1] == 0).all()) for d in flat)
+
+
+@pytest.mark.parametrize("tag,masked", edge.DISPARITY_VARIANTS)
+def test_edge_conditions_and_composite_fp64_matches_model(tag, masked):
+    """The golden generator's own conditions on the inputs, from the model alone (flat, whose differences are all exactly 0, is held
+    to the second only): a least pair gap of 1e-4, at most 1 % of an image's pixels undecided, both values in every error mask.  And
+    the check that the reference is right at the new shapes, for which there is no golden: the composite in fp64 against the model,
+    which state the same mathematics with no shared code: 1e-9, the bound tests/test_reconstruction_loss_cpu.py uses for the same
+    situation and far inside this file's TOL (measured: 1.8e-15 at most)."""
+    inp = edge.disparity_inputs(tag)
+    mask = inp["mask"] if masked else None
+    gap, undecided_share, both, undecided = model.conditions(inp["disps"], inp["images"], mask)
+    print(f"edge case {tag} mask={masked}: least pair gap {gap:.2e}; undecided {100 * undecided_share:.2f} %; both values {both}")
+    assert undecided_share <= edge.MAX_UNDECIDED
+    if tag != "flat":
+        assert gap >= edge.MIN_GAP and both
+    cr, g = edge.disparity_weights(tag)
+    m = model.forward(inp["disps"], inp["images"], mask)
+    ref = model.gradient(inp["disps"], inp["images"], mask, g, cr)
+    depth, reg, em, tab, thr, grads = _composite(inp, masked, torch.float64, cr, g)
+    e = dict(depth=model.rel(depth.detach(), m["depth"]), reg=model.rel(reg.detach(), m["reg"]), tab=model.rel(tab, m["tab"]),
+             thr=model.rel(thr, m["thr"]), d_disp=max(model.rel(a, b) for a, b in zip(grads, ref)))
+    print(f"edge case {tag} mask={masked}: composite fp64 vs model: " + " ".join(f"{k} {v:.2e}" for k, v in e.items()))
+    assert max(e.values()) < 1e-9 < TOL
+    assert all(np.isfinite(r).all() for r in ref) and bool(((em.numpy() == m["error_mask"]) | undecided).all())
+    if tag == "flat":                                                   # the exact zeros, in the model and in the composite
+        assert (m["reg"] == 0).all() and (m["tab"] == 0).all() and (m["thr"] == 0).all() and not m["error_mask"].any()
+        assert bool((reg == 0).all()) and bool((tab == 0).all()) and bool((thr == 0).all()) and not bool(em.any())
+        assert all((r == 0).all() for r in model.gradient(inp["disps"], inp["images"], None, None, cr))
+        assert m["depth"][:, 1].min() == m["depth"][:, 1].max() == model.ZFAR
+
+
+def test_edge_coarse_scale_0_owns_the_table():
+    """coarse0: the table, its threshold and the error mask come from scale 0, here the ratio-16 map, and are not those of the same
+    maps with the full-resolution one first -- a test against this reference notices scale 0 being picked by resolution."""
+    inp = edge.disparity_inputs("coarse0")
+    m = model.forward(inp["disps"], inp["images"], inp["mask"])
+    other = model.forward(edge.reordered(inp, (1, 0, 2))["disps"], inp["images"], inp["mask"])
+    assert np.array_equal(m["depth"][[1, 0, 2]], other["depth"]) and np.array_equal(m["reg"][[1, 0, 2]], other["reg"])
+    assert model.rel(m["tab"], other["tab"]) > 100 * TOL and model.rel(m["thr"], other["thr"]) > 100 * TOL
+    decided = ~model.conditions(inp["disps"], inp["images"], inp["mask"])[3]
+    assert ((m["error_mask"] != other["error_mask"]) & decided).sum() >= 16

@@ -12,6 +12,10 @@ Distances measured (max |difference| / max |reference|), composite fp32 vs golde
   (the golden's own distance to the model is about the same: the composite sits beside the model, the golden apart from both)
   through the function: fov 45 degrees vs model loss 7.4e-09 d_depth 7.7e-06; cameras with a gradient loss 2.2e-08 d T_alpha 5.4e-07
   composite fp64 vs model: at most 2.1e-14.
+
+The last section holds the cases at the kernels' edges (tests/_depth_loss_cases.py), for which there is no golden: what each reaches in
+the kernels' own numbers, the conditions on their inputs from the model alone, and the composite in fp64 against the model (1e-9; measured
+loss 2.8e-16, map 2.7e-14, d_depth 1.8e-13 at most).
 """
 import ctypes
 import inspect
@@ -279,3 +283,74 @@ def test_patch_lists_the_helper():
     from macarons_amd import patch
     assert "get_reconstruction_loss_fn" in patch._HELPERS_ALL["utility.macarons_utils"][1]
     assert "get_reconstruction_loss_fn" not in patch._HELPERS["utility.macarons_utils"][1]
+
+
+# ---- the cases at the kernels' edges (tests/_depth_loss_cases.py): what they reach, their conditions, and the reference itself -------------
+import _depth_loss_cases as edge                                       # noqa: E402
+
+EDGE_ALL = [(t, p, m) for t in edge.RECONSTRUCTION_TAGS for p, m in edge.RECONSTRUCTION_VARIANTS[t]]
+
+
+@pytest.fixture(scope="module")
+def edge_cases():
+    return {t: edge.reconstruction_case(t) for t in edge.RECONSTRUCTION_TAGS}
+
+
+def test_edge_cases_reach_what_they_are_for(edge_cases):
+    """The sizes in the kernels' own numbers, so that a later change of RL_T or of the chunk counts cannot silently empty a case:
+    tiles66 has more tiles than rl_finish_kernel has lanes and more pixels than one pass of rl_mask_count_kernel's 64 x 256 threads;
+    pairs6 has more (scale, image) pairs than rl_finish_kernel has waves; pairs6_dark has one image fully masked and one not; spill1's last
+    tile row and column hold one image row / column; rows3 has H = 3 and a two-column spill."""
+    S, B, H, W = edge_cases["tiles66"]["depth"].shape
+    assert edge.cdiv(H, 16) * edge.cdiv(W, 16) > 64 and edge.n_tiles(H, W) > edge.FINISH_LANES
+    assert H * W > 64 * 256 and H * W > edge.COUNT_CHUNKS * edge.COUNT_THREADS
+    assert edge.cdiv(H * W, edge.COUNT_CHUNKS) > edge.COUNT_THREADS                         # every chunk takes the second step
+    mask = edge_cases["tiles66"]["mask"]
+    assert bool((~mask).any()) and bool(mask.reshape(-1)[-edge.cdiv(H * W, edge.COUNT_CHUNKS):].all())   # and a dropped term is a set pixel
+    for tag in ("pairs6", "pairs6_dark"):
+        S, B, H, W = edge_cases[tag]["depth"].shape
+        assert S * B > 4 and S * B > edge.FINISH_WAVES and B > 1 and edge.n_tiles(H, W) > 1
+    assert not torch.equal(edge_cases["pairs6"]["depth"][2], edge_cases["pairs6"]["depth"][0])
+    dark = edge_cases["pairs6_dark"]["mask"]
+    assert not bool(dark[1].any()) and bool(dark[0].any()) and not bool(dark[0].all())
+    S, B, H, W = edge_cases["spill1"]["depth"].shape
+    assert H % edge.TILE == 1 and W % edge.TILE == 1 and H > edge.TILE and W > edge.TILE and B == 2
+    S, B, H, W = edge_cases["rows3"]["depth"].shape
+    assert H == 3 and W % edge.TILE == 2 and W > edge.TILE
+
+
+@pytest.mark.parametrize("tag,padding,masked", EDGE_ALL)
+def test_edge_conditions_and_composite_fp64_matches_model(edge_cases, tag, padding, masked):
+    """The conditions on the inputs, from the model alone -- at most 5 % of the pixels are near-ties (two best sources within 1e-3 of
+    the map's maximum), both sources are selected, tiles66 has at most 2 % kink pixels by test_upstream_width's rule, and the gradient is
+    not zero where a case looks for it -- and the check that the reference is right at the new shapes, for which there is no golden: the
+    composite in fp64 and the model state the same mathematics with no shared code, 1e-9 as for cases a-d."""
+    c = edge_cases[tag]
+    S, B, H, W = c["depth"].shape
+    d_loss = edge.D_LOSS[S].double()
+    with torch.no_grad():
+        m = model.reconstruction(*edge.model_args(c, masked), c["depth"], c["zfar"], c["ssim_factor"], padding)
+    ties = edge.near_tie_share(m)
+    shares = [float((m["index"] == a).double().mean()) for a in range(c["alpha_images"].shape[1])]
+    msg = f"edge case {tag} {padding} mask={masked}: near-ties {100 * ties:.2f} % of the pixels; selected {['%.0f %%' % (100 * s) for s in shares]}"
+    if tag == "tiles66":
+        kink = float(edge.kinks(c, m).double().mean())
+        msg += f"; kink pixels {100 * kink:.2f} %"
+        assert kink <= edge.MAX_KINKS
+    assert ties <= edge.MAX_NEAR_TIES and min(shares) > 0.1
+    d = c["depth"].double().requires_grad_(True)
+    loss, lmap, idx = ManyDepth.reconstruction_loss_composite(c["images"], c["alpha_images"], c["mask"] if masked else None, _cams(c).double(),
+                                                              d, c["zfar"], c["ssim_factor"], padding, return_map=True)
+    grad = torch.autograd.grad((loss * d_loss).sum(), d)[0]
+    ref = model.gradient(*edge.model_args(c, masked), c["depth"], c["zfar"], c["ssim_factor"], padding, d_loss=d_loss, force_index=idx)
+    e = (rel(loss, m["loss"]), rel(lmap, m["map"]), rel(grad, ref))
+    print(msg + f"; composite fp64 vs model: loss {e[0]:.2e} map {e[1]:.2e} d_depth {e[2]:.2e}")
+    assert torch.equal(idx, m["index"]) and max(e) < 1e-9
+    assert bool(torch.isfinite(ref).all()) and bool(torch.isfinite(m["loss"]).all())
+    if tag == "pairs6_dark":                                            # the fully masked image: no loss, exactly no gradient
+        assert bool((ref[:, 1] == 0).all()) and bool((grad[:, 1] == 0).all()) and bool((ref[:, 0] != 0).any())
+    if tag == "spill1":                                                 # the spill row and column, and their reflected partners
+        assert all(bool((ref[0, b, r] != 0).any()) and bool((ref[0, b, :, q] != 0).any()) for b in range(B) for r in (H - 2, H - 1)
+                   for q in (W - 2, W - 1))
+    if tag == "rows3":
+        assert bool((ref[0, 0, 1] != 0).any()) and bool((ref[0, 0, :, W - 2:] != 0).any())

@@ -142,31 +142,7 @@ def test_eight_sources(dev, cases):
 
 
 # ---- 2c. upstream's width ------------------------------------------------------------------------------------------------------------------
-def _wide_case(H=32, W=456):
-    """One image of upstream's width, two sources turned 0.15 rad either way and a few tenths of a unit off; smooth images as the golden's
-    (0.5 + four sinusoids of amplitude 0.12, 0.1 .. 0.6 rad/pixel), a wavy depth, a mask with a hole."""
-    import numpy as np
-    rng = np.random.default_rng(17)
-    yy, xx = np.meshgrid(np.arange(H, dtype=np.float64), np.arange(W, dtype=np.float64), indexing="ij")
-
-    def image(n):
-        out = np.full((n, 3, H, W), 0.5)
-        for i in range(n):
-            for ch in range(3):
-                for _ in range(4):
-                    k, th, ph = rng.uniform(0.1, 0.6), rng.uniform(0, 2 * np.pi), rng.uniform(0, 2 * np.pi)
-                    out[i, ch] += 0.12 * np.sin(k * (np.cos(th) * xx + np.sin(th) * yy) + ph)
-        return torch.from_numpy(np.clip(out, 0, 1).transpose(0, 2, 3, 1).astype(np.float32)).contiguous()
-
-    def rot_y(t):
-        return torch.tensor([[np.cos(t), 0.0, np.sin(t)], [0.0, 1.0, 0.0], [-np.sin(t), 0.0, np.cos(t)]], dtype=torch.float32)
-
-    mask = torch.ones(1, H, W, dtype=torch.bool)
-    mask[:, 8:20, 100:220] = False
-    depth = torch.from_numpy((3.0 + 1.5 * np.sin(0.03 * xx + 0.2 * yy)).astype(np.float32))[None, None]
-    return dict(images=image(1), alpha_images=image(2)[None], mask=mask, R=torch.eye(3)[None], T=torch.zeros(1, 3),
-                R_alpha=torch.stack([rot_y(0.15), rot_y(-0.15)])[None], T_alpha=torch.tensor([[[0.3, 0.0, 0.1], [-0.3, 0.1, 0.0]]]),
-                depth=depth, zfar=50.0, ssim_factor=0.85)
+from _depth_loss_cases import wide_case as _wide_case                  # noqa: E402  (32 x 456 here; the edge tests use it at 32 x 528)
 
 
 @pytest.mark.parametrize("padding", ("border", "zeros"))
