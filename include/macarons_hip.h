@@ -877,6 +877,28 @@ size_t mcr_disparity_head_backward_workspace_bytes(int64_t B, int64_t C, int64_t
 int mcr_disparity_head_backward(const float* x, const float* weight, const float* y, const float* d_y, float* d_x, float* d_weight,
                                 float* d_bias, int64_t B, int C, int Hs, int Ws, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- the expansion layers of the depth decoder (macarons/networks/ManyDepth.py:308-363 ExpansionLayer, expansion5..1 of :428-471): a
+ * transposed 3x3 convolution, ELU, a nearest resize, a channel concatenation, a reflection-padded 3x3 convolution and ELU, fused
+ * (expansion_layer.hip) -- the forward.
+ *
+ * mcr_expansion_layer: x [B,Cin,h,w], x_add [B,Cadd,H,W] (NULL with Cadd = 0), up_weight [Cin,Cmid,3,3] and up_bias [Cmid] (upstream's
+ *   upconv), i_weight [Cout,Cmid+Cadd,3,3] and i_bias [Cout] (upstream's iconv) -> y [B,Cout,H,W], all contiguous fp32:
+ *     u = ELU(conv_transpose2d(x, up_weight, up_bias; stride 1, padding 1))   [B,Cmid,h,w], kept in the workspace
+ *     y = ELU(conv2d(reflect_pad1(cat(nearest(u -> (H,W)), x_add)), i_weight, i_bias))
+ *   ELU with alpha 1 (expm1f below zero); nearest is torch's mode='nearest': source = min(floor(dst * (float)in / out), in - 1), in float.
+ *   Two launches of one kernel on the exact-fp32 matrix instruction (v_mfma_f32_16x16x4_f32): the first reads the transposed convolution
+ *   as a zero-padded correlation with the kernel flipped and the channel axes exchanged; the second applies the reflection index, the
+ *   nearest-source index and the u / x_add channel boundary while it stages a tile: no resized, concatenated or padded tensor exists.
+ *   Both weights are read in upstream's layouts.  A split of the channel sum among the waves of a workgroup is added in the order of the
+ *   waves; no atomics: two calls give the same bits.
+ * Refused before any launch: H or W below 2, h or w below 1, Cin, Cmid or Cout outside 1..512, Cadd below 0 or Cmid + Cadd above 512,
+ * B below 1, a tensor of 2^31 elements or more, a NULL operand (x_add only with Cadd > 0), a workspace that is missing, short or not
+ * 16-byte aligned.  The size function returns 0 for sizes that the entry refuses. */
+size_t mcr_expansion_layer_workspace_bytes(int64_t B, int64_t Cmid, int64_t h, int64_t w);
+int mcr_expansion_layer(const float* x, const float* x_add, const float* up_weight, const float* up_bias, const float* i_weight,
+                        const float* i_bias, float* y, int64_t B, int Cin, int Cmid, int Cadd, int Cout, int h, int w, int H, int W,
+                        void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

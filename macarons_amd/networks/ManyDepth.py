@@ -10,6 +10,11 @@ and that loss (ops.disparity_scales -> mcr_disparity_scales, csrc/disparity_scal
 `disparity_scales_composite` below is its plain-torch form.  And so are the decoder's four disparity heads, the last link upstream of those
 maps (ops.disparity_head -> mcr_disparity_head, csrc/disparity_head.hip): `DisparityLayer` mirrors upstream's class (ManyDepth.py:366-384),
 `adopt_disparity_layer` / `adopt_depth_decoder` put existing upstream instances on it, `disparity_head_composite` is its plain-torch form.
+What feeds those heads, the decoder's five expansion layers (ManyDepth.py:308-363: a transposed convolution, ELU, a nearest resize, a
+concatenation, a reflection-padded convolution, ELU), has a fused forward too (ops.expansion_layer -> mcr_expansion_layer,
+csrc/expansion_layer.hip, exact-fp32 matrix instructions): `ExpansionLayer` mirrors the class, `adopt_expansion_layer` and
+`adopt_depth_decoder` adopt upstream instances, `expansion_layer_composite` is the plain-torch form and `expansion_layer_route` says which
+of the two a forward takes.
 
 Needs neither PyTorch3D nor torchvision: a camera is its R, T (PyTorch3D's row-vector convention, view = world @ R + T) and the default
 60 degree field of view upstream never overrides; znear and zfar drop out of the sweep (they only shape the z the projection returns,
@@ -26,7 +31,8 @@ from torch import nn
 from .. import ops
 from ..ops import COST_VOLUME_FOV_SCALE
 
-__all__ = ["CostVolumeBuilder", "adopt_cost_volume_builder", "DisparityLayer", "adopt_disparity_layer", "adopt_depth_decoder"]
+__all__ = ["CostVolumeBuilder", "adopt_cost_volume_builder", "DisparityLayer", "adopt_disparity_layer", "ExpansionLayer",
+           "adopt_expansion_layer", "adopt_depth_decoder"]
 
 
 def pack_cameras(R, T, R_alpha, T_alpha):
@@ -342,16 +348,179 @@ def adopt_disparity_layer(layer):
     return layer
 
 
+# ---- the expansion layers ----------------------------------------------------------------------------------------------------------------------
+EXPANSION_LAYER_DEFAULT = "composite"          # what profiles/expansion_layer_times.json decides (see _expansion_forward)
+
+
+def expansion_layer_mode():
+    """'composite' or 'hip': the route of an expansion layer's forward when no gradient is recorded.  MCR_EXPANSION_LAYER=hip or
+    =composite chooses; otherwise EXPANSION_LAYER_DEFAULT, which is 'hip' only if profiles/expansion_layer_times.json shows the fused
+    entry faster than the composite with the intervals apart at all five of upstream's shapes, at B 1 and at B 4."""
+    import os
+    mode = os.environ.get("MCR_EXPANSION_LAYER", "").strip().lower()
+    return mode if mode in ("hip", "composite") else EXPANSION_LAYER_DEFAULT
+
+
+def expansion_layer_composite(x, x_add, up_weight, up_bias, i_weight, i_bias, output_size):
+    """ops.expansion_layer in plain torch (any device and dtype, differentiable): upstream's ExpansionLayer.forward as the seven ops torch
+    runs it as -- the transposed convolution, ELU, the nearest resize, the concatenation (with an x_add), the reflection-padded copy, the
+    convolution, ELU.  x [B,Cin,h,w], x_add [B,Cadd,H,W] or None, up_weight [Cin,Cmid,3,3], i_weight [Cout,Cmid+Cadd,3,3] -> [B,Cout,H,W]."""
+    u = F.elu(F.conv_transpose2d(x, up_weight, up_bias, stride=1, padding=1))
+    r = F.interpolate(u, size=tuple(int(v) for v in output_size), mode="nearest")
+    if x_add is not None:
+        r = torch.cat((r, x_add), dim=-3)
+    return F.elu(F.conv2d(F.pad(r, (1, 1, 1, 1), mode="reflect"), i_weight, i_bias))
+
+
+def _is_hip_tensor(t):
+    return t.is_cuda
+
+
+def _autocast_on(x):
+    """Autocast is enabled for the device type of x."""
+    try:
+        return torch.is_autocast_enabled(x.device.type)
+    except TypeError:                                             # a torch whose is_autocast_enabled takes no device type
+        return torch.is_autocast_enabled() if x.is_cuda else torch.is_autocast_cpu_enabled()
+
+
+def expansion_layer_route(x, x_add, params, output_size, additional_channels):
+    """'hip' or 'composite' for one forward: the fused entry serves contiguous float32 HIP tensors outside autocast, within the entry's
+    limits, when no gradient is recorded and the mode (expansion_layer_mode) is 'hip'.  params: (upconv.weight, upconv.bias, iconv.weight,
+    iconv.bias).  An x_add that the layer ignores (additional_channels None) is not an operand."""
+    if additional_channels is None:
+        x_add = None
+    elif x_add is None:
+        return "composite"                                       # upstream's own forward fails there; the composite fails the same way
+    if expansion_layer_mode() != "hip":
+        return "composite"
+    ts = [x, *params] + ([x_add] if x_add is not None else [])
+    if not all(isinstance(t, torch.Tensor) for t in ts):
+        return "composite"
+    if torch.is_grad_enabled() and any(t.requires_grad for t in ts):
+        return "composite"                                       # the backward is not on HIP yet: upstream's sequence under autograd
+    if _autocast_on(x):
+        return "composite"
+    if not all(_is_hip_tensor(t) and t.device == x.device and t.dtype == torch.float32 and t.is_contiguous() for t in ts):
+        return "composite"
+    cap = ops.EXPANSION_LAYER_MAX_CHANNELS
+    wu, _, wi, _ = params
+    if x.dim() != 4 or wu.dim() != 4 or wi.dim() != 4 or (x_add is not None and x_add.dim() != 4):
+        return "composite"
+    H, W = (int(v) for v in output_size)
+    B, Cin, Cmid, Cout, Ctot = x.shape[0], x.shape[1], wu.shape[1], wi.shape[0], wi.shape[1]
+    if B < 1 or min(x.shape[2:]) < 1 or min(H, W) < 2 or not (1 <= Cin <= cap and 1 <= Cmid <= cap and 1 <= Cout <= cap and Ctot <= cap):
+        return "composite"
+    if max(x.numel(), B * Cmid * x.shape[2] * x.shape[3], B * Ctot * H * W, B * Cout * H * W) >= 2 ** 31:
+        return "composite"
+    return "hip"
+
+
+def _expansion_forward(self, x, x_add=None):
+    """ExpansionLayer.forward (ManyDepth.py:351-363), same signature: x [B,Cin,h,w], x_add [B,Cadd,H,W] -> [B,Cout,H,W]; like upstream's,
+    x_add is concatenated only when both it and additional_channels are set.  The route is expansion_layer_route: the fused entry
+    (ops.expansion_layer) without a gradient to record under the mode 'hip', the composite under autograd whenever a gradient is
+    required, and for everything the entry does not take."""
+    if x_add is not None and self.additional_channels is None:
+        x_add = None
+    params = (self.upconv.weight, self.upconv.bias, self.iconv.weight, self.iconv.bias)
+    if expansion_layer_route(x, x_add, params, self.output_size, self.additional_channels) == "hip":
+        return ops.expansion_layer(x, x_add, *params, self.output_size)
+    return expansion_layer_composite(x, x_add, *params, self.output_size)
+
+
+class ExpansionLayer(nn.Module):
+    """Mirror of upstream's ExpansionLayer: the same constructor arguments, attributes and parameter names (`upconv.weight`
+    [Cin,Cmid,3,3], `upconv.bias`, `iconv.weight` [Cout,Cmid+Cadd,3,3], `iconv.bias`: upstream state dicts load).  The forward is
+    _expansion_forward."""
+
+    def __init__(self, input_channels, inner_channels, output_channels, output_size, additional_channels=None, kernel_size=3, stride=1,
+                 padding=1):
+        super().__init__()
+        self.upconv = nn.ConvTranspose2d(in_channels=input_channels, out_channels=inner_channels, kernel_size=kernel_size, stride=stride,
+                                         padding=padding)
+        self.upelu = nn.ELU()
+        total_inner_channels = inner_channels + (additional_channels if additional_channels is not None else 0)
+        self.iconv = nn.Conv2d(in_channels=total_inner_channels, out_channels=output_channels, kernel_size=kernel_size, stride=stride,
+                               padding=padding, padding_mode="reflect")
+        self.ielu = nn.ELU()
+        self.input_channels, self.output_channels, self.output_size = input_channels, output_channels, output_size
+        self.inner_channels, self.additional_channels = inner_channels, additional_channels
+        self.kernel_size, self.stride, self.padding = kernel_size, stride, padding
+
+    def upsample(self, x):
+        return F.interpolate(input=x, size=self.output_size, mode="nearest")
+
+    forward = _expansion_forward
+
+
+class _AdoptedExpansionForward:
+    """The `forward` of an adopted ExpansionLayer: a module-level callable holding the instance (see _AdoptedForward)."""
+
+    def __init__(self, layer):
+        self.layer = layer
+
+    def __call__(self, x, x_add=None):
+        return _expansion_forward(self.layer, x, x_add)
+
+
+def adopt_expansion_layer(layer):
+    """Put an existing upstream ExpansionLayer instance on the forward above: its `forward` is rebound (on the instance); it reads
+    `upconv`, `iconv`, `output_size` and `additional_channels`.  TypeError unless the layer is what the entry computes: `upconv` a 3 x 3,
+    stride 1, padding 1, output-padding 0, undilated, ungrouped transposed convolution with a bias; `iconv` a 3 x 3, stride 1, padding 1,
+    `reflect`, undilated, ungrouped convolution with a bias; both ELUs with alpha 1; `output_size` a pair of ints.  Returns the instance;
+    adopting twice changes nothing.  Loading a pickled adopted model needs this package importable."""
+    who = "adopt_expansion_layer"
+    common = [("kernel_size", (3, 3)), ("stride", (1, 1)), ("padding", (1, 1)), ("dilation", (1, 1)), ("groups", 1)]
+    facts = {"upconv": common + [("output_padding", (0, 0))], "iconv": common + [("padding_mode", "reflect")]}
+    wrong = []
+    for name, wanted in facts.items():
+        conv = getattr(layer, name, None)
+        if conv is None or not all(hasattr(conv, k) for k, _ in wanted) or getattr(conv, "bias", None) is None \
+                or not torch.is_tensor(getattr(conv, "weight", None)):
+            raise TypeError(f"{who}: not an ExpansionLayer, it has no `{name}` with a weight, a bias and a convolution's attributes")
+        wrong += [f"{name}.{k} = {getattr(conv, k)!r}" for k, v in wanted
+                  if (_pair(getattr(conv, k)) if isinstance(v, tuple) else getattr(conv, k)) != v]
+    if layer.upconv.weight.dim() != 4 or layer.iconv.weight.dim() != 4:
+        raise TypeError(f"{who}: the convolutions are not two-dimensional")
+    for name in ("upelu", "ielu"):
+        elu = getattr(layer, name, None)
+        if elu is None or not hasattr(elu, "alpha"):
+            raise TypeError(f"{who}: not an ExpansionLayer, it has no `{name}` with an alpha")
+        if float(elu.alpha) != 1.0:
+            wrong.append(f"{name}.alpha = {elu.alpha!r}")
+    size = getattr(layer, "output_size", None)
+    if not (isinstance(size, (tuple, list)) and len(size) == 2 and all(isinstance(v, int) and not isinstance(v, bool) for v in size)):
+        wrong.append(f"output_size = {size!r}")
+    if not hasattr(layer, "additional_channels"):
+        raise TypeError(f"{who}: not an ExpansionLayer, it has no `additional_channels`")
+    if wrong:
+        raise TypeError(f"{who}: the layer is a 3 x 3, stride 1, padding 1 transposed convolution, ELU, a nearest resize to a pair of ints "
+                        f"and a 3 x 3, stride 1, padding 1, reflect convolution, ELU; this one has {', '.join(wrong)}")
+    if not isinstance(vars(layer).get("forward"), _AdoptedExpansionForward):
+        object.__setattr__(layer, "forward", _AdoptedExpansionForward(layer))
+    return layer
+
+
+_EXPANSION_NAMES = ("expansion1", "expansion2", "expansion3", "expansion4", "expansion5")
+
+
 def adopt_depth_decoder(decoder):
-    """adopt_cost_volume_builder(decoder.cost_volume_builder) and adopt_disparity_layer on decoder.disp1 .. disp4 (upstream's
-    DepthDecoder, ManyDepth.py:387-529).  Returns the decoder.
+    """adopt_cost_volume_builder(decoder.cost_volume_builder), adopt_disparity_layer on decoder.disp1 .. disp4 and adopt_expansion_layer on
+    decoder.expansion1 .. expansion5 (upstream's DepthDecoder, ManyDepth.py:387-529).  A decoder with none of the five expansion layers
+    is adopted without them; one with some of them only is refused (TypeError).  Returns the decoder.
 
         adopt_depth_decoder(macarons.depth.depth_decoder)"""
     names = ("cost_volume_builder", "disp1", "disp2", "disp3", "disp4")
     missing = [a for a in names if not hasattr(decoder, a)]
     if missing:
         raise TypeError(f"adopt_depth_decoder: not a DepthDecoder, it lacks {missing}")
+    present = [a for a in _EXPANSION_NAMES if hasattr(decoder, a)]
+    if present and len(present) != len(_EXPANSION_NAMES):
+        raise TypeError(f"adopt_depth_decoder: the decoder has {present} but lacks {[a for a in _EXPANSION_NAMES if a not in present]}")
     adopt_cost_volume_builder(decoder.cost_volume_builder)
     for name in names[1:]:
         adopt_disparity_layer(getattr(decoder, name))
+    for name in present:
+        adopt_expansion_layer(getattr(decoder, name))
     return decoder

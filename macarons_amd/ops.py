@@ -1930,3 +1930,66 @@ def disparity_head_backward(x, weight, y, d_y, need=(True, True, True)):
                                             _p(d_b) if need[2] else None, c_i64(B), c_int(C), c_int(Hs), c_int(Ws), _p(ws),
                                             c_size(ws.numel()), _stream()), "mcr_disparity_head_backward")
     return d_x, d_w, d_b
+
+
+# ---- depth module: the expansion layers (transposed 3x3 conv + ELU, nearest resize, concat, reflect 3x3 conv + ELU) ----------------------
+EXPANSION_LAYER_MAX_CHANNELS = 512
+
+
+def _expansion_layer_args(x, x_add, up_weight, up_bias, i_weight, i_bias, output_size):
+    """The shapes first (ValueError, on any device), then the operands themselves (HIP, float32, contiguous).  x [B,Cin,h,w], x_add
+    [B,Cadd,H,W] or None, up_weight [Cin,Cmid,3,3], up_bias [Cmid], i_weight [Cout,Cmid+Cadd,3,3], i_bias [Cout], output_size (H, W)."""
+    cap = EXPANSION_LAYER_MAX_CHANNELS
+    if not isinstance(x, torch.Tensor) or x.dim() != 4:
+        raise ValueError(f"x must be [B,Cin,h,w], got {tuple(getattr(x, 'shape', ()))}")
+    B, Cin, h, w = (int(v) for v in x.shape)
+    try:
+        H, W = (int(v) for v in output_size)
+    except (TypeError, ValueError):
+        raise ValueError(f"output_size must be a pair (H, W), got {output_size!r}") from None
+    if B < 1 or not 1 <= Cin <= cap or h < 1 or w < 1:
+        raise ValueError(f"x is {tuple(x.shape)}: B, h and w must be at least 1 and Cin between 1 and {cap}")
+    if H < 2 or W < 2:
+        raise ValueError(f"the output is {H} x {W}, H and W must be at least 2 (the reflection padding)")
+    if not isinstance(up_weight, torch.Tensor) or up_weight.dim() != 4 or tuple(up_weight.shape[::3]) != (Cin, 3) or up_weight.shape[2] != 3:
+        raise ValueError(f"up_weight must be [Cin,Cmid,3,3] with Cin = {Cin}, got {tuple(getattr(up_weight, 'shape', ()))}")
+    Cmid = int(up_weight.shape[1])
+    Cadd = 0
+    if x_add is not None:
+        if not isinstance(x_add, torch.Tensor) or x_add.dim() != 4 or (int(x_add.shape[0]), int(x_add.shape[2]), int(x_add.shape[3])) != (B, H, W):
+            raise ValueError(f"x_add must be [B,Cadd,H,W] = [{B},Cadd,{H},{W}], got {tuple(getattr(x_add, 'shape', ()))}")
+        Cadd = int(x_add.shape[1])
+        if Cadd < 1:
+            raise ValueError("x_add has no channels; pass None instead")
+    if not 1 <= Cmid <= cap or Cmid + Cadd > cap:
+        raise ValueError(f"Cmid = {Cmid} and Cadd = {Cadd}: Cmid must be between 1 and {cap} and Cmid + Cadd at most {cap}")
+    if not isinstance(i_weight, torch.Tensor) or i_weight.dim() != 4 or tuple(i_weight.shape[1:]) != (Cmid + Cadd, 3, 3):
+        raise ValueError(f"i_weight must be [Cout,Cmid+Cadd,3,3] with Cmid + Cadd = {Cmid + Cadd}, got {tuple(getattr(i_weight, 'shape', ()))}")
+    Cout = int(i_weight.shape[0])
+    if not 1 <= Cout <= cap:
+        raise ValueError(f"Cout = {Cout} must be between 1 and {cap}")
+    for name, t, n in (("up_bias", up_bias, Cmid), ("i_bias", i_bias, Cout)):
+        if not isinstance(t, torch.Tensor) or tuple(t.shape) != (n,):
+            raise ValueError(f"{name} must be [{n}], got {tuple(getattr(t, 'shape', ()))}")
+    if max(B * Cin * h * w, B * Cmid * h * w, B * Cadd * H * W, B * Cout * H * W) > 2 ** 31 - 1:
+        raise ValueError(f"x is {tuple(x.shape)}, the output [{B},{Cout},{H},{W}]: a tensor has 2^31 elements or more")
+    ts = [_req(t, name) for name, t in (("x", x), ("up_weight", up_weight), ("up_bias", up_bias), ("i_weight", i_weight), ("i_bias", i_bias))]
+    return ts, (_req(x_add, "x_add") if x_add is not None else None), (B, Cin, Cmid, Cadd, Cout, h, w, H, W)
+
+
+def expansion_layer(x, x_add, up_weight, up_bias, i_weight, i_bias, output_size):
+    """y [B,Cout,H,W] = ELU(conv3x3(reflection_pad(cat(nearest(ELU(conv_transpose3x3(x, up_weight) + up_bias) -> output_size), x_add)),
+    i_weight) + i_bias) in one entry (mcr_expansion_layer): upstream's ExpansionLayer.forward (ManyDepth.py:351-363).  x [B,Cin,h,w],
+    x_add [B,Cadd,H,W] or None, the weights in upstream's layouts (upconv.weight [Cin,Cmid,3,3], iconv.weight [Cout,Cmid+Cadd,3,3]),
+    float32.  Exact fp32 products; the same bits on every call."""
+    (x, up_weight, up_bias, i_weight, i_bias), x_add, (B, Cin, Cmid, Cadd, Cout, h, w, H, W) = _expansion_layer_args(
+        x, x_add, up_weight, up_bias, i_weight, i_bias, output_size)
+    dev = x.device
+    y = torch.empty((B, Cout, H, W), dtype=torch.float32, device=dev)
+    L = lib()
+    ws = _entry_workspace(dev, L.mcr_expansion_layer_workspace_bytes, c_i64(B), c_i64(Cmid), c_i64(h), c_i64(w))
+    with torch.cuda.device(dev):
+        check(L.mcr_expansion_layer(_p(x), _p(x_add) if x_add is not None else None, _p(up_weight), _p(up_bias), _p(i_weight), _p(i_bias),
+                                    _p(y), c_i64(B), c_int(Cin), c_int(Cmid), c_int(Cadd), c_int(Cout), c_int(h), c_int(w), c_int(H),
+                                    c_int(W), _p(ws), c_size(ws.numel()), _stream()), "mcr_expansion_layer")
+    return y
