@@ -6,9 +6,11 @@
 // max(2^-22 |x|, 2^-25).  A product a w is evaluated as w_lo a_hi + w_hi a_lo + w_hi a_hi on v_mfma_f32_32x32x16_f16
 // (fp16 x fp16 products are exact in the fp32 accumulator); the dropped lo x lo term is <= 2^-22 |a w|.  Weights are
 // multiplied by a per-matrix power of two on the host (their low plane then stays a normal fp16 number) and the exact
-// inverse is applied in the epilogue FMA that adds the bias.  Measured 5e-7 against the fp64 oracle
-// (tests/test_networks_gpu.py::test_fused_local_transformer[6]).  Range: |activation| < 65504 (LayerNorm outputs are
-// <= sqrt(128)); variant 5 (bf16 hi/mid/lo) covers the whole fp32 range.
+// inverse is applied in the epilogue FMA that adds the bias.  The xyz offsets are multiplied by 2^8 in front of their split for the
+// same reason (the floor on them is 2^-33; see the embedding below).  Measured 5e-7 against the fp64 oracle
+// (tests/test_networks_gpu.py::test_fused_local_transformer[6]; per sequence, every weight set and input scale:
+// tests/test_local_pct_gpu.py).  Range: |activation| < 65504 (LayerNorm outputs are <= sqrt(128)) and |offset| < 255;
+// variant 5 (bf16 hi/mid/lo) covers the whole fp32 range.
 //
 // Built without SLP vectorisation: plain -O3 packs adjacent fp32 multiplies / FMAs of the epilogues into v_pk_*_f32, which issue
 // worse beside MFMAs than the two scalar instructions they replace (MI355X_MICROARCH per-instruction constants); measured
@@ -379,14 +381,19 @@ __global__ __launch_bounds__(256, 2) void local_pct6_kernel(const float* __restr
                 xyz[mt][0] = p[0]; xyz[mt][1] = p[1]; xyz[mt][2] = p[2];
             }
         }
-        // the activation fragment of the K = 16 step straight from registers: k = 0..2 = xyz in the lower lane half, zeros elsewhere
+        // the activation fragment of the K = 16 step straight from registers: k = 0..2 = xyz in the lower lane half, zeros elsewhere.
+        // The offsets are the one operand that arrives unscaled: at |x| ~ 1e-2 the low half of the split is a subnormal fp16 number
+        // and the split's absolute floor 2^-25 is 2^-18 |x|, not 2^-22 |x| (on weights 4x the unit scale that alone put one sequence
+        // in 64 at 7e-5 of the fp64 oracle, fp32 itself being at 6e-6).  So the product runs on L6_XYZ_SCALE x = 2^8 x: 22 bits from
+        // |x| = 2^-11 on, floor 2^-33, finite for |x| < 255.9.  The host has multiplied this layer's bias by the same power of two and
+        // divided isc[0] by it (packing.py), so nothing else changes here and every scaling is exact.
         const bool lowh = lane < 32;
 #pragma unroll
         for (int mt = 0; mt < 2; ++mt) {
             Split2 a;
             a.hi = make_uint4(0, 0, 0, 0); a.lo = make_uint4(0, 0, 0, 0);
-            split2h(lowh ? xyz[mt][0] : 0.f, lowh ? xyz[mt][1] : 0.f, a.hi.x, a.lo.x);
-            split2h(lowh ? xyz[mt][2] : 0.f, 0.f, a.hi.y, a.lo.y);
+            split2h(lowh ? xyz[mt][0] * L6_XYZ_SCALE : 0.f, lowh ? xyz[mt][1] * L6_XYZ_SCALE : 0.f, a.hi.x, a.lo.x);
+            split2h(lowh ? xyz[mt][2] * L6_XYZ_SCALE : 0.f, 0.f, a.hi.y, a.lo.y);
             acc[mt] = mfma_h(ring.b[0][1], a.hi, acc[mt]);
             acc[mt] = mfma_h(ring.b[0][0], a.lo, acc[mt]);
             acc[mt] = mfma_h(ring.b[0][0], a.hi, acc[mt]);

@@ -45,6 +45,9 @@ __host__ __device__ constexpr int l6_mat_off(int idx) {
 constexpr int L6_MATS_TOTAL = l6_mat_off(15);
 constexpr int L6_SCALES = L3_VECS_TOTAL;                      // offset of the 16 inverse scales inside the vector section
 constexpr int L6_BLOB_FLOATS = L6_MATS_TOTAL + L3_VECS_TOTAL + 32;
+// local_pct6 splits the xyz offsets as L6_XYZ_SCALE x (their low half would be a subnormal fp16 number otherwise); the variant-6 blob
+// carries the embedding's first bias times it and isc[0] divided by it (packing.py: L6_XYZ_SCALE, the same value)
+constexpr float L6_XYZ_SCALE = 256.f;
 
 // ---- blob of variant 7 (opt-in 16-bit matrix path): matrices as [n-tile][k16 step][lane][8 fp16] -- the HIGH plane of variant 6's
 // blob WITHOUT the per-matrix power of two (fp16(W), half a float per weight); then the same vectors (biases as they are)

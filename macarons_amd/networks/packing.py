@@ -265,6 +265,11 @@ def _pack_f16x2(W, scale, planes=2):
     return t.reshape(-1).view(torch.float32)
 
 
+# local_pct6.hip multiplies the xyz offsets by this power of two in front of their fp16 hi / lo split (lp_split.h: L6_XYZ_SCALE, the same
+# value); the variant-6 blob carries the first embedding layer's bias times it and that layer's inverse scale divided by it
+L6_XYZ_SCALE = 256.0
+
+
 def _pack_local_pct6(pct, planes=2):
     with torch.no_grad():
         f = lambda p: p.detach().float()
@@ -279,6 +284,9 @@ def _pack_local_pct6(pct, planes=2):
         # every bias is stored multiplied by its matrix's scale: the kernel starts the accumulator from it
         emb = pct.embedding
         s1 = add(_pad(f(emb.linear1.weight), 128, 16))
+        if planes == 2:                     # the kernel's product is W 2^e (x L6_XYZ_SCALE): bias and inverse scale follow (variant 7 takes x as it is)
+            s1 *= L6_XYZ_SCALE
+            inv[0] /= L6_XYZ_SCALE
         s2 = add(_pad(f(emb.linear2.weight), 128, 128))
         vecs += [_padv(f(emb.linear1.bias), 128) * s1, _padv(f(emb.linear2.bias), 128) * s2]
         for enc in pct.encoders:
