@@ -22,6 +22,7 @@
 //   * attention: one thread per (query, head, row): 16 scores (d = 8), softmax, 32-wide output written over
 //     the head's V block (the 16 threads of a (query, head) are consecutive lanes of one wave).
 #include "nn_kernels.h"
+#include "lp_blob.h"
 
 namespace mcr {
 
@@ -34,25 +35,12 @@ constexpr int LP_SLD = 196;       // sc row stride (floats)
 constexpr int LP_E = 128;
 
 // ---- packed parameter blob (built on the host: macarons_amd/networks/packing.py) -------------------------------
-// matrices (each [NT][G][64][4] floats), in order:
-//   0 emb1 (N128,K8)  1 emb2 (N128,K128)
-//   per encoder e (base 2 + 6e): qkv (N192,K128)  out (N128,K128)  ff1a ff1b (N128,K128)  ff2a ff2b (N128,K128)
-//   14 lin0 (N128,K128)
-// vectors, in order: emb1_b[128] emb2_b[128] | per encoder: qkv_c[192] out_b[128] ff1_c[256] ff2_b[128] | lin0_c[128]
-constexpr int LP_MAT_K8 = 128 * 8, LP_MAT_128 = 128 * 128, LP_MAT_QKV = 192 * 128;
-__host__ __device__ constexpr int lp_mat_off(int idx) {
-    // idx: 0 emb1, 1 emb2, 2+6e+{0 qkv,1 out,2 ff1a,3 ff1b,4 ff2a,5 ff2b}, 14 lin0
-    int off = 0;
-    for (int i = 0; i < idx; ++i) {
-        const bool is_qkv = (i >= 2 && i < 14 && ((i - 2) % 6) == 0);
-        off += i == 0 ? LP_MAT_K8 : (is_qkv ? LP_MAT_QKV : LP_MAT_128);
-    }
-    return off;
-}
+// the matrices and vectors of lp_blob.h; every matrix as [NT][G][64][4] floats (one float per weight), emb1's K padded to 8
+__host__ __device__ constexpr int lp_mat_off(int idx) { return LpBlob<8, 1, 1>::mat_off(idx); }
+constexpr int LP_MAT_K8 = LpBlob<8, 1, 1>::MAT_K0, LP_MAT_128 = LpBlob<8, 1, 1>::MAT_128, LP_MAT_QKV = LpBlob<8, 1, 1>::MAT_QKV;
 constexpr int LP_MATS_TOTAL = lp_mat_off(15);
-constexpr int LP_VEC_EMB1 = 0, LP_VEC_EMB2 = 128, LP_VEC_ENC0 = 256, LP_VEC_ENC_STRIDE = 192 + 128 + 256 + 128,
-              LP_VEC_LIN0 = LP_VEC_ENC0 + 2 * LP_VEC_ENC_STRIDE, LP_VECS_TOTAL = LP_VEC_LIN0 + 128;
 constexpr int LP_BLOB_FLOATS = LP_MATS_TOTAL + LP_VECS_TOTAL;
+static_assert(lp_mat_off(1) == LP_MAT_K8 && LP_BLOB_FLOATS == 248576, "variant-1 blob layout (packing.py packs to the same total)");
 
 // exact-erf GELU with erf from Abramowitz-Stegun 7.1.26 (|erf error| <= 1.5e-7): ~14 VALU ops instead of the ~35 of
 // the branchy libm erff; the epilogues are not overlapped with MFMA work in this kernel, so they matter.

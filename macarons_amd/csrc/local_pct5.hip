@@ -14,7 +14,7 @@
 // padded:   P  48 KB  x^ as planes [3][64 rows][16 chunks of 8 bf16], or q|k as fp32 [64][64] during attention
 //           F  32 KB  fp32 [64][128]: raw x for the LayerNorm / v and the attention output / a half of the FF hidden
 // Attention runs on the fp32 matrix pipe too (v_mfma_f32_16x16x4_f32, exact fp32): one wave per query, see the kernel body.
-#include "lp_split.h"
+#include "lp_tile.h"
 
 namespace mcr {
 
@@ -25,12 +25,8 @@ __device__ __forceinline__ int q_idx(int row, int col) { return row * 64 + ((((c
 __device__ __forceinline__ int q_chunk(int row, int chunk) { return row * 64 + ((chunk ^ (row & 15)) << 2); }
 __device__ __forceinline__ int p_chunk(int plane, int row, int chunk) { return (plane * 64 + row) * 16 + (chunk ^ (row & 15)); }   // uint4 index
 
-// The swizzled addresses are loop-invariant functions of the lane; left alone, LLVM hoists all of them out of the encoder
-// loop and spills them (172 scratch stores).  Re-deriving them from an opaque copy of the lane id per phase is cheaper.
-__device__ __forceinline__ int l5_opaque(int v) {
-    asm volatile("" : "+v"(v));
-    return v;
-}
+using tile::opaque;                               // (lp_tile.h: why the swizzled addresses are re-derived per phase)
+using tile::rows_allreduce;
 
 #ifndef L5_PF_N
 #define L5_PF_N 3
@@ -42,7 +38,7 @@ constexpr int L5_PF = L5_PF_N;                    // k16-steps of weights in fli
 template <int S, int NTW, bool INIT, bool PLANES>
 __device__ __forceinline__ void l5_gemm(f32x16 (&acc)[NTW][2], const void* __restrict__ Asrc, const float* __restrict__ Wp,
                                         int nt0, int lane_) {
-    const int lane = l5_opaque(lane_);
+    const int lane = opaque(lane_);
     const int i = lane & 31, h = lane >> 5, key = i & 15;
     const uint4* bp[NTW];
 #pragma unroll
@@ -120,7 +116,7 @@ __device__ __forceinline__ void l5_gemm(f32x16 (&acc)[NTW][2], const void* __res
 // XOR: one v_xor per element, the row part goes into the ds_write offset field.
 template <int LD, class G>
 __device__ __forceinline__ void l5_put(const f32x16 (&t)[2], float* buf, int ct, int lane_, G g) {
-    const int lane = l5_opaque(lane_);
+    const int lane = opaque(lane_);
     const int j = lane & 31, h = lane >> 5;
     const int w = ((((ct << 3) | (j >> 2)) ^ (h << 2)) << 2) | (j & 3) | (h * 4 * LD);
 #pragma unroll
@@ -138,7 +134,7 @@ __device__ __forceinline__ void l5_put(const f32x16 (&t)[2], float* buf, int ct,
 __device__ __forceinline__ void l5_gemm_qkv(f32x16 (&acc)[1][2], f32x16& acch, const uint4* __restrict__ P,
                                             const float* __restrict__ Wp, int wave, int lane_) {
     constexpr int S = 8, PF = L5_PF;
-    const int lane = l5_opaque(lane_);
+    const int lane = opaque(lane_);
     const int i = lane & 31, h = lane >> 5, key = i & 15, mh = wave & 1;
     const uint4* bp[2] = {reinterpret_cast<const uint4*>(Wp) + (size_t)wave * S * 3 * 64 + lane,
                           reinterpret_cast<const uint4*>(Wp) + (size_t)(4 + (wave >> 1)) * S * 3 * 64 + lane};
@@ -201,7 +197,7 @@ __device__ __forceinline__ void l5_gemm_qkv(f32x16 (&acc)[1][2], f32x16& acch, c
 // l5_put for ONE 32 x 32 C fragment: m-tile mt (wave-uniform) of column tile ct
 template <int LD, class G>
 __device__ __forceinline__ void l5_put_half(const f32x16& t, float* buf, int ct, int mt, int lane_, G g) {
-    const int lane = l5_opaque(lane_);
+    const int lane = opaque(lane_);
     const int j = lane & 31, h = lane >> 5;
     const int w = (((((ct << 3) | (j >> 2)) ^ (h << 2)) << 2) | (j & 3) | (h * 4 * LD)) + mt * 32 * LD;
 #pragma unroll
@@ -209,23 +205,10 @@ __device__ __forceinline__ void l5_put_half(const f32x16& t, float* buf, int ct,
         buf[((r & 3) + 8 * (r >> 2)) * LD + (w ^ ((((r & 3) + 8 * ((r >> 2) & 1))) << 2))] = g((float)t[r]);
 }
 
-// All-reduce over the four 16-lane rows of a wave (lanes l, l^16, l^32, l^48) without the LDS crossbar: gfx950's
-// v_permlane16_swap / v_permlane32_swap exchange rows / halves between two registers; fed the same value twice they return
-// (this row pair's even row | odd row) resp. (lower half | upper half) replicated, so one op on the pair is the reduction.
-template <class Op>
-__device__ __forceinline__ float l5_rows_allreduce(float v, Op op) {
-    const unsigned b = __builtin_bit_cast(unsigned, v);
-    const auto r = __builtin_amdgcn_permlane16_swap(b, b, false, false);
-    v = op(__builtin_bit_cast(float, (unsigned)r[0]), __builtin_bit_cast(float, (unsigned)r[1]));
-    const unsigned c = __builtin_bit_cast(unsigned, v);
-    const auto q = __builtin_amdgcn_permlane32_swap(c, c, false, false);
-    return op(__builtin_bit_cast(float, (unsigned)q[0]), __builtin_bit_cast(float, (unsigned)q[1]));
-}
-
 // LayerNorm (eps 1e-5, affine folded into the next weights) of the 64 rows of F, written as bf16 planes into P:
 // 4 threads per row, 32 columns each; two-pass (mean, then centred variance) like torch's.
 __device__ __forceinline__ void l5_norm(const float* F, uint4* P, int tid_) {
-    const int tid = l5_opaque(tid_);
+    const int tid = opaque(tid_);
     const int row = tid >> 2, part = tid & 3;
     float v[32];
     float sum = 0.f;
@@ -289,14 +272,14 @@ __global__ __launch_bounds__(256, 2) void local_pct5_kernel(const float* __restr
     l5_gemm<1, 1, true, false>(acc, F, mats + l3_mat_off(0), wave, lane);
     __syncthreads();                               // the offsets in F[:, 0:16] are consumed
     {
-        const float b = vecs[L3_VEC_EMB1 + wave * 32 + (lane & 31)];
+        const float b = vecs[LP_VEC_EMB1 + wave * 32 + (lane & 31)];
         l5_put<128>(acc[0], F, wave, lane, [&](float v) { return l3_gelu(v + b); });
     }
     __syncthreads();
     l5_gemm<8, 1, true, false>(xres, F, mats + l3_mat_off(1), wave, lane);
     {
         const int j = lane & 31, h = lane >> 5;
-        const float b = vecs[L3_VEC_EMB2 + wave * 32 + j];
+        const float b = vecs[LP_VEC_EMB2 + wave * 32 + j];
 #pragma unroll
         for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
@@ -314,7 +297,7 @@ __global__ __launch_bounds__(256, 2) void local_pct5_kernel(const float* __restr
 #pragma unroll 1
     for (int e = 0; e < 2; ++e) {
         const float* em = mats + l3_mat_off(2 + 6 * e);
-        const float* ev = vecs + L3_VEC_ENC0 + e * L3_VEC_ENC_STRIDE;
+        const float* ev = vecs + LP_VEC_ENC0 + e * LP_VEC_ENC_STRIDE;
         // ---- norm1 (folded) -> planes ; QKV (Attention.py:186-188, 287): q|k -> Pq, v -> F ----
         // 6 n-tiles over 4 waves: one each plus half of n-tile 4 or 5 (l5_gemm_qkv).
         __syncthreads();
@@ -341,7 +324,7 @@ __global__ __launch_bounds__(256, 2) void local_pct5_kernel(const float* __restr
         // probabilities are used as the A operand straight from their registers.  The output overwrites the head's V block.
         {
             typedef float f32x4 __attribute__((ext_vector_type(4)));
-            const int ln = l5_opaque(lane);
+            const int ln = opaque(lane);
             const int r0 = wave * 16, li = ln & 15, g = ln >> 4;
             // swizzled addresses as one per-lane word XOR a compile-time constant (row & 15 = li for q|k, 4g + s for v):
             const int wq = ((r0 + li) * 64) | (li << 2) | g;                                   // Pq[row = r0+li][chunk c][g]   = wq ^ (c << 2)
@@ -357,7 +340,7 @@ __global__ __launch_bounds__(256, 2) void local_pct5_kernel(const float* __restr
                     st = __builtin_amdgcn_mfma_f32_16x16x4f32(kk, qq, st, 0, 0, 0);
                 }
                 float mx = fmaxf(fmaxf(st[0], st[1]), fmaxf(st[2], st[3]));
-                mx = l5_rows_allreduce(mx, [](float a, float b) { return fmaxf(a, b); });
+                mx = rows_allreduce(mx, [](float a, float b) { return fmaxf(a, b); });
                 mx *= 0.35355339059327376220f;                                           // scores / sqrt(8)
                 float den = 0.f;
 #pragma unroll
@@ -365,7 +348,7 @@ __global__ __launch_bounds__(256, 2) void local_pct5_kernel(const float* __restr
                     st[r] = __expf(fmaf(st[r], 0.35355339059327376220f, -mx));
                     den += st[r];
                 }
-                den = l5_rows_allreduce(den, [](float a, float b) { return a + b; });
+                den = rows_allreduce(den, [](float a, float b) { return a + b; });
                 const float inv = __builtin_amdgcn_rcpf(den);
 #pragma unroll
                 for (int r = 0; r < 4; ++r) pr[hh][r] = st[r] * inv;
@@ -443,7 +426,7 @@ __global__ __launch_bounds__(256, 2) void local_pct5_kernel(const float* __restr
     __syncthreads();
     l5_gemm<8, 1, true, true>(acc, P, mats + l3_mat_off(14), wave, lane);
     {
-        const float b = vecs[L3_VEC_LIN0 + wave * 32 + (lane & 31)];
+        const float b = vecs[LP_VEC_LIN0 + wave * 32 + (lane & 31)];
         l5_put<128>(acc[0], F, wave, lane, [&](float v) { return v + b; });
     }
     __syncthreads();

@@ -39,19 +39,16 @@
 //               H  32 KB  fp16 planes (FF hidden half / GELU(emb1)), or v as fp32 [64][128], or the final fp32 tile
 //               St  2 KB  LayerNorm partials [4 waves][64 tokens] (mean, M2)
 // 16-byte chunks are XOR-swizzled by (row & 15) in every view.
-#include "lp_split.h"
+// The register-tile helpers this kernel shares with local_pct7.hip (the same structure on one plane) are in lp_tile.h.
+#ifdef L6_TRACE
+#define LP_TRACE L6_TRACE
+#endif
+#include "lp_tile.h"
 
 namespace mcr {
 namespace v6 {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-// The swizzled addresses are loop-invariant functions of the lane; left alone, LLVM hoists all of them out of the encoder
-// loop and spills them.  Re-deriving them from an opaque copy of the lane id per phase is cheaper.
-__device__ __forceinline__ int opaque(int v) {
-    asm volatile("" : "+v"(v));
-    return v;
-}
+using namespace tile;                              // opaque, pin, zero, init_bias, halves_sum, rows_allreduce, LP_T
 
 constexpr int PF = 3;                              // k16-steps of weights in flight per wave and tile
 struct WRing { uint4 b[PF][2]; };                  // [slot][plane hi, lo]
@@ -72,25 +69,19 @@ __device__ __forceinline__ void wload(WRing& r, const uint4* bp) {
     __builtin_amdgcn_sched_barrier(0);
 }
 
-// Pin accumulator chains to this point of the program: the MFMA builtins are pure, so instruction selection is free to delay a
-// whole chain to its next use (it deferred one m-tile's 24 MFMAs of a product past the following product and two barriers,
-// spilling the fragments it had loaded for them).  An empty asm that "rewrites" the accumulators orders them like a fence.
-__device__ __forceinline__ void pin(f32x16& a, f32x16& b) { asm volatile("" : "+v"(a), "+v"(b)); }
-__device__ __forceinline__ void pin(f32x16& a, f32x16& b, f32x16& c) { asm volatile("" : "+v"(a), "+v"(b), "+v"(c)); }
-
-__device__ __forceinline__ void zero(f32x16& a) {
-#pragma unroll
-    for (int r = 0; r < 16; ++r) a[r] = 0.f;
-}
-
 // acc[mt] (+)= W(n-tile) . act^T for both 32-token m-tiles; act = fp16 planes A [2][64][16] in LDS; the ring holds the
 // first PF k-steps of the weight tile (wload) and is refilled here.
-template <int S>
-__device__ __forceinline__ void gemm(f32x16 (&acc)[2], const uint4* __restrict__ A, WRing& r, const uint4* __restrict__ bp,
-                                     int lane_) {
+// With a slice of ANOTHER accumulator's epilogue beside every k-step's six MFMAs (fn(s), s = 0 .. S-1): vector
+// work of a finished product issued in the shadow of the next product's matrix work by the same wave.  The slice sits between
+// the fences with the MFMAs, so the scheduler is free to interleave the two.
+template <int S, class Fn>
+__device__ __forceinline__ void gemm_with(f32x16 (&acc)[2], const uint4* __restrict__ A, WRing& r, const uint4* __restrict__ bp,
+                                          int lane_, Fn fn) {
     const int lane = opaque(lane_);
     const int i = lane & 31, h = lane >> 5, key = i & 15;
     Split2 an[2];
+    // the activation fragments of k-step s for both m-tiles.  A lambda here and in gemm_qkv, not one function as in variant 7: as a
+    // function the swizzled addresses come out of different instructions (NOTES.md, "Fused local transformers: shared tile helpers")
     auto fetch = [&](int s) {
         const int c = (2 * s + h) ^ key;
 #pragma unroll
@@ -119,49 +110,16 @@ __device__ __forceinline__ void gemm(f32x16 (&acc)[2], const uint4* __restrict__
         acc[1] = mfma_h(whi, a1.lo, acc[1]);
         acc[0] = mfma_h(whi, a0.hi, acc[0]);
         acc[1] = mfma_h(whi, a1.hi, acc[1]);
-        pin(acc[0], acc[1]);
-        __builtin_amdgcn_sched_barrier(0);
-    }
-}
-
-// The same product with a slice of ANOTHER accumulator's epilogue beside every k-step's six MFMAs (fn(s), s = 0 .. S-1): vector
-// work of a finished product issued in the shadow of the next product's matrix work by the same wave.  The slice sits between
-// the fences with the MFMAs, so the scheduler is free to interleave the two.
-template <int S, class Fn>
-__device__ __forceinline__ void gemm_with(f32x16 (&acc)[2], const uint4* __restrict__ A, WRing& r, const uint4* __restrict__ bp,
-                                          int lane_, Fn fn) {
-    const int lane = opaque(lane_);
-    const int i = lane & 31, h = lane >> 5, key = i & 15;
-    Split2 an[2];
-    auto fetch = [&](int s) {
-        const int c = (2 * s + h) ^ key;
-#pragma unroll
-        for (int mt = 0; mt < 2; ++mt) {
-            an[mt].hi = A[(0 * 64 + mt * 32 + i) * 16 + c];
-            an[mt].lo = A[(1 * 64 + mt * 32 + i) * 16 + c];
-        }
-    };
-    fetch(0);
-#pragma unroll
-    for (int s = 0; s < S; ++s) {
-        const Split2 a0 = an[0], a1 = an[1];
-        if (s + 1 < S) fetch(s + 1);
-        const uint4 whi = r.b[s % PF][0], wlo = r.b[s % PF][1];
-        if (s + PF < S) {
-            r.b[s % PF][0] = bp[((s + PF) * 2 + 0) * 64];
-            r.b[s % PF][1] = bp[((s + PF) * 2 + 1) * 64];
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        acc[0] = mfma_h(wlo, a0.hi, acc[0]);
-        acc[1] = mfma_h(wlo, a1.hi, acc[1]);
-        acc[0] = mfma_h(whi, a0.lo, acc[0]);
-        acc[1] = mfma_h(whi, a1.lo, acc[1]);
-        acc[0] = mfma_h(whi, a0.hi, acc[0]);
-        acc[1] = mfma_h(whi, a1.hi, acc[1]);
         fn(s);
         pin(acc[0], acc[1]);
         __builtin_amdgcn_sched_barrier(0);
     }
+}
+// the plain product: an empty slice
+template <int S>
+__device__ __forceinline__ void gemm(f32x16 (&acc)[2], const uint4* __restrict__ A, WRing& r, const uint4* __restrict__ bp,
+                                     int lane_) {
+    gemm_with<S>(acc, A, r, bp, lane_, [](int) {});
 }
 
 // QKV product (N = 192 = 6 n-tiles over 4 waves), balanced: every wave takes its own n-tile w for both m-tiles plus HALF of
@@ -223,14 +181,6 @@ __device__ __forceinline__ void scale_add_bias(f32x16& x, float scale, const flo
         x[4 * g + 2] = fmaf(x[4 * g + 2], scale, b.z); x[4 * g + 3] = fmaf(x[4 * g + 3], scale, b.w);
     }
 }
-__device__ __forceinline__ void init_bias(f32x16& a, const float* __restrict__ vec, int nt, int lane_) {
-    const float4* p = reinterpret_cast<const float4*>(vec + 32 * nt + 4 * (opaque(lane_) >> 5));
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-        const float4 b = p[2 * g];
-        a[4 * g] = b.x; a[4 * g + 1] = b.y; a[4 * g + 2] = b.z; a[4 * g + 3] = b.w;
-    }
-}
 
 // store 4 consecutive features of one token as fp16 hi/lo: one ds_write_b64 per plane
 __device__ __forceinline__ void put4(uint2* __restrict__ planes, int idx, float v0, float v1, float v2, float v3) {
@@ -271,22 +221,6 @@ __device__ __forceinline__ void put_f32(float* __restrict__ buf, int LD, int chu
     for (int g = 0; g < 4; ++g)
         *reinterpret_cast<float4*>(row + (((chunk0 + 2 * g + h) ^ key) << 2)) =
             make_float4(f(t[4 * g], g, 0), f(t[4 * g + 1], g, 1), f(t[4 * g + 2], g, 2), f(t[4 * g + 3], g, 3));
-}
-
-// lanes l and l ^ 32 (the two halves of a token's 32 features in this wave): sum on both
-__device__ __forceinline__ float halves_sum(float v) {
-    const unsigned c = __builtin_bit_cast(unsigned, v);
-    const auto q = __builtin_amdgcn_permlane32_swap(c, c, false, false);
-    return __builtin_bit_cast(float, (unsigned)q[0]) + __builtin_bit_cast(float, (unsigned)q[1]);
-}
-template <class Op>
-__device__ __forceinline__ float rows_allreduce(float v, Op op) {           // over lanes l, l^16, l^32, l^48
-    const unsigned b = __builtin_bit_cast(unsigned, v);
-    const auto r = __builtin_amdgcn_permlane16_swap(b, b, false, false);
-    v = op(__builtin_bit_cast(float, (unsigned)r[0]), __builtin_bit_cast(float, (unsigned)r[1]));
-    const unsigned c = __builtin_bit_cast(unsigned, v);
-    const auto q = __builtin_amdgcn_permlane32_swap(c, c, false, false);
-    return op(__builtin_bit_cast(float, (unsigned)q[0]), __builtin_bit_cast(float, (unsigned)q[1]));
 }
 
 // LayerNorm, part 1: this wave's (mean, M2) over its 32 features of every token -> St[wave][token]
@@ -331,13 +265,6 @@ __device__ __forceinline__ void ln_finish(const f32x16 (&x)[2], const float2* __
     }
 }
 
-#ifdef L6_TRACE             // dev only: per-phase timestamps of one workgroup (tools/build_variant.py ... -DL6_TRACE=<block>)
-__device__ long long l6_trace_buf[64];
-#define L6_T() do { if (blockIdx.x == (L6_TRACE) && tid == 0) { l6_trace_buf[tp] = clock64(); l6_trace_buf[tp ? 63 : 62] = wall_clock64(); } ++tp; } while (0)
-#else
-#define L6_T() do { } while (0)
-#endif
-
 // grid = ceil(S / 4); S sequences of 16 offsets [S,16,3]; features[s*ld_feat + 0:256] = max(128) || avg(128)
 // feat_h != NULL: the pooled features go out as fp16 hi / lo planes (feat_h / feat_l, row stride ld_feat halves) instead of fp32:
 // the head GEMM (linear3p.hip) reads ready-made planes
@@ -361,13 +288,13 @@ __global__ __launch_bounds__(256, 2) void local_pct6_kernel(const float* __restr
     const long long s0 = (long long)blockIdx.x * L3_QPB;
     const int lane = lane0;
     int tp = 0; (void)tp;
-    L6_T();
+    LP_T();
     WRing ring;
     f32x16 acc[2], xres[2];
     // ---- Embedding (Attention.py:98-128): linear1 3->125 (K padded to 16), GELU -> H planes ; linear2 125->125 || xyz ----
     wload<1>(ring, wptr(mats + l6_mat_off(0), wave, 1, lane));
-    init_bias(acc[0], vecs + L3_VEC_EMB1, wave, lane);
-    init_bias(acc[1], vecs + L3_VEC_EMB1, wave, lane);
+    init_bias(acc[0], vecs + LP_VEC_EMB1, wave, lane);
+    init_bias(acc[1], vecs + LP_VEC_EMB1, wave, lane);
     float xyz[2][3];
     {
         const int j = lane & 31;
@@ -399,7 +326,7 @@ __global__ __launch_bounds__(256, 2) void local_pct6_kernel(const float* __restr
             acc[mt] = mfma_h(ring.b[0][0], a.hi, acc[mt]);
         }
     }
-    L6_T();                                        // emb1 product done
+    LP_T();                                        // emb1 product done
     wload<8>(ring, wptr(mats + l6_mat_off(1), wave, 8, lane));
     {
         const float sc = isc[0];
@@ -407,12 +334,12 @@ __global__ __launch_bounds__(256, 2) void local_pct6_kernel(const float* __restr
         for (int mt = 0; mt < 2; ++mt)
             put_planes(H, wave, mt, acc[mt], lane, [&](float v, int, int) { return l3_gelu(v * sc); });
     }
-    init_bias(xres[0], vecs + L3_VEC_EMB2, wave, lane);
-    init_bias(xres[1], vecs + L3_VEC_EMB2, wave, lane);
+    init_bias(xres[0], vecs + LP_VEC_EMB2, wave, lane);
+    init_bias(xres[1], vecs + LP_VEC_EMB2, wave, lane);
     __syncthreads();
-    L6_T();                                        // emb1 gelu + barrier
+    LP_T();                                        // emb1 gelu + barrier
     gemm<8>(xres, H, ring, wptr(mats + l6_mat_off(1), wave, 8, lane), lane);
-    L6_T();                                        // emb2 gemm
+    LP_T();                                        // emb2 gemm
     {
         const float sc = isc[1];
 #pragma unroll
@@ -431,7 +358,7 @@ __global__ __launch_bounds__(256, 2) void local_pct6_kernel(const float* __restr
 #pragma unroll 1
     for (int e = 0; e < 2; ++e) {
         const float* em = mats + l6_mat_off(2) + e * (L6_MAT_QKV + 5 * L6_MAT_128);
-        const float* ev = vecs + L3_VEC_ENC0 + e * L3_VEC_ENC_STRIDE;
+        const float* ev = vecs + LP_VEC_ENC0 + e * LP_VEC_ENC_STRIDE;
         const float* es = isc + 2 + 6 * e;          // 2^-e of qkv, out, ff1a, ff1b, ff2a (= ff2b); the forward scales 2^e sit 16 floats later
         const float* w_out = em + L6_MAT_QKV;
         const float* w_ff1a = w_out + L6_MAT_128;
@@ -444,13 +371,13 @@ __global__ __launch_bounds__(256, 2) void local_pct6_kernel(const float* __restr
         const uint4* bq1 = wptr(em, 4 + (wave >> 1), 8, lane);
         wload<8>(ring, bq0);
         wload<8>(ring1, bq1);
-        L6_T();                                    // (previous epilogue)
+        LP_T();                                    // (previous epilogue)
         ln_partial(xres, St, wave, lane);
         __syncthreads();                           // St visible; every wave is past its last read of P and H
-        L6_T();                                    // norm1 partial + barrier
+        LP_T();                                    // norm1 partial + barrier
         ln_finish(xres, St, P, wave, lane);
         __syncthreads();                           // x^ planes visible
-        L6_T();                                    // norm1 finish + barrier
+        LP_T();                                    // norm1 finish + barrier
         {
             f32x16 aq[2], ah;
             const int nth = 4 + (wave >> 1);
@@ -458,11 +385,11 @@ __global__ __launch_bounds__(256, 2) void local_pct6_kernel(const float* __restr
             init_bias(aq[1], ev, wave, lane);
             init_bias(ah, ev, nth, lane);
             gemm_qkv(aq, ah, P, ring, ring1, bq0, bq1, wave, lane);
-            L6_T();                                // qkv gemm
+            LP_T();                                // qkv gemm
             wload<8>(ring, wptr(w_out, wave, 8, lane));
             const float sc = es[0];
             __syncthreads();                       // x^ planes consumed: P may take q|k
-            L6_T();                                // barrier
+            LP_T();                                // barrier
             // n-tiles 0,1 = q,k -> Pq chunks 0..7 / 8..15; n-tiles 2..5 = v -> F chunks 8 (nt - 2) ..
             auto fb = [&](float v, int, int) { return v * sc; };
             float* dst = wave < 2 ? Pq : F;         // branch-free: the whole encoder stays one basic block
@@ -472,7 +399,7 @@ __global__ __launch_bounds__(256, 2) void local_pct6_kernel(const float* __restr
             put_f32(F, 128, 8 * (nth - 2), wave & 1, ah, lane, fb);
         }
         __syncthreads();
-        L6_T();                                    // qkv put + barrier
+        LP_T();                                    // qkv put + barrier
         // ---- attention (Attention.py:8-36) on the fp32 matrix pipe (v_mfma_f32_16x16x4_f32 = exact fp32 fma chains):
         // wave = query (16 tokens); per head  S^T = K Q^T (key rows, query columns: lane (qi, g) then owns S[qi][4g..4g+3]),
         // softmax over the keys = 4 registers x the 4 lane groups, O^T = V^T P^T with the key index j = 4g + s: lane (qi, g)
@@ -530,13 +457,13 @@ __global__ __launch_bounds__(256, 2) void local_pct6_kernel(const float* __restr
                     put4(p2, base + (((4 * hh + 2 * nt + (g >> 1)) ^ li) << 1), o[hh][nt][0], o[hh][nt][1], o[hh][nt][2], o[hh][nt][3]);
         }
         // ---- out projection + residual (Attention.py:201-202, 290): x += att W_o^T + b, accumulated in place ----
-        L6_T();                                    // attention
+        LP_T();                                    // attention
         scale_add_bias(xres[0], es[16 + 1], ev + 192, wave, lane);
         scale_add_bias(xres[1], es[16 + 1], ev + 192, wave, lane);
         __syncthreads();
-        L6_T();                                    // bias + barrier
+        LP_T();                                    // bias + barrier
         gemm<8>(xres, P, ring, wptr(w_out, wave, 8, lane), lane);
-        L6_T();                                    // out gemm
+        LP_T();                                    // out gemm
         wload<8>(ring, wptr(w_ff1a, wave, 8, lane));
         {
             const float sc = es[1];
@@ -550,15 +477,15 @@ __global__ __launch_bounds__(256, 2) void local_pct6_kernel(const float* __restr
         init_bias(acc[0], ev + 192 + 128, wave, lane);
         init_bias(acc[1], ev + 192 + 128, wave, lane);
         __syncthreads();                           // St visible; the attention output in P is consumed by every wave
-        L6_T();                                    // res + norm2 partial + barrier
+        LP_T();                                    // res + norm2 partial + barrier
         ln_finish(xres, St, P, wave, lane);
         __syncthreads();
-        L6_T();                                    // norm2 finish + barrier
+        LP_T();                                    // norm2 finish + barrier
         // FF1a, then FF1b with GELU(a) beside its MFMAs (hidden half a -> H), barrier, FF2a with GELU(b) beside its MFMAs
         // (hidden half b -> P, free once every wave is past FF1b), barrier, FF2b: two barriers instead of three and both GELU
         // epilogues in the shadow of matrix work
         gemm<8>(acc, P, ring, wptr(w_ff1a, wave, 8, lane), lane);
-        L6_T();                                    // ff1a gemm
+        LP_T();                                    // ff1a gemm
         wload<8>(ring, wptr(w_ff1b, wave, 8, lane));
         f32x16 accb[2];
         init_bias(accb[0], ev + 192 + 128 + 128, wave, lane);
@@ -570,25 +497,25 @@ __global__ __launch_bounds__(256, 2) void local_pct6_kernel(const float* __restr
                 put_quad(H, wave, s_ >> 2, s_ & 3, acc[s_ >> 2], pq_row, pq_key, [&](float v) { return l3_gelu(v * sc); });
             });
         }
-        L6_T();                                    // ff1b gemm + gelu a
+        LP_T();                                    // ff1b gemm + gelu a
         wload<8>(ring, wptr(w_ff2a, wave, 8, lane));
         scale_add_bias(xres[0], es[16 + 4], ev + 192 + 128 + 256, wave, lane);   // FF2 accumulates onto the residual in place
         scale_add_bias(xres[1], es[16 + 4], ev + 192 + 128 + 256, wave, lane);
         __syncthreads();                           // hidden half a visible; x^ planes in P consumed by every wave
-        L6_T();                                    // barrier
+        LP_T();                                    // barrier
         {
             const float sc = es[3];
             gemm_with<8>(xres, H, ring, wptr(w_ff2a, wave, 8, lane), lane, [&](int s_) {
                 put_quad(P, wave, s_ >> 2, s_ & 3, accb[s_ >> 2], pq_row, pq_key, [&](float v) { return l3_gelu(v * sc); });
             });
         }
-        L6_T();                                    // ff2a gemm + gelu b
+        LP_T();                                    // ff2a gemm + gelu b
         wload<8>(ring, wptr(w_ff2b, wave, 8, lane));
         __syncthreads();                           // hidden half b visible
-        L6_T();                                    // barrier
-        L6_T();                                    // (spare stamp: keeps the trace table of tools/trace_local_pct.py aligned)
+        LP_T();                                    // barrier
+        LP_T();                                    // (spare stamp: keeps the trace table of tools/trace_local_pct.py aligned)
         gemm<8>(xres, P, ring, wptr(w_ff2b, wave, 8, lane), lane);
-        L6_T();                                    // ff2b gemm
+        LP_T();                                    // ff2b gemm
         {
             const float sc = es[4];                 // ff2a and ff2b share one exponent
 #pragma unroll
@@ -597,12 +524,12 @@ __global__ __launch_bounds__(256, 2) void local_pct6_kernel(const float* __restr
                 for (int r = 0; r < 16; ++r) xres[mt][r] *= sc;
         }
     }
-    L6_T();
+    LP_T();
     // ---- final norm (folded) + linear0 128 -> 128 (SconeOcc.py:119-122) ----
     wload<8>(ring, wptr(mats + l6_mat_off(14), wave, 8, lane));
     ln_partial(xres, St, wave, lane);
-    init_bias(acc[0], vecs + L3_VEC_LIN0, wave, lane);
-    init_bias(acc[1], vecs + L3_VEC_LIN0, wave, lane);
+    init_bias(acc[0], vecs + LP_VEC_LIN0, wave, lane);
+    init_bias(acc[1], vecs + LP_VEC_LIN0, wave, lane);
     __syncthreads();
     ln_finish(xres, St, P, wave, lane);
     __syncthreads();
@@ -614,7 +541,7 @@ __global__ __launch_bounds__(256, 2) void local_pct6_kernel(const float* __restr
             put_f32(F, 128, 8 * wave, mt, acc[mt], lane, [&](float v, int, int) { return v * sc; });
     }
     __syncthreads();
-    L6_T();                                        // final norm + lin0
+    LP_T();                                        // final norm + lin0
     // ---- max || avg pool over the 16 tokens of each query (SconeOcc.py:124-126) ----
 #pragma unroll
     for (int r = 0; r < 2; ++r) {
@@ -643,14 +570,10 @@ __global__ __launch_bounds__(256, 2) void local_pct6_kernel(const float* __restr
             }
         }
     }
-    L6_T();
+    LP_T();
 }
 
 }  // namespace v6
-
-#ifdef L6_TRACE
-extern "C" int mcr_dev_read_trace(long long* out) { return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(v6::l6_trace_buf), sizeof(long long) * 64); }
-#endif
 
 void launch_local_pct6(hipStream_t s, const float* offs, float* feat, int64_t ld_feat, int64_t S, const float* blob, void* feat_h,
                        void* feat_l) {

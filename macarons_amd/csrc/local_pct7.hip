@@ -13,7 +13,8 @@
 // Range: |activation| < 65504 as on variant 6 (a non-finite occupancy raises the same range flag).
 //
 // Structure = local_pct6.hip (4 waves = 64 tokens x 128 channels on chip, products transposed, residual stream in registers,
-// Chan-combined LayerNorm statistics, GELU epilogues beside the next product's MFMAs) minus everything the low planes needed:
+// Chan-combined LayerNorm statistics, GELU epilogues beside the next product's MFMAs; the register-tile helpers the two share are
+// in lp_tile.h) minus everything the low planes needed:
 // a third of the MFMAs, half the fragment reads, half the LDS plane stores, half the weight bytes from L2, no split arithmetic.
 // No per-matrix power-of-two weight scale either (variant 6 needs it for its LOW plane): weights and biases as they are, rounded to
 // fp16 -- what a 16-bit matrix path means everywhere else; |w| >= 65520 becomes inf and ends in the range guard.
@@ -29,19 +30,15 @@
 // Row stride 272 bytes = 68 banks: the 16 rows a ds_read_b128 / ds_read_b32 group touches land 4 banks apart (conflict-free);
 // the fp32 [64][128] view keeps variant 6's XOR swizzle by (row & 15).
 // MCR_HIPCC_FLAGS: -fno-slp-vectorize
-#include "lp_split.h"
+#ifdef L7_TRACE
+#define LP_TRACE L7_TRACE
+#endif
+#include "lp_tile.h"
 
 namespace mcr {
 namespace v7 {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-// The swizzled addresses are loop-invariant functions of the lane; left alone, LLVM hoists all of them out of the encoder
-// loop and spills them.  Re-deriving them from an opaque copy of the lane id per phase is cheaper.
-__device__ __forceinline__ int opaque(int v) {
-    asm volatile("" : "+v"(v));
-    return v;
-}
+using namespace tile;                              // opaque, pin, zero, init_bias, halves_sum, rows_allreduce, LP_T
 
 #ifndef L7_PF
 #define L7_PF 3
@@ -81,48 +78,16 @@ __device__ __forceinline__ void wload(WRing& r, const uint4* bp) {
     __builtin_amdgcn_sched_barrier(0);
 }
 
-// Pin accumulator chains to this point of the program: the MFMA builtins are pure, so instruction selection is free to delay a
-// whole chain to its next use (it deferred one m-tile's 24 MFMAs of a product past the following product and two barriers,
-// spilling the fragments it had loaded for them).  An empty asm that "rewrites" the accumulators orders them like a fence.
-__device__ __forceinline__ void pin(f32x16& a, f32x16& b) { asm volatile("" : "+v"(a), "+v"(b)); }
-__device__ __forceinline__ void pin(f32x16& a, f32x16& b, f32x16& c) { asm volatile("" : "+v"(a), "+v"(b), "+v"(c)); }
-
-__device__ __forceinline__ void zero(f32x16& a) {
+// the activation fragments of k-step s for both m-tiles: chunk 2 s + h of rows 32 mt + i of the fp16 plane A [64][16]
+__device__ __forceinline__ void fetch(uint4 (&an)[2], const uint4* __restrict__ A, int s, int i, int h) {
+    const int c = 2 * s + h;
 #pragma unroll
-    for (int r = 0; r < 16; ++r) a[r] = 0.f;
+    for (int mt = 0; mt < 2; ++mt) an[mt] = A[(mt * 32 + i) * PR + c];
 }
 
 // acc[mt] (+)= W(n-tile) . act^T for both 32-token m-tiles; act = fp16 plane A [64][16] in LDS; the ring holds the
 // first PF k-steps of the weight tile (wload) and is refilled here.
-template <int S>
-__device__ __forceinline__ void gemm(f32x16 (&acc)[2], const uint4* __restrict__ A, WRing& r, const uint4* __restrict__ bp,
-                                     int lane_) {
-    const int lane = opaque(lane_);
-    const int i = lane & 31, h = lane >> 5;
-    uint4 an[2];
-    auto fetch = [&](int s) {
-        const int c = 2 * s + h;
-#pragma unroll
-        for (int mt = 0; mt < 2; ++mt) an[mt] = A[(mt * 32 + i) * PR + c];
-    };
-    fetch(0);
-    // software pipeline in program order, fenced: [next step's 2 fragment reads][the weight request PF steps ahead] |
-    // [this step's 2 MFMAs].
-#pragma unroll
-    for (int s = 0; s < S; ++s) {
-        const uint4 a0 = an[0], a1 = an[1];
-        if (s + 1 < S) fetch(s + 1);
-        const uint4 w = r.b[s % PF];
-        if (s + PF < S) r.b[s % PF] = bp[(s + PF) * 64];
-        __builtin_amdgcn_sched_barrier(0);
-        acc[0] = mfma_h(w, a0, acc[0]);
-        acc[1] = mfma_h(w, a1, acc[1]);
-        pin(acc[0], acc[1]);
-        __builtin_amdgcn_sched_barrier(0);
-    }
-}
-
-// The same product with a slice of ANOTHER accumulator's epilogue beside every k-step's two MFMAs (fn(s), s = 0 .. S-1): vector
+// With a slice of ANOTHER accumulator's epilogue beside every k-step's two MFMAs (fn(s), s = 0 .. S-1): vector
 // work of a finished product issued in the shadow of the next product's matrix work by the same wave.
 template <int S, class Fn>
 __device__ __forceinline__ void gemm_with(f32x16 (&acc)[2], const uint4* __restrict__ A, WRing& r, const uint4* __restrict__ bp,
@@ -130,16 +95,13 @@ __device__ __forceinline__ void gemm_with(f32x16 (&acc)[2], const uint4* __restr
     const int lane = opaque(lane_);
     const int i = lane & 31, h = lane >> 5;
     uint4 an[2];
-    auto fetch = [&](int s) {
-        const int c = 2 * s + h;
-#pragma unroll
-        for (int mt = 0; mt < 2; ++mt) an[mt] = A[(mt * 32 + i) * PR + c];
-    };
-    fetch(0);
+    fetch(an, A, 0, i, h);
+    // software pipeline in program order, fenced: [next step's 2 fragment reads][the weight request PF steps ahead] |
+    // [this step's 2 MFMAs].
 #pragma unroll
     for (int s = 0; s < S; ++s) {
         const uint4 a0 = an[0], a1 = an[1];
-        if (s + 1 < S) fetch(s + 1);
+        if (s + 1 < S) fetch(an, A, s + 1, i, h);
         const uint4 w = r.b[s % PF];
         if (s + PF < S) r.b[s % PF] = bp[(s + PF) * 64];
         __builtin_amdgcn_sched_barrier(0);
@@ -150,6 +112,12 @@ __device__ __forceinline__ void gemm_with(f32x16 (&acc)[2], const uint4* __restr
         __builtin_amdgcn_sched_barrier(0);
     }
 }
+// the plain product: an empty slice
+template <int S>
+__device__ __forceinline__ void gemm(f32x16 (&acc)[2], const uint4* __restrict__ A, WRing& r, const uint4* __restrict__ bp,
+                                     int lane_) {
+    gemm_with<S>(acc, A, r, bp, lane_, [](int) {});
+}
 
 // QKV product (N = 192 = 6 n-tiles over 4 waves), balanced: every wave takes its own n-tile w for both m-tiles plus HALF of
 // n-tile 4 + (w >> 1): the m-tile w & 1.
@@ -159,17 +127,12 @@ __device__ __forceinline__ void gemm_qkv(f32x16 (&acc)[2], f32x16& acch, const u
     const int lane = opaque(lane_);
     const int i = lane & 31, h = lane >> 5, mh = wave & 1;
     uint4 an[2];
-    auto fetch = [&](int s) {
-        const int c = 2 * s + h;
-#pragma unroll
-        for (int mt = 0; mt < 2; ++mt) an[mt] = A[(mt * 32 + i) * PR + c];
-    };
-    fetch(0);
+    fetch(an, A, 0, i, h);
 #pragma unroll
     for (int s = 0; s < S; ++s) {
         const uint4 a0 = an[0], a1 = an[1];
         const uint4 ah = mh ? a1 : a0;
-        if (s + 1 < S) fetch(s + 1);
+        if (s + 1 < S) fetch(an, A, s + 1, i, h);
         const uint4 w = r0.b[s % PF], v = r1.b[s % PF];
         if (s + PF < S) {
             r0.b[s % PF] = bp0[(s + PF) * 64];
@@ -194,14 +157,6 @@ __device__ __forceinline__ void add_bias(f32x16& x, const float* __restrict__ ve
     for (int g = 0; g < 4; ++g) {
         const float4 b = p[2 * g];
         x[4 * g] += b.x; x[4 * g + 1] += b.y; x[4 * g + 2] += b.z; x[4 * g + 3] += b.w;
-    }
-}
-__device__ __forceinline__ void init_bias(f32x16& a, const float* __restrict__ vec, int nt, int lane_) {
-    const float4* p = reinterpret_cast<const float4*>(vec + 32 * nt + 4 * (opaque(lane_) >> 5));
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-        const float4 b = p[2 * g];
-        a[4 * g] = b.x; a[4 * g + 1] = b.y; a[4 * g + 2] = b.z; a[4 * g + 3] = b.w;
     }
 }
 
@@ -238,22 +193,6 @@ __device__ __forceinline__ void put_f32(float* __restrict__ buf, int LD, int kma
     for (int g = 0; g < 4; ++g)
         *reinterpret_cast<float4*>(row + (((chunk0 + 2 * g + h) ^ key) << 2)) =
             make_float4(f(t[4 * g], g, 0), f(t[4 * g + 1], g, 1), f(t[4 * g + 2], g, 2), f(t[4 * g + 3], g, 3));
-}
-
-// lanes l and l ^ 32 (the two halves of a token's 32 features in this wave): sum on both
-__device__ __forceinline__ float halves_sum(float v) {
-    const unsigned c = __builtin_bit_cast(unsigned, v);
-    const auto q = __builtin_amdgcn_permlane32_swap(c, c, false, false);
-    return __builtin_bit_cast(float, (unsigned)q[0]) + __builtin_bit_cast(float, (unsigned)q[1]);
-}
-template <class Op>
-__device__ __forceinline__ float rows_allreduce(float v, Op op) {           // over lanes l, l^16, l^32, l^48
-    const unsigned b = __builtin_bit_cast(unsigned, v);
-    const auto r = __builtin_amdgcn_permlane16_swap(b, b, false, false);
-    v = op(__builtin_bit_cast(float, (unsigned)r[0]), __builtin_bit_cast(float, (unsigned)r[1]));
-    const unsigned c = __builtin_bit_cast(unsigned, v);
-    const auto q = __builtin_amdgcn_permlane32_swap(c, c, false, false);
-    return op(__builtin_bit_cast(float, (unsigned)q[0]), __builtin_bit_cast(float, (unsigned)q[1]));
 }
 
 // LayerNorm, part 1: this wave's (mean, M2) over its 32 features of every token -> St[wave][token].  One pass (sum and sum of
@@ -313,13 +252,6 @@ __device__ __forceinline__ void ln_finish(const f32x16 (&x)[2], const float2* __
     }
 }
 
-#ifdef L7_TRACE             // dev only: per-phase timestamps of one workgroup (tools/build_variant.py ... -DL7_TRACE=<block>)
-__device__ long long l7_trace_buf[64];
-#define L7_T() do { if (blockIdx.x == (L7_TRACE) && tid == 0) { l7_trace_buf[tp] = clock64(); l7_trace_buf[tp ? 63 : 62] = wall_clock64(); } ++tp; } while (0)
-#else
-#define L7_T() do { } while (0)
-#endif
-
 // grid = ceil(S / 4); S sequences of 16 offsets [S,16,3]; features[s*ld_feat + 0:256] = max(128) || avg(128)
 // feat_h != NULL: the pooled features go out as ONE fp16 plane (row stride ld_feat halves) instead of fp32: the head GEMM
 // (linear3p.hip, single-plane form) reads it as it is
@@ -345,13 +277,13 @@ __global__ __launch_bounds__(256, L7_WGS) void local_pct7_kernel(const float* __
     const long long s0 = (long long)blockIdx.x * L3_QPB;
     const int lane = lane0;
     int tp = 0; (void)tp;
-    L7_T();
+    LP_T();
     WRing ring;
     f32x16 acc[2], xres[2];
     // ---- Embedding (Attention.py:98-128): linear1 3->125 (K padded to 16), GELU -> H planes ; linear2 125->125 || xyz ----
     wload<1>(ring, wptr(mats + l7_mat_off(0), wave, 1, lane));
-    init_bias(acc[0], vecs + L3_VEC_EMB1, wave, lane);
-    init_bias(acc[1], vecs + L3_VEC_EMB1, wave, lane);
+    init_bias(acc[0], vecs + LP_VEC_EMB1, wave, lane);
+    init_bias(acc[1], vecs + LP_VEC_EMB1, wave, lane);
     float xyz[2][3];
     {
         const int j = lane & 31;
@@ -375,17 +307,17 @@ __global__ __launch_bounds__(256, L7_WGS) void local_pct7_kernel(const float* __
             acc[mt] = mfma_h(ring.b[0], a, acc[mt]);
         }
     }
-    L7_T();                                        // emb1 product done
+    LP_T();                                        // emb1 product done
     wload<8>(ring, wptr(mats + l7_mat_off(1), wave, 8, lane));
 #pragma unroll
     for (int mt = 0; mt < 2; ++mt)
         put_planes(H, wave, mt, acc[mt], lane, [&](float v, int, int) { return l7_gelu(v); });
-    init_bias(xres[0], vecs + L3_VEC_EMB2, wave, lane);
-    init_bias(xres[1], vecs + L3_VEC_EMB2, wave, lane);
+    init_bias(xres[0], vecs + LP_VEC_EMB2, wave, lane);
+    init_bias(xres[1], vecs + LP_VEC_EMB2, wave, lane);
     __syncthreads();
-    L7_T();                                        // emb1 gelu + barrier
+    LP_T();                                        // emb1 gelu + barrier
     gemm<8>(xres, H, ring, wptr(mats + l7_mat_off(1), wave, 8, lane), lane);
-    L7_T();                                        // emb2 gemm
+    LP_T();                                        // emb2 gemm
     {
         const bool cat = wave == 3 && lane >= 32;  // features 125..127 = the raw xyz (Attention.py:123-126): n-tile 3, g = 3, h = 1, e = 1..3
 #pragma unroll
@@ -399,7 +331,7 @@ __global__ __launch_bounds__(256, L7_WGS) void local_pct7_kernel(const float* __
 #pragma unroll 1
     for (int e = 0; e < 2; ++e) {
         const float* em = mats + l7_mat_off(2) + e * (L7_MAT_QKV + 5 * L7_MAT_128);
-        const float* ev = vecs + L3_VEC_ENC0 + e * L3_VEC_ENC_STRIDE;
+        const float* ev = vecs + LP_VEC_ENC0 + e * LP_VEC_ENC_STRIDE;
         const float* w_out = em + L7_MAT_QKV;
         const float* w_ff1a = w_out + L7_MAT_128;
         const float* w_ff1b = w_out + L7_MAT_128 * 2;
@@ -411,13 +343,13 @@ __global__ __launch_bounds__(256, L7_WGS) void local_pct7_kernel(const float* __
         const uint4* bq1 = wptr(em, 4 + (wave >> 1), 8, lane);
         wload<8>(ring, bq0);
         wload<8>(ring1, bq1);
-        L7_T();                                    // (previous epilogue)
+        LP_T();                                    // (previous epilogue)
         ln_partial(xres, St, wave, lane);
         __syncthreads();                           // St visible; every wave is past its last read of P and H
-        L7_T();                                    // norm1 partial + barrier
+        LP_T();                                    // norm1 partial + barrier
         ln_finish(xres, St, P, wave, lane);
         __syncthreads();                           // x^ planes visible
-        L7_T();                                    // norm1 finish + barrier
+        LP_T();                                    // norm1 finish + barrier
         {
             f32x16 aq[2], ah;
             const int nth = 4 + (wave >> 1);
@@ -425,10 +357,10 @@ __global__ __launch_bounds__(256, L7_WGS) void local_pct7_kernel(const float* __
             init_bias(aq[1], ev, wave, lane);
             init_bias(ah, ev, nth, lane);
             gemm_qkv(aq, ah, P, ring, ring1, bq0, bq1, wave, lane);
-            L7_T();                                // qkv gemm
+            LP_T();                                // qkv gemm
             wload<8>(ring, wptr(w_out, wave, 8, lane));
             __syncthreads();                       // x^ planes consumed: P may take q|k
-            L7_T();                                // barrier
+            LP_T();                                // barrier
             // n-tiles 0, 1 = q, k -> halves 0..31 / 32..63 of the P rows; n-tiles 2..5 = v -> the H plane (halves 32 (nt - 2) ..): one
             // rounding to fp16 where the values are produced, like every other matrix operand of this variant
             auto fb = [&](float v, int, int) { return v; };
@@ -439,7 +371,7 @@ __global__ __launch_bounds__(256, L7_WGS) void local_pct7_kernel(const float* __
             put_planes(H, nth - 2, wave & 1, ah, lane, fb);
         }
         __syncthreads();
-        L7_T();                                    // qkv put + barrier
+        LP_T();                                    // qkv put + barrier
         // ---- attention (Attention.py:8-36) on v_mfma_f32_16x16x16_f16 (fp16 q | k | v and soft-max weights, fp32 scores / soft-max /
         // accumulation): wave = query (16 tokens); per head  S^T = K Q^T (A = K: lane (key li, g) holds dims 4 (g & 1) .., B = Q^T: lane
         // (query li, g) holds dims 4 g .. for g < 2 and ZEROS for g >= 2 -- the head has 8 dims, the MFMA's k is 16), so lane (qi, g) owns
@@ -496,28 +428,28 @@ __global__ __launch_bounds__(256, L7_WGS) void local_pct7_kernel(const float* __
                     put4(p2, base + 2 * (4 * hh + 2 * nt), o[hh][nt][0], o[hh][nt][1], o[hh][nt][2], o[hh][nt][3]);
         }
         // ---- out projection + residual (Attention.py:201-202, 290): x += att W_o^T + b, accumulated in place ----
-        L7_T();                                    // attention
+        LP_T();                                    // attention
         add_bias(xres[0], ev + 192, wave, lane);
         add_bias(xres[1], ev + 192, wave, lane);
         __syncthreads();
-        L7_T();                                    // bias + barrier
+        LP_T();                                    // bias + barrier
         gemm<8>(xres, P, ring, wptr(w_out, wave, 8, lane), lane);
-        L7_T();                                    // out gemm
+        LP_T();                                    // out gemm
         wload<8>(ring, wptr(w_ff1a, wave, 8, lane));
         // ---- norm2 (folded) -> planes P ; FF 128 -> 256 (GELU) -> 128 + residual (Attention.py:293-298), two halves ----
         ln_partial(xres, St, wave, lane);
         init_bias(acc[0], ev + 192 + 128, wave, lane);
         init_bias(acc[1], ev + 192 + 128, wave, lane);
         __syncthreads();                           // St visible; the attention output in P is consumed by every wave
-        L7_T();                                    // res + norm2 partial + barrier
+        LP_T();                                    // res + norm2 partial + barrier
         ln_finish(xres, St, P, wave, lane);
         __syncthreads();
-        L7_T();                                    // norm2 finish + barrier
+        LP_T();                                    // norm2 finish + barrier
         // FF1a, then FF1b with GELU(a) beside its MFMAs (hidden half a -> H), barrier, FF2a with GELU(b) beside its MFMAs
         // (hidden half b -> P, free once every wave is past FF1b), barrier, FF2b: two barriers instead of three and both GELU
         // epilogues in the shadow of matrix work
         gemm<8>(acc, P, ring, wptr(w_ff1a, wave, 8, lane), lane);
-        L7_T();                                    // ff1a gemm
+        LP_T();                                    // ff1a gemm
         wload<8>(ring, wptr(w_ff1b, wave, 8, lane));
         f32x16 accb[2];
         init_bias(accb[0], ev + 192 + 128 + 128, wave, lane);
@@ -526,29 +458,29 @@ __global__ __launch_bounds__(256, L7_WGS) void local_pct7_kernel(const float* __
         gemm_with<8>(accb, P, ring, wptr(w_ff1b, wave, 8, lane), lane, [&](int s_) {
             put_quad(H, wave, s_ >> 2, s_ & 3, acc[s_ >> 2], pq_row, [&](float v) { return l7_gelu(v); });
         });
-        L7_T();                                    // ff1b gemm + gelu a
+        LP_T();                                    // ff1b gemm + gelu a
         wload<8>(ring, wptr(w_ff2a, wave, 8, lane));
         add_bias(xres[0], ev + 192 + 128 + 256, wave, lane);   // FF2 accumulates onto the residual in place
         add_bias(xres[1], ev + 192 + 128 + 256, wave, lane);
         __syncthreads();                           // hidden half a visible; x^ planes in P consumed by every wave
-        L7_T();                                    // barrier
+        LP_T();                                    // barrier
         gemm_with<8>(xres, H, ring, wptr(w_ff2a, wave, 8, lane), lane, [&](int s_) {
             put_quad(P, wave, s_ >> 2, s_ & 3, accb[s_ >> 2], pq_row, [&](float v) { return l7_gelu(v); });
         });
-        L7_T();                                    // ff2a gemm + gelu b
+        LP_T();                                    // ff2a gemm + gelu b
         wload<8>(ring, wptr(w_ff2b, wave, 8, lane));
         __syncthreads();                           // hidden half b visible
-        L7_T();                                    // barrier
-        L7_T();                                    // (spare stamp: keeps the trace table of tools/trace_local_pct.py aligned)
+        LP_T();                                    // barrier
+        LP_T();                                    // (spare stamp: keeps the trace table of tools/trace_local_pct.py aligned)
         gemm<8>(xres, P, ring, wptr(w_ff2b, wave, 8, lane), lane);
-        L7_T();                                    // ff2b gemm
+        LP_T();                                    // ff2b gemm
     }
-    L7_T();
+    LP_T();
     // ---- final norm (folded) + linear0 128 -> 128 (SconeOcc.py:119-122) ----
     wload<8>(ring, wptr(mats + l7_mat_off(14), wave, 8, lane));
     ln_partial(xres, St, wave, lane);
-    init_bias(acc[0], vecs + L3_VEC_LIN0, wave, lane);
-    init_bias(acc[1], vecs + L3_VEC_LIN0, wave, lane);
+    init_bias(acc[0], vecs + LP_VEC_LIN0, wave, lane);
+    init_bias(acc[1], vecs + LP_VEC_LIN0, wave, lane);
     __syncthreads();
     ln_finish(xres, St, P, wave, lane);
     __syncthreads();
@@ -557,7 +489,7 @@ __global__ __launch_bounds__(256, L7_WGS) void local_pct7_kernel(const float* __
     for (int mt = 0; mt < 2; ++mt)
         put_f32(F, 128, 15, 8 * wave, mt, acc[mt], lane, [&](float v, int, int) { return v; });
     __syncthreads();
-    L7_T();                                        // final norm + lin0
+    LP_T();                                        // final norm + lin0
     // ---- max || avg pool over the 16 tokens of each query (SconeOcc.py:124-126) ----
 #pragma unroll
     for (int r = 0; r < 2; ++r) {
@@ -583,14 +515,10 @@ __global__ __launch_bounds__(256, L7_WGS) void local_pct7_kernel(const float* __
             }
         }
     }
-    L7_T();
+    LP_T();
 }
 
 }  // namespace v7
-
-#ifdef L7_TRACE
-extern "C" int mcr_dev_read_trace(long long* out) { return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(v7::l7_trace_buf), sizeof(long long) * 64); }
-#endif
 
 void launch_local_pct7(hipStream_t s, const float* offs, float* feat, int64_t ld_feat, int64_t S, const float* blob, void* feat_h) {
     if (S <= 0) return;

@@ -1,8 +1,11 @@
-// Shared pieces of the split-precision fused local transformers (local_pct5.hip: exact bf16 hi/mid/lo, six MFMAs per
-// fp32 product; local_pct6.hip: fp16 hi/lo, three MFMAs): parameter-blob layouts, the operand splits, the MFMA
-// wrappers and the exact-erf GELU.  Reference mapping in local_pct.hip (SconeOcc.py:104-130).
+// Shared pieces of the reduced-precision fused local transformers (local_pct5.hip: exact bf16 hi/mid/lo, six MFMAs per
+// fp32 product; local_pct6.hip: fp16 hi/lo, three MFMAs; local_pct7.hip: one fp16 plane, one MFMA) and of the planes GEMMs
+// (linear3*.hip): the variants' parameter blobs (layout function in lp_blob.h), the operand splits, the MFMA wrappers and
+// the exact-erf GELU.  The register-tile helpers of the kernels themselves are in lp_tile.h.  Reference mapping in
+// local_pct.hip (SconeOcc.py:104-130).
 #pragma once
 #include "nn_kernels.h"
+#include "lp_blob.h"
 
 namespace mcr {
 
@@ -15,53 +18,33 @@ typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 constexpr int L3_T = 64, L3_QPB = 4;
 // ---- blob of variant 5: matrices as [n-tile][k16 step][plane hi,mid,lo][lane][8 bf16] (1.5 floats per weight), then
 // the vectors of the v1 blob
-constexpr int L3_MAT_K16 = 128 * 16 * 3 / 2, L3_MAT_128 = 128 * 128 * 3 / 2, L3_MAT_QKV = 192 * 128 * 3 / 2;
-__host__ __device__ constexpr int l3_mat_off(int idx) {
-    int off = 0;
-    for (int i = 0; i < idx; ++i) {
-        const bool is_qkv = (i >= 2 && i < 14 && ((i - 2) % 6) == 0);
-        off += i == 0 ? L3_MAT_K16 : (is_qkv ? L3_MAT_QKV : L3_MAT_128);
-    }
-    return off;
-}
+__host__ __device__ constexpr int l3_mat_off(int idx) { return LpBlob<16, 3, 2>::mat_off(idx); }
+constexpr int L3_MAT_K16 = LpBlob<16, 3, 2>::MAT_K0, L3_MAT_128 = LpBlob<16, 3, 2>::MAT_128, L3_MAT_QKV = LpBlob<16, 3, 2>::MAT_QKV;
 constexpr int L3_MATS_TOTAL = l3_mat_off(15);
-constexpr int L3_VEC_EMB1 = 0, L3_VEC_EMB2 = 128, L3_VEC_ENC0 = 256, L3_VEC_ENC_STRIDE = 192 + 128 + 256 + 128,
-              L3_VEC_LIN0 = L3_VEC_ENC0 + 2 * L3_VEC_ENC_STRIDE, L3_VECS_TOTAL = L3_VEC_LIN0 + 128;
-constexpr int L3_BLOB_FLOATS = L3_MATS_TOTAL + L3_VECS_TOTAL;
+constexpr int L3_BLOB_FLOATS = L3_MATS_TOTAL + LP_VECS_TOTAL;
+static_assert(L3_BLOB_FLOATS == 373504, "variant-5 blob layout (packing.py packs to the same total)");
 
 // ---- blob of variant 6: matrices as [n-tile][k16 step][plane hi,lo][lane][8 fp16] (1 float per weight), every matrix
 // multiplied by a power of two 2^e_i on the host so that its fp16 low plane stays in the normal range; then the same
 // vectors (every bias times its matrix's 2^e_i); then 16 floats: 2^-e_i for the 15 matrices (applied in the epilogues) + one
 // pad; then 16 floats: 2^e_i (products accumulated onto the residual stream scale it up first)
-constexpr int L6_MAT_K16 = 128 * 16, L6_MAT_128 = 128 * 128, L6_MAT_QKV = 192 * 128;
-__host__ __device__ constexpr int l6_mat_off(int idx) {
-    int off = 0;
-    for (int i = 0; i < idx; ++i) {
-        const bool is_qkv = (i >= 2 && i < 14 && ((i - 2) % 6) == 0);
-        off += i == 0 ? L6_MAT_K16 : (is_qkv ? L6_MAT_QKV : L6_MAT_128);
-    }
-    return off;
-}
+__host__ __device__ constexpr int l6_mat_off(int idx) { return LpBlob<16, 1, 1>::mat_off(idx); }
+constexpr int L6_MAT_K16 = LpBlob<16, 1, 1>::MAT_K0, L6_MAT_128 = LpBlob<16, 1, 1>::MAT_128, L6_MAT_QKV = LpBlob<16, 1, 1>::MAT_QKV;
 constexpr int L6_MATS_TOTAL = l6_mat_off(15);
-constexpr int L6_SCALES = L3_VECS_TOTAL;                      // offset of the 16 inverse scales inside the vector section
-constexpr int L6_BLOB_FLOATS = L6_MATS_TOTAL + L3_VECS_TOTAL + 32;
+constexpr int L6_SCALES = LP_VECS_TOTAL;                      // offset of the 16 inverse scales inside the vector section
+constexpr int L6_BLOB_FLOATS = L6_MATS_TOTAL + LP_VECS_TOTAL + 32;
+static_assert(L6_BLOB_FLOATS == 249632, "variant-6 blob layout (packing.py packs to the same total)");
 // local_pct6 splits the xyz offsets as L6_XYZ_SCALE x (their low half would be a subnormal fp16 number otherwise); the variant-6 blob
 // carries the embedding's first bias times it and isc[0] divided by it (packing.py: L6_XYZ_SCALE, the same value)
 constexpr float L6_XYZ_SCALE = 256.f;
 
 // ---- blob of variant 7 (opt-in 16-bit matrix path): matrices as [n-tile][k16 step][lane][8 fp16] -- the HIGH plane of variant 6's
 // blob WITHOUT the per-matrix power of two (fp16(W), half a float per weight); then the same vectors (biases as they are)
-constexpr int L7_MAT_K16 = 128 * 16 / 2, L7_MAT_128 = 128 * 128 / 2, L7_MAT_QKV = 192 * 128 / 2;
-__host__ __device__ constexpr int l7_mat_off(int idx) {
-    int off = 0;
-    for (int i = 0; i < idx; ++i) {
-        const bool is_qkv = (i >= 2 && i < 14 && ((i - 2) % 6) == 0);
-        off += i == 0 ? L7_MAT_K16 : (is_qkv ? L7_MAT_QKV : L7_MAT_128);
-    }
-    return off;
-}
+__host__ __device__ constexpr int l7_mat_off(int idx) { return LpBlob<16, 1, 2>::mat_off(idx); }
+constexpr int L7_MAT_K16 = LpBlob<16, 1, 2>::MAT_K0, L7_MAT_128 = LpBlob<16, 1, 2>::MAT_128, L7_MAT_QKV = LpBlob<16, 1, 2>::MAT_QKV;
 constexpr int L7_MATS_TOTAL = l7_mat_off(15);
-constexpr int L7_BLOB_FLOATS = L7_MATS_TOTAL + L3_VECS_TOTAL;
+constexpr int L7_BLOB_FLOATS = L7_MATS_TOTAL + LP_VECS_TOTAL;
+static_assert(L7_BLOB_FLOATS == 125696, "variant-7 blob layout (packing.py packs to the same total)");
 
 __device__ __forceinline__ unsigned pack2h(const float a, const float b) {      // {fp16(b), fp16(a)}, round to nearest even: v_cvt_pk_f16_f32
     const f32x2 x = {a, b};
