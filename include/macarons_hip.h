@@ -907,6 +907,34 @@ int mcr_expansion_layer(const float* x, const float* x_add, const float* up_weig
                         const float* i_bias, float* y, int64_t B, int Cin, int Cmid, int Cadd, int Cout, int h, int w, int H, int W,
                         void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- the expansion layers, the backward (expansion_layer_bwd.hip).
+ *
+ * mcr_expansion_layer_backward: x, x_add, up_weight, i_weight as the forward's; u [B,Cmid,h,w], the transposed convolution after its ELU
+ *   (the front of the forward's workspace after a call); y [B,Cout,H,W], what the forward returned; d_y [B,Cout,H,W]; all contiguous fp32.
+ *   With near() the nearest-source index, refl() the reflection index, c = cat(nearest(u), x_add):
+ *     g2 = d_y (y > 0 ? 1 : y + 1);   d_i_bias [Cout] = sum g2;   d_i_weight [Cout,Cmid+Cadd,3,3] = sum_{b,i,j} g2 c[refl(i+di-1),refl(j+dj-1)];
+ *     d_c = the transposed reflection-padded convolution of g2 with i_weight;   d_x_add [B,Cadd,H,W] = d_c[:, Cmid:];
+ *     d_u[s,t] = the sum of d_c[:, :Cmid] over the pixels (i,j) with near(i) = s, near(j) = t (none where the map shrinks: 0);
+ *     g1 = d_u (u > 0 ? 1 : u + 1);   d_up_bias [Cmid] = sum g1;   d_up_weight [Cin,Cmid,3,3] = sum_{b,s,t} x[s,t] g1[s+ki-1,t+kj-1];
+ *     d_x [B,Cin,h,w] = the zero-padded correlation of g1 with up_weight.
+ *   Any of the six outputs may be NULL and is then not computed; a launch runs only if an output that is asked for depends on it (with
+ *   d_i_weight / d_i_bias alone no data gradient is formed; d_x_add alone needs neither d_x's correlation nor the weight pass of the
+ *   transposed convolution); all six NULL is refused.  The two data gradients are launches of the forward's kernel (zero padding, no bias,
+ *   no ELU), a gather between them folds the ring, sums the nearest ranges and applies ELU'(u); the two weight gradients run on
+ *   v_mfma_f32_16x16x4_f32 over the pixels, nine accumulators per 16 x 16 block of channel pairs and a tenth for the bias gradient,
+ *   the pixels divided among workgroups by a rule of the shape alone, one partial per output and workgroup in the workspace, added in
+ *   a fixed order in double by a finish launch.  No floating-point atomics: two calls give the same bits.  workspace: g2, the
+ *   correlation over the padded domain [B,Cmid+Cadd,H+2,W+2], g1 and the partials.
+ * Refused before any launch: what the forward refuses (sizes, a tensor of 2^31 elements or more -- here also the padded correlation --,
+ * a NULL operand, x_add only with Cadd > 0), d_x_add with Cadd = 0, a workspace that is missing, short or not 16-byte aligned.  The size
+ * function returns 0 for sizes that the entry refuses. */
+size_t mcr_expansion_layer_backward_workspace_bytes(int64_t B, int64_t Cin, int64_t Cmid, int64_t Cadd, int64_t Cout, int64_t h, int64_t w,
+                                                    int64_t H, int64_t W);
+int mcr_expansion_layer_backward(const float* x, const float* x_add, const float* up_weight, const float* i_weight, const float* u,
+                                 const float* y, const float* d_y, float* d_x, float* d_x_add, float* d_up_weight, float* d_up_bias,
+                                 float* d_i_weight, float* d_i_bias, int64_t B, int Cin, int Cmid, int Cadd, int Cout, int h, int w, int H,
+                                 int W, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -650,3 +650,54 @@ class DisparityHeadFunction(torch.autograd.Function):
             ins = [t.detach().requires_grad_(n) for t, n in zip((x, weight, bias), need)]
             grads = iter(torch.autograd.grad(disparity_head_composite(*ins), [t for t, n in zip(ins, need) if n], grad_y))
         return tuple(next(grads) if n else None for n in need)
+
+
+# ---- depth module, the expansion layers: HIP forward + HIP backward ------------------------------------------------------------------------
+def expansion_layer_backward_mode():
+    """'composite' (default) or 'hip' (env MCR_EXPANSION_LAYER_BWD=hip: the fused forward and the HIP backward
+    mcr_expansion_layer_backward, through ExpansionLayerFunction).  The default is the torch composite under autograd because
+    profiles/expansion_layer_backward_times.json does not show a forward-and-backward step through the Function faster with the
+    intervals apart at every shape (seven rows of ten: all five of upstream's shapes at B 1, expansion2 and expansion1 at B 4; not at
+    expansion5, expansion4 and expansion3 at B 4, where the library's convolutions are faster than the exact-fp32 kernels), and the
+    route stays opt-in whatever that file shows (NOTES.md); the five layers with the four heads, all three knobs on, are faster with
+    the intervals apart at both batch sizes."""
+    return _env_mode(os.environ.get("MCR_EXPANSION_LAYER_BWD", ""), ("hip",), "composite")
+
+
+class ExpansionLayerFunction(torch.autograd.Function):
+    """apply(x, x_add, up_weight, up_bias, i_weight, i_bias, output_size) -> y [B,Cout,H,W] of ops.expansion_layer (mcr_expansion_layer);
+    x_add None: no concatenation.  Saves x, x_add, the weights, u (the transposed convolution after its ELU, which the forward leaves at
+    the front of its workspace) and y (and the biases, which only the composite route reads).  backward = ops.expansion_layer_backward
+    (mcr_expansion_layer_backward: no atomics, the same bits on every run) with expansion_layer_backward_mode() == 'hip'; a gradient
+    that no input needs is not computed, nor a launch that only it depends on.  With the mode 'composite' the backward is autograd
+    through networks.ManyDepth.expansion_layer_composite instead (plain torch on the same device, recomputed; for A/B runs -- the
+    module's forward does not come here in that mode).  Differentiable once."""
+
+    @staticmethod
+    def forward(ctx, x, x_add, up_weight, up_bias, i_weight, i_bias, output_size):
+        from . import ops
+        ctx.output_size, ctx.has_add = tuple(int(v) for v in output_size), x_add is not None
+        with torch.no_grad():
+            y, u = ops.expansion_layer(x, x_add, up_weight, up_bias, i_weight, i_bias, ctx.output_size, return_u=True)
+        ctx.save_for_backward(x, up_weight, up_bias, i_weight, i_bias, u, y, *((x_add,) if ctx.has_add else ()))
+        return y
+
+    @staticmethod
+    def backward(ctx, grad_y):
+        _once("the expansion layer is", "its backward runs without a graph")
+        x, up_weight, up_bias, i_weight, i_bias, u, y = ctx.saved_tensors[:7]
+        x_add = ctx.saved_tensors[7] if ctx.has_add else None
+        need = tuple(ctx.needs_input_grad[:6])
+        if not ctx.has_add:
+            need = (need[0], False) + need[2:]
+        if not any(need):
+            return (None,) * 7
+        if expansion_layer_backward_mode() == "hip":
+            from . import ops
+            return ops.expansion_layer_backward(x, x_add, up_weight, i_weight, u, y, grad_y.float().contiguous(), ctx.output_size,
+                                                need=need) + (None,)
+        from .networks.ManyDepth import expansion_layer_composite
+        with torch.enable_grad():
+            ins = [None if t is None else t.detach().requires_grad_(n) for t, n in zip((x, x_add, up_weight, up_bias, i_weight, i_bias), need)]
+            grads = iter(torch.autograd.grad(expansion_layer_composite(*ins, ctx.output_size), [t for t, n in zip(ins, need) if n], grad_y))
+        return tuple(next(grads) if n else None for n in need) + (None,)

@@ -385,20 +385,26 @@ def _autocast_on(x):
 
 
 def expansion_layer_route(x, x_add, params, output_size, additional_channels):
-    """'hip' or 'composite' for one forward: the fused entry serves contiguous float32 HIP tensors outside autocast, within the entry's
-    limits, when no gradient is recorded and the mode (expansion_layer_mode) is 'hip'.  params: (upconv.weight, upconv.bias, iconv.weight,
-    iconv.bias).  An x_add that the layer ignores (additional_channels None) is not an operand."""
+    """'hip', 'function' or 'composite' for one forward.  The fused entry serves contiguous float32 HIP tensors outside autocast, within
+    the entry's limits: 'hip' (ops.expansion_layer) when no gradient is recorded and the mode (expansion_layer_mode) is 'hip';
+    'function' (autograd.ExpansionLayerFunction: the fused forward and the HIP backward) when a gradient is to be recorded and
+    autograd.expansion_layer_backward_mode() is 'hip' (MCR_EXPANSION_LAYER_BWD=hip; MCR_EXPANSION_LAYER, the knob of the forward without
+    a gradient, has no say there).  params: (upconv.weight, upconv.bias, iconv.weight, iconv.bias).  An x_add that the layer ignores
+    (additional_channels None) is not an operand."""
     if additional_channels is None:
         x_add = None
     elif x_add is None:
         return "composite"                                       # upstream's own forward fails there; the composite fails the same way
-    if expansion_layer_mode() != "hip":
-        return "composite"
     ts = [x, *params] + ([x_add] if x_add is not None else [])
     if not all(isinstance(t, torch.Tensor) for t in ts):
         return "composite"
-    if torch.is_grad_enabled() and any(t.requires_grad for t in ts):
-        return "composite"                                       # the backward is not on HIP yet: upstream's sequence under autograd
+    recorded = torch.is_grad_enabled() and any(t.requires_grad for t in ts)
+    if recorded:
+        from ..autograd import expansion_layer_backward_mode
+        if expansion_layer_backward_mode() != "hip":
+            return "composite"                                   # upstream's sequence under autograd: the HIP backward is opt-in
+    elif expansion_layer_mode() != "hip":
+        return "composite"
     if _autocast_on(x):
         return "composite"
     if not all(_is_hip_tensor(t) and t.device == x.device and t.dtype == torch.float32 and t.is_contiguous() for t in ts):
@@ -413,19 +419,26 @@ def expansion_layer_route(x, x_add, params, output_size, additional_channels):
         return "composite"
     if max(x.numel(), B * Cmid * x.shape[2] * x.shape[3], B * Ctot * H * W, B * Cout * H * W) >= 2 ** 31:
         return "composite"
-    return "hip"
+    if recorded and B * Ctot * (H + 2) * (W + 2) >= 2 ** 31:
+        return "composite"                                       # the backward's G carries the ring
+    return "function" if recorded else "hip"
 
 
 def _expansion_forward(self, x, x_add=None):
     """ExpansionLayer.forward (ManyDepth.py:351-363), same signature: x [B,Cin,h,w], x_add [B,Cadd,H,W] -> [B,Cout,H,W]; like upstream's,
     x_add is concatenated only when both it and additional_channels are set.  The route is expansion_layer_route: the fused entry
-    (ops.expansion_layer) without a gradient to record under the mode 'hip', the composite under autograd whenever a gradient is
-    required, and for everything the entry does not take."""
+    (ops.expansion_layer) without a gradient to record under the mode 'hip'; with a gradient required, ExpansionLayerFunction under
+    MCR_EXPANSION_LAYER_BWD=hip and the composite under autograd otherwise (the default); the composite for everything the entry does
+    not take."""
     if x_add is not None and self.additional_channels is None:
         x_add = None
     params = (self.upconv.weight, self.upconv.bias, self.iconv.weight, self.iconv.bias)
-    if expansion_layer_route(x, x_add, params, self.output_size, self.additional_channels) == "hip":
+    route = expansion_layer_route(x, x_add, params, self.output_size, self.additional_channels)
+    if route == "hip":
         return ops.expansion_layer(x, x_add, *params, self.output_size)
+    if route == "function":
+        from ..autograd import ExpansionLayerFunction
+        return ExpansionLayerFunction.apply(x, x_add, *params, self.output_size)
     return expansion_layer_composite(x, x_add, *params, self.output_size)
 
 

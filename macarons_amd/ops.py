@@ -1936,9 +1936,10 @@ def disparity_head_backward(x, weight, y, d_y, need=(True, True, True)):
 EXPANSION_LAYER_MAX_CHANNELS = 512
 
 
-def _expansion_layer_args(x, x_add, up_weight, up_bias, i_weight, i_bias, output_size):
-    """The shapes first (ValueError, on any device), then the operands themselves (HIP, float32, contiguous).  x [B,Cin,h,w], x_add
-    [B,Cadd,H,W] or None, up_weight [Cin,Cmid,3,3], up_bias [Cmid], i_weight [Cout,Cmid+Cadd,3,3], i_bias [Cout], output_size (H, W)."""
+def _expansion_layer_shapes(x, x_add, up_weight, up_bias, i_weight, i_bias, output_size, biases=True):
+    """The shapes (ValueError, on any device) -> (B, Cin, Cmid, Cadd, Cout, h, w, H, W).  x [B,Cin,h,w], x_add [B,Cadd,H,W] or None,
+    up_weight [Cin,Cmid,3,3], up_bias [Cmid], i_weight [Cout,Cmid+Cadd,3,3], i_bias [Cout], output_size (H, W); biases False: the
+    backward, which reads none."""
     cap = EXPANSION_LAYER_MAX_CHANNELS
     if not isinstance(x, torch.Tensor) or x.dim() != 4:
         raise ValueError(f"x must be [B,Cin,h,w], got {tuple(getattr(x, 'shape', ()))}")
@@ -1968,28 +1969,79 @@ def _expansion_layer_args(x, x_add, up_weight, up_bias, i_weight, i_bias, output
     Cout = int(i_weight.shape[0])
     if not 1 <= Cout <= cap:
         raise ValueError(f"Cout = {Cout} must be between 1 and {cap}")
-    for name, t, n in (("up_bias", up_bias, Cmid), ("i_bias", i_bias, Cout)):
+    for name, t, n in (("up_bias", up_bias, Cmid), ("i_bias", i_bias, Cout)) if biases else ():
         if not isinstance(t, torch.Tensor) or tuple(t.shape) != (n,):
             raise ValueError(f"{name} must be [{n}], got {tuple(getattr(t, 'shape', ()))}")
     if max(B * Cin * h * w, B * Cmid * h * w, B * Cadd * H * W, B * Cout * H * W) > 2 ** 31 - 1:
         raise ValueError(f"x is {tuple(x.shape)}, the output [{B},{Cout},{H},{W}]: a tensor has 2^31 elements or more")
+    return B, Cin, Cmid, Cadd, Cout, h, w, H, W
+
+
+def _expansion_layer_args(x, x_add, up_weight, up_bias, i_weight, i_bias, output_size):
+    """The shapes first (_expansion_layer_shapes), then the operands themselves (HIP, float32, contiguous)."""
+    sizes = _expansion_layer_shapes(x, x_add, up_weight, up_bias, i_weight, i_bias, output_size)
     ts = [_req(t, name) for name, t in (("x", x), ("up_weight", up_weight), ("up_bias", up_bias), ("i_weight", i_weight), ("i_bias", i_bias))]
-    return ts, (_req(x_add, "x_add") if x_add is not None else None), (B, Cin, Cmid, Cadd, Cout, h, w, H, W)
+    return ts, (_req(x_add, "x_add") if x_add is not None else None), sizes
 
 
-def expansion_layer(x, x_add, up_weight, up_bias, i_weight, i_bias, output_size):
+def expansion_layer(x, x_add, up_weight, up_bias, i_weight, i_bias, output_size, return_u=False):
     """y [B,Cout,H,W] = ELU(conv3x3(reflection_pad(cat(nearest(ELU(conv_transpose3x3(x, up_weight) + up_bias) -> output_size), x_add)),
     i_weight) + i_bias) in one entry (mcr_expansion_layer): upstream's ExpansionLayer.forward (ManyDepth.py:351-363).  x [B,Cin,h,w],
     x_add [B,Cadd,H,W] or None, the weights in upstream's layouts (upconv.weight [Cin,Cmid,3,3], iconv.weight [Cout,Cmid+Cadd,3,3]),
-    float32.  Exact fp32 products; the same bits on every call."""
+    float32.  Exact fp32 products; the same bits on every call.  return_u: (y, u) with u [B,Cmid,h,w] the transposed convolution after
+    its ELU, which the backward reads -- the front of the entry's workspace, here a freshly allocated one instead of the shared arena
+    that the next call overwrites."""
     (x, up_weight, up_bias, i_weight, i_bias), x_add, (B, Cin, Cmid, Cadd, Cout, h, w, H, W) = _expansion_layer_args(
         x, x_add, up_weight, up_bias, i_weight, i_bias, output_size)
     dev = x.device
     y = torch.empty((B, Cout, H, W), dtype=torch.float32, device=dev)
     L = lib()
-    ws = _entry_workspace(dev, L.mcr_expansion_layer_workspace_bytes, c_i64(B), c_i64(Cmid), c_i64(h), c_i64(w))
+    if return_u:
+        nbytes = max(int(L.mcr_expansion_layer_workspace_bytes(c_i64(B), c_i64(Cmid), c_i64(h), c_i64(w))), 4 * B * Cmid * h * w)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    else:
+        ws = _entry_workspace(dev, L.mcr_expansion_layer_workspace_bytes, c_i64(B), c_i64(Cmid), c_i64(h), c_i64(w))
     with torch.cuda.device(dev):
         check(L.mcr_expansion_layer(_p(x), _p(x_add) if x_add is not None else None, _p(up_weight), _p(up_bias), _p(i_weight), _p(i_bias),
                                     _p(y), c_i64(B), c_int(Cin), c_int(Cmid), c_int(Cadd), c_int(Cout), c_int(h), c_int(w), c_int(H),
                                     c_int(W), _p(ws), c_size(ws.numel()), _stream()), "mcr_expansion_layer")
+    if return_u:
+        return y, ws[:4 * B * Cmid * h * w].view(torch.float32).view(B, Cmid, h, w)
     return y
+
+
+def expansion_layer_backward(x, x_add, up_weight, i_weight, u, y, d_y, output_size, need=(True,) * 6):
+    """(d_x, d_x_add, d_up_weight, d_up_bias, d_i_weight, d_i_bias) of sum(d_y * y) for y, u = expansion_layer(..., return_u=True), in one
+    entry (mcr_expansion_layer_backward); u [B,Cmid,h,w], y and d_y [B,Cout,H,W].  need: which of the six are computed, the others are
+    None; d_x_add is None without an x_add whatever need says; nothing left to compute is refused.  Each launch runs only if an output
+    that is asked for depends on it.  No atomics: two calls give the same bits."""
+    need = tuple(bool(n) for n in need)
+    if len(need) != 6:
+        raise ValueError("expansion_layer_backward: need names (d_x, d_x_add, d_up_weight, d_up_bias, d_i_weight, d_i_bias)")
+    if x_add is None:
+        need = (need[0], False) + need[2:]
+    if not any(need):
+        raise ValueError("expansion_layer_backward: need must name at least one of (d_x, d_x_add, d_up_weight, d_up_bias, d_i_weight, "
+                         "d_i_bias); d_x_add counts only with an x_add")
+    B, Cin, Cmid, Cadd, Cout, h, w, H, W = _expansion_layer_shapes(x, x_add, up_weight, None, i_weight, None, output_size, biases=False)
+    for name, t, shape in (("u", u, (B, Cmid, h, w)), ("y", y, (B, Cout, H, W)), ("d_y", d_y, (B, Cout, H, W))):
+        if not isinstance(t, torch.Tensor) or tuple(t.shape) != shape:
+            raise ValueError(f"{name} must be {list(shape)}, got {tuple(getattr(t, 'shape', ()))}")
+    if B * (Cmid + Cadd) * (H + 2) * (W + 2) > 2 ** 31 - 1:
+        raise ValueError(f"the output [{B},{Cout},{H},{W}] with {Cmid + Cadd} concatenated channels: a tensor of the backward has 2^31 "
+                         "elements or more")
+    x, up_weight, i_weight = _req(x, "x"), _req(up_weight, "up_weight"), _req(i_weight, "i_weight")
+    x_add = _req(x_add, "x_add") if x_add is not None else None
+    u, y, d_y = _req(u, "u"), _req(y, "y"), _req(d_y, "d_y")
+    dev = x.device
+    shapes = ((B, Cin, h, w), (B, Cadd, H, W), (Cin, Cmid, 3, 3), (Cmid,), (Cout, Cmid + Cadd, 3, 3), (Cout,))
+    outs = [torch.empty(shape, dtype=torch.float32, device=dev) if n else None for shape, n in zip(shapes, need)]
+    L = lib()
+    ws = _entry_workspace(dev, L.mcr_expansion_layer_backward_workspace_bytes, c_i64(B), c_i64(Cin), c_i64(Cmid), c_i64(Cadd), c_i64(Cout),
+                          c_i64(h), c_i64(w), c_i64(H), c_i64(W))
+    with torch.cuda.device(dev):
+        check(L.mcr_expansion_layer_backward(_p(x), _p(x_add) if x_add is not None else None, _p(up_weight), _p(i_weight), _p(u), _p(y),
+                                             _p(d_y), *[_p(o) if o is not None else None for o in outs], c_i64(B), c_int(Cin),
+                                             c_int(Cmid), c_int(Cadd), c_int(Cout), c_int(h), c_int(w), c_int(H), c_int(W), _p(ws),
+                                             c_size(ws.numel()), _stream()), "mcr_expansion_layer_backward")
+    return tuple(outs)
