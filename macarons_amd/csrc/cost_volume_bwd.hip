@@ -35,8 +35,7 @@ __global__ __launch_bounds__(256) void cv_maxabs_kernel(const float* __restrict_
     const float* gb = g + (size_t)blockIdx.y * batch_stride;
     for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < per_batch; t += (int64_t)gridDim.x * blockDim.x)
         m = max(m, __float_as_uint(fabsf(gb[t])));                          // NaN patterns lie above infinity's
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m = max(m, (unsigned)__shfl_xor((int)m, o, 64));
+    m = wave_max_all(m);
     if ((threadIdx.x & 63) == 0 && m) atomicMax(maxbits, m);
 }
 
@@ -129,27 +128,20 @@ __global__ __launch_bounds__(256) void cv_scatter_kernel(const float2* __restric
 
 // In place: counts[0..n) -> exclusive offsets, counts[n] = the total; cursor[j] = offset j.  One workgroup; thread i owns a contiguous chunk.
 __global__ __launch_bounds__(CV_SCAN_THREADS) void cv_scan_kernel(unsigned* __restrict__ counts, unsigned* __restrict__ cursor, int64_t n) {
-    __shared__ unsigned part[CV_SCAN_THREADS];
+    __shared__ unsigned s_wave[CV_SCAN_THREADS / 64];
     const int64_t per = (n + CV_SCAN_THREADS - 1) / CV_SCAN_THREADS;
     const int64_t j0 = min(n, (int64_t)threadIdx.x * per), j1 = min(n, j0 + per);
     unsigned s = 0;
     for (int64_t j = j0; j < j1; ++j) s += counts[j];
-    part[threadIdx.x] = s;
-    __syncthreads();
-    for (int o = 1; o < CV_SCAN_THREADS; o <<= 1) {                        // inclusive scan of the chunk totals
-        const unsigned v = (int)threadIdx.x >= o ? part[threadIdx.x - o] : 0u;
-        __syncthreads();
-        part[threadIdx.x] += v;
-        __syncthreads();
-    }
-    unsigned run = part[threadIdx.x] - s;
+    unsigned total;
+    unsigned run = block_exclusive_scan<CV_SCAN_THREADS / 64>(s, s_wave, &total);      // of the chunk totals
     for (int64_t j = j0; j < j1; ++j) {
         const unsigned c = counts[j];
         counts[j] = run;
         cursor[j] = run;
         run += c;
     }
-    if (threadIdx.x == CV_SCAN_THREADS - 1) counts[n] = part[CV_SCAN_THREADS - 1];
+    if (threadIdx.x == CV_SCAN_THREADS - 1) counts[n] = total;
 }
 
 // A wave per destination: its four rows take every fourth entry of the list, lane l of each row channels 4l .. 4l+3, and the rows' integer
@@ -178,8 +170,8 @@ __global__ __launch_bounds__(256) void cv_dest_sum_kernel(const unsigned* __rest
             a0 += cv_signed(bits, 0, q), a1 += cv_signed(bits, 1, q), a2 += cv_signed(bits, 2, q), a3 += cv_signed(bits, 3, q);
         }
     }
-    a0 += __shfl_xor(a0, 16, 64), a1 += __shfl_xor(a1, 16, 64), a2 += __shfl_xor(a2, 16, 64), a3 += __shfl_xor(a3, 16, 64);
-    a0 += __shfl_xor(a0, 32, 64), a1 += __shfl_xor(a1, 32, 64), a2 += __shfl_xor(a2, 32, 64), a3 += __shfl_xor(a3, 32, 64);
+    a0 = lanes_reduce<16, 32>(a0, op_add{}), a1 = lanes_reduce<16, 32>(a1, op_add{});        // the wave's four rows
+    a2 = lanes_reduce<16, 32>(a2, op_add{}), a3 = lanes_reduce<16, 32>(a3, op_add{});
     if (sub) return;
     const double back = gmax * (1.0 / 4294967296.0) / ((double)A * CV_C);
     float4 o;

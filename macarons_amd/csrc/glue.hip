@@ -109,10 +109,7 @@ __global__ __launch_bounds__(SMP_BLOCK) void smp_block_sums(const float* __restr
     double cs[SMP_CHUNKS];
 #pragma unroll
     for (int c = 0; c < SMP_CHUNKS; ++c) {
-        double v = pv[c] > min_occ ? (double)pv[c] : 0.0;
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-        cs[c] = v;
+        cs[c] = wave_sum_all(pv[c] > min_occ ? (double)pv[c] : 0.0);
     }
     if ((threadIdx.x & 63) == 0) {
 #pragma unroll
@@ -121,7 +118,7 @@ __global__ __launch_bounds__(SMP_BLOCK) void smp_block_sums(const float* __restr
     __syncthreads();
     if (threadIdx.x < SMP_CHUNKS) {
         const int k = blockIdx.x * SMP_CHUNKS + threadIdx.x;
-        if (k < n_blocks) block_sums[k] = (s[threadIdx.x * 4] + s[threadIdx.x * 4 + 1]) + (s[threadIdx.x * 4 + 2] + s[threadIdx.x * 4 + 3]);
+        if (k < n_blocks) block_sums[k] = four_wave_sum(s + threadIdx.x * 4);
         __threadfence();                                              // the sums are visible before the ticket
     }
     __syncthreads();
@@ -133,6 +130,7 @@ __global__ __launch_bounds__(SMP_BLOCK) void smp_block_sums(const float* __restr
     if (!last) return;
     __threadfence();
     // exclusive scan of the block sums in place (sequential chunks of 256: n_blocks is a few hundred)
+    // (not wave.h's block scan: these are doubles, and this scan's association is part of the sampler's bits)
     for (int base = 0; base < n_blocks; base += SMP_BLOCK) {
         const int k = base + threadIdx.x;
         const double x = k < n_blocks ? __builtin_nontemporal_load(block_sums + k) : 0.0;
@@ -185,12 +183,7 @@ __global__ __launch_bounds__(256) void smp_search(const float* __restrict__ pred
             run += kept[e] ? (double)p : 0.0;
             v[e] = run;                            // inclusive sums inside the lane's quad
         }
-        double incl = run;                         // inclusive scan of the lane totals across the wave
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const double t = __shfl_up(incl, o, 64);
-            if (lane >= o) incl += t;
-        }
+        const double incl = wave_inclusive_scan(run);      // of the lane totals across the wave
         const double base = block_off[blk] + (incl - run);
         int first = 4;                             // first kept element of the quad that reaches the target
         int lastk = -1;
@@ -494,21 +487,17 @@ __global__ __launch_bounds__(256) void proj_bounds_kernel(const float* __restric
                                                           float* __restrict__ bounds) {
     __shared__ float s[4][4];
     const float* Mp = proj + blockIdx.x * 16;
-    float mnx = __builtin_inff(), mxx = -__builtin_inff(), mny = __builtin_inff(), mxy = -__builtin_inff();
+    float mn[2] = {__builtin_inff(), __builtin_inff()}, mx[2] = {-__builtin_inff(), -__builtin_inff()};      // x, y
     for (long long i = threadIdx.x; i < M; i += 256) {
         float nx, ny;
         project_xy(Mp, pc[3 * i], pc[3 * i + 1], pc[3 * i + 2], nx, ny);
-        mnx = fminf(mnx, nx); mxx = fmaxf(mxx, nx);
-        mny = fminf(mny, ny); mxy = fmaxf(mxy, ny);
+        mn[0] = fminf(mn[0], nx); mx[0] = fmaxf(mx[0], nx);
+        mn[1] = fminf(mn[1], ny); mx[1] = fmaxf(mx[1], ny);
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        mnx = fminf(mnx, __shfl_xor(mnx, o, 64)); mxx = fmaxf(mxx, __shfl_xor(mxx, o, 64));
-        mny = fminf(mny, __shfl_xor(mny, o, 64)); mxy = fmaxf(mxy, __shfl_xor(mxy, o, 64));
-    }
+    wave_minmax<2>(mn, mx);
     if ((threadIdx.x & 63) == 0) {
         float* r = s[threadIdx.x >> 6];
-        r[0] = mnx; r[1] = mxx; r[2] = mny; r[3] = mxy;
+        r[0] = mn[0]; r[1] = mx[0]; r[2] = mn[1]; r[3] = mx[1];
     }
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -563,14 +552,13 @@ __global__ __launch_bounds__(256) void multi_gain_kernel(const float* __restrict
         for (int k = 1; k < n_cam; ++k) m = fmaxf(m, v[(size_t)c[k] * N + n]);
         acc += (double)m;
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
+    acc = wave_sum_all(acc);
     if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = acc;
     __syncthreads();
     if (threadIdx.x == 0) {
         long long tuples = 1;
         for (int k = 0; k < n_cam; ++k) tuples *= C;
-        out[(size_t)b * tuples + tup] = (float)(((s[0] + s[1]) + (s[2] + s[3])) / (double)N);
+        out[(size_t)b * tuples + tup] = (float)(four_wave_sum(s) / (double)N);
     }
 }
 
@@ -630,11 +618,10 @@ __global__ __launch_bounds__(256) void macarons_gain_kernel(float* __restrict__ 
         vis[(size_t)b * N + n] = v;
         acc += (double)v;
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
+    acc = wave_sum_all(acc);
     if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = acc;
     __syncthreads();
-    if (threadIdx.x == 0) gains[b] = (float)(((s[0] + s[1]) + (s[2] + s[3])) / (double)N) * volume[b];
+    if (threadIdx.x == 0) gains[b] = (float)(four_wave_sum(s) / (double)N) * volume[b];
 }
 
 // K12: depth map -> world points (Camera.project_depth_in_3D macarons_utils.py:2339-2360 / utils.project_depth_back_to_3D
@@ -670,14 +657,7 @@ using namespace mcr;
 
 // ---- arg-max exchange records (multi-GPU camera sharding, testers/shapenet.py:172 = torch.max over cameras) ------------
 // record[b] = (max_c gains[b,c], idx_offset + first arg-max) as two fp32 (camera indices < 2^24 are exact): one 8-byte record
-// per cloud is what the ranks all-gather.  One wave per cloud; ties -> lowest index like torch.max.
-// torch.max ordering: NaN beats every number (the first NaN wins), otherwise the larger value, ties to the lower index.
-__device__ __forceinline__ bool best_before(float v, float i, float bv, float bi) {
-    const bool vn = v != v, bn = bv != bv;
-    if (vn != bn) return vn;
-    if (!vn && v != bv) return v > bv;
-    return i < bi;
-}
+// per cloud is what the ranks all-gather.  One wave per cloud; torch.max's ordering is best_before / wave_best of wave.h.
 
 __global__ __launch_bounds__(64) void best_record_kernel(const float* __restrict__ gains, int C, long long idx_offset,
                                                          float* __restrict__ rec) {
@@ -690,11 +670,7 @@ __global__ __launch_bounds__(64) void best_record_kernel(const float* __restrict
         const float v = g[c];
         if (best_before(v, (float)c, bv, bi)) { bv = v; bi = (float)c; }
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float ov = __shfl_xor(bv, o, 64), oi = __shfl_xor(bi, o, 64);
-        if (best_before(ov, oi, bv, bi)) { bv = ov; bi = oi; }
-    }
+    wave_best(bv, bi);
     if (lane == 0) {
         rec[2 * b] = bv;
         rec[2 * b + 1] = (float)idx_offset + bi;               // camera indices < 2^24 are exact in fp32
@@ -721,11 +697,7 @@ __global__ __launch_bounds__(64) void nbv_decide_kernel(float* __restrict__ gain
             const float v = g[c];
             if (best_before(v, (float)c, bv, bi)) { bv = v; bi = (float)c; }
         }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const float ov = __shfl_xor(bv, o, 64), oi = __shfl_xor(bi, o, 64);
-            if (best_before(ov, oi, bv, bi)) { bv = ov; bi = oi; }
-        }
+        wave_best(bv, bi);
     }
     if (lane == 0) {
         max_gain[b] = bv;

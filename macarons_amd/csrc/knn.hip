@@ -136,9 +136,7 @@ __global__ __launch_bounds__(KNN_BLOCK) void knn_mfma_kernel(const float* __rest
     asm volatile("" : "+v"(zero));                 // keep it in registers (not rematerialised as 16 moves per tile)
     int* qi = s_q + threadIdx.x;
     auto flush = [&]() {                           // exact distances of the queued candidates (their tile is still in LDS), insertion
-        int maxc = cnt;
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) maxc = max(maxc, __shfl_xor(maxc, o, 64));
+        const int maxc = wave_max_all(cnt);
         for (int sidx = 0; sidx < maxc; ++sidx)
             if (sidx < cnt) {
                 const int idx = qi[sidx * KNN_BLOCK], li = idx - t0;
@@ -164,7 +162,7 @@ __global__ __launch_bounds__(KNN_BLOCK) void knn_mfma_kernel(const float* __rest
             if (i < nt) pm = fmaxf(pm, pn);
         }
 #pragma unroll
-        for (int o = 32; o > 0; o >>= 1) pm = fmaxf(pm, __shfl_xor(pm, o, 64));
+        for (int o = 32; o > 0; o >>= 1) pm = fmaxf(pm, __shfl_xor(pm, o, 64));     // (not wave_max_all: same steps, but the call reschedules this kernel)
         if (lane == 0) atomicMax(&s_pmax, __builtin_bit_cast(unsigned, pm));  // non-negative floats order like their bit patterns
         __syncthreads();
         {
@@ -357,7 +355,7 @@ __device__ __forceinline__ float kg_unord(int i) { return __builtin_bit_cast(flo
 template <int PER>
 __device__ __forceinline__ void kg_block_scan(int* v, int* s_wave /* [16] */) {      // v 16-byte aligned, PER % 4 == 0
     static_assert(PER % 4 == 0, "whole int4 per thread");
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     int4* v4 = reinterpret_cast<int4*>(v) + tid * (PER / 4);
     int loc[PER], sum = 0;
 #pragma unroll
@@ -365,14 +363,7 @@ __device__ __forceinline__ void kg_block_scan(int* v, int* s_wave /* [16] */) { 
         const int4 x = v4[e];
         loc[4 * e] = sum; sum += x.x; loc[4 * e + 1] = sum; sum += x.y; loc[4 * e + 2] = sum; sum += x.z; loc[4 * e + 3] = sum; sum += x.w;
     }
-    int inc = sum;                                 // inclusive wave scan of the thread sums
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) { const int t = __shfl_up(inc, o, 64); if (lane >= o) inc += t; }
-    if (lane == 63) s_wave[wave] = inc;
-    __syncthreads();
-    int base = 0;
-    for (int w = 0; w < wave; ++w) base += s_wave[w];
-    base += inc - sum;
+    const int base = block_exclusive_scan<KG_BUILD_BLOCK / 64>(sum, s_wave);       // of the thread sums
 #pragma unroll
     for (int e = 0; e < PER / 4; ++e) v4[e] = make_int4(base + loc[4 * e], base + loc[4 * e + 1], base + loc[4 * e + 2], base + loc[4 * e + 3]);
     __syncthreads();
@@ -403,12 +394,8 @@ __global__ __launch_bounds__(KG_BUILD_BLOCK) void kg_build_cloud_kernel(const Kg
         mx[0] = fmaxf(mx[0], x); mx[1] = fmaxf(mx[1], y); mx[2] = fmaxf(mx[2], z);
         pm = fmaxf(pm, (x * x + y * y) + z * z);
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-#pragma unroll
-        for (int a = 0; a < 3; ++a) { mn[a] = fminf(mn[a], __shfl_xor(mn[a], o, 64)); mx[a] = fmaxf(mx[a], __shfl_xor(mx[a], o, 64)); }
-        pm = fmaxf(pm, __shfl_xor(pm, o, 64));
-    }
+    wave_minmax<3>(mn, mx);
+    pm = wave_max_all(pm);
     if (lane == 0) {
 #pragma unroll
         for (int a = 0; a < 3; ++a) { s_red[a][wave] = mn[a]; s_red[3 + a][wave] = mx[a]; }
@@ -450,10 +437,7 @@ __global__ __launch_bounds__(KG_BUILD_BLOCK) void kg_build_cloud_kernel(const Kg
             const float4 p = cb[t * 32 + j];
             lo[0] = hi[0] = p.x; lo[1] = hi[1] = p.y; lo[2] = hi[2] = p.z;
         }
-#pragma unroll
-        for (int o = 16; o > 0; o >>= 1)
-#pragma unroll
-            for (int a = 0; a < 3; ++a) { lo[a] = fminf(lo[a], __shfl_xor(lo[a], o, 64)); hi[a] = fmaxf(hi[a], __shfl_xor(hi[a], o, 64)); }
+        wave_minmax<3, 32>(lo, hi);
         if (j == 0 && t < n_sub) {
             bb[2 * t] = make_float4(lo[0], lo[1], lo[2], 0.f);
             bb[2 * t + 1] = make_float4(hi[0], hi[1], hi[2], 0.f);
@@ -476,10 +460,7 @@ __global__ __launch_bounds__(256) void kg_qbbox_kernel(const float* __restrict__
     for (int i = blockIdx.x * 256 + threadIdx.x; i < Q; i += gridDim.x * 256)
 #pragma unroll
         for (int a = 0; a < 3; ++a) { const float v = xb[(size_t)i * 3 + a]; mn[a] = fminf(mn[a], v); mx[a] = fmaxf(mx[a], v); }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1)
-#pragma unroll
-        for (int a = 0; a < 3; ++a) { mn[a] = fminf(mn[a], __shfl_xor(mn[a], o, 64)); mx[a] = fmaxf(mx[a], __shfl_xor(mx[a], o, 64)); }
+    wave_minmax<3>(mn, mx);
     if ((threadIdx.x & 63) == 0)
 #pragma unroll
         for (int a = 0; a < 3; ++a) { s_red[a][threadIdx.x >> 6] = mn[a]; s_red[3 + a][threadIdx.x >> 6] = mx[a]; }
@@ -679,7 +660,7 @@ __global__ __launch_bounds__(MODE ? 64 * KG_SPLIT : 64, MODE ? 2 : 4) void knn_g
         {
             float lo[3] = {qx, qy, qz}, hi[3] = {qx, qy, qz};
 #pragma unroll
-            for (int o = 4; o > 0; o >>= 1)
+            for (int o = 4; o > 0; o >>= 1)                  // (not wave.h's wave_minmax<3, 8>: the same steps, but the call reschedules this kernel)
 #pragma unroll
                 for (int a = 0; a < 3; ++a) { lo[a] = fminf(lo[a], __shfl_xor(lo[a], o, 64)); hi[a] = fmaxf(hi[a], __shfl_xor(hi[a], o, 64)); }
 #pragma unroll
@@ -722,7 +703,7 @@ __global__ __launch_bounds__(MODE ? 64 * KG_SPLIT : 64, MODE ? 2 : 4) void knn_g
             }
         }
 #pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
+        for (int o = 32; o > 0; o >>= 1) {                               // (an arg-MIN, no NaN case: not wave.h's wave_best)
             const float ob = __shfl_xor(best, o, 64);
             const int ot = __shfl_xor(best_t, o, 64);
             if (ob < best || (ob == best && ot < best_t)) { best = ob; best_t = ot; }
@@ -753,9 +734,7 @@ __global__ __launch_bounds__(MODE ? 64 * KG_SPLIT : 64, MODE ? 2 : 4) void knn_g
     for (int r = 0; r < 16; ++r) zero[r] = 0.f;
     asm volatile("" : "+v"(zero));
     auto flush = [&]() {                           // exact distances of the queued candidates (ring positions), insertion, new thresholds
-        int maxc = cnt;
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) maxc = max(maxc, __shfl_xor(maxc, o, 64));
+        const int maxc = wave_max_all(cnt);
         KG_LOCAL(dbg_rounds += maxc; dbg_flushes += 1; dbg_mine += cnt);
         for (int sidx = 0; sidx < maxc; ++sidx)
             if (sidx < cnt) {
@@ -766,10 +745,8 @@ __global__ __launch_bounds__(MODE ? 64 * KG_SPLIT : 64, MODE ? 2 : 4) void knn_g
         tau = fminf(__builtin_bit_cast(float, khi[K - 1]), tau_parked);
         thr = (tau - q2) + eps;
         cnt = 0; staged = 0;
-        float tq = fminf(tau, __shfl_xor(tau, 32, 64));              // either half list bounds the query's 16th distance
-#pragma unroll
-        for (int o = 16; o > 0; o >>= 1) tq = fmaxf(tq, __shfl_xor(tq, o, 64));
-        R2 = tq;
+        const float tq = lanes_reduce<32, 32>(tau, op_min{});        // either half list bounds the query's 16th distance
+        R2 = lanes_reduce<16, 1>(tq, op_max{});
     };
     auto fetch = [&](int t) -> float4 { return cb[t * 32 + j]; };
     auto process = [&](const float4 p) {           // p = candidate j of the sub-tile (both lane halves hold it)
@@ -863,8 +840,7 @@ __global__ __launch_bounds__(MODE ? 64 * KG_SPLIT : 64, MODE ? 2 : 4) void knn_g
         flush();
         KG_T(3);
         KG_LOCAL(KG_COUNT(0, dbg_tiles); KG_COUNT(1, dbg_rounds); KG_COUNT(2, dbg_flushes);
-                 int mx_ = dbg_mine, sm_ = dbg_mine;
-                 for (int o_ = 32; o_ > 0; o_ >>= 1) { mx_ = max(mx_, __shfl_xor(mx_, o_, 64)); sm_ += __shfl_xor(sm_, o_, 64); }
+                 const int mx_ = wave_max_all(dbg_mine), sm_ = wave_sum_all(dbg_mine);
                  KG_COUNT(3, mx_); KG_COUNT(4, sm_ / 64));
         kg_output<K, OFFSETS, true>(khi, klo, s_mem, s_row, lane, b, Q, q, valid, qx, qy, qz, pcb, out_idx, out_dist, out_pts);
         KG_T(4);

@@ -227,7 +227,7 @@ __global__ __launch_bounds__(SMALL ? 256 : 512, SMALL ? 2 : 1) void linear3p_ker
                 }
                 sacc = fmaf(y[0], v4.x, sacc); sacc = fmaf(y[1], v4.y, sacc); sacc = fmaf(y[2], v4.z, sacc); sacc = fmaf(y[3], v4.w, sacc);
             }
-            part[t] = sacc + __shfl_xor(sacc, 32, 64);     // (a + b == b + a: both halves hold the same value)
+            part[t] = lanes_reduce<32, 32>(sacc, op_add{});     // (a + b == b + a: both halves hold the same value)
         }
         __syncthreads();                                   // every wave is done with the stages: the LDS is free
         float* red = reinterpret_cast<float*>(S);          // [8 waves][128 rows]

@@ -187,7 +187,7 @@ __device__ __forceinline__ void lp_center(const float* src, int lds_, float* xs,
         v[c] = q.x; v[c + 1] = q.y; v[c + 2] = q.z; v[c + 3] = q.w;
         sum += (q.x + q.y) + (q.z + q.w);
     }
-    sum += __shfl_xor(sum, 1, 64);
+    sum += __shfl_xor(sum, 1, 64);         // (not wave.h's lanes_reduce<1, 2>: the same steps, but the call reschedules this kernel)
     sum += __shfl_xor(sum, 2, 64);
     const float mu = sum * (1.0f / 128.f);
     float sq = 0.f;

@@ -73,11 +73,10 @@ __global__ __launch_bounds__(256) void macarons_gain_bwd_kernel(const float* __r
         if (u < 0 || u >= S) continue;                // (skipped above as well)
         acc += (double)(vis[row + u] * gain_distance_factor(world + (row + u) * pts_dim, cx, cy, cz, distance_th, mode));
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
+    acc = wave_sum_all(acc);
     if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = acc;
     __syncthreads();
-    if (threadIdx.x == 0) d_volume[b] = g[b] * (float)(((s[0] + s[1]) + (s[2] + s[3])) / (double)S);
+    if (threadIdx.x == 0) d_volume[b] = g[b] * (float)(four_wave_sum(s) / (double)S);
 }
 
 }  // namespace mcr

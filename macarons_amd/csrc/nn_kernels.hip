@@ -833,7 +833,7 @@ __global__ __launch_bounds__(256, att_occ(DQ, QG)) void attention_mfma_kernel(co
             for (int sub = 0; sub < 4; ++sub)
 #pragma unroll
                 for (int r = 0; r < 4; ++r) tmax = fmaxf(tmax, st[qg][sub][r]);
-            tmax = fmaxf(tmax, __shfl_xor(tmax, 16, 64));
+            tmax = fmaxf(tmax, __shfl_xor(tmax, 16, 64));           // (not wave.h's lanes_reduce<16, 32>: the same steps, but the call reschedules this kernel)
             tmax = fmaxf(tmax, __shfl_xor(tmax, 32, 64));
             const float m_new = fmaxf(m[qg], tmax);
             const float alpha = __builtin_amdgcn_exp2f(m[qg] - m_new);   // m = -inf on the first tile -> 0 (o = l = 0 anyway)
@@ -918,7 +918,7 @@ __global__ __launch_bounds__(256, att_occ(DQ, QG)) void attention_mfma_kernel(co
 #pragma unroll
     for (int qg = 0; qg < QG; ++qg) {
         float lq = l[qg];
-        lq += __shfl_xor(lq, 16, 64);
+        lq += __shfl_xor(lq, 16, 64);                               // (as for tmax above: hand-written)
         lq += __shfl_xor(lq, 32, 64);
         const int qbase = q0 + 16 * qg;
         if (SPLIT) {
@@ -1181,6 +1181,7 @@ __global__ __launch_bounds__(16 * POOL_LONG_RL) void pool_long_kernel(const floa
         }
     }
     // the 4 row lanes of a wave (lanes cl, cl+16, cl+32, cl+48), then the 16 waves in order
+    // (not wave.h's lanes_reduce<16, 32>: the same steps, but the call reschedules this kernel)
     mx = fmaxf(mx, __shfl_xor(mx, 16));
     sm += __shfl_xor(sm, 16);
     mx = fmaxf(mx, __shfl_xor(mx, 32));

@@ -155,9 +155,7 @@ __global__ __launch_bounds__(1024) void key_histogram_kernel(const int* __restri
             const int first = __builtin_ctzll(has);
             const int kf = __shfl(cur, first, 64);
             if (__all(n == 0 || cur == kf)) {
-                unsigned tot = n;
-#pragma unroll
-                for (int o = 32; o > 0; o >>= 1) tot += __shfl_xor(tot, o, 64);
+                const unsigned tot = wave_sum_all(n);
                 if ((tid & 63) == first) atomicAdd(&s_cnt[kf], tot);
             } else if (n) {
                 atomicAdd(&s_cnt[cur], n);
@@ -169,19 +167,9 @@ __global__ __launch_bounds__(1024) void key_histogram_kernel(const int* __restri
         if (k >= 0 && k <= nk) atomicAdd(&s_cnt[k], 1u);
     }
     __syncthreads();
-    // exclusive scan over k = 0 .. 1023 (entries above nk are zero): lane prefix inside a wave, then the 16 wave totals
+    // exclusive scan over k = 0 .. 1023 (entries above nk are zero)
     const unsigned c = s_cnt[tid];
-    unsigned incl = c;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const unsigned up = __shfl_up(incl, o, 64);
-        if ((tid & 63) >= o) incl += up;
-    }
-    if ((tid & 63) == 63) s_wave[tid >> 6] = incl;
-    __syncthreads();
-    unsigned base = 0;
-    for (int w = 0; w < (tid >> 6); ++w) base += s_wave[w];
-    const unsigned excl = base + incl - c;
+    const unsigned excl = block_exclusive_scan<16>(c, s_wave);
     if (tid <= nk) { counts[tid] = c; offsets[tid] = excl; }
     if (tid == nk) offsets[nk + 1] = excl + c;
 }
@@ -245,17 +233,7 @@ __global__ __launch_bounds__(GRP_MAXK) void grp_scan_kernel(unsigned* __restrict
             run += c;
         }
     }
-    unsigned incl = run;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const unsigned up = __shfl_up(incl, o, 64);
-        if ((k & 63) >= o) incl += up;
-    }
-    if ((k & 63) == 63) s_wave[k >> 6] = incl;
-    __syncthreads();
-    unsigned base = 0;
-    for (int w = 0; w < (k >> 6); ++w) base += s_wave[w];
-    const unsigned excl = base + incl - run;
+    const unsigned excl = block_exclusive_scan<GRP_MAXK / 64>(run, s_wave);
     if (k <= nk) { counts[k] = run; offsets[k] = excl; }
     if (k == nk) offsets[nk + 1] = excl + run;
 }
@@ -558,14 +536,10 @@ __global__ __launch_bounds__(256) void camera_box_kernel(const float* __restrict
 #pragma unroll
         for (int a = 0; a < 3; ++a) { hi[a] = fmaxf(hi[a], p[a]); lo[a] = fminf(lo[a], p[a]); }
     }
+    wave_minmax<3>(lo, hi);
+    if ((threadIdx.x & 63) == 0) {
 #pragma unroll
-    for (int a = 0; a < 3; ++a) {
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            hi[a] = fmaxf(hi[a], __shfl_xor(hi[a], o, 64));
-            lo[a] = fminf(lo[a], __shfl_xor(lo[a], o, 64));
-        }
-        if ((threadIdx.x & 63) == 0) { s_hi[threadIdx.x >> 6][a] = hi[a]; s_lo[threadIdx.x >> 6][a] = lo[a]; }
+        for (int a = 0; a < 3; ++a) { s_hi[threadIdx.x >> 6][a] = hi[a]; s_lo[threadIdx.x >> 6][a] = lo[a]; }
     }
     __syncthreads();
     if (threadIdx.x != 0) return;
@@ -611,11 +585,10 @@ __global__ __launch_bounds__(256) void macarons_gain_inv_kernel(const float* __r
         }
         acc += (double)(vis_u[(size_t)b * S + u] * f);
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
+    acc = wave_sum_all(acc);
     if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = acc;
     __syncthreads();
-    if (threadIdx.x == 0) gains[b] = nu[b] > 0 ? (float)(((s[0] + s[1]) + (s[2] + s[3])) / (double)S) * volume[b] : 0.f;
+    if (threadIdx.x == 0) gains[b] = nu[b] > 0 ? (float)(four_wave_sum(s) / (double)S) * volume[b] : 0.f;
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -678,28 +651,6 @@ __global__ void sup_mark_kernel(const unsigned char* __restrict__ mask, const fl
     }
 }
 
-// exclusive scan of one int per thread over a block of SUP_THREADS (4 waves): shuffles inside a wave, 4 partial sums through LDS
-__device__ __forceinline__ int sup_block_exclusive(int v, int* __restrict__ s_wave, int& total) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    int inc = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int n = __shfl_up(inc, o, 64);
-        if (lane >= o) inc += n;
-    }
-    __syncthreads();                                       // (s_wave may still be read from the previous round)
-    if (lane == 63) s_wave[w] = inc;
-    __syncthreads();
-    int base = 0;
-    total = 0;
-#pragma unroll
-    for (int k = 0; k < SUP_THREADS / 64; ++k) {
-        if (k < w) base += s_wave[k];
-        total += s_wave[k];
-    }
-    return base + inc - v;
-}
-
 // pos[p] = rank of p among the set entries of mask, -1 elsewhere; n_pred = their number.  ONE block: a thread counts a contiguous
 // piece, the pieces are scanned, the thread walks its piece again (P is a few 10^5 bytes).
 __global__ __launch_bounds__(SUP_THREADS) void sup_pos_kernel(const unsigned char* __restrict__ mask, long long P, int* __restrict__ pos,
@@ -710,7 +661,7 @@ __global__ __launch_bounds__(SUP_THREADS) void sup_pos_kernel(const unsigned cha
     int n = 0;
     for (long long p = p0; p < p1; ++p) n += mask[p] ? 1 : 0;
     int total;
-    int r = sup_block_exclusive(n, s_wave, total);
+    int r = block_exclusive_scan<SUP_THREADS / 64>(n, s_wave, &total);
     for (long long p = p0; p < p1; ++p) pos[p] = mask[p] ? r++ : -1;
     if (threadIdx.x == 0) *n_pred = total;
 }
@@ -726,8 +677,7 @@ __global__ __launch_bounds__(SUP_THREADS) void sup_count_kernel(const unsigned* 
     }
     int n = 0;
     for (long long w = threadIdx.x; w < W; w += SUP_THREADS) n += __popc(bitmap[(long long)c * W + w]);
-    int total;
-    sup_block_exclusive(n, s_wave, total);
+    const int total = block_sum_256(n, s_wave);
     if (threadIdx.x == 0) sel_counts[c] = total;
 }
 
@@ -740,8 +690,7 @@ __global__ __launch_bounds__(SUP_THREADS) void sup_compact_kernel(const unsigned
     const int c = blockIdx.x;
     int n = 0;
     for (int k = threadIdx.x; k < c && k < nk; k += SUP_THREADS) n += (int)sel_counts[k];
-    int first;
-    sup_block_exclusive(n, s_wave, first);
+    const int first = block_sum_256(n, s_wave);
     if (c >= nk) {
         if (threadIdx.x == 0) sel_off[nk] = sel_off[nk + 1] = first;
         return;
@@ -752,7 +701,7 @@ __global__ __launch_bounds__(SUP_THREADS) void sup_compact_kernel(const unsigned
         const long long w = w0 + threadIdx.x;
         unsigned bits = w < W ? bitmap[(long long)c * W + w] : 0u;
         int total;
-        long long o = run + sup_block_exclusive(__popc(bits), s_wave, total);
+        long long o = run + block_exclusive_scan<SUP_THREADS / 64, true>((int)__popc(bits), s_wave, &total);   // (true: s_wave is still being read, in round 0 by the sum above, later by the round before)
         while (bits) {
             const int b = __ffs(bits) - 1;
             bits &= bits - 1;

@@ -144,39 +144,30 @@ __global__ __launch_bounds__(256) void sh_reduce_kernel(const float* __restrict_
     const float* p = partial + ((size_t)b * C + c) * n_wtiles;
     double acc = 0.0;
     for (int t = threadIdx.x; t < n_wtiles; t += 256) acc += (double)p[t];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
+    acc = wave_sum_all(acc);
     if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = acc;
     __syncthreads();
-    if (threadIdx.x == 0) gains[(size_t)b * C + c] = (float)((s_w[0] + s_w[1]) + (s_w[2] + s_w[3])) * inv_n;
+    if (threadIdx.x == 0) gains[(size_t)b * C + c] = (float)four_wave_sum(s_w) * inv_n;
 }
 
 // The decision behind the gains (testers/shapenet.py:172: torch.max over the cameras): record[b] = (max_c gains[b][c], first arg-max as
-// fp32) with torch.max's ordering -- NaN beats every number (the first NaN wins), ties go to the lower index.  One block per cloud.
+// fp32) with torch.max's ordering (best_before / wave_best of wave.h, shared with the decision glue).  One block per cloud.
 __global__ __launch_bounds__(256) void sh_best_kernel(const float* __restrict__ gains, int C, float* __restrict__ record) {
     __shared__ float s_v[4], s_i[4];
     const int b = blockIdx.x, lane = threadIdx.x & 63;
     float bv = -__builtin_inff(), bi = 3.0e38f;
     bool first = true;
-    auto before = [](float v, float i, float ov, float oi) {          // (v, i) precedes (ov, oi)
-        const bool vn = v != v, on = ov != ov;
-        return vn != on ? vn : (!vn && v != ov ? v > ov : i < oi);
-    };
     for (int c = threadIdx.x; c < C; c += 256) {
         const float g = gains[(size_t)b * C + c];
-        if (first || before(g, (float)c, bv, bi)) { bv = g; bi = (float)c; }
+        if (first || best_before(g, (float)c, bv, bi)) { bv = g; bi = (float)c; }
         first = false;
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float ov = __shfl_xor(bv, o, 64), oi = __shfl_xor(bi, o, 64);
-        if (before(ov, oi, bv, bi)) { bv = ov; bi = oi; }
-    }
+    wave_best(bv, bi);
     if (lane == 0) { s_v[threadIdx.x >> 6] = bv; s_i[threadIdx.x >> 6] = bi; }
     __syncthreads();
     if (threadIdx.x == 0) {
         for (int w = 1; w < 4; ++w)
-            if (before(s_v[w], s_i[w], bv, bi)) { bv = s_v[w]; bi = s_i[w]; }
+            if (best_before(s_v[w], s_i[w], bv, bi)) { bv = s_v[w]; bi = s_i[w]; }
         record[2 * b] = bv;
         record[2 * b + 1] = bi;
     }

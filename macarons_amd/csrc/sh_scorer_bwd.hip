@@ -201,14 +201,13 @@ __global__ __launch_bounds__(256) void sh_bwd_cams_reduce_kernel(const float* __
         const float* p = part + (((size_t)b * C + c) * 3 + j) * n_wtiles;
         double acc = 0.0;
         for (int t = threadIdx.x; t < n_wtiles; t += 256) acc += (double)p[t];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
+        acc = wave_sum_all(acc);
         if ((threadIdx.x & 63) == 0) s_w[j][threadIdx.x >> 6] = acc;
     }
     __syncthreads();
     if (threadIdx.x < 3) {
         const int j = threadIdx.x;
-        d_cams[((size_t)b * C + c) * 3 + j] = (float)((s_w[j][0] + s_w[j][1]) + (s_w[j][2] + s_w[j][3]));
+        d_cams[((size_t)b * C + c) * 3 + j] = (float)four_wave_sum(s_w[j]);
     }
 }
 

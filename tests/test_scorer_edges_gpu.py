@@ -153,6 +153,46 @@ def test_exact_operands_under_every_override(dev, wps):
     assert np.array_equal(gains.cpu().numpy(), gains_w) and np.array_equal(record.cpu().numpy(), record_w)
 
 
+@pytest.mark.parametrize("C", [1, 65, 257])             # 257: the stride loop of the record's kernel and its four-wave merge
+@pytest.mark.parametrize("row", ["random", "zeros", "nan", "nan_cameras"])
+def test_record_is_best_record_of_the_gains(dev, row, C):
+    """The scorer's record and ops.best_record decide by one rule (best_before / wave_best of csrc/wave.h): the record of
+    sh_coverage_gain_best equals best_record of sh_coverage_gain's gains on the same inputs, bit for bit, and both say what torch.max
+    says on the CPU.  zeros: the second cloud's harmonics are all zero, every camera ties and index 0 wins.  nan: the second cloud's
+    harmonics hold a NaN; the first NaN camera wins.  nan_cameras: cameras C // 2 and C - 1 of the second cloud are NaN, so only their
+    gains are: a NaN beats every number, and of the two the lower index wins (at C = 257 they sit in different waves and strides)."""
+    from macarons_amd import ops
+    B, N = 2, 64
+    rng = np.random.default_rng(1000 + C)
+    pts = rng.uniform(-.5, .5, (B, N, 3)).astype(np.float32)
+    harm = (rng.standard_normal((B, N, 64)) * .5).astype(np.float32)
+    cams = rng.standard_normal((B, C, 3))
+    cams = (1.5 * cams / np.linalg.norm(cams, axis=-1, keepdims=True)).astype(np.float32)
+    if row == "zeros":
+        harm[1] = 0
+    if row == "nan":
+        harm[1, 17, 5] = np.nan
+    if row == "nan_cameras":
+        cams[1, [C // 2, C - 1]] = np.nan
+    p, h, c = T(pts, dev), T(harm, dev), T(cams, dev)
+    gains_b, record = ops.sh_coverage_gain_best(p, h, c)
+    gains = ops.sh_coverage_gain(p, h, c)
+    want = ops.best_record(gains)
+    bits = lambda t: t.cpu().numpy().view(np.uint32)
+    assert np.array_equal(bits(gains_b), bits(gains))
+    assert np.array_equal(bits(record), bits(want)), (record, want)
+    gains, record = gains.cpu(), record.cpu()
+    top = torch.max(gains, dim=1)
+    assert np.array_equal(record[:, 0].numpy(), top.values.numpy(), equal_nan=True) and torch.equal(record[:, 1].long(), top.indices)
+    if row == "zeros":
+        assert bool((gains[1] == gains[1, 0]).all()) and record[1, 1] == 0
+    if row == "nan_cameras":
+        assert torch.isnan(gains[1]).nonzero().flatten().tolist() == sorted({C // 2, C - 1})
+    if row in ("nan", "nan_cameras"):
+        first = int(torch.isnan(gains[1]).nonzero()[0])
+        assert bool(torch.isnan(record[1, 0])) and record[1, 1] == first and not bool(torch.isnan(gains[0]).any())
+
+
 def test_exact_operands_relu_and_stride_4(dev):
     """The same split with relu and a point stride of 4: z itself is not exact, its sign is; a zero row gives exactly 0."""
     from macarons_amd import ops

@@ -76,6 +76,72 @@ def main(out_path):
             x, w, b = normal(M, K, scale=1.), normal(512, K, scale=K ** -.5), normal(512, scale=1.)
             keep(f"linear.{M}x{K}", ops.linear(x, w, b, gelu=True))
 
+    # ---- the kernels that reduce, scan or decide through csrc/wave.h: scorer record and backward, decision glue, scene store,
+    # supervision selection, the grid search's build, the plane sweep's backward -- one seeded call each at the smallest size that
+    # reaches every kernel of the entry (more than one wave, a ragged tail, NaN and tied gains for the arg-max)
+    rs = np.random.default_rng(600)
+    f32 = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev)
+    for C in (65, 257):                                     # 257: the stride loop and the four-wave merge of the scorer's record
+        p, h = f32(rs.uniform(-.5, .5, (3, 200, 4))), f32(rs.standard_normal((3, 200, 64)) * .5)
+        h[1] = 0.                                           # every camera ties
+        h[2, 5, 3] = float("nan")                           # NaN gains
+        c = rs.standard_normal((3, C, 3))
+        c = f32(1.5 * c / np.linalg.norm(c, axis=-1, keepdims=True))
+        gains, rec = ops.sh_coverage_gain_best(p, h, c)
+        keep(f"wave.scorer.{C}.gains", gains); keep(f"wave.scorer.{C}.record", rec)
+        keep(f"wave.best_record.{C}", ops.best_record(gains, 3))
+        for n, t in zip(("max", "idx", "record"), ops.nbv_decide(gains.clone(), torch.tensor([4, 0, 2], dtype=torch.int32, device=dev))):
+            keep(f"wave.nbv_decide.{C}.{n}", t)
+        for n, t in zip(("d_harm", "d_pts", "d_cams"), ops.sh_scorer_backward(p[:1], h[:1], c[:1], f32(rs.standard_normal((1, C))), False, True)):
+            keep(f"wave.scorer_bwd.{C}.{n}", t)
+    keep("wave.multi_gain", ops.coverage_gain_multiple(p[:1], h[:1], c[:1, :5].contiguous(), 2)[0])
+    K, S = 3, 700
+    vis_u, world = f32(rs.uniform(0, 1, (K, S))), f32(rs.uniform(-2, 2, (K, S, 4)))
+    nu = torch.tensor([S, 0, 300], dtype=torch.int32, device=dev)
+    inv = torch.from_numpy(np.stack([rs.integers(0, max(int(n), 1), S) for n in nu.tolist()])).to(dev)
+    cam, vol = f32(rs.uniform(-3, 3, (K, 3))), f32(rs.uniform(.5, 2, K))
+    Mv = np.tile(np.eye(4), (K, 1, 1)) + rs.standard_normal((K, 4, 4)) * .05
+    for smooth in (False, True):
+        keep(f"wave.macarons_gain.{smooth}", ops.macarons_gain_(vis_u.clone(), world, cam, vol, 1.5, smooth))
+        keep(f"wave.macarons_gain_indexed.{smooth}", ops.macarons_gain_indexed(vis_u, world, inv, nu, cam, vol, 1.5, smooth))
+        d_vis, d_vol = ops.macarons_gain_backward(f32(rs.standard_normal(K)), vis_u, world, inv, nu, cam, vol, 1.5, smooth, need_volume=True)
+        keep(f"wave.macarons_gain_bwd.{smooth}.d_vis", d_vis); keep(f"wave.macarons_gain_bwd.{smooth}.d_volume", d_vol)
+    for n, t in zip(("center", "cam_view"), ops.camera_boxes(world, nu, f32(Mv), cam, 0.25)):
+        keep(f"wave.camera_boxes.{n}", t)
+    P = 3001
+    X, pr = f32(rs.uniform(-.5, .5, (P, 3))), f32(rs.uniform(0, 1, (P, 1)))
+    for n, t in zip(("res", "res_h", "inverse", "uniq", "n_unique", "volume"),
+                    ops.sample_proxy(X, pr, f32(rs.standard_normal((P, 64))), f32(rs.uniform(0, 1, 500)), 0.25, return_volume=True, padded=True)):
+        keep(f"wave.sample_proxy.{n}", t)
+    for n, t in zip(("mask", "bounds"), ops.filter_proxy_mask(X, f32(rs.uniform(-.4, .4, (777, 3))), f32(Mv[:2]), 0.05)):
+        keep(f"wave.filter_proxy.{n}", t)
+    nk = 71
+    key = np.repeat(rs.integers(-1, nk + 2, 400), rs.integers(1, 60, 400)).astype(np.int32)      # runs, some values out of range
+    key = torch.from_numpy(key).to(dev)
+    for n, t in zip(("counts", "offsets"), ops.key_histogram(key, nk)):
+        keep(f"wave.key_histogram.{n}", t)
+    for n, t in zip(("order", "counts", "offsets"), ops.group_by_key(key, nk)):
+        keep(f"wave.group_by_key.{n}", t)
+    grid, lo, hi = (2, 1, 2), np.array([-4., -2., -4.]), np.array([4., 2., 4.])
+    pp = rs.uniform(-1, 1, (P, 3)) * [3.9, 1.9, 3.9]
+    cells = [rs.permutation(P)[:n] for n in (900, 0, 1700, 40)]          # the proxy indices stored in each cell (one cell is empty)
+    fts = np.stack((np.concatenate(cells), rs.standard_normal(sum(map(len, cells)))), 1)
+    off = np.concatenate(([0], np.cumsum([len(c_) for c_ in cells]))).astype(np.int64)
+    sel = ops.supervision_select(torch.from_numpy(rs.random(P) < .4).to(dev), f32(pp), f32(np.concatenate((lo, hi, (hi - lo) / grid))), grid,
+                                 f32(fts), int(off[-1]), torch.from_numpy(off).to(dev))
+    keep("wave.supervision.counts", sel.counts); keep("wave.supervision.rows_order", sel.rows_order); keep("wave.supervision.pos", sel.pos)
+    pts, dists, idx = ops.knn_points(cube(1, 1000, 3), cube(1, 2048, 3), 16, subtract_query=True)       # M = 2048: the grid search
+    keep("wave.knn_grid.pts", pts); keep("wave.knn_grid.dists", dists); keep("wave.knn_grid.idx", idx)
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import _cost_volume_cases as cvc
+    from macarons_amd.networks import ManyDepth
+    cv = cvc.inputs(*cvc.SHAPES["scan"])
+    cams = ManyDepth.pack_cameras(cv["R"], cv["T"], cv["R_alpha"], cv["T_alpha"]).to(dev)
+    d_out = torch.randn((cv["x"].shape[0], cv["D"]) + tuple(cv["x"].shape[-2:]), generator=torch.Generator().manual_seed(601)).to(dev)
+    for n, t in zip(("d_x", "d_x_alpha"), ops.cost_volume_backward(cv["x"].to(dev), cv["x_alpha"].to(dev), cams, cv["depth_bins"].to(dev), d_out,
+                                                                   cv["H"], cv["W"])):
+        keep(f"wave.cost_volume_bwd.{n}", t)
+
     for v in (1, 5, 6, 7):
         with ops.variant(v), torch.no_grad():
             # ---- SconeVis / PCTransformer: 1 x 2048 and 8 x 2048 tokens (8 sequences cross the 512-block threshold of the 128-query
