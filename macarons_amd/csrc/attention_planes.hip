@@ -44,13 +44,16 @@ __device__ __forceinline__ ap_u32x2 ap_read_tr(unsigned addr) {       // 4 keys 
 // max over the four lanes (li, g = 0..3) that share a query: v_permlane32_swap / v_permlane16_swap exchange halves / neighbouring 16-lane
 // rows between two registers in one instruction each -- no LDS round trip (two dependent ds_bpermute were ~250 cycles of every tile's
 // critical path)
+// (the swaps' results are copied out as (unsigned) rvalues first, as in lp_tile.h: __builtin_bit_cast(float, a[1]) applied to the vector
+// element itself reads element 0 under hipcc, the two fmaxf then fold away and every lane keeps lane group 0's maximum instead of the
+// query's -- still a soft-max while the true maximum is within 16 units of log 2, beyond that the weights leave the fp16 range: NaN)
 __device__ __forceinline__ float ap_max_lane_groups(float x) {
     const unsigned u = __builtin_bit_cast(unsigned, x);
     const auto a = __builtin_amdgcn_permlane32_swap(u, u, false, false);          // -> [lo, lo], [hi, hi]
-    x = fmaxf(__builtin_bit_cast(float, a[0]), __builtin_bit_cast(float, a[1]));
+    x = fmaxf(__builtin_bit_cast(float, (unsigned)a[0]), __builtin_bit_cast(float, (unsigned)a[1]));
     const unsigned v = __builtin_bit_cast(unsigned, x);
     const auto b = __builtin_amdgcn_permlane16_swap(v, v, false, false);          // -> rows [0, 0, 2, 2], [1, 1, 3, 3]
-    return fmaxf(__builtin_bit_cast(float, b[0]), __builtin_bit_cast(float, b[1]));
+    return fmaxf(__builtin_bit_cast(float, (unsigned)b[0]), __builtin_bit_cast(float, (unsigned)b[1]));
 }
 
 #ifndef MCR_AP_OCC_16
