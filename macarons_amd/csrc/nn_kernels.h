@@ -39,7 +39,8 @@ struct Epilogue { const float* bias; int act; Rows residual; RowBias row_bias; }
 // fp32 tiling accumulates k in the same order.
 void launch_linear(hipStream_t s, Rows X, Rows W, const Epilogue& e, RowsOut Y, int64_t M, int N, int K, int64_t route_rows);
 
-// Split-precision (exact bf16 hi/mid/lo, six MFMAs per product) variant for the large GEMMs (linear3.hip); launch_linear
+// Split-precision variant for the large GEMMs (linear3.hip): the operands' split into bf16 hi/mid/lo is exact, the product keeps six
+// of the nine plane products -- the three dropped ones stay below 2^-21 sum_k |x||w| (derivation in linear3.hip) -- ; launch_linear
 // routes to it when linear3_applicable().
 bool linear3_shape_ok(const float* X, int64_t ldx, const float* W, int64_t ldw, int N, int K);
 bool linear3_applicable(const float* X, int64_t ldx, const float* W, int64_t ldw, int64_t M, int N, int K);
