@@ -153,6 +153,35 @@ int mcr_attention_planes(const float* qkv, int64_t ldq, float* out, int64_t ldo,
 int mcr_colmax_broadcast(const float* X, int64_t ldx, float* Y, int64_t ldy, int64_t S, int64_t L, int E, void* stream);
 int mcr_pool_max_avg(const float* X, int64_t ldx, float* Y, int64_t ldy, int64_t S, int64_t L, int E, void* stream);
 
+/* ---- the padded-sequence forward as blocks: BRING-UP / TEST entries ------------------------------------------------------------------
+ * The forms of the blocks above that the networks run on padded batches (the NBV step without a host sync, the ragged occupancy
+ * pass): lens is a DEVICE int[S], sequence s takes part with its first n = min(L, max(1, lens[s])) rows; lens may be NULL (n = L).
+ * The networks call the same launchers directly; these entries add no kernel.
+ * mcr_attention_lens: mcr_attention with keys = the first n rows of the sequence (every one of the L query rows still gets an
+ *   output; rows >= n are finite and otherwise unspecified).  split_mode as mcr_attention_planes (1: keys over two blocks whenever
+ *   L >= 512; 0: never; -1: only when the unsplit grid leaves CUs idle); workspace: mcr_attention_workspace_bytes, 16-byte aligned;
+ *   it may be NULL for split_mode 0 and -1 (never split then), a split_mode of 1 at L >= 512 without it, or any workspace too small
+ *   for a split that the mode allows, is refused.  mcr_call_variant(1) selects the fp32 P V form.  lens exists on the matrix-pipe
+ *   kernel alone: qkv 16-byte aligned and ldq % 4 == 0, refused otherwise (3); without lens as mcr_attention_ws.  S <= 32767
+ *   (without lens: any S at L = 16).
+ * mcr_pool_max_avg_lens: mcr_pool_max_avg over the first n rows: the max, and the mean as sum / n.
+ * mcr_colmax_broadcast_lens: mcr_colmax_broadcast with the max over the first n rows, written to ALL L rows of the sequence.  ex
+ *   (optional): columns 0 .. ex_cols - 1 of a second array [S * L, ex_ld] are copied to ex_dst [S * L, ldy] -- the leading dimension
+ *   of Y -- on the way (all L rows); needs ex_dst, 0 < ex_cols <= ex_ld, ex_cols <= ldy, ex_ld < 2^31.  Without ex: ex_cols = 0,
+ *   ex_dst NULL.
+ * mcr_layernorm_planes: mcr_layernorm (eps 1e-5) with the result written as fp16 planes hi = fp16(y), lo = fp16(y - hi) [M, ldp]:
+ *   the planes mcr_split_to_planes gives for mcr_layernorm's rows, bit for bit.  Yl may be NULL (the high plane alone).  E <= 512;
+ *   E, ldx, ldp and alignment as mcr_split_to_planes (E % 4 == 0, ldx % 4 == 0, X 16-byte aligned, ldp % 4 == 0, planes 8-byte
+ *   aligned); gamma, beta 4-byte aligned.
+ * Leading dimensions and alignment otherwise as the entries without lens; a call outside them returns non-zero and writes nothing. */
+int mcr_attention_lens(const float* qkv, int64_t ldq, float* out, int64_t ldo, int64_t S, int64_t L, int n_heads, int qk_dim, int v_dim,
+                       const int* lens, int split_mode, void* workspace, size_t workspace_bytes, void* stream);
+int mcr_pool_max_avg_lens(const float* X, int64_t ldx, float* Y, int64_t ldy, int64_t S, int64_t L, int E, const int* lens, void* stream);
+int mcr_colmax_broadcast_lens(const float* X, int64_t ldx, float* Y, int64_t ldy, int64_t S, int64_t L, int E, const int* lens,
+                              const float* ex, int64_t ex_ld, int ex_cols, float* ex_dst, void* stream);
+int mcr_layernorm_planes(const float* X, int64_t ldx, const float* gamma, const float* beta, void* Yh, void* Yl, int64_t ldp, int64_t M,
+                         int E, void* stream);
+
 /* ---- the planes GEMMs of variants 6 / 7 as blocks (linear3p.hip): BRING-UP / TEST entries -----------------------------------------
  * The matrix path of the default numerics: both operands stored as fp16 planes, hi = fp16(x) (round to nearest even) and
  * lo = fp16(x - hi), and multiplied as W_lo X_hi + W_hi X_lo + W_hi X_hi in fp32 (n_planes = 2), or the high planes alone
@@ -213,7 +242,7 @@ int mcr_linear_planes_dot(const void* Xh, const void* Xl, int64_t ldx, const voi
  * mcr_pool_max_avg_backward: for mcr_pool_max_avg given dY [S, ldy] = [d_max (E) | d_avg (E)]: dX[(s, r), c] = d_avg[s, c] / L, plus
  *   d_max[s, c] on the lowest row r holding the column's max (torch.max(dim)'s choice on ties).  Written, not accumulated.  Any S;
  *   leading dimensions >= the row (ldy >= 2 E), operands 4-byte aligned.
- * mcr_pool_max_avg_backward_lens: the same for padded sequences (mcr_pool_max_avg's lens form; lens: DEVICE int[S]): with n = min(L,
+ * mcr_pool_max_avg_backward_lens: the same for padded sequences (the backward of mcr_pool_max_avg_lens; lens: DEVICE int[S]): with n = min(L,
  *   max(1, lens[s])) the arg-max runs over the first n rows (ties: the lowest row), the mean's share is d_avg / n, and rows >= n are
  *   written as exact zeros. */
 size_t mcr_attention_backward_workspace_bytes(int64_t S, int64_t L, int n_heads, int v_dim);

@@ -348,6 +348,33 @@ int mcr_attention_ws(const float* qkv, int64_t ldq, float* out, int64_t ldo, int
     return 0;
 }
 
+// TEST entry: launch_attention as the encoders call it (networks.hip: run_encoder*, pct_bwd.hip) -- per-sequence lengths and an explicit
+// split mode.  Adds no kernel.
+int mcr_attention_lens(const float* qkv, int64_t ldq, float* out, int64_t ldo, int64_t S, int64_t L, int n_heads, int qk_dim, int v_dim,
+                       const int* lens, int split_mode, void* workspace, size_t workspace_bytes, void* stream) {
+    VariantScope variant_scope_;
+    MCR_REQUIRE(qkv && out, "mcr_attention_lens: null pointer");
+    MCR_REQUIRE(S > 0 && L > 0, "mcr_attention_lens: empty problem");
+    MCR_REQUIRE(n_heads == 4 && ((qk_dim == 32 && v_dim == 128) || (qk_dim == 64 && v_dim == 256)),
+                "mcr_attention_lens: supported head layouts are 4 heads with (qk,v) = (32,128) or (64,256); got %d heads (%d,%d)",
+                n_heads, qk_dim, v_dim);
+    MCR_REQUIRE(split_mode >= -1 && split_mode <= 1, "mcr_attention_lens: split_mode must be 1, 0 or -1 (got %d)", split_mode);
+    // (with lens a 16-token sequence runs the matrix-pipe kernel too: one grid.z slot per sequence)
+    MCR_REQUIRE((L == 16 && !lens) || S <= 32767, "mcr_attention_lens: too many long sequences");
+    MCR_REQUIRE(ldq >= 2 * qk_dim + v_dim && ldo >= v_dim, "mcr_attention_lens: leading dimension too small");
+    // the launcher drops to the unsplit form when the scratch is short; here a split that was asked for must be possible
+    if (split_mode != 0 && L >= 512 && (workspace || split_mode == 1)) {
+        MCR_REQUIRE(workspace && workspace_bytes >= mcr_attention_workspace_bytes(S, L, n_heads, v_dim),
+                    "mcr_attention_lens: workspace too small for the key split (%zu bytes, %zu needed)", workspace ? workspace_bytes : (size_t)0,
+                    mcr_attention_workspace_bytes(S, L, n_heads, v_dim));
+        MCR_REQUIRE((uintptr_t)workspace % 16 == 0, "mcr_attention_lens: the workspace must be 16-byte aligned");
+    }
+    const AttnSplit split{(float*)workspace, workspace ? workspace_bytes / sizeof(float) : 0, split_mode};
+    launch_attention((hipStream_t)stream, {qkv, ldq}, {out, ldo}, S, (int)L, n_heads, qk_dim, v_dim, lens, split, attn_pv_half());
+    MCR_LAUNCH_CHECK("mcr_attention_lens");      // (lens off the matrix-pipe kernel: the launcher's refusal, 3)
+    return 0;
+}
+
 // planes [2][T][W3] fp16 (the bytes of the fp32 rows) + key-split scratch
 struct AttnPlanesScratch { _Float16* planes; float* split; };
 static AttnPlanesScratch carve_attention_planes(Arena& a, int64_t S, int64_t L, int n_heads, int qk_dim, int v_dim) {
@@ -401,6 +428,36 @@ int mcr_pool_max_avg(const float* X, int64_t ldx, float* Y, int64_t ldy, int64_t
     return 0;
 }
 
+// TEST entries: the padded-sequence forms of the two launchers above, as run_pc_transformer and the SconeVis embedding call them
+// (lens: device int [S], may be NULL).  They add no kernel.
+int mcr_pool_max_avg_lens(const float* X, int64_t ldx, float* Y, int64_t ldy, int64_t S, int64_t L, int E, const int* lens, void* stream) {
+    MCR_REQUIRE(X && Y && S > 0 && L > 0 && E > 0, "mcr_pool_max_avg_lens: bad arguments");
+    MCR_REQUIRE(L <= 0x7fffffffll, "mcr_pool_max_avg_lens: L must fit an int");
+    MCR_REQUIRE(ldx >= E && ldy >= 2 * (int64_t)E, "mcr_pool_max_avg_lens: leading dimension too small");
+    launch_pool_max_avg((hipStream_t)stream, X, ldx, Y, ldy, S, (int)L, E, lens);
+    MCR_LAUNCH_CHECK("mcr_pool_max_avg_lens");
+    return 0;
+}
+
+int mcr_colmax_broadcast_lens(const float* X, int64_t ldx, float* Y, int64_t ldy, int64_t S, int64_t L, int E, const int* lens, const float* ex,
+                              int64_t ex_ld, int ex_cols, float* ex_dst, void* stream) {
+    MCR_REQUIRE(X && Y && S > 0 && L > 0 && E > 0, "mcr_colmax_broadcast_lens: bad arguments");
+    MCR_REQUIRE(L <= 0x7fffffffll, "mcr_colmax_broadcast_lens: L must fit an int");
+    MCR_REQUIRE(ldx >= E && ldy >= E, "mcr_colmax_broadcast_lens: leading dimension too small");
+    if (ex) {
+        // pool_long_kernel / copy2d_kernel: column j < ex_cols of row m is read at ex[m * ex_ld + j] (ex_ld an int) and written at
+        // ex_dst[m * ldy + j]
+        MCR_REQUIRE(ex_dst, "mcr_colmax_broadcast_lens: ex without ex_dst");
+        MCR_REQUIRE(ex_cols > 0 && ex_cols <= ex_ld && ex_cols <= ldy, "mcr_colmax_broadcast_lens: need 0 < ex_cols <= ex_ld and ex_cols <= ldy (got %d)", ex_cols);
+        MCR_REQUIRE(ex_ld <= 0x7fffffffll, "mcr_colmax_broadcast_lens: ex_ld must fit an int");
+    } else {
+        MCR_REQUIRE(ex_cols == 0 && !ex_dst, "mcr_colmax_broadcast_lens: ex_cols / ex_dst without ex");
+    }
+    launch_colmax_broadcast((hipStream_t)stream, X, ldx, Y, ldy, S, (int)L, E, lens, ex, (int)ex_ld, ex_cols, ex_dst);
+    MCR_LAUNCH_CHECK("mcr_colmax_broadcast_lens");
+    return 0;
+}
+
 // *flag |= 1 if any of x[0 .. n) is inf / NaN: the range guard of the fp16-split matrix path for outputs that leave through an entry
 // point without a flag of its own (SconeVis' harmonics)
 int mcr_nonfinite_flag(const float* x, int64_t n, int* flag, void* stream) {
@@ -424,6 +481,20 @@ int mcr_split_to_planes(const float* X, int64_t ldx, void* Ph, void* Pl, int64_t
     MCR_REQUIRE(ldp % 4 == 0 && al8(Ph) && al8(Pl), "mcr_split_to_planes: ldp must be a multiple of 4 and the planes 8-byte aligned");
     launch_split_to_planes((hipStream_t)stream, {X, ldx}, {(_Float16*)Ph, (_Float16*)Pl, ldp}, M, E);
     MCR_LAUNCH_CHECK("mcr_split_to_planes");
+    return 0;
+}
+
+// LayerNorm whose rows leave as planes (the encoders' norm1 / norm2 and the PCTransformer's norm on the planes path).  The operands obey
+// mcr_split_to_planes' rules, so that the two-step form mcr_split_to_planes(mcr_layernorm(x)) takes the same arguments.
+int mcr_layernorm_planes(const float* X, int64_t ldx, const float* gamma, const float* beta, void* Yh, void* Yl, int64_t ldp, int64_t M, int E,
+                         void* stream) {
+    MCR_REQUIRE(X && gamma && beta && Yh, "mcr_layernorm_planes: null pointer");
+    MCR_REQUIRE(M > 0 && E > 0 && E <= 512 && E % 4 == 0, "mcr_layernorm_planes: need M > 0 and E a multiple of 4 in 4 .. 512 (got %d)", E);
+    MCR_REQUIRE(ldx >= E && ldp >= E, "mcr_layernorm_planes: leading dimension too small");
+    MCR_REQUIRE(ldx % 4 == 0 && al16(X), "mcr_layernorm_planes: ldx must be a multiple of 4 and X 16-byte aligned");
+    MCR_REQUIRE(ldp % 4 == 0 && al8(Yh) && al8(Yl), "mcr_layernorm_planes: ldp must be a multiple of 4 and the planes 8-byte aligned");
+    launch_layernorm_planes((hipStream_t)stream, {X, ldx}, gamma, beta, {(_Float16*)Yh, (_Float16*)Yl, ldp}, M, E);
+    MCR_LAUNCH_CHECK("mcr_layernorm_planes");
     return 0;
 }
 

@@ -375,7 +375,11 @@ __global__ __launch_bounds__(256) void layernorm_planes_kernel(const float* __re
     for (int e = 0; e < EPL; ++e) {
         const int c = lane + e * 64;
         if (c < E) {
-            const float y = (v[e] - mean) * rstd * g[c] + b[c];
+            float y = (v[e] - mean) * rstd * g[c] + b[c];
+            // y is the fp32 value layernorm_kernel stores; the split starts from it.  Without the barrier hipcc folds the conversion
+            // into the affine fma (v_fma_mixlo_f16: ONE rounding, straight to fp16), and hi is no longer fp16(y) where the fp32
+            // rounding of y lands on an fp16 tie: one fp16 ulp off the split of the fp32 rows in about 1 of 2^13 elements
+            asm volatile("" : "+v"(y));
             const _Float16 hi = (_Float16)y;
             Yh[m * ldp + c] = hi;
             if (Yl) Yl[m * ldp + c] = (_Float16)(y - (float)hi);          // (NULL: the single-plane variant 7 keeps fp16(y) alone)

@@ -106,9 +106,9 @@ def backward_route(heads, S, L):
 # launchers' conditions allow: QG = 2 needs cdiv(L, 128) * 4 * S >= 512 (S = 64 at L = 129; S = 63 stays at QG = 1), SPLIT needs a
 # workspace, L >= 512 and cdiv(L, 64) * 4 * S <= 256 (S <= 7 at L = 576; S = 8 is unsplit); planes with split_mode = 1 split whatever S
 # is, so their SPLIT QG = 2 form is cdiv(512, 128) * 4 * 2 S >= 512: S = 16.
-# NOT reachable from a building-block entry (the gap that remains; the network entries reach them): attention_mfma_kernel's SPLIT
-# forms at QG = 2 (mode -1 asks for cdiv(L, 64) * 4 * S <= 256 and cdiv(L, 128) * 8 * S >= 512 at once: no L >= 512 has both), its
-# `lens` argument (no building-block entry passes it), and attention_planes_kernel's NP = 1 forms (variant 7: test_variant7_gpu.py).
+# NOT reachable from the entries of THIS table: attention_mfma_kernel's SPLIT forms at QG = 2 (mode -1 asks for cdiv(L, 64) * 4 * S <=
+# 256 and cdiv(L, 128) * 8 * S >= 512 at once: no L >= 512 has both) and its `lens` argument -- mcr_attention_lens reaches both
+# (tests/_padded_cases.py has their rows) -- and attention_planes_kernel's NP = 1 forms (variant 7: test_variant7_gpu.py).
 def _route_table():
     rows = [("attention_small_kernel<16,4,8,32,4>", "mcr_attention", "32x128", 5, 16, "any alignment"),
             ("attention_small_kernel<16,4,8,32,4> +mask", "mcr_attention_masked", "32x128", 5, 16, "any alignment")]
