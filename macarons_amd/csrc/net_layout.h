@@ -1,4 +1,4 @@
-// Host-only: the two data formats the network entry points (networks.hip; the backwards: scone_vis_bwd.hip, pct_bwd.hip,
+// Host-only: the two data formats the network entry points (pct.hip, scone_vis.hip, scone_occ.hip; the backwards: scone_vis_bwd.hip, pct_bwd.hip,
 // scone_occ_bwd.hip) share with their callers.
 //   1. The weight tables (arrays of device pointers; order documented in include/macarons_hip.h, produced by networks/packing.py):
 //      slot names, table lengths, the structs the entries work on, ONE reader per struct and ONE validation.  No table index is

@@ -1,5 +1,5 @@
 // Device-side building blocks of the SCONE networks (K4-K8 of SURVEY §2.3) for gfx950.
-// Launch helpers are declared here and defined in nn_kernels.hip; networks.hip composes them.
+// Launch helpers are declared here and defined in nn_kernels.hip; the network files (pct.hip, scone_vis.hip, scone_occ.hip) compose them.
 #pragma once
 #include "common.h"
 

@@ -164,7 +164,7 @@ class BlobCache:
 
 def weight_planes(W):
     """[2, N, K] fp16 = hi | lo planes of W * 2^8 (hi = fp16(x), lo = fp16(x - hi)): what split_weights_kernel (linear3h.hip) writes per
-    call, built once per parameter version for the encoders' planes GEMMs (run_encoder_planes, networks.hip)."""
+    call, built once per parameter version for the encoders' planes GEMMs (run_encoder_planes, pct.hip)."""
     with torch.no_grad():
         x = W.detach().float() * 256.0
         hi = x.half()

@@ -1,4 +1,4 @@
-"""The *_workspace_bytes functions of networks.hip and of the backward sources (bwd_blocks.hip, attention_bwd.hip, pct_bwd.hip,
+"""The *_workspace_bytes functions of the forward sources (fwd_blocks.hip, pct.hip, scone_vis.hip, scone_occ.hip) and of the backward sources (bwd_blocks.hip, attention_bwd.hip, pct_bwd.hip,
 scone_vis_bwd.hip, scone_occ_bwd.hip), one library against another (plain host code: no GPU).
 
     python tools/compare_workspace_sizes.py OLD/libmacarons_hip.so NEW/libmacarons_hip.so

@@ -2,7 +2,7 @@
 power (hwmon of the GPU's PCI function, >= 40 Hz) and shader clock while each kernel runs back to back for ~4 s, three alternating
 rounds on ONE box.  J per query = mean W x seconds / queries; cycles per 16 384 queries = mean sclk x ms.  Closes the round-3 question
 "is there energy left to save in v8?" (VERDICT r3 next #4).
-    python tools/build_variant.py v8 "networks.hip,+tools/experiments/local_pct8.hip" -DMCR_DEV_LOCAL_PCT8      (build container)
+    python tools/build_variant.py v8 "numerics.hip,pct.hip,+tools/experiments/local_pct8.hip" -DMCR_DEV_LOCAL_PCT8      (build container)
     python tools/energy_local_pct.py > gpurun_out/local_pct8_energy.txt                                         (GPU box)"""
 import ctypes, os, sys, time
 import torch
