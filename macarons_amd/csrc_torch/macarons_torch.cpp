@@ -504,7 +504,7 @@ at::Tensor h2d(const at::Tensor& src, int64_t device_index) {
 // The (cell, chunk) job tables of the occupancy-field pass (macarons_utils.compute_scene_occupancy_probability_field; upstream walks the
 // cells in Python, macarons_utils.py:1443-1478) from the counts the decision has just read back -- the ~30 numpy calls of the Python
 // restatement (100 us between the read-back and the first launch behind it, with the GPU idle) as one loop.  Integer work only: the
-// tables are those of the numpy code, element for element (tests/test_draws_cpu.py).
+// tables are those of the numpy code (macarons_utils._plan_jobs over the visited cells), element for element (tests/test_draws_cpu.py).
 //   hostc: int64 CPU = [visit (n_cells) | pad | counts (n_cells) | pad | sel_off (n_cells + 2) | n_oof]   (the layout of mcr_field_select)
 //   s_off [n_cells + 1]: the surface store's cell offsets; nbm [n_cells, 27]: neighbour cells, -1 padded; xf_all [n_cells, 20] fp32;
 //   perm int32: the view-space bin permutation
@@ -543,6 +543,7 @@ std::tuple<at::Tensor, at::Tensor> field_jobs(const at::Tensor& hostc, const at:
     int64_t* me = meta.data_ptr<int64_t>();
     int64_t *job_q = me + 5, *job_m = job_q + J, *q_start = job_m + J, *m_start = q_start + J + 1;
     const int64_t perm_bytes = perm_c.numel() * 4;
+    // 32 B per job row, 32 B per segment row, 80 B of transform per job, then the permutation: ops.field_table_offsets in Python
     at::Tensor raw = at::empty({32 * (J + n_seg) + 80 * J + perm_bytes}, at::kByte);
     int64_t* jt = reinterpret_cast<int64_t*>(raw.data_ptr<uint8_t>());
     int64_t* st = jt + 4 * J;

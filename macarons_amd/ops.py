@@ -1463,9 +1463,21 @@ def field_select(proxy_points, supervision_occ, out_of_field, proxy_proba, store
     return s
 
 
+# The uploaded table of the occupancy passes: J job rows (4 int64) | n_seg surface-segment rows (4 int64) | J transforms (20 fp32) | the
+# bin permutation (int32) | whatever the caller appends
+FIELD_JOB_ROW_BYTES, FIELD_SEGMENT_ROW_BYTES, FIELD_TRANSFORM_ROW_BYTES = 32, 32, 80
+
+
+def field_table_offsets(J, n_seg):
+    """Byte offsets of (segment table, transform table, bin permutation) in the uploaded table of J jobs and n_seg segments."""
+    o_seg = FIELD_JOB_ROW_BYTES * J
+    o_xf = o_seg + FIELD_SEGMENT_ROW_BYTES * n_seg
+    return o_seg, o_xf, o_xf + FIELD_TRANSFORM_ROW_BYTES * J
+
+
 def field_build(tables, J, n_seg, sel, proxy_points, S_all, view_states, bin_perm, vh_matrix_t, T, tot, X_world, vh):
     """The jobs of the occupancy-field pass (mcr_field_build).  tables: ONE uploaded fp64-free buffer = int64 [J*4 + n_seg*4] followed
-    (as raw bytes) by fp32 [J*20]; X_world [>=T,3] and vh [>=T,64] are written in their first T rows.
+    (as raw bytes) by fp32 [J*20] (field_table_offsets); X_world [>=T,3] and vh [>=T,64] are written in their first T rows.
     -> (rows int32 [T], row_job int32 [T], X_q [T,3], pc_all [tot,3])."""
     dev = proxy_points.device
     ib = torch.empty(2 * T, dtype=torch.int32, device=dev)
@@ -1473,9 +1485,10 @@ def field_build(tables, J, n_seg, sel, proxy_points, S_all, view_states, bin_per
     fb = torch.empty(3 * (T + tot), dtype=torch.float32, device=dev)
     X_q, pc_all = fb[:3 * T].view(T, 3), fb[3 * T:].view(tot, 3)
     base = tables.data_ptr()
+    o_seg, o_xf, _ = field_table_offsets(J, n_seg)
     n_bins = view_states.shape[1]
     with torch.cuda.device(dev):
-        check(lib().mcr_field_build(c_vp(base), c_int(J), c_vp(base + 32 * J), c_int(n_seg), c_vp(base + 32 * (J + n_seg)), _p(sel.rows_order),
+        check(lib().mcr_field_build(c_vp(base), c_int(J), c_vp(base + o_seg), c_int(n_seg), c_vp(base + o_xf), _p(sel.rows_order),
                                     _p(proxy_points), _p(S_all), _p(view_states), c_int(n_bins), _p(bin_perm) if bin_perm is not None else c_vp(0),
                                     _p(vh_matrix_t), c_i64(T),
                                     c_i64(tot), _p(rows), _p(row_job), _p(X_world), _p(X_q), _p(vh), _p(pc_all), _stream()), "mcr_field_build")

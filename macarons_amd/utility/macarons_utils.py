@@ -4,6 +4,7 @@
 PyTorch3D camera objects stay outside: cameras are passed as the 40-float records of mcr_points_in_fov
 (M_view, M_proj, ndc bounds, centre, range) and a prediction-view matrix.
 """
+import collections
 import os
 
 import numpy as np
@@ -46,6 +47,15 @@ def sensor_distance_threshold(params, fov_camera, cell_resolution):
     pixel_size = 2. / min(params.image_height, params.image_width)
     epsilon = math.sqrt(math.pi) / 2. * cell_resolution
     return focal_length * epsilon / pixel_size
+
+
+def _distance_threshold(params, fov_camera, cell_resolution):
+    """(distance_th, smooth) of params.distance_factor_th: a number -> itself; None or 'smooth' -> the sensor's threshold."""
+    th = params.distance_factor_th
+    smooth = th == 'smooth'
+    if th is None or smooth:
+        th = sensor_distance_threshold(params, fov_camera, cell_resolution)
+    return th, smooth
 
 
 def get_distance_factor(params, pts, X_cam, fov_camera, cell_resolution):
@@ -161,6 +171,36 @@ class SceneCamera:
         return self._m_view_host
 
 
+def _keep_on(scene, name, value):
+    """Keep what is constant for a scene on the scene object (where it takes attributes); returns the value."""
+    try:
+        setattr(scene, name, value)
+    except Exception:
+        pass
+    return value
+
+
+def _index_feature(proxy_scene, device):
+    """[P,1] fp32: every proxy point's own index, the feature it is registered with in the proxy grid."""
+    pp, f = proxy_scene.proxy_points, getattr(proxy_scene, "_mcr_index_feature", None)
+    if f is None or f.shape[0] != pp.shape[0] or f.device != pp.device:
+        f = _keep_on(proxy_scene, "_mcr_index_feature", torch.arange(pp.shape[0], device=device, dtype=torch.float32).view(-1, 1))
+    return f
+
+
+def _box_diag(proxy_scene):
+    """Diagonal of the scene's bounding box: read back once per scene, not once per decision or step."""
+    d = getattr(proxy_scene, "_mcr_box_diag", None)
+    return _keep_on(proxy_scene, "_mcr_box_diag", torch.linalg.norm(proxy_scene.x_max - proxy_scene.x_min).item()) if d is None else d
+
+
+def _prediction_camera_or(camera, prediction_camera):
+    """The prediction camera of an occupancy pass: by default the camera's fov_camera_0, as upstream."""
+    if prediction_camera is None and camera is None:
+        raise NameError("Both camera and prediction_camera are equal to None.")
+    return camera.fov_camera_0 if prediction_camera is None else prediction_camera
+
+
 def macarons_nbv_decision(params, macarons, proxy_scene, surface_scene, camera, depth, depth_mask, neighbor_records, X_neighbors,
                           device, samples=None, return_signed_distances=False, range_guard=True, group=None, uniform_draws="per_camera"):
     """One next-best-view decision of the MACARONS loop after the depth map of the current pose is known -- the body of
@@ -200,14 +240,7 @@ def macarons_nbv_decision(params, macarons, proxy_scene, surface_scene, camera, 
     # 1 ---- proxy points in the current field of view, offered to their grid cells with their index as feature (every point is offered,
     # the ones outside the frustum flagged invalid: compacting them first -- `points[mask]` -- is a read-back of the count)
     fov_mask = ops.points_in_fov(ps.proxy_points, rec.view(1, 40))[0]
-    P_all = ps.proxy_points.shape[0]
-    idx_f = getattr(ps, "_mcr_index_feature", None)
-    if idx_f is None or idx_f.shape[0] != P_all or idx_f.device != ps.proxy_points.device:
-        idx_f = torch.arange(P_all, device=device, dtype=torch.float32).view(-1, 1)
-        try:
-            ps._mcr_index_feature = idx_f
-        except Exception:
-            pass
+    idx_f = _index_feature(ps, device)
     fused = hasattr(ps, "fill_cells_begin")
     if fused:
         fill = ps.fill_cells_begin(ps.proxy_points, features=idx_f, valid=fov_mask)
@@ -227,18 +260,9 @@ def macarons_nbv_decision(params, macarons, proxy_scene, surface_scene, camera, 
     # read-back per camera object (a read-back per decision stalled the host behind the fill / selection launches: 0.2-0.3 ms)
     Mv = rec[:16].view(4, 4)                          # (the device copy of the record already holds it: no second upload)
     K = neighbor_records.shape[0]
-    th = params.distance_factor_th
-    smooth = th == 'smooth'
-    if th is None or smooth:
-        th = sensor_distance_threshold(params, camera, surface_scene.cell_resolution)
+    th, smooth = _distance_threshold(params, camera, surface_scene.cell_resolution)
     vis_model = macarons.visibility                 # `macarons` = the SCONE part (Macarons.scone upstream): .occupancy / .visibility
-    diag = getattr(ps, "_mcr_box_diag", None)       # a constant of the scene: read back once, not once per decision
-    if diag is None:
-        diag = torch.linalg.norm(ps.x_max - ps.x_min).item()
-        try:
-            ps._mcr_box_diag = diag
-        except Exception:
-            pass
+    diag = _box_diag(ps)
     occ_net = getattr(macarons, "occupancy", macarons)
     nrec, xn = ops.h2d(neighbor_records, torch.float32, device), ops.h2d(X_neighbors, torch.float32, device)
     k0, k1 = mdist.shard_range(K, rank, world)
@@ -489,10 +513,6 @@ def _world_to_view_matrix(prediction_camera):
     return prediction_camera.get_world_to_view_transform().get_matrix().reshape(-1, 4, 4)[0]
 
 
-def _lin(idx3, gw, gh):
-    return (idx3[..., 0] * gw + idx3[..., 1]) * gh + idx3[..., 2]
-
-
 def _grid_tables(scene, device):
     """What never changes for a scene grid, built once and kept on the scene object: the cell keys in linear-id (= lexicographic)
     order, key -> linear id, every cell's 27-neighbourhood (clamped, unique, sorted: get_neighboring_cells), and device tables of
@@ -521,11 +541,7 @@ def _grid_tables(scene, device):
     tab = {"device": str(device), "keys": keys, "lin_of": lin_of, "neighbours": nbl, "neighbour_matrix": nbm,
            "neighbour_matrix_t": torch.from_numpy(nbm), "centers": centers,
            "diag": diag, "centers_host": centers.cpu(), "diag_host": diag.cpu()}
-    try:
-        scene._mcr_grid_tables = tab
-    except Exception:
-        pass
-    return tab
+    return _keep_on(scene, "_mcr_grid_tables", tab)
 
 
 class _ForeignStore:
@@ -580,7 +596,6 @@ def _job_groups(cloud_sizes):
     of its cloud).  The batched draws (torch.ops.macarons.scone_occ_draws: prefix-only Fisher-Yates, the engine advanced over the rest)
     cost ~0.4 ms per million indices, less than the ~40 launches an extra group repeats: ONE group below 3 M indices (the bench scene
     draws 1 M: 7.8 / 8.4 / 9.0 ms for 1 / 2 / 3 groups), at most three.  env MCR_FIELD_GROUPS=n forces n."""
-    import os
     J = len(cloud_sizes)
     work = np.cumsum(np.asarray(cloud_sizes, np.float64))
     forced = os.environ.get("MCR_FIELD_GROUPS")
@@ -613,7 +628,6 @@ _NATIVE_FIELD_JOBS = []
 def _native_field_jobs():
     """Is torch.ops.macarons.field_jobs there (the C++ extension built)?  MCR_NATIVE_FIELD_JOBS=0: the numpy restatement (A/B, tests)."""
     if not _NATIVE_FIELD_JOBS:
-        import os
         ok = os.environ.get("MCR_NATIVE_FIELD_JOBS", "1") != "0"
         if ok:
             try:
@@ -648,30 +662,95 @@ def _field_prepare(params, proxy_scene, prediction_camera, device, ticket=None):
     (:1468-1478), the bin permutation of move_view_state_to_view_space (:863-931)."""
     from . import scone_utils as su
     tab = _grid_tables(proxy_scene, device)
-    Mv_any = _world_to_view_matrix(prediction_camera)
-    Mv_host = Mv_any.detach().to("cpu", torch.float32).reshape(4, 4)    # (a device matrix is read back here)
+    Mv_host = _world_to_view_matrix(prediction_camera).detach().to("cpu", torch.float32).reshape(4, 4)   # (a device matrix is read back here)
     cw, dg = tab["centers_host"], tab["diag_host"]
     n = cw.shape[0]
     if ticket is not None:
         xf_all_t, perm_t = torch.ops.macarons.field_prepare_wait(ticket)
-        return {"tab": tab, "xf_all": xf_all_t.numpy(), "perm": perm_t.numpy(), "xf_all_t": xf_all_t, "perm_t": perm_t,
-                "vh_mt": _vh_matrix_t(params, device)}
-    if torch.is_tensor(prediction_camera) and _native_field_jobs() and hasattr(torch.ops.macarons, "field_prepare"):
+    elif torch.is_tensor(prediction_camera) and _native_field_jobs() and hasattr(torch.ops.macarons, "field_prepare"):
         # the same ATen operators from ONE C++ call (bit-identical; tests/test_draws_cpu.py)
         su.view_space_bin_permutation(torch.eye(3), params.view_state_n_elev, params.view_state_n_azim) \
             if (params.view_state_n_elev, params.view_state_n_azim) not in su._REF_DIRECTIONS else None
         xf_all_t, perm_t = torch.ops.macarons.field_prepare(Mv_host, cw, dg, su._REF_DIRECTIONS[(params.view_state_n_elev, params.view_state_n_azim)],
                                                             float(params.prediction_neighborhood_size), params.view_state_n_elev,
                                                             params.view_state_n_azim)
-        return {"tab": tab, "xf_all": xf_all_t.numpy(), "perm": perm_t.numpy(), "xf_all_t": xf_all_t, "perm_t": perm_t,
-                "vh_mt": _vh_matrix_t(params, device)}
-    cen_h = (torch.cat((cw, torch.ones(n, 1)), 1) @ Mv_host)[:, :3]
-    inv_h = (1.0 / (params.prediction_neighborhood_size * dg)).float()
-    xf_all_t = torch.cat((Mv_host.reshape(1, 16).expand(n, -1), cen_h, inv_h.view(n, 1)), 1).contiguous()
-    perm_t = su.view_space_bin_permutation((Mv_host[:3, :3].contiguous() if torch.is_tensor(prediction_camera) else prediction_camera),
-                                           params.view_state_n_elev, params.view_state_n_azim, device).to(torch.int32)
+    else:
+        cen_h = (torch.cat((cw, torch.ones(n, 1)), 1) @ Mv_host)[:, :3]
+        inv_h = (1.0 / (params.prediction_neighborhood_size * dg)).float()
+        xf_all_t = torch.cat((Mv_host.reshape(1, 16).expand(n, -1), cen_h, inv_h.view(n, 1)), 1).contiguous()
+        perm_t = su.view_space_bin_permutation((Mv_host[:3, :3].contiguous() if torch.is_tensor(prediction_camera) else prediction_camera),
+                                               params.view_state_n_elev, params.view_state_n_azim, device).to(torch.int32)
     return {"tab": tab, "xf_all": xf_all_t.numpy(), "perm": perm_t.numpy(), "xf_all_t": xf_all_t, "perm_t": perm_t,
             "vh_mt": _vh_matrix_t(params, device)}
+
+
+class _SurfaceCells:
+    """The surface scene as the occupancy passes read it: the flat `store`; per proxy cell (linear id) where its surface points lie in it,
+    `s_start` / `s_len`; `aligned`: the surface grid is the proxy grid (the store's offsets ARE that table); `nb_len` [n_cells, 27] and
+    `m_cell`: surface points of every neighbour cell and of the whole neighbourhood, computed when first read (the native tables never ask)."""
+
+    def __init__(self, store, s_start, s_len, aligned, nbm):
+        self.store, self.s_start, self.s_len, self.aligned, self._nbm = store, s_start, s_len, aligned, nbm
+
+    def __getattr__(self, name):                        # (reached by the first read of nb_len or m_cell only)
+        if name not in ("nb_len", "m_cell"):
+            raise AttributeError(name)
+        self.nb_len = np.where(self._nbm >= 0, self.s_len[np.maximum(self._nbm, 0)], 0)
+        self.m_cell = self.nb_len.sum(1)
+        return self.__dict__[name]
+
+
+def _surface_cells(surface_scene, tab, device):
+    """The surface scene's flat store seen from the proxy grid of `tab` (_grid_tables): sizes are host numbers, no read-back."""
+    ss, keys, lin_of, n_cells = surface_scene, tab["keys"], tab["lin_of"], len(tab["keys"])
+    s_st = _store_of(ss, device)
+    s_keys = keys if set(ss.cells.keys()) == set(keys) else sorted(ss.cells.keys(), key=lambda k: lin_of.get(k, 0))
+    aligned = len(s_keys) == n_cells
+    if aligned:
+        s_len, s_start = np.diff(s_st.off), s_st.off[:-1]
+    else:                                               # a surface scene on another grid: by key
+        s_len = np.zeros(n_cells, np.int64); s_start = np.zeros(n_cells, np.int64)
+        for i_, k in enumerate(s_keys):
+            s_len[lin_of[k]] = s_st.off[i_ + 1] - s_st.off[i_]; s_start[lin_of[k]] = s_st.off[i_]
+    return _SurfaceCells(s_st, s_start, s_len, aligned, tab["neighbour_matrix"])
+
+
+# The (cell, chunk) jobs of an occupancy pass: J jobs over n_seg surface segments, T query rows and tot cloud points in all; per job its
+# cell (None from torch.ops.macarons.field_jobs, which gathers the transforms itself), query rows and cloud points with their running sums
+# [J + 1]; raw: the ONE upload (uint8, laid out as ops.field_table_offsets says; None without a job)
+_JobPlan = collections.namedtuple("_JobPlan", "J n_seg T tot job_cell job_q job_m q_start m_start raw")
+
+
+def _plan_jobs(cells_run, counts, sel_off, surf, nbm, xf_all, perm, chunk, tail=False):
+    """The job tables of the cells `cells_run` (linear ids, in the order they are to run), plain numpy on host numbers: one job per (cell,
+    chunk of <= `chunk` of its counts[c] selected rows, which start at sel_off[c]); a job's cloud: its cell's non-empty neighbours (`nbm`
+    [n_cells, 27], -1 padded) out of the surface view `surf`, ascending.  raw = job rows (first selected row, first query row, first cloud
+    point, 0) | segment rows (first store point, first cloud point, job, 0) | xf_all[cell] per job | perm (int32); `tail`: then, from the
+    next multiple of 8 bytes, q_start as int64 (the supervision pass's scatter reads the jobs' first rows on the device)."""
+    cells_run, counts = np.asarray(cells_run, np.int64), np.asarray(counts)
+    n_chunks = -(-counts[cells_run] // chunk)
+    job_cell = np.repeat(cells_run, n_chunks)                              # one job per (cell, chunk of <= 20 000 queries)
+    J = int(job_cell.size)
+    if not J:                                                              # nothing to upload, T = tot = 0
+        return _JobPlan(0, 0, 0, 0, job_cell, job_cell, job_cell, np.zeros(1, np.int64), np.zeros(1, np.int64), None)
+    lo = (np.arange(J) - np.repeat(np.cumsum(n_chunks) - n_chunks, n_chunks)) * chunk
+    job_q = np.minimum(chunk, counts[job_cell] - lo).astype(np.int64)
+    job_m = surf.m_cell[job_cell].astype(np.int64)
+    q_start, m_start = np.concatenate(([0], np.cumsum(job_q))), np.concatenate(([0], np.cumsum(job_m)))
+    jt = np.stack((sel_off[job_cell] + lo, q_start[:-1], m_start[:-1], np.zeros(J, np.int64)), 1).astype(np.int64)
+    # surface segments of every job: its cell's non-empty neighbours, in ascending cell order
+    seg_len = surf.nb_len[job_cell]                                        # [J, 27]
+    keep = seg_len > 0
+    seg_l = seg_len[keep]
+    st_ = np.stack((surf.s_start[nbm[job_cell][keep]], np.cumsum(seg_l) - seg_l, np.nonzero(keep)[0], np.zeros(seg_l.size, np.int64)),
+                   1).astype(np.int64)
+    xf = np.ascontiguousarray(xf_all[job_cell])
+    parts = [jt.reshape(-1).view(np.uint8), st_.reshape(-1).view(np.uint8), xf.reshape(-1).view(np.uint8),
+             perm.view(np.uint8)]
+    if tail:
+        parts += [np.zeros(-sum(p.size for p in parts) % 8, np.uint8), q_start.astype(np.int64).view(np.uint8)]
+    return _JobPlan(J, int(st_.shape[0]), int(q_start[-1]), int(m_start[-1]), job_cell, job_q, job_m, q_start, m_start,
+                    np.concatenate(parts))
 
 
 def compute_scene_occupancy_probability_field(params, macarons, camera, surface_scene, proxy_scene, device,
@@ -701,15 +780,9 @@ def compute_scene_occupancy_probability_field(params, macarons, camera, surface_
     the network's draws (the fill's draws: upstream's order on the CPU generator); host work to run once the whole pass is queued
     (the fill's gather: the GPU is busy meanwhile)."""
     from .. import dist as mdist
-    world, rank = mdist.group_world_rank(group)            # group=None: local, whatever process groups exist
-    ps, ss = proxy_scene, surface_scene
-    gl, gw, gh = ps.grid_l, ps.grid_w, ps.grid_h
-    n_cells = gl * gw * gh
-    nh = params.n_harmonics
-    if prediction_camera is None:
-        if camera is None:
-            raise NameError("Both camera and prediction_camera are equal to None.")
-        prediction_camera = camera.fov_camera_0
+    ps = proxy_scene
+    n_cells = ps.grid_l * ps.grid_w * ps.grid_h
+    prediction_camera = _prediction_camera_or(camera, prediction_camera)
     # ---- selection: which proxy points take part, grouped by the cell that stores them (:1428-1442); ONE read-back of the counts
     if _selection is None:
         sel = _field_select(ps, device, use_supervision_occ_mask)
@@ -720,76 +793,36 @@ def compute_scene_occupancy_probability_field(params, macarons, camera, surface_
     visit, counts = hostc[:n_cells], hostc[n_cells + 1:2 * n_cells + 1]
     sel_off = hostc[2 * n_cells + 2:3 * n_cells + 4]
     n_oof = int(hostc[3 * n_cells + 4])
-    tab = prep["tab"]                                    # static per scene: cells in linear-id order, their centres / diagonals, 27-neighbourhoods
-    keys, lin_of = tab["keys"], tab["lin_of"]
     # ---- host: which cells run, their surface neighbourhoods (sizes are host numbers: no read-back), the (cell, chunk) jobs
-    s_st = _store_of(ss, device)
-    s_keys = keys if set(ss.cells.keys()) == set(keys) else sorted(ss.cells.keys(), key=lambda k: lin_of.get(k, 0))
-    if len(s_keys) == n_cells:
-        s_len, s_start = np.diff(s_st.off), s_st.off[:-1]
-    else:                                               # a surface scene on another grid: by key
-        s_len = np.zeros(n_cells, np.int64); s_start = np.zeros(n_cells, np.int64)
-        for i_, k in enumerate(s_keys):
-            s_len[lin_of[k]] = s_st.off[i_ + 1] - s_st.off[i_]; s_start[lin_of[k]] = s_st.off[i_]
-    nbm = tab["neighbour_matrix"]                        # [n_cells, 27], -1 padded
-    native = len(s_keys) == n_cells and _native_field_jobs()
-    if native:
-        # the job tables by ONE C++ call (torch.ops.macarons.field_jobs: the loop form of the numpy code below, same tables element for
-        # element) -- this host work sits between the decision's read-back and the first launch behind it, with the GPU idle
-        raw_t, meta_t = torch.ops.macarons.field_jobs(torch.from_numpy(np.ascontiguousarray(hostc)), torch.from_numpy(np.ascontiguousarray(s_st.off)),
-                                                      tab["neighbour_matrix_t"], prep["xf_all_t"], prep["perm_t"], n_cells, int(chunk),
+    surf = _surface_cells(surface_scene, prep["tab"], device)
+    if surf.aligned and _native_field_jobs():
+        # the plan by ONE C++ call (torch.ops.macarons.field_jobs: the loop form of _plan_jobs over the visited cells, same tables element
+        # for element) -- this host work sits between the decision's read-back and the first launch behind it, with the GPU idle
+        raw_t, meta_t = torch.ops.macarons.field_jobs(torch.from_numpy(np.ascontiguousarray(hostc)), torch.from_numpy(np.ascontiguousarray(surf.store.off)),
+                                                      prep["tab"]["neighbour_matrix_t"], prep["xf_all_t"], prep["perm_t"], n_cells, int(chunk),
                                                       int(params.k_for_knn))
         meta = meta_t.numpy()
-        J, n_seg, T, tot = int(meta[0]), int(meta[1]), int(meta[2]), int(meta[3])
-        job_q, job_m = meta[5:5 + J], meta[5 + J:5 + 2 * J]
-        q_start, m_start = meta[5 + 2 * J:6 + 3 * J], meta[6 + 3 * J:7 + 4 * J]
+        J = int(meta[0])
+        plan = _JobPlan(J, int(meta[1]), int(meta[2]), int(meta[3]), None, meta[5:5 + J], meta[5 + J:5 + 2 * J],
+                        meta[5 + 2 * J:6 + 3 * J], meta[6 + 3 * J:7 + 4 * J], raw_t if J else None)
     else:
-        nb_len = np.where(nbm >= 0, s_len[np.maximum(nbm, 0)], 0)          # surface points of every neighbour cell
-        m_cell = nb_len.sum(1)
-        run = (np.asarray(visit) != 0) & (m_cell > 2 * 2 * params.k_for_knn) & (np.asarray(counts) > 0)       # :1455-1456
-        cells_run = np.nonzero(run)[0]
-        n_chunks = -(-np.asarray(counts)[cells_run] // chunk)
-        job_cell = np.repeat(cells_run, n_chunks)                          # one job per (cell, chunk of <= 20 000 queries)
-        J = int(job_cell.size)
-        T = tot = 0
-    P = ps.proxy_points.shape[0]
-    if J and not native:
-        lo = (np.arange(J) - np.repeat(np.cumsum(n_chunks) - n_chunks, n_chunks)) * chunk
-        job_q = np.minimum(chunk, np.asarray(counts)[job_cell] - lo).astype(np.int64)
-        job_m = m_cell[job_cell].astype(np.int64)
-        q_start = np.concatenate(([0], np.cumsum(job_q)))
-        m_start = np.concatenate(([0], np.cumsum(job_m)))
-        T, tot = int(q_start[-1]), int(m_start[-1])
-        jt = np.stack((sel_off[job_cell] + lo, q_start[:-1], m_start[:-1], np.zeros(J, np.int64)), 1).astype(np.int64)
-        # surface segments of every job: its cell's non-empty neighbours, in ascending cell order
-        seg_len = nb_len[job_cell]                                         # [J, 27]
-        keep = seg_len > 0
-        seg_job = np.nonzero(keep)[0]
-        seg_l = seg_len[keep]
-        seg_dst = np.cumsum(seg_l) - seg_l
-        st_ = np.stack((s_start[nbm[job_cell][keep]], seg_dst, seg_job, np.zeros(seg_l.size, np.int64)), 1).astype(np.int64)
+        run = (np.asarray(visit) != 0) & (surf.m_cell > 2 * 2 * params.k_for_knn) & (np.asarray(counts) > 0)       # :1455-1456
+        plan = _plan_jobs(np.nonzero(run)[0], counts, sel_off, surf, prep["tab"]["neighbour_matrix"], prep["xf_all"], prep["perm"], chunk)
+    J, T = plan.J, plan.T
     N_out = T + n_oof
     X_world = torch.empty((N_out, 3), dtype=torch.float32, device=device)
-    view_harmonics = torch.empty((N_out, nh), dtype=torch.float32, device=device)
+    view_harmonics = torch.empty((N_out, params.n_harmonics), dtype=torch.float32, device=device)
     occ_probs = torch.empty((N_out, 1), dtype=torch.float32, device=device)
     rows = None
     if J:
         # ---- ONE upload: job table, segment table, per-job transform (world->view matrix, box centre in view space, 1 / (neighbourhood
         # size x cell diagonal), :1468-1478), the bin permutation of move_view_state_to_view_space (:863-931)
-        if native:
-            tables = ops.h2d(raw_t, torch.uint8, device)
-        else:
-            xf = np.ascontiguousarray(prep["xf_all"][job_cell])
-            raw = np.concatenate((jt.reshape(-1).view(np.uint8), st_.reshape(-1).view(np.uint8), xf.reshape(-1).view(np.uint8),
-                                  prep["perm"].view(np.uint8)))
-            tables = ops.h2d(raw, torch.uint8, device)
-            n_seg = int(st_.shape[0])
-        perm_d = tables[32 * (J + n_seg) + 80 * J:].view(torch.int32)
-        rows, row_job, X_q, pc_all = ops.field_build(tables, J, n_seg, sel, ps.proxy_points, s_st.pts, ps.view_states, perm_d,
-                                                     prep["vh_mt"], T, tot, X_world, view_harmonics)
-        vh = view_harmonics[:T]
+        tables = ops.h2d(plan.raw, torch.uint8, device)
+        perm_d = tables[ops.field_table_offsets(J, plan.n_seg)[2]:].view(torch.int32)
+        rows, row_job, X_q, pc_all = ops.field_build(tables, J, plan.n_seg, sel, ps.proxy_points, surf.store.pts, ps.view_states, perm_d,
+                                                     prep["vh_mt"], T, plan.tot, X_world, view_harmonics)
+        built = (row_job, X_q, pc_all, view_harmonics[:T])
         occ_out = occ_probs[:T]
-        sizes_m, sizes_q = job_m.tolist(), job_q.tolist()
         # ---- occupancy of all jobs
         if use_supervision_occ_instead_of_predicted:
             if _between is not None:
@@ -797,62 +830,12 @@ def compute_scene_occupancy_probability_field(params, macarons, camera, surface_
             occ_out.copy_(ps.proxy_supervision_occ[rows.long()])
         else:
             occ_net = getattr(macarons, "occupancy", macarons)
-            if hasattr(occ_net, "forward_ragged") and mdist.exchange_on(group):
-                if _between is not None:
-                    _between()
-                if ragged_perms is None:                # rank 0 draws for every job, in job order (what the 1-rank pass draws)
-                    ragged_perms = _broadcast_job_perms(occ_net, sizes_m, device, group, rank)
-                t0, t1 = mdist.shard_range(T, rank, world)
-                mine = [j for j in range(J) if q_start[j] < t1 and q_start[j + 1] > t0]
-                if mine:
-                    q_l = [int(min(q_start[j + 1], t1) - max(q_start[j], t0)) for j in mine]
-                    p0, p1 = int(m_start[mine[0]]), int(m_start[mine[-1] + 1])
-                    draws_l = (_slice_index_arrays(occ_net, ragged_perms, sizes_m, mine[0], mine[-1] + 1) if isinstance(ragged_perms, dict)
-                               else [ragged_perms[j] for j in mine])
-                    kw = {"index_arrays": draws_l} if isinstance(draws_l, dict) else {"perms": draws_l}
-                    occ_l = occ_net.forward_ragged(pc_all[p0:p1].contiguous(), [sizes_m[j] for j in mine], X_q[t0:t1].contiguous(),
-                                                   vh[t0:t1].contiguous(), q_l, **kw).view(-1, 1)
-                else:                                   # empty row shard (T < world): no kernels, the all-gather is joined
-                    occ_l = torch.zeros(0, 1, dtype=torch.float32, device=device)
-                occ_out.copy_(mdist.allgather_rows(occ_l, T, group))
-            elif hasattr(occ_net, "forward_ragged"):
-                # The jobs run in G consecutive GROUPS when their hidden draws are made here on the CPU generator (~1 ms per 400k
-                # permuted indices, inherent to the reference's stream): the first launches of EVERY group (which need no draw) are queued
-                # at once, then, while the GPU works on group g, the host draws for group g + 1 -- only the first group's draws pass with
-                # the GPU short of work.  Every job computes what it computes alone (launch shapes are chosen per cloud), so the grouping
-                # does not change a bit of the result; the draws stay in job order.
-                given = ragged_perms["groups"] if (isinstance(ragged_perms, dict) and "groups" in ragged_perms) else None
-                if given is not None:
-                    groups = [(j0, j1) for j0, j1, _ in given]
-                elif ragged_perms is None:
-                    groups = _job_groups(sizes_m)
-                else:
-                    groups = [(0, J)]
-                hdls = []
-                for gi, (j0, j1) in enumerate(groups):
-                    t0, t1, p0, p1 = int(q_start[j0]), int(q_start[j1]), int(m_start[j0]), int(m_start[j1])
-                    whole = (j0, j1) == (0, J)
-                    hdls.append(occ_net.forward_ragged_begin(pc_all if whole else pc_all[p0:p1], sizes_m[j0:j1], X_q if whole else X_q[t0:t1],
-                                                             vh if whole else vh[t0:t1], sizes_q[j0:j1], row_job=row_job if whole else None,
-                                                             arena="scone_occ_ragged" if gi == 0 else f"scone_occ_ragged_g{gi}"))
-                if _between is not None:
-                    _between()                          # phase 1 is queued; the fill's CPU draws come first, as upstream (Cell.fill, then the pass)
-                used = []
-                for gi, (j0, j1) in enumerate(groups):
-                    t0, t1 = int(q_start[j0]), int(q_start[j1])
-                    src = given[gi][2] if given is not None else ragged_perms
-                    kw = {"index_arrays": src} if isinstance(src, dict) else {"perms": src}
-                    occ_net.forward_ragged_finish(hdls[gi], out=occ_out if (j0, j1) == (0, J) else occ_out[t0:t1], **kw)
-                    used.append((j0, j1, occ_net.last_ragged_perms))
-                ragged_perms = used[0][2] if len(used) == 1 else {"groups": used}
-            else:                                       # any other module with the reference's call signature: job by job
-                if _between is not None:
-                    _between()
-                r0, p0 = 0, 0
-                for q, m in zip(sizes_q, sizes_m):
-                    occ_out[r0:r0 + q] = macarons(mode='occupancy', partial_point_cloud=pc_all[p0:p0 + m][None], proxy_points=X_q[r0:r0 + q][None],
-                                                  view_harmonics=vh[r0:r0 + q][None]).view(-1, 1)
-                    r0, p0 = r0 + q, p0 + m
+            if not hasattr(occ_net, "forward_ragged"):
+                _occ_by_module(macarons, plan, built, occ_out, _between)
+            elif mdist.exchange_on(group):
+                ragged_perms = _occ_exchanged(occ_net, plan, built, occ_out, ragged_perms, device, group, _between)
+            else:
+                ragged_perms = _occ_grouped(occ_net, plan, built, occ_out, ragged_perms, _between)
             if record is not None:
                 record["ragged_perms"] = ragged_perms
     elif _between is not None:
@@ -865,6 +848,81 @@ def compute_scene_occupancy_probability_field(params, macarons, camera, surface_
     if _after is not None:
         _after()
     return X_world, view_harmonics, occ_probs
+
+
+def _occ_exchanged(occ_net, plan, built, occ_out, ragged_perms, device, group, between):
+    """The field pass's occupancy routes take the plan, the built job tensors (row_job [T], X_q [T,3], pc_all [tot,3], vh [T,64]) and the rows
+    to fill, and run `between` (the fill's CPU draws: upstream's order is Cell.fill, then the pass) exactly once.  This one, over the ranks of
+    `group`: the T query rows are block-partitioned, each rank runs the jobs its rows belong to with rank 0's draws (made after `between`),
+    the occupancies are all-gathered.  Returns the draws of all jobs."""
+    from .. import dist as mdist
+    world, rank = mdist.group_world_rank(group)
+    (_, X_q, pc_all, vh), (J, T, q_start, m_start), sizes_m = built, (plan.J, plan.T, plan.q_start, plan.m_start), plan.job_m.tolist()
+    if between is not None:
+        between()
+    if ragged_perms is None:                # rank 0 draws for every job, in job order (what the 1-rank pass draws)
+        ragged_perms = _broadcast_job_perms(occ_net, sizes_m, device, group, rank)
+    t0, t1 = mdist.shard_range(T, rank, world)
+    mine = [j for j in range(J) if q_start[j] < t1 and q_start[j + 1] > t0]
+    if mine:
+        q_l = [int(min(q_start[j + 1], t1) - max(q_start[j], t0)) for j in mine]
+        p0, p1 = int(m_start[mine[0]]), int(m_start[mine[-1] + 1])
+        draws_l = (_slice_index_arrays(occ_net, ragged_perms, sizes_m, mine[0], mine[-1] + 1) if isinstance(ragged_perms, dict)
+                   else [ragged_perms[j] for j in mine])
+        kw = {"index_arrays": draws_l} if isinstance(draws_l, dict) else {"perms": draws_l}
+        occ_l = occ_net.forward_ragged(pc_all[p0:p1].contiguous(), [sizes_m[j] for j in mine], X_q[t0:t1].contiguous(),
+                                       vh[t0:t1].contiguous(), q_l, **kw).view(-1, 1)
+    else:                                   # empty row shard (T < world): no kernels, the all-gather is joined
+        occ_l = torch.zeros(0, 1, dtype=torch.float32, device=device)
+    occ_out.copy_(mdist.allgather_rows(occ_l, T, group))
+    return ragged_perms
+
+
+def _occ_grouped(occ_net, plan, built, occ_out, ragged_perms, between):
+    """On this device.  The jobs run in G consecutive GROUPS when their hidden draws are made here on the CPU generator (~1 ms per 400k
+    permuted indices, inherent to the reference's stream): the first launches of EVERY group (which need no draw) are queued at once,
+    then, while the GPU works on group g, the host draws for group g + 1 -- only the first group's draws pass with the GPU short of
+    work.  Every job computes what it computes alone (launch shapes are chosen per cloud), so the grouping does not change a bit of the
+    result; the draws stay in job order.  Returns the draws used."""
+    row_job, X_q, pc_all, vh = built
+    J, q_start, m_start = plan.J, plan.q_start, plan.m_start
+    sizes_m, sizes_q = plan.job_m.tolist(), plan.job_q.tolist()
+    given = ragged_perms["groups"] if (isinstance(ragged_perms, dict) and "groups" in ragged_perms) else None
+    if given is not None:
+        groups = [(j0, j1) for j0, j1, _ in given]
+    elif ragged_perms is None:
+        groups = _job_groups(sizes_m)
+    else:
+        groups = [(0, J)]
+    hdls = []
+    for gi, (j0, j1) in enumerate(groups):
+        t0, t1, p0, p1 = int(q_start[j0]), int(q_start[j1]), int(m_start[j0]), int(m_start[j1])
+        whole = (j0, j1) == (0, J)
+        hdls.append(occ_net.forward_ragged_begin(pc_all if whole else pc_all[p0:p1], sizes_m[j0:j1], X_q if whole else X_q[t0:t1],
+                                                 vh if whole else vh[t0:t1], sizes_q[j0:j1], row_job=row_job if whole else None,
+                                                 arena="scone_occ_ragged" if gi == 0 else f"scone_occ_ragged_g{gi}"))
+    if between is not None:
+        between()                           # phase 1 of all groups is queued
+    used = []
+    for gi, (j0, j1) in enumerate(groups):
+        t0, t1 = int(q_start[j0]), int(q_start[j1])
+        src = given[gi][2] if given is not None else ragged_perms
+        kw = {"index_arrays": src} if isinstance(src, dict) else {"perms": src}
+        occ_net.forward_ragged_finish(hdls[gi], out=occ_out if (j0, j1) == (0, J) else occ_out[t0:t1], **kw)
+        used.append((j0, j1, occ_net.last_ragged_perms))
+    return used[0][2] if len(used) == 1 else {"groups": used}
+
+
+def _occ_by_module(macarons, plan, built, occ_out, between):
+    """Any other module with the reference's call signature: job by job."""
+    _, X_q, pc_all, vh = built
+    if between is not None:
+        between()
+    r0, p0 = 0, 0
+    for q, m in zip(plan.job_q.tolist(), plan.job_m.tolist()):
+        occ_out[r0:r0 + q] = macarons(mode='occupancy', partial_point_cloud=pc_all[p0:p0 + m][None], proxy_points=X_q[r0:r0 + q][None],
+                                      view_harmonics=vh[r0:r0 + q][None]).view(-1, 1)
+        r0, p0 = r0 + q, p0 + m
 
 
 def _broadcast_job_perms(occ_net, cloud_sizes, device, group, rank):
@@ -947,16 +1005,12 @@ def compute_occupancy_probability_for_supervision(params, macarons, camera, prox
     receives what repeats the pass: `sample_perm`, `cell_perm`, `candidates`, `visited` (linear ids of the cells that ran, in order),
     `job_cell`, `job_q`, `job_m`, `n_dummy`, `rows`, `row_job`, the job tensors `pc` / `x` / `view_harmonics`, `occ` (the network's
     rows) and `last_ragged_perms`.  default_value and min_length are upstream's unused parameters."""
-    ps, ss = proxy_scene, surface_scene
+    ps = proxy_scene
     occ_net = getattr(macarons, "occupancy", macarons)
     if not hasattr(occ_net, "forward_ragged_begin"):
         raise NotImplementedError("compute_occupancy_probability_for_supervision needs SconeOcc.forward_ragged (the batched HIP pass)")
-    if prediction_camera is None:
-        if camera is None:
-            raise NameError("Both camera and prediction_camera are equal to None.")
-        prediction_camera = camera.fov_camera_0
-    gl, gw, gh = ps.grid_l, ps.grid_w, ps.grid_h
-    n_cells = gl * gw * gh
+    prediction_camera = _prediction_camera_or(camera, prediction_camera)
+    n_cells = ps.grid_l * ps.grid_w * ps.grid_h
     if n_cells > 1023:
         raise NotImplementedError(f"the fused supervision pass handles grids of up to 1023 cells, this one has {n_cells}")
     nh, k = params.n_harmonics, params.k_for_knn
@@ -982,69 +1036,32 @@ def compute_occupancy_probability_for_supervision(params, macarons, camera, prox
     cand = np.nonzero(englobing)[0]                          # linear order = torch.unique(dim=0)'s lexicographic order (:1297)
     cell_perm = torch.randperm(len(cand))                   # :1308
     # ---- 3. the walk (:1310-1373): sizes are host numbers
-    tab = prep["tab"]
-    keys, lin_of = tab["keys"], tab["lin_of"]
-    s_st = _store_of(ss, device)
-    s_keys = keys if set(ss.cells.keys()) == set(keys) else sorted(ss.cells.keys(), key=lambda k_: lin_of.get(k_, 0))
-    if len(s_keys) == n_cells:
-        s_len, s_start = np.diff(s_st.off), s_st.off[:-1]
-    else:                                                   # a surface scene on another grid: by key
-        s_len = np.zeros(n_cells, np.int64); s_start = np.zeros(n_cells, np.int64)
-        for i_, k_ in enumerate(s_keys):
-            s_len[lin_of[k_]] = s_st.off[i_ + 1] - s_st.off[i_]; s_start[lin_of[k_]] = s_st.off[i_]
-    nbm = tab["neighbour_matrix"]
-    nb_len = np.where(nbm >= 0, s_len[np.maximum(nbm, 0)], 0)
-    m_cell = nb_len.sum(1)
+    surf = _surface_cells(surface_scene, prep["tab"], device)
     visited = []
     for c in cand[cell_perm.numpy()]:
         if len(visited) >= cap:
             break
-        if m_cell[c] > 2 * 2 * k and counts[c] > 0:          # :1341
+        if surf.m_cell[c] > 2 * 2 * k and counts[c] > 0:     # :1341
             visited.append(int(c))
     n_dummy = max(0, n_pass_max - len(visited))              # :1376
-    cells_run = np.asarray(visited, np.int64)
-    n_chunks = -(-counts[cells_run] // chunk) if len(visited) else np.zeros(0, np.int64)
-    job_cell = np.repeat(cells_run, n_chunks)                # one job per (cell, chunk of <= `chunk` queries): a cell is ONE pass
-    J = int(job_cell.size)
-    T = tot = 0
-    rows = row_job = X_q = pc_all = vh = None
-    if J:
-        lo = (np.arange(J) - np.repeat(np.cumsum(n_chunks) - n_chunks, n_chunks)) * chunk
-        job_q = np.minimum(chunk, counts[job_cell] - lo).astype(np.int64)
-        job_m = m_cell[job_cell].astype(np.int64)
-        q_start = np.concatenate(([0], np.cumsum(job_q)))
-        m_start = np.concatenate(([0], np.cumsum(job_m)))
-        T, tot = int(q_start[-1]), int(m_start[-1])
-        jt = np.stack((sel_off[job_cell] + lo, q_start[:-1], m_start[:-1], np.zeros(J, np.int64)), 1).astype(np.int64)
-        seg_len = nb_len[job_cell]                            # surface segments: the cell's non-empty neighbours, ascending cell order
-        keep = seg_len > 0
-        seg_l = seg_len[keep]
-        st_ = np.stack((s_start[nbm[job_cell][keep]], np.cumsum(seg_l) - seg_l, np.nonzero(keep)[0], np.zeros(seg_l.size, np.int64)),
-                       1).astype(np.int64)
-        n_seg = int(st_.shape[0])
-        xf = np.ascontiguousarray(prep["xf_all"][job_cell])
-        # ONE upload: job table | segment table | per-job transform | bin permutation | the jobs' first query rows (for the scatter)
-        raw = np.concatenate((jt.reshape(-1).view(np.uint8), st_.reshape(-1).view(np.uint8), xf.reshape(-1).view(np.uint8),
-                              prep["perm"].astype(np.int32).view(np.uint8)))
-        pad = (-raw.size) % 8
-        raw = np.concatenate((raw, np.zeros(pad, np.uint8), q_start.astype(np.int64).view(np.uint8)))
-        tables = ops.h2d(raw, torch.uint8, device)
-        n_perm = prep["perm"].size
-        o_perm = 32 * (J + n_seg) + 80 * J
-        perm_d = tables[o_perm:o_perm + 4 * n_perm].view(torch.int32)
-        job_off_d = tables[o_perm + 4 * n_perm + pad:].view(torch.int64)
-        X_world = torch.empty((T, 3), dtype=torch.float32, device=device)
-        vh = torch.empty((T + n_dummy * (k + 1), nh), dtype=torch.float32, device=device)
-        rows, row_job, X_q, pc_all = ops.field_build(tables, J, n_seg, sel, ps.proxy_points, s_st.pts, ps.view_states, perm_d,
-                                                     prep["vh_mt"], T, tot, X_world, vh)
-        sizes_m, sizes_q = job_m.tolist(), job_q.tolist()
-    else:
-        job_q = job_m = np.zeros(0, np.int64)
-        sizes_m, sizes_q = [], []
-        job_off_d = None
-        vh = torch.empty((n_dummy * (k + 1), nh), dtype=torch.float32, device=device)
-    # ---- 4. the dummy passes (:1376-1388) as the LAST jobs: raw proxy points, zero harmonics; their rows are never scattered
+    # one job per (cell, chunk of <= `chunk` queries), IN VISITING ORDER: a cell is ONE pass; the jobs' first query rows ride along as
+    # the upload's tail (for the scatter)
+    plan = _plan_jobs(visited, counts, sel_off, surf, prep["tab"]["neighbour_matrix"], prep["xf_all"], prep["perm"], chunk, tail=True)
+    J, T, sizes_m, sizes_q = plan.J, plan.T, plan.job_m.tolist(), plan.job_q.tolist()
     T_all = T + n_dummy * (k + 1)
+    vh = torch.empty((T_all, nh), dtype=torch.float32, device=device)
+    rows = row_job = row_job_all = X_q = pc_all = job_off_d = None
+    if J:
+        tables = ops.h2d(plan.raw, torch.uint8, device)
+        o_perm = ops.field_table_offsets(J, plan.n_seg)[2]
+        o_end = o_perm + 4 * prep["perm"].size
+        perm_d = tables[o_perm:o_end].view(torch.int32)
+        job_off_d = tables[o_end + (-o_end) % 8:].view(torch.int64)
+        X_world = torch.empty((T, 3), dtype=torch.float32, device=device)
+        rows, row_job, X_q, pc_all = ops.field_build(tables, J, plan.n_seg, sel, ps.proxy_points, surf.store.pts, ps.view_states, perm_d,
+                                                     prep["vh_mt"], T, plan.tot, X_world, vh)
+        row_job_all = row_job
+    # ---- 4. the dummy passes (:1376-1388) as the LAST jobs: raw proxy points, zero harmonics; their rows are never scattered
     if n_dummy:
         d_pc, d_x = ps.proxy_points[:2 * 2 * k + 1], ps.proxy_points[:k + 1]
         vh[T:].zero_()
@@ -1054,8 +1071,6 @@ def compute_occupancy_probability_for_supervision(params, macarons, camera, prox
         row_job_all = torch.cat((row_job, d_job)) if J else d_job
         sizes_m = sizes_m + [int(d_pc.shape[0])] * n_dummy
         sizes_q = sizes_q + [int(d_x.shape[0])] * n_dummy
-    else:
-        row_job_all = row_job
     if J + n_dummy == 0:                                    # a cap of 0: nothing runs, upstream returns the sampled points' zeros
         if record is not None:
             record.update(sample_perm=sample_perm, cell_perm=cell_perm, candidates=cand, visited=visited, n_dummy=0)
@@ -1077,8 +1092,8 @@ def compute_occupancy_probability_for_supervision(params, macarons, camera, prox
     else:
         probas = ops.supervision_scatter(rows, occ.reshape(-1), job_off_d, J, pos, n_out)
     if record is not None:
-        record.update(sample_perm=sample_perm, cell_perm=cell_perm, candidates=cand, visited=visited, job_cell=job_cell, job_q=job_q,
-                      job_m=job_m, n_dummy=n_dummy, rows=rows, row_job=row_job_all, pc=pc_all, x=X_q, view_harmonics=vh,
+        record.update(sample_perm=sample_perm, cell_perm=cell_perm, candidates=cand, visited=visited, job_cell=plan.job_cell, job_q=plan.job_q,
+                      job_m=plan.job_m, n_dummy=n_dummy, rows=rows, row_job=row_job_all, pc=pc_all, x=X_q, view_harmonics=vh,
                       cloud_sizes=sizes_m, query_sizes=sizes_q, occ=occ.detach(), pos=pos, job_offsets=job_off_d,
                       last_ragged_perms=occ_net.last_ragged_perms)
     return prediction_mask, probas
@@ -1335,23 +1350,13 @@ def scone_supervision_step(params, macarons, proxy_scene, surface_scene, frames,
     # 4, 5 ---- predictions, with their graphs
     prediction_mask = predicted_occs = predicted_gains = None
     if predict:
-        if prediction_camera is None:
-            raise NameError("Both camera and prediction_camera are equal to None.")
+        prediction_camera = _prediction_camera_or(None, prediction_camera)
         prediction_mask, predicted_occs = compute_occupancy_probability_for_supervision(
             params, macarons, None, ps, close_mask, ss, n_cell_per_occ_forward_pass, device, prediction_camera=prediction_camera,
             differentiable=True, record=record)
-        th = params.distance_factor_th
-        smooth = th == 'smooth'
-        if th is None or smooth:
-            th = sensor_distance_threshold(params, cams[0], ss.cell_resolution)
-        diag = getattr(ps, "_mcr_box_diag", None)       # a constant of the scene: read back once, not once per step
-        if diag is None:
-            diag = torch.linalg.norm(ps.x_max - ps.x_min).item()
-            try:
-                ps._mcr_box_diag = diag
-            except Exception:
-                pass
-        Mv = prediction_camera if torch.is_tensor(prediction_camera) else _world_to_view_matrix(prediction_camera)
+        th, smooth = _distance_threshold(params, cams[0], ss.cell_resolution)
+        diag = _box_diag(ps)
+        Mv =prediction_camera if torch.is_tensor(prediction_camera) else _world_to_view_matrix(prediction_camera)
         Mv = ops.h2d(Mv.reshape(1, 4, 4), torch.float32, device).expand(K, -1, -1)
         predicted_gains = predict_coverage_gain_for_cameras(macarons.visibility, X_world, view_harmonics, occ_probs, recs, xc, Mv, diag,
                                                             seq_len=params.seq_len, min_occ=params.min_occ_for_proxy_points,
@@ -1367,14 +1372,7 @@ def scone_supervision_step(params, macarons, proxy_scene, surface_scene, frames,
                                                  surface_epsilon_factor=params.surface_epsilon_factor).view(K, 1)
     ss.set_all_features_to_value(value=1.)
     # 9, 10 ---- proxy scene
-    idx_f = getattr(ps, "_mcr_index_feature", None)
-    if idx_f is None or idx_f.shape[0] != P or idx_f.device != ps.proxy_points.device:
-        idx_f = torch.arange(P, device=device, dtype=torch.float32).view(-1, 1)
-        try:
-            ps._mcr_index_feature = idx_f
-        except Exception:
-            pass
-    ps.fill_cells(ps.proxy_points, features=idx_f, valid=fov_bits != 0)
+    ps.fill_cells(ps.proxy_points, features=_index_feature(ps, device), valid=fov_bits != 0)
     ops.proxy_scene_update_frames_(ps.proxy_points, fov_bits, sgn, xc, 3 * ps.distance_between_proxy_points, params.carving_tolerance,
                                    ps.score_threshold, ps.view_state_n_elev, ps.view_state_n_azim, ps.view_states, ps.proxy_n_inside_fov,
                                    ps.proxy_n_behind_depth, ps.proxy_supervision_occ, ps.out_of_field)

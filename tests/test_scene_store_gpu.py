@@ -301,10 +301,15 @@ def test_field_build(dev, T):
     s_off = np.concatenate(([0], np.cumsum(rng.integers(0, 40, nk) * (rng.random(nk) < 0.7)))).astype(np.int64)
     S_all = rng.standard_normal((int(s_off[-1]), 3)).astype(F)
     pp = rng.standard_normal((P, 3)).astype(F)
-    jt, st, job_cell, T_, tot, n_chunks = _job_tables((counts[:nk] > 0).astype(np.int64), counts[:nk], sel_off, s_off, _neighbour_matrix(grid), chunk, 1)
+    nbm = _neighbour_matrix(grid)
+    jt, st, job_cell, T_, tot, n_chunks = _job_tables((counts[:nk] > 0).astype(np.int64), counts[:nk], sel_off, s_off, nbm, chunk, 1)
     J, n_seg = len(jt), len(st)
     assert T_ == T and tot > 0 and n_seg > J and (T != 4097 or (n_chunks[0] == 3 and J == 8)) and (T != 1 or J == 1)
-    xf = rng.standard_normal((nk, 20)).astype(F)[job_cell]
+    xf_all = rng.standard_normal((nk, 20)).astype(F)
+    xf = xf_all[job_cell]
+    from macarons_amd.utility import macarons_utils as mu                  # the product's planner: the same jobs, the same upload (below)
+    surf = mu._SurfaceCells(None, s_off[:-1], np.diff(s_off), True, nbm)
+    cells_run = np.nonzero((counts[:nk] > 0) & (surf.m_cell > 2 * 2 * 1))[0]
     sel = _Sel()
     sel.rows_order = _t(rows_order, dev, torch.int32)
     pp_d, S_d = _t(pp, dev), _t(S_all, dev)
@@ -316,6 +321,8 @@ def test_field_build(dev, T):
             tag = (T, n_bins, perm is not None)
             raw = np.concatenate((jt.reshape(-1).view(np.uint8), st.reshape(-1).view(np.uint8), np.ascontiguousarray(xf).reshape(-1).view(np.uint8),
                                   (perm if perm is not None else np.zeros(0, np.int32)).view(np.uint8)))
+            plan = mu._plan_jobs(cells_run, counts[:nk], sel_off, surf, nbm, xf_all, perm if perm is not None else np.zeros(0, np.int32), chunk)
+            assert (plan.J, plan.n_seg, plan.T, plan.tot) == (J, n_seg, T, tot) and np.array_equal(plan.raw, raw), tag
             tables = _t(raw, dev, torch.uint8)
             perm_d = tables[32 * (J + n_seg) + 80 * J:].view(torch.int32) if perm is not None else None
             X_world = torch.full((T + 3, 3), -7., device=dev)
