@@ -59,20 +59,11 @@ def _guarded(impl, scone_occ, range_guard, group, draws, device, scone_vis=None)
     capturing = torch.cuda.is_current_stream_capturing()
     prev = scone_occ.range_guard
     guard = range_guard and prev != "off" and ops.current_variant() in (6, 7)
-    scone_occ.range_guard = "defer" if (guard or prev != "off") else "off"
-    # SconeVis (its encoders run on the same fp16 planes) reports into the SAME flag: one read-back covers both networks
-    vis_prev = None
-    if scone_vis is not None and hasattr(scone_vis, "range_guard"):
-        vis_prev = (scone_vis.range_guard, scone_vis._range_flag)
-        scone_vis.range_guard = scone_occ.range_guard
-    try:
-        # the flag exists on every rank before the step (not only on ranks that run a guarded forward: a rank with an empty query
-        # shard runs none), so that whether the all-reduce below is entered depends on rank-invariant state only; and whenever the
-        # step reports it (range_guard=False too), so that SconeVis writes into it rather than into a flag of its own
-        flagged = scone_occ.range_guard != "off" and ops.current_variant() in (6, 7)
-        scone_occ.clear_range_flag(device if flagged else None)
-        if vis_prev is not None:
-            scone_vis._range_flag = scone_occ.range_flag()
+    # the flag exists on every rank before the step (not only on ranks that run a guarded forward: a rank with an empty query shard
+    # runs none), so that whether the all-reduce below is entered depends on rank-invariant state only; and whenever the step reports
+    # it (range_guard=False too), so that SconeVis (the scope's peer) writes into it rather than into a flag of its own
+    flagged = prev != "off" and ops.current_variant() in (6, 7)
+    with scone_occ.range_scope("off" if prev == "off" else "defer", device if flagged else None, peer=scone_vis):
         kw = draws() if (guard and not capturing) else {}
         out = impl(**kw)
         flag = scone_occ.range_flag() if ops.current_variant() in (6, 7) else None
@@ -95,10 +86,6 @@ def _guarded(impl, scone_occ, range_guard, group, draws, device, scone_vis=None)
                     out = impl(**kw)
                 out["range_flag"], out["fallback_variant"] = None, 5
                 out.pop("host", None)
-    finally:
-        scone_occ.range_guard = prev
-        if vis_prev is not None:
-            scone_vis.range_guard, scone_vis._range_flag = vis_prev
     return out
 
 

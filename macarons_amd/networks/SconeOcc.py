@@ -6,10 +6,11 @@ Hidden RNG: SconeOcc.forward draws torch.randperm on the CPU
 (SconeOcc.py:269 and :311 twice).  This class draws them on the host in the same order, or takes them
 explicitly through `perms=` so tests can pin them.
 """
+import dataclasses
+
 import numpy as np
-import os
 import torch
-import torch.nn.functional as F          # noqa: F401
+import torch.nn.functional as F          # noqa: F401  (not used here: a public name of upstream's module, tests/test_patch_reference.py)
 from torch import nn
 
 from .. import autograd as A
@@ -17,7 +18,10 @@ from .. import ops, _lib
 from .Attention import (Embedding, Encoder, FeedForward, MultiHeadSelfAttention, attention, knn_gather,   # noqa: F401
                         _f32c, _inference_only)     # the public ones are what upstream's `from .Attention import *` hands on
 from ..utility.utils import get_knn_points   # noqa: F401  (SconeOcc.py:4)
-from .packing import encoder_weight_planes, padded_weight_planes, weight_planes, RangeGuard, BlobCache, HeadPlaneCache, TableCache, param_key, invalidate as _invalidate_key, freeze as _freeze_key
+from ..utility.host import batched_draws_ok, native_op
+from .packing import (BlobCache, HeadPlaneCache, TableCache, _param_key, grad_slots, planes_tail, table_slots, invalidate as _invalidate_key,
+                      freeze as _freeze_key)
+from .range_guard import RangeGuard
 
 
 class XEmbedding(nn.Module):
@@ -40,22 +44,78 @@ class XEmbedding(nn.Module):
         return ops.linear(res, _f32c(self.linear3.weight), _f32c(self.linear3.bias), gelu=True)
 
 
-_NATIVE_RAGGED = []
-
-
 def _native_ragged_tables():
-    """Is torch.ops.macarons.ragged_tables there (the C++ extension built)?  MCR_NATIVE_RAGGED_TABLES=0: the numpy restatement (A/B, tests)."""
-    if not _NATIVE_RAGGED:
-        import os
-        ok = os.environ.get("MCR_NATIVE_RAGGED_TABLES", "1") != "0"
-        if ok:
-            try:
-                from .. import torch_ops  # noqa: F401
-                ok = hasattr(torch.ops.macarons, "ragged_tables")
-            except Exception:
-                ok = False
-        _NATIVE_RAGGED.append(ok)
-    return _NATIVE_RAGGED[0]
+    """Is torch.ops.macarons.ragged_tables there (the C++ extension built)?  MCR_NATIVE_RAGGED_TABLES=0: ragged_job_tables (A/B, tests)."""
+    return native_op("ragged_tables", "MCR_NATIVE_RAGGED_TABLES")      # (read from os.environ there, once)
+
+
+def ragged_job_tables(cloud_sizes, query_sizes, rows, with_row_job):
+    """The tables a ragged pass uploads in front of its first launch, as one int64 array (what torch.ops.macarons.ragged_tables builds in
+    one C++ loop): cloud offsets [J + 1] | one (job, first query row, rows, 0) record per block of `rows` queries | with_row_job: the
+    job of every query row [T].  A job without queries has no block."""
+    J = len(cloud_sizes)
+    off0 = np.concatenate(([0], np.cumsum(cloud_sizes))).astype(np.int64)
+    qs = np.asarray(query_sizes, np.int64)
+    q0 = np.concatenate(([0], np.cumsum(qs)))
+    nb = -(-qs // rows)                                              # query blocks per job
+    bj = np.repeat(np.arange(J, dtype=np.int64), nb)                 # job of every block
+    b_in = np.arange(int(nb.sum()), dtype=np.int64) - np.repeat(np.cumsum(nb) - nb, nb)     # block index inside its job
+    blocks = np.stack((bj, q0[bj] + b_in * rows, np.minimum(rows, qs[bj] - b_in * rows), np.zeros_like(bj)), 1)
+    parts = [off0, blocks.reshape(-1)]
+    if with_row_job:
+        parts.append(np.repeat(np.arange(J, dtype=np.int64), qs))
+    return np.concatenate(parts)
+
+
+def ragged_index_arrays(perms, off0, J, Lg):
+    """The index arrays of a ragged pass's down-sampled clouds from given draws (per job the three index tensors of draw_perms), as
+    one int64 array (what torch.ops.macarons.scone_occ_draws returns for its own draws): g_idx [J, Lg] | idx1 | idx2 | off1 [J + 1] |
+    off2 [J + 1] | global_len [J].  off0: the clouds' offsets [J + 1]."""
+    p0s = [np.asarray(p[0], dtype=np.int64)[:Lg] for p in perms]
+    p1s = [np.asarray(p[1], dtype=np.int64) for p in perms]
+    p2s = [np.asarray(p[2], dtype=np.int64) for p in perms]
+    n0 = np.asarray([len(p) for p in p0s], np.int64)
+    n1 = np.asarray([len(p) for p in p1s], np.int64)
+    n2 = np.asarray([len(p) for p in p2s], np.int64)
+    off1 = np.concatenate(([0], np.cumsum(n1)))
+    off2 = np.concatenate(([0], np.cumsum(n2)))
+    g_idx = np.repeat(off0[:J], Lg).reshape(J, Lg)                # padding rows: any valid point (masked by global_len)
+    col = np.arange(int(n0.sum()), dtype=np.int64) - np.repeat(np.cumsum(n0) - n0, n0)
+    g_idx[np.repeat(np.arange(J), n0), col] = np.concatenate(p0s) + np.repeat(off0[:J], n0)
+    idx1 = np.concatenate(p1s) + np.repeat(off0[:J], n1)
+    idx2 = np.concatenate(p2s) + np.repeat(off1[:J], n2)          # scale 2 indexes scale 1's rows (SconeOcc.py:311)
+    return np.concatenate([g_idx.reshape(-1), idx1, idx2, off1, off2, n0])
+
+
+@dataclasses.dataclass(slots=True)
+class _Begun:
+    """Handle of forward_begin (opaque to callers): the contiguous inputs phase 1 ran on, and what forward(begun=) checks before it
+    trusts them."""
+    pc: torch.Tensor
+    x: torch.Tensor
+    variant: int
+    sizes: list
+    src: tuple
+    epoch: int
+
+
+@dataclasses.dataclass(slots=True)
+class _RaggedPass:
+    """Handle of forward_ragged_begin (opaque to callers): the inputs, the uploaded tables, the pass's memo of weight images per
+    variant (`images`), and the epoch of the arena that holds phase 1's results (`epoch1`, known once phase 1 is queued)."""
+    pc: torch.Tensor
+    x: torch.Tensor
+    vh: torch.Tensor
+    variant: int
+    cloud_sizes: list
+    query_sizes: list
+    off0: np.ndarray
+    d_off0: torch.Tensor
+    d_row_job: torch.Tensor
+    d_blocks: torch.Tensor
+    arena: str
+    images: dict = dataclasses.field(default_factory=dict)
+    epoch1: int = None
 
 
 class PCTransformer(nn.Module):
@@ -92,26 +152,8 @@ class PCTransformer(nn.Module):
     def _grad_slots(self):
         """(parameters, slots): every parameter of the module with its place in weight_table() -- (table index, row slice or None);
         w_q / w_k / w_v are rows 0:32 / 32:64 / 64:192 of their encoder's packed qkv entries."""
-        slots = {id(t): (k, None) for k, t in enumerate((self.embedding.linear1.weight, self.embedding.linear1.bias,
-                                                          self.embedding.linear2.weight, self.embedding.linear2.bias))}
-        for e, enc in enumerate(self.encoders):
-            o = 4 + 12 * e
-            qk = enc.mhsa.w_q.weight.shape[0]
-            rows = ((0, qk), (qk, 2 * qk), (2 * qk, 2 * qk + enc.mhsa.w_v.weight.shape[0]))
-            for lin, r in zip((enc.mhsa.w_q, enc.mhsa.w_k, enc.mhsa.w_v), rows):
-                slots[id(lin.weight)], slots[id(lin.bias)] = (o + 2, r), (o + 3, r)
-            for k, t in enumerate((enc.norm1.weight, enc.norm1.bias)):
-                slots[id(t)] = (o + k, None)
-            for k, t in enumerate((enc.mhsa.out.weight, enc.mhsa.out.bias, enc.norm2.weight, enc.norm2.bias, enc.ff.linear1.weight,
-                                   enc.ff.linear1.bias, enc.ff.linear2.weight, enc.ff.linear2.bias)):
-                slots[id(t)] = (o + 4 + k, None)
-        for k, t in enumerate((self.norm.weight, self.norm.bias, self.linear0.weight, self.linear0.bias)):
-            slots[id(t)] = (28 + k, None)
-        params = tuple(self.parameters())
-        missing = [n for n, p in self.named_parameters() if id(p) not in slots]
-        if missing:
-            raise NotImplementedError(f"PCTransformer HIP backward: parameters outside the weight table: {missing}")
-        return params, tuple(slots[id(p)] for p in params)
+        return grad_slots(self, table_slots(self.embedding, self.encoders, (self.norm.weight, self.norm.bias, self.linear0.weight,
+                                                                            self.linear0.bias)))
 
     def forward(self, pc, mask=None):
         """pc [n_clouds, seq_len, 3] -> [n_clouds, feature_dim].  Differentiable (once) without a mask: HIP forward, HIP backward
@@ -138,13 +180,8 @@ class PCTransformer(nn.Module):
         return ops.pc_transformer_forward(pc, self.weight_table(), self.feature_dim)
 
     def weight_table_with_planes(self):
-        """weight_table() + the encoders' weights as fp16 hi/lo planes (8 blobs) + the end layers' (3): include/macarons_hip.h, PLANES / END PLANES."""
-        t = self.weight_table()
-        for e in self.encoders:
-            t += encoder_weight_planes(e)
-        t += list(padded_weight_planes(self.embedding.linear2.weight, self.embedding.linear2.bias, 128, 128))
-        t += [weight_planes(self.linear0.weight)]
-        return t
+        """weight_table() + the encoders' weights as fp16 hi/lo planes (8 blobs) + the end layers' (3): packing.planes_tail."""
+        return self.weight_table() + planes_tail(self.encoders, self.embedding, (self.linear0.weight,))
 
 
 class SconeOcc(RangeGuard, nn.Module):
@@ -184,24 +221,6 @@ class SconeOcc(RangeGuard, nn.Module):
         self._table_cache = TableCache()
         self._head_cache = HeadPlaneCache()
         self._key_cache = {}
-        # Range guard of the default numerics (variant 6: matrix products on fp16 hi/lo planes, valid for |activation| < 65504;
-        # the reference is plain fp32, Attention.py:98-128): the kernels flag a non-finite occupancy -- what an out-of-range
-        # activation turns into -- and the forward is repeated on variant 5 (bf16 hi/mid/lo, the whole fp32 range).
-        #   "sync"  (default: correct for a drop-in caller -- the reference never returns NaN here) read the flag after every forward
-        #           (one 4-byte read-back = a pipeline drain) and repeat that forward at once on variant 5: the FIRST overflowed
-        #           stand-alone forward already returns finite occupancies within the 1e-4 contract;
-        #   "defer" leave it in range_flag() for the caller: nbv_step / macarons_nbv_decision switch to this for their duration and
-        #           check ONE flag once, at the end of the decision (the performance paths never pay the per-forward read-back);
-        #   "async" (opt-in) never stalls: after every forward the flag is copied to pinned host memory behind the kernels; the NEXT
-        #           forward (or check_range()) looks at copies that have landed.  A set flag means an earlier forward returned
-        #           non-finite occupancies (visible as such to the caller): it is reported once (RuntimeWarning) and every later
-        #           forward of this module runs on variant 5 -- for a caller that keeps upstream's chunk loop and cannot afford a
-        #           device->host round trip per chunk, and checks check_range(wait=True) at its own boundaries;
-        #   "off"   no check.
-        self.range_guard = "sync"
-        self._range_flag = None
-        self._range_pending = []            # (pinned host int32 [1], event) of forwards whose flag has not been looked at yet
-        self._full_range = False            # True once an overflow was seen: variant 5 from then on
 
     def freeze_weight_caches(self, on=True):
         """Inference mode: fingerprint the parameters once, now, and trust them unchanged until freeze_weight_caches(False) or
@@ -248,22 +267,12 @@ class SconeOcc(RangeGuard, nn.Module):
                     self.linear3):
             slots[id(lin.weight)], slots[id(lin.bias)] = (o, None), (o + 1, None)
             o += 2
-        params = tuple(self.parameters())
-        missing = [n for n, p_ in self.named_parameters() if id(p_) not in slots]
-        if missing:
-            raise NotImplementedError(f"SconeOcc HIP backward: parameters outside the weight table: {missing}")
-        return params, tuple(slots[id(p_)] for p_ in params)
+        return grad_slots(self, slots)
 
     def weight_table_with_planes(self):
-        """weight_table() + the global transformer's encoder weights as fp16 hi/lo planes (8 blobs): see SconeVis.weight_table_with_planes."""
-        t = self.weight_table()
+        """weight_table() + the global transformer's encoder weights as fp16 hi/lo planes (8 blobs) and its end layers' (3)."""
         g = self.global_transformer
-        for e in g.encoders:
-            t += encoder_weight_planes(e)
-        # the layers either side of the encoders (3 blobs): the embedding's second layer zero-padded to 128 x 128 (+ its padded bias), linear0
-        t += list(padded_weight_planes(g.embedding.linear2.weight, g.embedding.linear2.bias, 128, 128))
-        t += [weight_planes(g.linear0.weight)]
-        return t
+        return self.weight_table() + planes_tail(g.encoders, g.embedding, (g.linear0.weight,))
 
     def ds_factor(self, full_seq_len):
         """SconeOcc.py:281-288."""
@@ -329,138 +338,84 @@ class SconeOcc(RangeGuard, nn.Module):
             raise NotImplementedError("forward_ragged implements the default architecture on the fused local-transformer path")
         dev = x.device
         J = len(cloud_sizes)
-        L = _lib.lib()
-        Lg = self.seq_len
         pc = pc.contiguous()
-        variant = ops.current_variant()
-        rows = int(L.mcr_knn_rows_per_block())
+        rows = int(_lib.lib().mcr_knn_rows_per_block())
         if _native_ragged_tables():                                      # one C++ loop (this runs in front of the pass's first launch)
             host = torch.ops.macarons.ragged_tables([int(m) for m in cloud_sizes], [int(q) for q in query_sizes], rows, row_job is None)
-            n_blk4 = host.numel() - (J + 1) - (sum(int(q) for q in query_sizes) if row_job is None else 0)
-            off0 = host[:J + 1].numpy()
-            early = ops.h2d(host, torch.int64, dev)
         else:
-            off0 = np.concatenate(([0], np.cumsum(cloud_sizes))).astype(np.int64)
-            qs = np.asarray(query_sizes, np.int64)
-            q0 = np.concatenate(([0], np.cumsum(qs)))
-            nb = -(-qs // rows)                                              # query blocks per job
-            bj = np.repeat(np.arange(J, dtype=np.int64), nb)                 # job of every block
-            b_in = np.arange(int(nb.sum()), dtype=np.int64) - np.repeat(np.cumsum(nb) - nb, nb)     # block index inside its job
-            blocks = np.stack((bj, q0[bj] + b_in * rows, np.minimum(rows, qs[bj] - b_in * rows), np.zeros_like(bj)), 1)
-            parts = [off0, blocks.reshape(-1)]
-            if row_job is None:
-                parts.append(np.repeat(np.arange(J, dtype=np.int64), qs))
-            early = ops.h2d(np.concatenate(parts), torch.int64, dev)
-            n_blk4 = blocks.size
-        d_off0 = early[:J + 1]
-        d_blocks = early[J + 1:J + 1 + n_blk4].to(torch.int32).view(-1, 4)
-        d_row_job = early[J + 1 + n_blk4:].to(torch.int32) if row_job is None else row_job
-        state = {}
-
-        def caches(v):
-            key = param_key(self, self._key_cache)                  # one fingerprint of the parameters for every derived image
-            state[v] = ([c.get(t, v, key) for c, t in zip(self._blob_caches, self.local_transformers)],
-                        self._head_cache.get(self, key) if v in (6, 7) else None, self._table_cache.get(self, self.weight_table_with_planes, key))
-            return state[v]
-
-        def phase1(v):
-            blobs, head, table = state[v] if v in state else caches(v)
-            ops.scone_occ_forward_ragged(None, None, [pc], [d_off0], x, view_harmonics, d_row_job, d_blocks, table, blobs, head, None,
-                                         phase=1, Lg=Lg, arena=arena)
-
+            host = torch.from_numpy(ragged_job_tables(cloud_sizes, query_sizes, rows, row_job is None))
+        n_blk4 = host.numel() - (J + 1) - (sum(int(q) for q in query_sizes) if row_job is None else 0)
+        early = ops.h2d(host, torch.int64, dev)
+        h = _RaggedPass(pc=pc, x=x, vh=view_harmonics, variant=ops.current_variant(), cloud_sizes=cloud_sizes,
+                        query_sizes=query_sizes, off0=host[:J + 1].numpy(), d_off0=early[:J + 1],
+                        d_blocks=early[J + 1:J + 1 + n_blk4].to(torch.int32).view(-1, 4),
+                        d_row_job=early[J + 1 + n_blk4:].to(torch.int32) if row_job is None else row_job, arena=arena)
         with torch.no_grad():
-            phase1(variant)
-        return {"pc": pc, "x": x, "vh": view_harmonics, "J": J, "Lg": Lg, "variant": variant, "off0": off0, "d_off0": d_off0,
-                "d_row_job": d_row_job, "d_blocks": d_blocks, "state": state, "caches": caches, "phase1": phase1,
-                "cloud_sizes": cloud_sizes, "query_sizes": query_sizes, "arena": arena, "epoch1": ops.scone_occ_epoch(dev, arena)}
+            self._ragged_phase1(h, h.variant)
+        h.epoch1 = ops.scone_occ_epoch(dev, arena)
+        return h
+
+    def _ragged_phase1(self, h, v):
+        table, blobs, head = self._images(v, h.images)
+        ops.scone_occ_forward_ragged(None, None, [h.pc], [h.d_off0], h.x, h.vh, h.d_row_job, h.d_blocks, table, blobs, head, None,
+                                     phase=1, Lg=self.seq_len, arena=h.arena)
+
+    def _ragged_index_arrays(self, h, perms):
+        """The uploaded index arrays of the pass's down-sampled clouds (`last_ragged_perms`) from `perms`, or from draws made here."""
+        J, Lg = len(h.cloud_sizes), self.seq_len
+        if perms is None and not batched_draws_ok():                     # torch.randperm was replaced from Python: honour it
+            perms = [self.draw_perms(int(m)) for m in h.cloud_sizes]
+        if perms is None:
+            # the 3 J draws in job order on the CPU generator -- exactly the draws J sequential forward() calls make -- by ONE call
+            # into the C++ extension (the same at::randperm calls; no dispatcher round trip and no numpy per draw), which returns
+            # the index arrays ready to upload
+            from .. import torch_ops  # noqa: F401
+            sz = [self.scale_sizes(int(m)) for m in h.cloud_sizes]
+            flat = torch.ops.macarons.scone_occ_draws([s_[0] for s_ in sz], [s_[1] for s_ in sz], [s_[2] for s_ in sz], Lg)
+            n1, n2 = sum(s_[1] for s_ in sz), sum(s_[2] for s_ in sz)
+        else:
+            flat = ragged_index_arrays(perms, h.off0, J, Lg)
+            n1, n2 = sum(len(p[1]) for p in perms), sum(len(p[2]) for p in perms)
+        d = ops.h2d(flat, torch.int64, h.x.device)                       # ONE upload
+        cut, o = [], 0
+        for n in (J * Lg, n1, n2, J + 1, J + 1, J):
+            cut.append(d[o:o + n]); o += n
+        return {"g_idx": cut[0], "idx1": cut[1], "idx2": cut[2], "off1": cut[3], "off2": cut[4], "g_len": cut[5].to(torch.int32)}
 
     def forward_ragged_finish(self, h, perms=None, index_arrays=None, out=None, differentiable=False):
         """Second half of forward_ragged: the hidden draws (unless given), the down-sampled clouds, phase 2.  differentiable: see
         forward_ragged."""
-        self._check_differentiable(differentiable, h["pc"], out)
-        L = _lib.lib()
-        pc, x, view_harmonics, J, Lg, variant, off0 = h["pc"], h["x"], h["vh"], h["J"], h["Lg"], h["variant"], h["off0"]
-        cloud_sizes, d_off0, d_row_job, d_blocks, state, caches, phase1 = (h["cloud_sizes"], h["d_off0"], h["d_row_job"], h["d_blocks"],
-                                                                          h["state"], h["caches"], h["phase1"])
-        dev = x.device
-        if index_arrays is not None:
-            ia = index_arrays
-            self.last_ragged_perms = ia                                    # (a caller that repeats the pass on another variant re-uses the draws)
-            pc_global = pc[ia["g_idx"]].view(J, Lg, 3)
-            pc1 = pc[ia["idx1"]]
-            pc2 = pc1[ia["idx2"]]
-            g_len_d, d_off1, d_off2 = ia["g_len"], ia["off1"], ia["off2"]
-        else:
-            from ..utility.host import batched_draws_ok
-            if perms is None and not batched_draws_ok():                 # torch.randperm was replaced from Python: honour it
-                perms = [self.draw_perms(int(m)) for m in cloud_sizes]
-            if perms is None:
-                # the 3 J draws in job order on the CPU generator -- exactly the draws J sequential forward() calls make -- by ONE call
-                # into the C++ extension (the same at::randperm calls; no dispatcher round trip and no numpy per draw), which returns
-                # the index arrays below ready to upload
-                from .. import torch_ops  # noqa: F401
-                sz = [self.scale_sizes(int(m)) for m in cloud_sizes]
-                flat = torch.ops.macarons.scone_occ_draws([s_[0] for s_ in sz], [s_[1] for s_ in sz], [s_[2] for s_ in sz], Lg)
-                n1, n2 = sum(s_[1] for s_ in sz), sum(s_[2] for s_ in sz)
-            else:
-                # ---- index arrays of the down-sampled clouds, built on the host from the given draws
-                p0s = [np.asarray(p[0], dtype=np.int64)[:Lg] for p in perms]
-                p1s = [np.asarray(p[1], dtype=np.int64) for p in perms]
-                p2s = [np.asarray(p[2], dtype=np.int64) for p in perms]
-                n0 = np.asarray([len(p) for p in p0s], np.int64)
-                n1a = np.asarray([len(p) for p in p1s], np.int64)
-                n2a = np.asarray([len(p) for p in p2s], np.int64)
-                off1 = np.concatenate(([0], np.cumsum(n1a)))
-                off2 = np.concatenate(([0], np.cumsum(n2a)))
-                g_idx = np.repeat(off0[:J], Lg).reshape(J, Lg)                # padding rows: any valid point (masked by global_len)
-                col = np.arange(int(n0.sum()), dtype=np.int64) - np.repeat(np.cumsum(n0) - n0, n0)
-                g_idx[np.repeat(np.arange(J), n0), col] = np.concatenate(p0s) + np.repeat(off0[:J], n0)
-                idx1 = np.concatenate(p1s) + np.repeat(off0[:J], n1a)
-                idx2 = np.concatenate(p2s) + np.repeat(off1[:J], n2a)          # scale 2 indexes scale 1's rows (SconeOcc.py:311)
-                flat = np.concatenate([g_idx.reshape(-1), idx1, idx2, off1, off2, n0])
-                n1, n2 = int(off1[-1]), int(off2[-1])
-            d = ops.h2d(flat, torch.int64, dev)                            # ONE upload
-            cut, o = [], 0
-            for n in (J * Lg, n1, n2, J + 1, J + 1, J):
-                cut.append(d[o:o + n]); o += n
-            ia = {"g_idx": cut[0], "idx1": cut[1], "idx2": cut[2], "off1": cut[3], "off2": cut[4], "g_len": cut[5].to(torch.int32)}
-            self.last_ragged_perms = ia                                    # (a caller that repeats the pass re-uses the draws: index_arrays=)
-            pc_global = pc[ia["g_idx"]].view(J, Lg, 3)
-            pc1 = pc[ia["idx1"]]
-            pc2 = pc1[ia["idx2"]]
-            g_len_d, d_off1, d_off2 = ia["g_len"], ia["off1"], ia["off2"]
+        self._check_differentiable(differentiable, h.pc, out)
+        pc, x, view_harmonics, variant, dev = h.pc, h.x, h.vh, h.variant, h.x.device
+        ia = index_arrays if index_arrays is not None else self._ragged_index_arrays(h, perms)
+        self.last_ragged_perms = ia         # (a caller that repeats the pass -- on another variant, on another rank -- re-uses the draws: index_arrays=)
+        pc_global = pc[ia["g_idx"]].view(len(h.cloud_sizes), self.seq_len, 3)
+        pc1 = pc[ia["idx1"]]
+        pc2 = pc1[ia["idx2"]]
 
         def run(v, flag, redo_phase1, out_):
             if redo_phase1:
-                phase1(v)
-            blobs, head, table = state[v] if v in state else caches(v)
-            return ops.scone_occ_forward_ragged(pc_global, g_len_d, [pc, pc1, pc2], [d_off0, d_off1, d_off2], x, view_harmonics,
-                                                d_row_job, d_blocks, table, blobs, head, flag, phase=2, out=out_, arena=h["arena"])
+                self._ragged_phase1(h, v)
+            table, blobs, head = self._images(v, h.images)
+            return ops.scone_occ_forward_ragged(pc_global, ia["g_len"], [pc, pc1, pc2], [h.d_off0, ia["off1"], ia["off2"]], x, view_harmonics,
+                                                h.d_row_job, h.d_blocks, table, blobs, head, flag, phase=2, out=out_, arena=h.arena)
+
+        # (phase 1's results live in the stream's arena: if anything else wrote it since -- another thread on this stream -- redo it)
+        stale = lambda: ops.scone_occ_epoch(dev, h.arena) != h.epoch1       # noqa: E731
         if differentiable and A.needs_grad(self, x, view_harmonics):
-            # HIP forward (the launches below, no range flag), HIP backward: one node over the rows of all jobs
+            # HIP forward (the launches above, no range flag), HIP backward: one node over the rows of all jobs
             params, slots = self._grad_slots()
-            sz = [self.scale_sizes(int(m)) for m in cloud_sizes]
+            sz = [self.scale_sizes(int(m)) for m in h.cloud_sizes]
             return A.SconeOccRaggedFunction.apply(
-                lambda: run(variant, None, ops.scone_occ_epoch(dev, h["arena"]) != h["epoch1"], None), self.weight_table, slots,
-                [[s_[i] for s_ in sz] for i in range(self.n_scale)], h["query_sizes"], pc_global, g_len_d, [pc, pc1, pc2], d_row_job,
+                lambda: run(variant, None, stale(), None), self.weight_table, slots,
+                [[s_[i] for s_ in sz] for i in range(self.n_scale)], h.query_sizes, pc_global, ia["g_len"], [pc, pc1, pc2], h.d_row_job,
                 x, view_harmonics, *params)
-        flag = None
         guard = self._effective_guard()
-        if variant in (6, 7) and guard != "off":
-            if self._range_flag is None or self._range_flag.device != dev:
-                self._range_flag = torch.zeros(1, dtype=torch.int32, device=dev)
-            elif guard in ("sync", "async"):
-                self._range_flag.zero_()
-            flag = self._range_flag
+        flag = self._arm_range(dev, guard) if variant in (6, 7) and guard != "off" else None
         with torch.no_grad():
-            # (phase 1's results live in the stream's arena: if anything else wrote it since -- another thread on this stream -- redo it)
-            res = run(variant, flag, ops.scone_occ_epoch(dev, h["arena"]) != h["epoch1"], out)
-            if flag is not None and guard == "sync" and int(flag):
-                with ops.variant(5):
-                    res = run(5, None, True, out)
-            elif flag is not None and guard == "async":
-                self._post_range_check(flag)
-        return res
+            res = run(variant, flag, stale(), out)
+            redo = self._settle_range(flag, guard, lambda: run(5, None, True, out))
+        return res if redo is None else redo
 
     def scale_sizes(self, full_seq_len):
         """Points of the three neighbourhood clouds of a forward on a cloud of full_seq_len points (SconeOcc.py:282-288, :311)."""
@@ -469,11 +424,19 @@ class SconeOcc(RangeGuard, nn.Module):
             sizes.append(sizes[-1] // ds)
         return sizes
 
-    def _images(self, variant):
-        key = param_key(self, self._key_cache)                      # one fingerprint of the parameters for every derived image
+    def _images(self, variant, memo=None):
+        """(table, blobs, head): the weight images of a variant -- pointer table with planes, packed local-transformer blobs, split head
+        planes -- each rebuilt only when the parameters' fingerprint changed.  memo (a ragged pass's dict): one fingerprint walk per
+        variant per PASS rather than per call (host time in front of the pass's launches)."""
+        if memo is not None and variant in memo:
+            return memo[variant]
+        key = _param_key(self, self._key_cache)                     # one fingerprint of the parameters for every derived image
         blobs = [c.get(t, variant, key) for c, t in zip(self._blob_caches, self.local_transformers)] if self.fused_local else None
         head = self._head_cache.get(self, key) if variant in (6, 7) else None
-        return self._table_cache.get(self, self.weight_table_with_planes, key), blobs, head
+        images = (self._table_cache.get(self, self.weight_table_with_planes, key), blobs, head)
+        if memo is not None:
+            memo[variant] = images
+        return images
 
     def forward_begin(self, pc, x):
         """Extension: queue the part of forward(pc, x, ...) that needs neither the view harmonics nor the hidden draws (the query
@@ -491,7 +454,7 @@ class SconeOcc(RangeGuard, nn.Module):
         with torch.no_grad():
             table, blobs, head = self._images(variant)
             ops.scone_occ_forward(None, [pc0, None, None], x_, None, table, blobs, head, None, phase=1, M_scale=sizes, Lg=self.seq_len)
-        return {"pc": pc0, "x": x_, "variant": variant, "sizes": sizes, "src": (pc, x), "epoch": ops.scone_occ_epoch(pc0.device, "scone_occ")}
+        return _Begun(pc=pc0, x=x_, variant=variant, sizes=sizes, src=(pc, x), epoch=ops.scone_occ_epoch(pc0.device, "scone_occ"))
 
     def forward(self, pc, x, view_harmonics, mask=None, verbose=False, perms=None, begun=None):
         """pc [n_clouds, M, 3], x [n_clouds, Q, 3], view_harmonics [n_clouds, Q, 64] -> [n_clouds, Q, 1].
@@ -509,10 +472,7 @@ class SconeOcc(RangeGuard, nn.Module):
         if perms is None:
             perms = self.draw_perms(full_seq_len)
         dev = pc.device
-        L = _lib.lib()
-        if self._effective_guard() == "async" and (self._range_pending or self._full_range):
-            self.check_range()
-        if self._full_range and ops.current_variant() in (6, 7):        # an earlier forward overflowed the fp16 split: full range from now on
+        if self._range_reenter():
             with ops.variant(5):
                 return self.forward(pc, x, view_harmonics, mask, verbose, perms, None)
         variant = ops.current_variant()
@@ -520,30 +480,24 @@ class SconeOcc(RangeGuard, nn.Module):
         # nothing else has written the arena that holds its phase-1 results (ops.scone_occ_epoch).  Checked BEFORE anything of the
         # handle is used: a stale or foreign handle is ignored and the whole forward runs on `pc` / `x`.
         sizes = self.scale_sizes(full_seq_len)
-        if begun is not None and not (begun["src"][0] is pc and begun["src"][1] is x and begun["variant"] == variant
-                                      and begun["sizes"] == sizes and [p_.shape[-1] for p_ in perms] == [self.seq_len] + sizes[1:]
-                                      and begun["epoch"] == ops.scone_occ_epoch(dev, "scone_occ")):
+        if begun is not None and not (begun.src[0] is pc and begun.src[1] is x and begun.variant == variant
+                                      and begun.sizes == sizes and [p_.shape[-1] for p_ in perms] == [self.seq_len] + sizes[1:]
+                                      and begun.epoch == ops.scone_occ_epoch(dev, "scone_occ")):
             begun = None
         pc_global = self._take(pc, perms[0])                                          # SconeOcc.py:269
-        scales = [begun["pc"] if begun is not None else pc.contiguous()]
+        scales = [begun.pc if begun is not None else pc.contiguous()]
         for p in perms[1:]:
             scales.append(self._take(scales[-1], p))                                  # :311
         phase = 0
         if begun is not None:
-            phase, x = 2, begun["x"]
+            phase, x = 2, begun.x
 
         def run(variant, pc_global, scales, x_, vh_, flag, phase=0):
             table, blobs, head = self._images(variant)
             return ops.scone_occ_forward(pc_global, scales, x_, vh_, table, blobs, head, flag, phase=phase)
 
-        flag = None
         guard = self._effective_guard()
-        if variant in (6, 7) and guard != "off":
-            if self._range_flag is None or self._range_flag.device != dev:
-                self._range_flag = torch.zeros(1, dtype=torch.int32, device=dev)
-            elif guard in ("sync", "async"):
-                self._range_flag.zero_()
-            flag = self._range_flag
+        flag = self._arm_range(dev, guard) if variant in (6, 7) and guard != "off" else None
         if A.needs_grad(self, pc, x, view_harmonics) and A.scone_occ_backward_mode() == "hip" and not pc.requires_grad:
             # HIP forward, HIP backward (autograd.SconeOccFunction); a gradient for the surface points takes the `pct` route below
             params, slots = self._grad_slots()
@@ -570,9 +524,6 @@ class SconeOcc(RangeGuard, nn.Module):
             res = A.with_torch_backward(hip, composite, (pc, x, view_harmonics), self)
         else:
             res = run(variant, pc_global, scales, x, view_harmonics, flag, phase)
-            if flag is not None and guard == "sync" and int(flag):      # out of the fp16 range: the full-range path
-                with ops.variant(5):
-                    res = run(5, pc_global, scales, x, view_harmonics, None)
-            elif flag is not None and guard == "async":
-                self._post_range_check(flag)
+            redo = self._settle_range(flag, guard, lambda: run(5, pc_global, scales, x, view_harmonics, None))
+            res = res if redo is None else redo                         # (out of the fp16 range: the full-range result)
         return res.view(n_clouds, n_sample, self.output_dim)

@@ -21,7 +21,8 @@ from .. import ops
 from .Attention import Embedding, Encoder, FeedForward, MultiHeadSelfAttention, attention, knn_gather, _f32c   # noqa: F401
 from ..utility.CustomGeometry import get_spherical_coords                                                # noqa: F401
 from ..utility.spherical_harmonics import clear_spherical_harmonics_cache, get_spherical_harmonics       # noqa: F401
-from .packing import RangeGuard, TableCache, encoder_weight_planes, padded_weight_planes, weight_planes, freeze as _freeze_key
+from .packing import TableCache, grad_slots, planes_tail, table_slots, freeze as _freeze_key
+from .range_guard import RangeGuard
 
 
 class SconeVis(RangeGuard, nn.Module):
@@ -88,39 +89,14 @@ class SconeVis(RangeGuard, nn.Module):
 
     def weight_table_with_planes(self):
         """weight_table() + per encoder the four weight matrices as fp16 hi/lo planes (the planes GEMMs of variant 6 then skip their
-        per-call split launches: 12 of a forward's launches)."""
-        t = self.weight_table()
-        for e in self.encoders:
-            t += encoder_weight_planes(e)
-        # the layers either side of the encoders (5 blobs): the embedding's second layer zero-padded to 128 x 128 (+ its padded bias), fc1 / fc2 / fc3
-        t += list(padded_weight_planes(self.embedding.linear2.weight, self.embedding.linear2.bias, 128, 128))
-        t += [weight_planes(self.fc1.weight), weight_planes(self.fc2.weight), weight_planes(self.fc3.weight)]
-        return t
+        per-call split launches: 12 of a forward's launches) + the layers either side of the encoders (5 blobs: packing.planes_tail)."""
+        return self.weight_table() + planes_tail(self.encoders, self.embedding, (self.fc1.weight, self.fc2.weight, self.fc3.weight))
 
     def _grad_slots(self):
         """(parameters, slots): every parameter of the module with its place in weight_table() -- (table index, row slice or None);
         w_q / w_k / w_v are rows 0:64 / 64:128 / 128:384 of their encoder's packed qkv entries."""
-        slots = {id(self.embedding.linear1.weight): (0, None), id(self.embedding.linear1.bias): (1, None),
-                 id(self.embedding.linear2.weight): (2, None), id(self.embedding.linear2.bias): (3, None)}
-        for e, enc in enumerate(self.encoders):
-            o = 4 + 12 * e
-            qk = enc.mhsa.w_q.weight.shape[0]
-            rows = ((0, qk), (qk, 2 * qk), (2 * qk, 2 * qk + enc.mhsa.w_v.weight.shape[0]))
-            for lin, r in zip((enc.mhsa.w_q, enc.mhsa.w_k, enc.mhsa.w_v), rows):
-                slots[id(lin.weight)], slots[id(lin.bias)] = (o + 2, r), (o + 3, r)
-            for k, t in enumerate((enc.norm1.weight, enc.norm1.bias)):
-                slots[id(t)] = (o + k, None)
-            for k, t in enumerate((enc.mhsa.out.weight, enc.mhsa.out.bias, enc.norm2.weight, enc.norm2.bias, enc.ff.linear1.weight,
-                                   enc.ff.linear1.bias, enc.ff.linear2.weight, enc.ff.linear2.bias)):
-                slots[id(t)] = (o + 4 + k, None)
-        for k, t in enumerate((self.norm.weight, self.norm.bias, self.fc1.weight, self.fc1.bias, self.fc2.weight, self.fc2.bias,
-                               self.fc3.weight, self.fc3.bias)):
-            slots[id(t)] = (40 + k, None)
-        params = tuple(self.parameters())
-        missing = [n for n, p in self.named_parameters() if id(p) not in slots]
-        if missing:
-            raise NotImplementedError(f"SconeVis HIP backward: parameters outside the weight table: {missing}")
-        return params, tuple(slots[id(p)] for p in params)
+        return grad_slots(self, table_slots(self.embedding, self.encoders, (
+            self.norm.weight, self.norm.bias, self.fc1.weight, self.fc1.bias, self.fc2.weight, self.fc2.bias, self.fc3.weight, self.fc3.bias)))
 
     def forward(self, pts, mask=None, view_harmonics=None, lengths=None):
         """pts [n_clouds, seq_len, 4], view_harmonics [n_clouds, seq_len, 64] -> [n_clouds, seq_len, 64].
@@ -143,33 +119,22 @@ class SconeVis(RangeGuard, nn.Module):
             res = ops.linear(res, _f32c(self.fc1.weight), _f32c(self.fc1.bias), gelu=True)
             res = ops.linear(torch.cat((res, view_harmonics), dim=-1), _f32c(self.fc2.weight), _f32c(self.fc2.bias), gelu=True)
             return ops.linear(res, _f32c(self.fc3.weight), _f32c(self.fc3.bias)).view(n_clouds, seq_len, self.n_harmonics)
-        # Range guard (packing.RangeGuard): on variant 6 the encoders of a cloud of >= 512 points run their GEMMs on fp16 hi/lo planes
-        # (|activation| < 65504); harmonics that come out non-finite raise the flag.  "sync" (default): read now, repeat on variant 5 --
-        # a stand-alone forward never returns non-finite harmonics; "defer": left in range_flag() (nbv_step and macarons_nbv_decision
-        # share SconeOcc's flag and read it once per decision); "async" (opt-in): looked at without a stall by a later forward /
-        # check_range(); "off": nothing.
-        if self._effective_guard() == "async" and (self._range_pending or self._full_range):
-            self.check_range()
-        if self._full_range and ops.current_variant() in (6, 7):
+        # Range guard (range_guard.py): on variant 6 the encoders of a cloud of >= 512 points run their GEMMs on fp16 hi/lo planes;
+        # harmonics that come out non-finite raise the flag
+        if self._range_reenter():
             with ops.variant(5):
                 return self.forward(pts, mask, view_harmonics, lengths)
-        # (under stream capture "sync" / "async" act as "defer": the flag kernel stays in the graph, the read-back does not)
         guard = self._effective_guard()
         guarded = ops.current_variant() in (6, 7) and seq_len >= 512 and guard != "off"
 
         def hip(p, vh):
-            res_ = ops.scone_vis_forward(p, vh, self._table_cache.get(self, self.weight_table_with_planes), lengths)
+            launch = lambda: ops.scone_vis_forward(p, vh, self._table_cache.get(self, self.weight_table_with_planes), lengths)   # noqa: E731
+            res_ = launch()
             if guarded:
-                if self._range_flag is None or self._range_flag.device != p.device:
-                    self._range_flag = torch.zeros(1, dtype=torch.int32, device=p.device)
-                elif guard in ("sync", "async"):
-                    self._range_flag.zero_()
-                ops.nonfinite_flag_(res_, self._range_flag)
-                if guard == "sync" and int(self._range_flag):
-                    with ops.variant(5):
-                        res_ = ops.scone_vis_forward(p, vh, self._table_cache.get(self, self.weight_table_with_planes), lengths)
-                elif guard == "async":
-                    self._post_range_check(self._range_flag)
+                flag = self._arm_range(p.device, guard)         # (zeroed behind the forward's kernels, in front of the one that writes it)
+                ops.nonfinite_flag_(res_, flag)
+                redo = self._settle_range(flag, guard, launch)
+                res_ = res_ if redo is None else redo
             return res_
         if A.needs_grad(self, pts, view_harmonics):     # trainers (pretrain_scone_vis.py:224): HIP forward, HIP backward
             if A.scone_vis_backward_mode() == "composite":          # (env MCR_SCONE_VIS_BWD=composite: the torch backward, A/B)

@@ -118,11 +118,6 @@ def _param_key(module, cache):
     return tuple(key)
 
 
-def param_key(module, cache):
-    """Public form of the fingerprint: one key per forward, shared by all derived-image caches of the module."""
-    return _param_key(module, cache)
-
-
 def freeze(module, cache, on=True):
     """Inference mode for the fingerprint: take it ONCE now and return that key until unfreeze / invalidate -- the caller promises
     not to change the parameters meanwhile (a deployed model: weights loaded once).  Saves the ~50 us walk over the parameters in
@@ -189,6 +184,49 @@ def padded_weight_planes(W, bias, n_pad, k_pad):
         b = torch.zeros(n_pad, dtype=torch.float32, device=W.device)
         b[:n] = bias.detach().float()
         return torch.stack((hi, (x - hi.float()).half())).contiguous(), b.contiguous()
+
+
+def planes_tail(encoders, embedding, end_weights):
+    """What weight_table_with_planes() appends behind a transformer's weight_table() (include/macarons_hip.h, PLANES / END PLANES):
+    four blobs per encoder, then the layers either side of the encoders -- the embedding's second layer zero-padded to 128 x 128
+    (+ its padded bias) and the planes of the module's own end layers."""
+    t = []
+    for e in encoders:
+        t += encoder_weight_planes(e)
+    t += list(padded_weight_planes(embedding.linear2.weight, embedding.linear2.bias, 128, 128))
+    return t + [weight_planes(W) for W in end_weights]
+
+
+def table_slots(embedding, encoders, tail, offset=0):
+    """{id(parameter): (table index, row slice or None)} of a transformer whose weight_table() starts at table entry `offset`: the
+    embedding's four tensors, 12 entries per encoder (Encoder.weight_table: w_q / w_k / w_v are row slices of the packed qkv pair),
+    then the module's own `tail` tensors."""
+    slots = {id(t): (offset + k, None) for k, t in enumerate((embedding.linear1.weight, embedding.linear1.bias,
+                                                              embedding.linear2.weight, embedding.linear2.bias))}
+    for e, enc in enumerate(encoders):
+        o = offset + 4 + 12 * e
+        qk = enc.mhsa.w_q.weight.shape[0]
+        rows = ((0, qk), (qk, 2 * qk), (2 * qk, 2 * qk + enc.mhsa.w_v.weight.shape[0]))
+        for lin, r in zip((enc.mhsa.w_q, enc.mhsa.w_k, enc.mhsa.w_v), rows):
+            slots[id(lin.weight)], slots[id(lin.bias)] = (o + 2, r), (o + 3, r)
+        for k, t in enumerate((enc.norm1.weight, enc.norm1.bias)):
+            slots[id(t)] = (o + k, None)
+        for k, t in enumerate((enc.mhsa.out.weight, enc.mhsa.out.bias, enc.norm2.weight, enc.norm2.bias, enc.ff.linear1.weight,
+                               enc.ff.linear1.bias, enc.ff.linear2.weight, enc.ff.linear2.bias)):
+            slots[id(t)] = (o + 4 + k, None)
+    for k, t in enumerate(tail):
+        slots[id(t)] = (offset + 4 + 12 * len(encoders) + k, None)
+    return slots
+
+
+def grad_slots(module, slots):
+    """(parameters, slots) as the HIP backwards take them: every parameter of `module` with its place in weight_table(); a parameter
+    the slot map does not know is refused."""
+    params = tuple(module.parameters())
+    missing = [n for n, p in module.named_parameters() if id(p) not in slots]
+    if missing:
+        raise NotImplementedError(f"{type(module).__name__} HIP backward: parameters outside the weight table: {missing}")
+    return params, tuple(slots[id(p)] for p in params)
 
 
 class TableCache:
@@ -318,7 +356,6 @@ def _pack_local_pct6(pct, planes=2):
     return blob
 
 
-
 def pack_head_planes(W):
     """[N, K] fp32 (K % 8 == 0) -> (planes, inv_scale): fp16 hi / lo planes of W * 2^e in the layout linear3h.hip reads,
     [plane][n][K/8][8 fp16] (returned as an int32 tensor, 4 words per 8 weights), and 2^-e.  e is chosen per matrix like the
@@ -357,72 +394,3 @@ class HeadPlaneCache:
                          (ctypes.c_float * 4)(*[inv for _, inv in packed]))
             self._key = key
         return self._val
-
-
-class RangeGuard:
-    """Range guard of the default numerics (variant 6: matrix operands as fp16 hi/lo planes, valid for |activation| < 65504; the
-    reference is plain fp32), shared by SconeOcc and SconeVis.  The kernels OR a device flag when an output comes out non-finite --
-    what an out-of-range activation turns into; `range_guard` says who looks at it (see SconeOcc.__init__).  Default "sync": a
-    stand-alone forward never hands back non-finite values (the reference is plain fp32 and cannot); nbv_step / macarons_nbv_decision
-    switch to "defer" for their duration (one read-back per decision).  With "async" (opt-in) a module that saw an overflow runs on the
-    full-range variant 5 from then on."""
-    range_guard = "sync"
-    _range_flag = None
-    _range_pending = ()
-    _range_pool = ()
-    _full_range = False
-
-    def range_flag(self):
-        """int32 device tensor [1]: 1 if a forward since clear_range_flag() produced a non-finite occupancy (None before the first
-        guarded forward)."""
-        return self._range_flag
-
-    def _effective_guard(self):
-        """range_guard, except under stream capture: a read-back ("sync") or a host copy ("async") cannot be part of a graph, so a
-        captured forward leaves the flag in range_flag() ("defer") for whoever replays the graph to look at."""
-        g = self.range_guard
-        if g in ("sync", "async") and torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
-            return "defer"
-        return g
-
-    def _post_range_check(self, flag):
-        """"async" guard: queue a copy of the flag to pinned host memory behind the forward's kernels (no stall)."""
-        host = torch.empty(1, dtype=torch.int32).pin_memory() if not self._range_pool else self._range_pool.pop()
-        host.copy_(flag, non_blocking=True)
-        ev = torch.cuda.Event()
-        ev.record(torch.cuda.current_stream(flag.device))
-        self._range_pending = list(self._range_pending) + [(host, ev)]
-
-    _range_pool = ()
-
-    def check_range(self, wait=False):
-        """Look at the range flags of earlier forwards ("async" guard).  wait=False: only copies that have already landed (never stalls);
-        wait=True: wait for all of them.  -> True if an overflow of the fp16-split path was seen (now or earlier); from then on this
-        module runs on the full-range variant 5.  The forward that overflowed returned non-finite occupancies."""
-        keep = []
-        for host, ev in self._range_pending:
-            if wait:
-                ev.synchronize()
-            if wait or ev.query():
-                if int(host[0]) and not self._full_range:
-                    import warnings
-                    warnings.warn(type(self).__name__ + ": an activation left the fp16 range of the default matrix path (variant 6) -- that forward "
-                                  "returned non-finite values; this module runs on the full-range variant 5 from now on "
-                                  "(range_guard='sync' repeats the forward itself at the price of a read-back per call)", RuntimeWarning, stacklevel=3)
-                    self._full_range = True
-                if not isinstance(self._range_pool, list):
-                    self._range_pool = []
-                self._range_pool.append(host)
-            else:
-                keep.append((host, ev))
-        self._range_pending = keep
-        return self._full_range
-
-    def clear_range_flag(self, device=None):
-        """Zero the flag; with `device`, create it there first if this module has not run a guarded forward on it yet (a rank whose
-        query shard is empty never runs one, yet has to bring a flag to the step's all-reduce)."""
-        if device is not None and (self._range_flag is None or self._range_flag.device != torch.device(device)):
-            self._range_flag = torch.zeros(1, dtype=torch.int32, device=device)
-        elif self._range_flag is not None:
-            self._range_flag.zero_()
-

@@ -9,7 +9,7 @@ import torch
 import numpy as np
 
 from ._lib import lib, check, MacaronsHipError, c_i64, c_int, c_size, c_vp, c_f32
-from .utility.host import limit_host_threads
+from .utility.host import limit_host_threads, native_op
 
 # torch's intra-op pool follows the machine's core count, not the container's CPU quota: an oversubscribed parallel region gets
 # the whole process throttled, the launching thread included (utility/host.py has the measurement)
@@ -1002,21 +1002,9 @@ def coverage_gain_multiple(pts, harmonics, cams, n_cam, use_sigmoid=True):
 _pinned_pool = {}        # (device index) -> list of [pinned uint8 buffer, event of its last copy]
 
 
-_NATIVE_H2D = []
-
-
 def _native_h2d():
     """Is torch.ops.macarons.h2d there (the C++ extension built)?  MCR_NATIVE_H2D=0: the Python restatement below (A/B)."""
-    if not _NATIVE_H2D:
-        ok = os.environ.get("MCR_NATIVE_H2D", "1") != "0"
-        if ok:
-            try:
-                from . import torch_ops  # noqa: F401
-                ok = hasattr(torch.ops.macarons, "h2d")
-            except Exception:
-                ok = False
-        _NATIVE_H2D.append(ok)
-    return _NATIVE_H2D[0]
+    return native_op("h2d", "MCR_NATIVE_H2D")      # (read from os.environ there, once)
 
 
 def h2d(data, dtype, device):

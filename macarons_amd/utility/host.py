@@ -60,6 +60,26 @@ def limit_host_threads(n=None):
     return torch.get_num_threads()
 
 
+# ---- host operators of the C++ extension that have a Python / numpy restatement ------------------------------------------------------
+_NATIVE_OPS = {}
+
+
+def native_op(op_name, env_name):
+    """Is torch.ops.macarons.<op_name> there (the C++ extension built)?  <env_name>=0 in the environment opts out (the restatement
+    runs: A/B, tests) without loading the extension.  Asked once per operator."""
+    ok = _NATIVE_OPS.get(op_name)
+    if ok is None:
+        ok = os.environ.get(env_name, "1") != "0"
+        if ok:
+            try:
+                from .. import torch_ops  # noqa: F401
+                ok = hasattr(torch.ops.macarons, op_name)
+            except Exception:
+                ok = False
+        _NATIVE_OPS[op_name] = ok
+    return ok
+
+
 # ---- the reference's hidden torch.randperm draws, batched ---------------------------------------------------------------------------
 _TORCH_RANDPERM = torch.randperm
 

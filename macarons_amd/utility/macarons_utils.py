@@ -5,6 +5,7 @@ PyTorch3D camera objects stay outside: cameras are passed as the 40-float record
 (M_view, M_proj, ndc bounds, centre, range) and a prediction-view matrix.
 """
 import collections
+import contextlib
 import os
 
 import numpy as np
@@ -12,6 +13,7 @@ import torch
 
 from .. import autograd as A
 from .. import ops
+from .host import native_op
 from .scone_utils import sample_proxy_points  # noqa: F401  (same sampler as the SCONE regime)
 
 
@@ -343,14 +345,9 @@ def macarons_nbv_decision(params, macarons, proxy_scene, surface_scene, camera, 
     guard_before = getattr(occ_net, "range_guard", None)
     deferred = range_guard and guard_before in ("sync", "async") and hasattr(occ_net, "forward_ragged")
     record = {}
-    vis_prev = None
-    if deferred:
-        occ_net.range_guard = "defer"
-        occ_net.clear_range_flag(device)                # (exists on every rank before the pass: the all-reduce below is rank-invariant)
-        if hasattr(vis_model, "range_guard"):           # SconeVis reports into the SAME flag: one read-back covers both networks
-            vis_prev = (vis_model.range_guard, vis_model._range_flag)
-            vis_model.range_guard, vis_model._range_flag = "defer", occ_net.range_flag()
-    try:
+    # deferred: ONE flag for both networks (SconeVis, the scope's peer, reports into SconeOcc's), there on every rank before the pass
+    # (the all-reduce below is rank-invariant), read back once
+    with occ_net.range_scope("defer", device, peer=vis_model) if deferred else contextlib.nullcontext():
         X_world, view_harmonics, occ_probs, gains = field_and_gains(None, samples, record)
         # `if coverage_gain > max_coverage_gain` from -1: the first strict maximum (a NaN gain never wins upstream; here it would)
         rec_best = None if xch else ops.best_record(gains.view(1, K), 0)
@@ -369,11 +366,6 @@ def macarons_nbv_decision(params, macarons, proxy_scene, surface_scene, camera, 
                 occ_net.clear_range_flag()
                 fallback = 5
                 rec_best = None if xch else ops.best_record(gains.view(1, K), 0)
-    finally:
-        if deferred:
-            occ_net.range_guard = guard_before
-        if vis_prev is not None:
-            vis_model.range_guard, vis_model._range_flag = vis_prev
     if xch:                                             # ties -> the lowest index over all ranks = the first strict maximum
         max_gain, next_idx = mdist.allgather_best(gains.view(1, -1), k0, group)
         out = {"next_idx": next_idx[0], "max_gain": max_gain[0], "cam_range": (k0, k1)}
@@ -622,21 +614,9 @@ def _vh_matrix_t(params, device):
     return m
 
 
-_NATIVE_FIELD_JOBS = []
-
-
 def _native_field_jobs():
     """Is torch.ops.macarons.field_jobs there (the C++ extension built)?  MCR_NATIVE_FIELD_JOBS=0: the numpy restatement (A/B, tests)."""
-    if not _NATIVE_FIELD_JOBS:
-        ok = os.environ.get("MCR_NATIVE_FIELD_JOBS", "1") != "0"
-        if ok:
-            try:
-                from .. import torch_ops  # noqa: F401
-                ok = hasattr(torch.ops.macarons, "field_jobs")
-            except Exception:
-                ok = False
-        _NATIVE_FIELD_JOBS.append(ok)
-    return _NATIVE_FIELD_JOBS[0]
+    return native_op("field_jobs", "MCR_NATIVE_FIELD_JOBS")      # (read from os.environ there, once)
 
 
 def _field_prepare_begin(params, proxy_scene, prediction_camera, device):

@@ -11,6 +11,7 @@ import torch
 
 from .. import ops
 from .CustomGeometry import get_cartesian_coords, get_spherical_coords
+from .host import native_op
 from .spherical_harmonics import get_spherical_harmonics
 
 
@@ -128,22 +129,11 @@ def view_space_bin_indices(X_cam_inv, n_elev, n_azim):
 
 
 _REF_DIRECTIONS = {}
-_NATIVE_BINS = []
 
 
 def _native_bins():
     """Is torch.ops.macarons.view_space_bins there (the C++ extension built)?  MCR_NATIVE_BINS=0: the Python restatement (A/B, tests)."""
-    if not _NATIVE_BINS:
-        import os
-        ok = os.environ.get("MCR_NATIVE_BINS", "1") != "0"
-        if ok:
-            try:
-                from .. import torch_ops  # noqa: F401
-                ok = hasattr(torch.ops.macarons, "view_space_bins")
-            except Exception:
-                ok = False
-        _NATIVE_BINS.append(ok)
-    return _NATIVE_BINS[0]
+    return native_op("view_space_bins", "MCR_NATIVE_BINS")      # (read from os.environ there, once)
 
 
 def view_space_bin_permutation(fov_camera, n_elev, n_azim, device="cpu"):

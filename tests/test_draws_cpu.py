@@ -19,6 +19,21 @@ def test_randperm_prefixes_is_the_loop_of_torch_randperm():
         assert torch.equal(got, want) and torch.equal(torch.randperm(11), after)
 
 
+def _restated_index_arrays(perms, sizes, Lg):
+    """The index arrays of a ragged pass from its jobs' draws, job by job: the frozen statement scone_occ_draws and the product's numpy
+    builder (SconeOcc.ragged_index_arrays) are compared with.  A cloud shorter than Lg pads its global rows with its first point."""
+    J = len(sizes)
+    off0 = np.concatenate(([0], np.cumsum(sizes)))
+    g_idx, g_len, idx1, idx2, off1, off2 = np.zeros((J, Lg), np.int64), np.zeros(J, np.int64), [], [], [0], [0]
+    for j, (p0, p1, p2) in enumerate(perms):
+        p0, p1, p2 = np.asarray(p0), np.asarray(p1), np.asarray(p2)
+        n0 = min(len(p0), Lg)
+        g_idx[j, :n0] = off0[j] + p0[:n0]; g_idx[j, n0:] = off0[j]; g_len[j] = n0
+        idx1.append(off0[j] + p1); idx2.append(off1[-1] + p2)
+        off1.append(off1[-1] + len(p1)); off2.append(off2[-1] + len(p2))
+    return np.concatenate([g_idx.reshape(-1), np.concatenate(idx1), np.concatenate(idx2), off1, off2, g_len])
+
+
 def test_scone_occ_draws_are_draw_perms_job_by_job():
     import macarons_amd.torch_ops  # noqa: F401
     M = importlib.import_module("macarons_amd.networks.SconeOcc")
@@ -30,19 +45,40 @@ def test_scone_occ_draws_are_draw_perms_job_by_job():
     torch.manual_seed(3)
     perms = [occ.draw_perms(m) for m in sizes]                     # SconeOcc.py:269, :311 -- three torch.randperm per forward
     after = torch.randperm(5)
-    off0 = np.concatenate(([0], np.cumsum(sizes)))
-    g_idx, g_len, idx1, idx2, off1, off2 = np.zeros((J, Lg), np.int64), np.zeros(J, np.int64), [], [], [0], [0]
-    for j, (p0, p1, p2) in enumerate(perms):
-        p0, p1, p2 = np.asarray(p0), np.asarray(p1), np.asarray(p2)
+    for j, (_, p1, p2) in enumerate(perms):
         assert len(p1) == sz[j][1] and len(p2) == sz[j][2]
-        n0 = min(len(p0), Lg)
-        g_idx[j, :n0] = off0[j] + p0[:n0]; g_idx[j, n0:] = off0[j]; g_len[j] = n0
-        idx1.append(off0[j] + p1); idx2.append(off1[-1] + p2)
-        off1.append(off1[-1] + len(p1)); off2.append(off2[-1] + len(p2))
-    want = np.concatenate([g_idx.reshape(-1), np.concatenate(idx1), np.concatenate(idx2), off1, off2, g_len])
+    want = _restated_index_arrays(perms, sizes, Lg)
     torch.manual_seed(3)
     got = torch.ops.macarons.scone_occ_draws([s[0] for s in sz], [s[1] for s in sz], [s[2] for s in sz], Lg)
     assert np.array_equal(got.numpy(), want) and torch.equal(torch.randperm(5), after)
+    # the product's numpy builder, handed the same draws, lays them out as the extension does
+    built = M.ragged_index_arrays(perms, np.concatenate(([0], np.cumsum(sizes))).astype(np.int64), J, Lg)
+    assert built.dtype == np.int64 and np.array_equal(built, got.numpy())
+
+
+def test_ragged_index_arrays_equal_the_restatement():
+    """SconeOcc.ragged_index_arrays (numpy; what forward_ragged uploads when the draws are given) == the job-by-job restatement, on
+    random draws of random job lists: clouds shorter than seq_len (padding rows of the global down-sample), of exactly seq_len, and
+    longer; one job and many.  No device, no extension."""
+    M = importlib.import_module("macarons_amd.networks.SconeOcc")
+    with contextlib.redirect_stdout(io.StringIO()):
+        occ = M.SconeOcc()
+    Lg = occ.seq_len
+    rng = np.random.default_rng(11)
+    torch.manual_seed(11)
+    n_short = n_long = 0
+    for trial in range(30):
+        J = int(rng.integers(1, 9))
+        sizes = [int(m) for m in rng.choice([65, 130, 700, 1024, Lg - 1, Lg, Lg + 1, 2300, 5000], J)]
+        perms = [occ.draw_perms(m) for m in sizes]
+        off0 = np.concatenate(([0], np.cumsum(sizes))).astype(np.int64)
+        got = M.ragged_index_arrays(perms, off0, J, Lg)
+        assert got.dtype == np.int64 and np.array_equal(got, _restated_index_arrays(perms, sizes, Lg)), trial
+        g_len = got[-J:]
+        assert g_len.tolist() == [min(m, Lg) for m in sizes]
+        n_short += sum(m < Lg for m in sizes)
+        n_long += sum(m > Lg for m in sizes)
+    assert n_short > 20 and n_long > 20
 
 
 def test_native_bin_permutation_equals_the_python_restatement():
@@ -284,26 +320,50 @@ def test_native_field_jobs_equal_the_numpy_tables():
         assert (plan.raw is None and J == 0) or np.array_equal(plan.raw, raw_t.numpy()), trial
 
 
-def test_native_ragged_tables_equal_the_numpy_tables():
-    """torch.ops.macarons.ragged_tables == the numpy tables of SconeOcc.forward_ragged_begin (cloud offsets, query blocks, row -> job)."""
-    import numpy as np
-    import torch
-    import importlib
-    so = importlib.import_module("macarons_amd.networks.SconeOcc")     # (the package re-exports the CLASS under the module's name)
-    if not so._native_ragged_tables():
-        import pytest
-        pytest.skip("C++ extension not built")
+def _ragged_table_cases():
+    """The 100 random job lists of the ragged-table tests (jobs without queries included), each with and without the row -> job part."""
     rng = np.random.default_rng(0)
     for _ in range(100):
         J = int(rng.integers(1, 30)); cs = rng.integers(16, 5000, J).tolist(); qs = rng.integers(0, 900, J).tolist(); rows = int(rng.choice([64, 128]))
         for wr in (True, False):
-            a = torch.ops.macarons.ragged_tables(cs, qs, rows, wr).numpy()
-            off0 = np.concatenate(([0], np.cumsum(cs))).astype(np.int64); q = np.asarray(qs, np.int64); q0 = np.concatenate(([0], np.cumsum(q)))
-            nb = -(-q // rows); bj = np.repeat(np.arange(J, dtype=np.int64), nb)
-            b_in = np.arange(int(nb.sum()), dtype=np.int64) - np.repeat(np.cumsum(nb) - nb, nb)
-            blocks = np.stack((bj, q0[bj] + b_in * rows, np.minimum(rows, q[bj] - b_in * rows), np.zeros_like(bj)), 1)
-            parts = [off0, blocks.reshape(-1)] + ([np.repeat(np.arange(J, dtype=np.int64), q)] if wr else [])
-            assert np.array_equal(a, np.concatenate(parts))
+            yield cs, qs, rows, wr
+
+
+def _restated_ragged_tables(cs, qs, rows, wr):
+    """The numpy code of SconeOcc.forward_ragged_begin as it stood before SconeOcc.ragged_job_tables existed, restated: the frozen
+    statement the product builder and the extension are compared with."""
+    J = len(cs)
+    off0 = np.concatenate(([0], np.cumsum(cs))).astype(np.int64); q = np.asarray(qs, np.int64); q0 = np.concatenate(([0], np.cumsum(q)))
+    nb = -(-q // rows); bj = np.repeat(np.arange(J, dtype=np.int64), nb)
+    b_in = np.arange(int(nb.sum()), dtype=np.int64) - np.repeat(np.cumsum(nb) - nb, nb)
+    blocks = np.stack((bj, q0[bj] + b_in * rows, np.minimum(rows, q[bj] - b_in * rows), np.zeros_like(bj)), 1)
+    parts = [off0, blocks.reshape(-1)] + ([np.repeat(np.arange(J, dtype=np.int64), q)] if wr else [])
+    return np.concatenate(parts)
+
+
+def test_ragged_job_tables_equal_the_restatement():
+    """SconeOcc.ragged_job_tables -- the product's numpy builder of the tables forward_ragged_begin uploads (cloud offsets, query blocks,
+    row -> job) -- == the restatement, on the 100 random job lists.  No device, no extension."""
+    so = importlib.import_module("macarons_amd.networks.SconeOcc")     # (the package re-exports the CLASS under the module's name)
+    n_zero = 0
+    for cs, qs, rows, wr in _ragged_table_cases():
+        got = so.ragged_job_tables(cs, qs, rows, wr)
+        assert got.dtype == np.int64 and np.array_equal(got, _restated_ragged_tables(cs, qs, rows, wr))
+        n_zero += sum(q == 0 for q in qs)
+    assert n_zero > 0                                                   # (jobs without queries: no block, no row)
+
+
+def test_native_ragged_tables_equal_the_numpy_tables():
+    """torch.ops.macarons.ragged_tables == the product's numpy builder (SconeOcc.ragged_job_tables) == the restatement of the tables of
+    SconeOcc.forward_ragged_begin (cloud offsets, query blocks, row -> job)."""
+    so = importlib.import_module("macarons_amd.networks.SconeOcc")     # (the package re-exports the CLASS under the module's name)
+    if not so._native_ragged_tables():
+        import pytest
+        pytest.skip("C++ extension not built")
+    for cs, qs, rows, wr in _ragged_table_cases():
+        a = torch.ops.macarons.ragged_tables(cs, qs, rows, wr).numpy()
+        assert np.array_equal(a, _restated_ragged_tables(cs, qs, rows, wr))
+        assert np.array_equal(a, so.ragged_job_tables(cs, qs, rows, wr))
 
 
 def test_native_field_prepare_equals_the_python_restatement():

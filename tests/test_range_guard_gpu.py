@@ -1,4 +1,4 @@
-"""The range guard of the 16-bit matrix paths (packing.RangeGuard) end to end.
+"""The range guard of the 16-bit matrix paths (networks/range_guard.py) end to end.
 
 Variant 6 (the default) and variant 7 feed the large GEMMs, the long-sequence attention and the fused local transformers fp16 operands,
 valid for |activation| < 65504; the reference is plain fp32.  The kernels OR a device flag when an output comes out non-finite

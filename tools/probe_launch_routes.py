@@ -192,10 +192,10 @@ def main(out_path):
                 keep(f"v{v}.ragged.{tag}.phases", occ.forward_ragged_finish(h, perms=perms))
                 ia, J = occ.last_ragged_perms, len(cloud_sizes)
                 pc1 = pc[ia["idx1"]]
-                local_blobs, head, table = h["state"][v]
+                table, local_blobs, head = h.images[v]
                 keep(f"v{v}.ragged.{tag}.single",
                      ops.scone_occ_forward_ragged(pc[ia["g_idx"]].view(J, occ.seq_len, 3), ia["g_len"], [pc, pc1, pc1[ia["idx2"]]],
-                                                  [h["d_off0"], ia["off1"], ia["off2"]], x, vh, h["d_row_job"], h["d_blocks"], table, local_blobs,
+                                                  [h.d_off0, ia["off1"], ia["off2"]], x, vh, h.d_row_job, h.d_blocks, table, local_blobs,
                                                   head, None, phase=0))
                 occ.range_guard = "sync"
         with ops.variant(v):                                # ---- SconeVis backward at 1 x 2048
