@@ -964,6 +964,47 @@ int mcr_expansion_layer_backward(const float* x, const float* x_add, const float
                                  float* d_i_weight, float* d_i_bias, int64_t B, int Cin, int Cmid, int Cadd, int Cout, int h, int w, int H,
                                  int W, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- the front of the depth module's ResNet encoder (macarons/networks/ManyDepth.py:33-50 FeatureExtractor, run on the target and on
+ * the source images by DepthDecoder.forward, :486-500): the 7x7 / 2 convolution, BatchNorm, ReLU and the 3x3 / 2 max-pool in one launch
+ * (resnet_stem.hip), the basic blocks of `layer1` in two launches each (basic_block.hip) -- the forward, for BatchNorm in EVAL mode.
+ *
+ * An eval-mode BatchNorm is given as torch's four vectors (weight, bias, running_mean, running_var, each [C]) and eps.  In float, per
+ * channel:  a = weight * (1.0f / sqrtf(var + eps));  b = fmaf(-mean, a, bias);  BN(z) = fmaf(z, a, b).
+ *
+ * mcr_resnet_stem: x [N0,Cin,H,W] and x_more [N1,Cin,H,W] (NULL with N1 = 0; x may be NULL with N0 = 0) are the images 0 .. N0-1 and
+ *   N0 .. N0+N1-1, weight [Cout,Cin,7,7], bias [Cout] or NULL, all contiguous fp32:
+ *     z      = conv2d(image, weight, bias; stride 2, zero padding 3)        [.,Cout,Hc,Wc], Hc = (H-1)/2+1, Wc = (W-1)/2+1
+ *     conv1  = max(fmaf(z + bias, a, b), 0)                                  [N0,Cout,Hc,Wc]: for x's images only; may be NULL, then not written
+ *     pooled = max_pool2d(., 3, stride 2, padding 1)                         [N0+N1,Cout,Hp,Wp], Hp = (Hc-1)/2+1, Wp = (Wc-1)/2+1;
+ *   window cells outside the map are ignored.  One launch on v_mfma_f32_16x16x4_f32 (K = Cin 49 in the weight's order, padded with
+ *   zeros to a multiple of 4); a workgroup owns 2 x 15 pooled pixels of an image and every output channel, stages the input tile once
+ *   (even and odd columns apart, for the stride) and the weights in LDS, recomputes the one-row, one-column halo of the pooling windows,
+ *   and pools out of LDS.  No atomics: two calls give the same bits.
+ * mcr_basic_block: x, y [B,C,H,W] (y not x), w1 and w2 [C,C,3,3] (stride 1, zero padding 1, no bias), two BatchNorms:
+ *     t = max(BN1(conv2d(x, w1)), 0)   [B,C,H,W], kept at the front of the workspace;     y = max(BN2(conv2d(t, w2)) + x, 0)
+ *   Two launches of the expansion layers' kernel with an epilogue of scale, shift, residual and ReLU.
+ * mcr_feature_extractor: the stem, then n_blocks (0..4) basic blocks on `pooled` -> features [N0+N1,Cout,Hp,Wp] and, where asked for,
+ *   conv1 [N0,Cout,Hc,Wc]: 1 + 2 n_blocks launches.  block_pointers: a HOST array of ten device pointers per block (w1, bn1 weight, bias,
+ *   mean, var, w2, bn2 weight, bias, mean, var); block_eps: a HOST array of two eps per block.
+ * Refused before any launch: H or W below 1, Cin outside 1..8 and Cout outside 1..64 (the stem), C outside 1..512 (the block), n_blocks
+ * outside 0..4, N0 or N1 below 0 or N0 + N1 below 1, B below 1, a tensor of 2^31 elements or more, a NULL operand (x only with N0 > 0,
+ * x_more only with N1 > 0; conv1 and the convolution's bias are optional), a workspace that is missing, short or not 16-byte aligned
+ * (the block, and the extractor with n_blocks > 0; the stem takes none).  The size functions return 0 for sizes that the entries refuse;
+ * the extractor's also for n_blocks = 0, which needs no scratch: its workspace may then be NULL. */
+int mcr_resnet_stem(const float* x, const float* x_more, const float* weight, const float* bias, const float* bn_weight,
+                    const float* bn_bias, const float* bn_mean, const float* bn_var, float eps, float* pooled, float* conv1, int64_t N0,
+                    int64_t N1, int Cin, int Cout, int H, int W, void* stream);
+size_t mcr_basic_block_workspace_bytes(int64_t B, int64_t C, int64_t H, int64_t W);
+int mcr_basic_block(const float* x, const float* w1, const float* bn1_weight, const float* bn1_bias, const float* bn1_mean,
+                    const float* bn1_var, float eps1, const float* w2, const float* bn2_weight, const float* bn2_bias,
+                    const float* bn2_mean, const float* bn2_var, float eps2, float* y, int64_t B, int C, int H, int W, void* workspace,
+                    size_t workspace_bytes, void* stream);
+size_t mcr_feature_extractor_workspace_bytes(int64_t N0, int64_t N1, int64_t Cin, int64_t Cout, int64_t H, int64_t W, int64_t n_blocks);
+int mcr_feature_extractor(const float* x, const float* x_more, const float* weight, const float* bias, const float* bn_weight,
+                          const float* bn_bias, const float* bn_mean, const float* bn_var, float eps,
+                          const float* const* block_pointers, const float* block_eps, int n_blocks, float* features, float* conv1,
+                          int64_t N0, int64_t N1, int Cin, int Cout, int H, int W, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

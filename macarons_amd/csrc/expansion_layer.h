@@ -48,12 +48,25 @@ __device__ __forceinline__ void el_fill_table(int* off0, int* off1, int R, int R
 // [Cout,C0+C1,3,3].  BWD 0, the forward: UP is the transposed convolution's launch (h0 x w0 = H x W, zero padding), the other the
 // convolution's (reflection, src0 through the nearest index with scales sy = h0 / H, sx = w0 / W); bias and ELU in the epilogue.  BWD 1 and
 // 2, the backward's two data gradients: zero padding with either weight order, no bias, no ELU; BWD 1 reads the source one row and one
-// column earlier (an (h0 + 2) x (w0 + 2) output over an h0 x w0 source).
-template <bool UP, int TH, int NSEG, int MA, int WK, int KC, int BWD = 0>
+// column earlier (an (h0 + 2) x (w0 + 2) output over an h0 x w0 source).  AFFINE, the ResNet basic block's convolutions (basic_block.hip):
+// zero padding with the convolution's weight order, and the epilogue `epi` instead of bias and ELU -- an eval-mode BatchNorm as a scale
+// and a shift per output channel, an optional residual, ReLU.  The other instantiations do not read `epi`.
+struct ElAffine {
+    const float *bn_weight, *bn_bias, *bn_mean, *bn_var;   // torch's four vectors [Cout]
+    const float* residual;                                 // [B,Cout,H,W] added after the BatchNorm, or NULL
+    float eps;
+};
+// a = weight / sqrt(var + eps) and b = bias - mean a of channel c, in float: the same expressions as resnet_stem.hip's
+__device__ __forceinline__ void el_affine_of(const ElAffine& e, int c, float& a, float& b) {
+    a = e.bn_weight[c] * (1.0f / sqrtf(e.bn_var[c] + e.eps));
+    b = fmaf(-e.bn_mean[c], a, e.bn_bias[c]);
+}
+
+template <bool UP, int TH, int NSEG, int MA, int WK, int KC, int BWD = 0, bool AFFINE = false>
 __global__ __launch_bounds__(256) void el_conv_kernel(const float* __restrict__ src0, const float* __restrict__ src1,
                                                       const float* __restrict__ weight, const float* __restrict__ bias, float* __restrict__ out,
                                                       int C0, int C1, int h0, int w0, int Cout, int H, int W, float sy, float sx, int tiles_x,
-                                                      int tiles, int co_blocks) {
+                                                      int tiles, int co_blocks, ElAffine epi) {
     constexpr int NT = 256, WP = 4 / WK, ROWS = TH / WP, TW = 16 * NSEG, RW = TW + 2, R = RW * (TH + 2), RS = el_pad16(R);
     constexpr int CO_T = 16 * MA, CS = el_pad2(KC * 9), NACC = ROWS * NSEG * MA;
     constexpr int XS = KC * RS, WN = CO_T * KC * 9, KI = (KC * R + NT - 1) / NT, KW = (WN + NT - 1) / NT;
@@ -72,7 +85,7 @@ __global__ __launch_bounds__(256) void el_conv_kernel(const float* __restrict__ 
     const float* s0 = src0 + (size_t)b * C0 * plane0;
     const float* s1 = C1 ? src1 + (size_t)b * C1 * plane1 : src0;
 
-    el_fill_table<UP || BWD != 0, BWD == 1 ? 1 : 0>(off0, off1, R, RW, y0, x0, h0, w0, H, W, sy, sx, tid, NT);
+    el_fill_table<UP || BWD != 0 || AFFINE, BWD == 1 ? 1 : 0>(off0, off1, R, RW, y0, x0, h0, w0, H, W, sy, sx, tid, NT);
     __syncthreads();
 
     // A chunk of KC channels travels through registers, every load in flight at once and from an address that exists (what is absent is
@@ -168,6 +181,14 @@ __global__ __launch_bounds__(256) void el_conv_kernel(const float* __restrict__ 
     for (int n = 0; n < NACC; ++n)
 #pragma unroll
         for (int j = 0; j < 4; ++j) sm[((wave * NACC + n) * 4 + j) * 64 + lane] = acc[n][j];
+    if (AFFINE) {                                                  // scale and shift once per channel, in the tables nobody reads any more
+        static_assert(!AFFINE || CO_T <= R, "a table entry per output channel of the tile");
+        if (tid < CO_T && co0 + tid < Cout) {
+            float a, sh;
+            el_affine_of(epi, co0 + tid, a, sh);
+            off0[tid] = __float_as_int(a), off1[tid] = __float_as_int(sh);
+        }
+    }
     __syncthreads();
     float* ob = out + (size_t)b * Cout * plane1;
     for (int o = tid; o < CO_T * TH * TW; o += NT) {
@@ -179,7 +200,16 @@ __global__ __launch_bounds__(256) void el_conv_kernel(const float* __restrict__ 
 #pragma unroll
         for (int q = 1; q < WK; ++q) z += sm[(((w0_ + q) * NACC + n) * 4 + j) * 64 + l];
         const int i = y0 + ty, jx = x0 + tx;
-        if (co0 + co < Cout && i < H && jx < W) ob[(size_t)(co0 + co) * plane1 + (size_t)i * W + jx] = BWD ? z : el_elu(z + bias[co0 + co]);
+        if (co0 + co < Cout && i < H && jx < W) {
+            const size_t at = (size_t)(co0 + co) * plane1 + (size_t)i * W + jx;
+            if (AFFINE) {
+                float v = fmaf(z, __int_as_float(off0[co]), __int_as_float(off1[co]));
+                if (epi.residual) v += epi.residual[(size_t)b * Cout * plane1 + at];
+                ob[at] = fmaxf(v, 0.f);
+            } else {
+                ob[at] = BWD ? z : el_elu(z + bias[co0 + co]);
+            }
+        }
     }
 }
 
@@ -192,12 +222,12 @@ static ElTile el_tile(int64_t B, int Cout, int H, int W) {
     return B * cdiv(Cout, 32) * cdiv(H, 4) * cdiv(W, 32) < 256 ? EL_SPLIT : EL_ROWS32;
 }
 
-template <bool UP, int BWD, int TH, int NSEG, int MA, int WK, int KC>
+template <bool UP, int BWD, int TH, int NSEG, int MA, int WK, int KC, bool AFFINE = false>
 static void el_launch_as(hipStream_t st, const float* src0, const float* src1, const float* weight, const float* bias, float* out, int64_t B,
-                         int C0, int C1, int h0, int w0, int Cout, int H, int W) {
+                         int C0, int C1, int h0, int w0, int Cout, int H, int W, ElAffine epi = ElAffine{}) {
     const int tx = (int)cdiv(W, 16 * NSEG), tiles = tx * (int)cdiv(H, TH), cob = (int)cdiv(Cout, 16 * MA);
-    hipLaunchKernelGGL((el_conv_kernel<UP, TH, NSEG, MA, WK, KC, BWD>), dim3((unsigned)(B * cob * tiles)), dim3(256), 0, st, src0, src1, weight,
-                       bias, out, C0, C1, h0, w0, Cout, H, W, (float)h0 / (float)H, (float)w0 / (float)W, tx, tiles, cob);
+    hipLaunchKernelGGL((el_conv_kernel<UP, TH, NSEG, MA, WK, KC, BWD, AFFINE>), dim3((unsigned)(B * cob * tiles)), dim3(256), 0, st, src0, src1, weight,
+                       bias, out, C0, C1, h0, w0, Cout, H, W, (float)h0 / (float)H, (float)w0 / (float)W, tx, tiles, cob, epi);
 }
 
 template <bool UP, int BWD = 0>

@@ -1,8 +1,8 @@
 """The plane sweep of the depth module on HIP: a mirror of upstream's `CostVolumeBuilder` (macarons/networks/ManyDepth.py:80-305) whose
 forward builds the cost volume with one fused entry (ops.cost_volume -> mcr_cost_volume, csrc/cost_volume.hip) instead of upstream's
 cameras / unprojection / projection / bicubic resize / 96-fold feature copy / grid_sample / mean / norm sequence, and the seam that puts
-an existing upstream instance on that path (`adopt_cost_volume_builder`).  The rest of the depth network -- the ResNet encoder and
-decoder, the pose decoder, `apply_depth_model` -- is convolutions the vendor library serves and stays upstream's.  The photometric
+an existing upstream instance on that path (`adopt_cost_volume_builder`).  The rest of the depth network -- layers 2-4 of the ResNet
+encoder, the pose decoder, `apply_depth_model` -- is convolutions the vendor library serves and stays upstream's.  The photometric
 reconstruction loss is fused on HIP as well (ops.reconstruction_loss -> mcr_reconstruction_loss, csrc/reconstruction_loss.hip, behind
 utility.macarons_utils.get_reconstruction_loss_fn); `reconstruction_loss_composite` below is the same mathematics in plain
 differentiable torch, for the cases the entry does not take and for the tests.  So is the step between the network's disparity maps
@@ -14,7 +14,11 @@ What feeds those heads, the decoder's five expansion layers (ManyDepth.py:308-36
 concatenation, a reflection-padded convolution, ELU), has a fused forward too (ops.expansion_layer -> mcr_expansion_layer,
 csrc/expansion_layer.hip, exact-fp32 matrix instructions): `ExpansionLayer` mirrors the class, `adopt_expansion_layer` and
 `adopt_depth_decoder` adopt upstream instances, `expansion_layer_composite` is the plain-torch form and `expansion_layer_route` says which
-of the two a forward takes.
+of the two a forward takes.  The front of the encoder -- the 7 x 7 convolution, BatchNorm, ReLU, the max-pool and the basic blocks of
+`layer1`, which the decoder runs on the target and on every source image -- is one entry in eval mode (ops.feature_extractor ->
+mcr_feature_extractor, csrc/resnet_stem.hip and csrc/basic_block.hip): `BasicBlock` and `FeatureExtractor` mirror the classes,
+`adopt_feature_extractor` and `adopt_depth_front` adopt upstream instances, the `*_composite` functions are the plain-torch forms and
+`feature_extractor_route` says which a forward takes.
 
 Needs neither PyTorch3D nor torchvision: a camera is its R, T (PyTorch3D's row-vector convention, view = world @ R + T) and the default
 60 degree field of view upstream never overrides; znear and zfar drop out of the sweep (they only shape the z the projection returns,
@@ -32,7 +36,7 @@ from .. import ops
 from ..ops import COST_VOLUME_FOV_SCALE
 
 __all__ = ["CostVolumeBuilder", "adopt_cost_volume_builder", "DisparityLayer", "adopt_disparity_layer", "ExpansionLayer",
-           "adopt_expansion_layer", "adopt_depth_decoder"]
+           "adopt_expansion_layer", "adopt_depth_decoder", "BasicBlock", "FeatureExtractor", "adopt_feature_extractor", "adopt_depth_front"]
 
 
 def pack_cameras(R, T, R_alpha, T_alpha):
@@ -536,4 +540,332 @@ def adopt_depth_decoder(decoder):
         adopt_disparity_layer(getattr(decoder, name))
     for name in present:
         adopt_expansion_layer(getattr(decoder, name))
+    return decoder
+
+
+# ---- the front of the ResNet encoder: the feature extractor ---------------------------------------------------------------------------------
+FEATURE_EXTRACTOR_DEFAULT = "hip"              # what profiles/feature_extractor_times.json decides (see feature_extractor_mode)
+
+
+def feature_extractor_mode():
+    """'composite' or 'hip': the route of the feature extractor in eval mode when no gradient is recorded.  MCR_FEATURE_EXTRACTOR=hip or
+    =composite chooses; otherwise FEATURE_EXTRACTOR_DEFAULT, which is 'hip' only if profiles/feature_extractor_times.json shows the whole
+    extractor through the adopted route below upstream's piecewise sequence with the intervals apart, at B 1 and at B 4."""
+    import os
+    mode = os.environ.get("MCR_FEATURE_EXTRACTOR", "").strip().lower()
+    return mode if mode in ("hip", "composite") else FEATURE_EXTRACTOR_DEFAULT
+
+
+def _batch_norm_eval(z, bn, eps):
+    weight, bias, mean, var = bn
+    return F.batch_norm(z, mean, var, weight, bias, False, 0.0, eps)
+
+
+def resnet_stem_composite(x, weight, bias, bn, eps):
+    """ops.resnet_stem in plain torch (any device and dtype): the four ops upstream runs -- the 7 x 7 / 2 convolution, the BatchNorm on
+    its running statistics (bn = (weight, bias, running_mean, running_var)), ReLU, the 3 x 3 / 2 max-pool.  x [N,Cin,H,W] -> (pooled,
+    conv1), conv1 the map after ReLU."""
+    conv1 = F.relu(_batch_norm_eval(F.conv2d(x, weight, bias, stride=2, padding=3), bn, eps))
+    return F.max_pool2d(conv1, kernel_size=3, stride=2, padding=1), conv1
+
+
+def basic_block_composite(x, w1, bn1, eps1, w2, bn2, eps2, stride=1, downsample=None):
+    """ops.basic_block in plain torch (any device and dtype): torchvision's BasicBlock.forward with both BatchNorms on their running
+    statistics -- and with the stride of the first convolution and the `downsample` of the identity, which the entry does not serve."""
+    t = F.relu(_batch_norm_eval(F.conv2d(x, w1, None, stride=stride, padding=1), bn1, eps1))
+    y = _batch_norm_eval(F.conv2d(t, w2, None, stride=1, padding=1), bn2, eps2)
+    return F.relu(y + (x if downsample is None else downsample(x)))
+
+
+def feature_extractor_composite(x, weight, bias, bn, eps, blocks):
+    """ops.feature_extractor in plain torch on one image operand: the stem, then every (w1, bn1, eps1, w2, bn2, eps2) of `blocks`.
+    -> (features, conv1)."""
+    y, conv1 = resnet_stem_composite(x, weight, bias, bn, eps)
+    for blk in blocks:
+        y = basic_block_composite(y, *blk)
+    return y, conv1
+
+
+def _bn_operands(bn):
+    return (bn.weight, bn.bias, bn.running_mean, bn.running_var), float(bn.eps)
+
+
+def _block_operands(block):
+    bn1, eps1 = _bn_operands(block.bn1)
+    bn2, eps2 = _bn_operands(block.bn2)
+    return (block.conv1.weight, bn1, eps1, block.conv2.weight, bn2, eps2)
+
+
+def _flat(operands):
+    for t in operands:
+        if isinstance(t, (tuple, list)):
+            yield from _flat(t)
+        elif torch.is_tensor(t):
+            yield t
+
+
+def _conv_facts(name, conv, wanted):
+    """The attributes of `conv` that differ from `wanted`, as 'name.attribute = value' strings (a missing one reads as None)."""
+    wrong = []
+    for k, v in wanted:
+        got = getattr(conv, k, None)
+        if (_pair(got) if isinstance(v, tuple) and got is not None else got) != v:
+            wrong.append(f"{name}.{k} = {got!r}")
+    return wrong
+
+
+def _bn_facts(name, bn):
+    wrong = []
+    for k in ("weight", "bias", "running_mean", "running_var"):
+        if not torch.is_tensor(getattr(bn, k, None)):
+            wrong.append(f"{name}.{k} = {getattr(bn, k, None)!r}")
+    if not isinstance(getattr(bn, "eps", None), float):
+        wrong.append(f"{name}.eps = {getattr(bn, 'eps', None)!r}")
+    return wrong
+
+
+_BLOCK_CONV = [("kernel_size", (3, 3)), ("stride", (1, 1)), ("padding", (1, 1)), ("dilation", (1, 1)), ("groups", 1), ("padding_mode", "zeros"),
+               ("bias", None)]
+
+
+def _block_facts(name, block):
+    """What keeps a basic block from the entry: its convolutions are 3 x 3 / 1 / 1, zeros, without bias, its BatchNorms affine with running
+    statistics, its stride 1 and its downsample None."""
+    parts = [p for p in ("conv1", "bn1", "conv2", "bn2") if not hasattr(block, p)]
+    if parts:
+        return [f"{name} lacks {parts}"]
+    wrong = _conv_facts(f"{name}.conv1", block.conv1, _BLOCK_CONV) + _conv_facts(f"{name}.conv2", block.conv2, _BLOCK_CONV)
+    wrong += _bn_facts(f"{name}.bn1", block.bn1) + _bn_facts(f"{name}.bn2", block.bn2)
+    if getattr(block, "downsample", None) is not None:
+        wrong.append(f"{name}.downsample = {type(block.downsample).__name__}")
+    if getattr(block, "stride", 1) not in (1, (1, 1)):
+        wrong.append(f"{name}.stride = {block.stride!r}")
+    for a, b in (("conv1", "conv2"),):
+        wa, wb = getattr(block.conv1, "weight", None), getattr(block.conv2, "weight", None)
+        if not (torch.is_tensor(wa) and torch.is_tensor(wb) and wa.dim() == 4 and wa.shape == wb.shape and wa.shape[0] == wa.shape[1]):
+            wrong.append(f"{name}: {a}.weight and {b}.weight are not two [C,C,3,3]")
+    return wrong
+
+
+def _extractor_blocks(fe):
+    layer = fe.layer
+    try:
+        return list(layer)
+    except TypeError:
+        return None
+
+
+def _extractor_facts(fe):
+    """What keeps a feature extractor (conv1, bn1, relu, maxpool, layer) from the entry, as strings; empty: the entry computes it."""
+    wrong = _conv_facts("conv1", fe.conv1, [("kernel_size", (7, 7)), ("stride", (2, 2)), ("padding", (3, 3)), ("dilation", (1, 1)),
+                                            ("groups", 1), ("padding_mode", "zeros")])
+    if not (torch.is_tensor(getattr(fe.conv1, "weight", None)) and fe.conv1.weight.dim() == 4):
+        wrong.append("conv1.weight is not [Cout,Cin,7,7]")
+    wrong += _bn_facts("bn1", fe.bn1)
+    wrong += _conv_facts("maxpool", fe.maxpool, [("kernel_size", (3, 3)), ("stride", (2, 2)), ("padding", (1, 1)), ("dilation", (1, 1)),
+                                                 ("ceil_mode", False), ("return_indices", False)])
+    if not isinstance(fe.relu, nn.ReLU):
+        wrong.append(f"relu = {type(fe.relu).__name__}")
+    blocks = _extractor_blocks(fe)
+    if blocks is None or len(blocks) > ops.FEATURE_EXTRACTOR_MAX_BLOCKS:
+        wrong.append(f"layer is not a sequence of at most {ops.FEATURE_EXTRACTOR_MAX_BLOCKS} blocks")
+    else:
+        for k, block in enumerate(blocks):
+            wrong += _block_facts(f"layer[{k}]", block)
+    return wrong
+
+
+def _extractor_operands(fe):
+    """(weight, bias, bn, eps, blocks): the arguments of ops.feature_extractor after the images."""
+    bn, eps = _bn_operands(fe.bn1)
+    return fe.conv1.weight, fe.conv1.bias, bn, eps, [_block_operands(b) for b in _extractor_blocks(fe)]
+
+
+def _hip_operands_ok(images, operands):
+    """Contiguous float32 tensors on one HIP device, outside autocast, none to be differentiated."""
+    ts = [t for t in images if t is not None] + list(_flat(operands))
+    x = ts[0]
+    if not all(isinstance(t, torch.Tensor) for t in ts) or _autocast_on(x):
+        return False
+    if torch.is_grad_enabled() and any(t.requires_grad for t in ts):
+        return False
+    return all(_is_hip_tensor(t) and t.device == x.device and t.dtype == torch.float32 and t.is_contiguous() for t in ts)
+
+
+def feature_extractor_route(fe, x, x_more=None):
+    """'hip' or 'composite' for one pass of the extractor over x [N0,Cin,H,W] and, in the same call, x_more [N1,Cin,H,W].  'hip'
+    (ops.feature_extractor) only when every BatchNorm involved has training == False, no gradient is to be recorded, the tensors are
+    contiguous float32 on one HIP device outside autocast and within the entry's limits, the extractor is what the entry computes
+    (_extractor_facts) and the mode (feature_extractor_mode) is 'hip'.  Anything else is upstream's own sequence of modules."""
+    if feature_extractor_mode() != "hip":
+        return "composite"
+    if not all(hasattr(fe, a) for a in ("conv1", "bn1", "relu", "maxpool", "layer")) or _extractor_facts(fe):
+        return "composite"
+    blocks = _extractor_blocks(fe)
+    if fe.bn1.training or any(b.bn1.training or b.bn2.training for b in blocks):
+        return "composite"
+    images = [t for t in (x, x_more) if t is not None]
+    if not images or not all(isinstance(t, torch.Tensor) and t.dim() == 4 and t.shape[1:] == images[0].shape[1:] for t in images):
+        return "composite"
+    if not _hip_operands_ok(images, _extractor_operands(fe)):
+        return "composite"
+    w = fe.conv1.weight
+    N, (Cin, H, W), Cout = sum(int(t.shape[0]) for t in images), (int(v) for v in images[0].shape[1:]), int(w.shape[0])
+    if N < 1 or H < 1 or W < 1 or w.shape[1] != Cin or not (1 <= Cin <= ops.RESNET_STEM_MAX_CIN and 1 <= Cout <= ops.RESNET_STEM_MAX_COUT):
+        return "composite"
+    if any(b.conv1.weight.shape[0] != Cout for b in blocks):
+        return "composite"
+    Hc, Wc, _, _ = ops.resnet_stem_sizes(H, W)
+    if max(N * Cin * H * W, N * Cout * Hc * Wc) >= 2 ** 31:
+        return "composite"
+    return "hip"
+
+
+def _extractor_pieces(fe, x):
+    """Upstream's own sequence on one image operand (ManyDepth.py:486-491) -> (features, conv1)."""
+    conv1 = fe.relu(fe.bn1(fe.conv1(x)))
+    return fe.layer(fe.maxpool(conv1)), conv1
+
+
+def extractor_front(fe, x, sources):
+    """(features of x, features of sources, conv1 of x) as the decoder's forward needs them: where feature_extractor_route says 'hip', ONE
+    ops.feature_extractor call for both operands; otherwise the extractor's modules piece by piece on x and then on the sources, as
+    upstream calls them (ManyDepth.py:486-500)."""
+    if feature_extractor_route(fe, x, sources) == "hip":
+        features, conv1 = ops.feature_extractor(x, sources, *_extractor_operands(fe))
+        return features[:x.shape[0]], features[x.shape[0]:], conv1
+    layer1, conv1 = _extractor_pieces(fe, x)
+    return layer1, _extractor_pieces(fe, sources)[0], conv1
+
+
+def _extractor_forward(self, x):
+    """FeatureExtractor.forward (ManyDepth.py:43-50), same signature: x [N,Cin,H,W] -> layer(maxpool(relu(bn1(conv1(x))))).  The route is
+    feature_extractor_route: one fused entry in eval mode without a gradient under the mode 'hip', the modules themselves otherwise."""
+    if feature_extractor_route(self, x) == "hip":
+        return ops.feature_extractor(x, None, *_extractor_operands(self), want_conv1=False)[0]
+    return _extractor_pieces(self, x)[0]
+
+
+def _block_forward(self, x):
+    """torchvision's BasicBlock.forward, the module sequence and nothing else: a block on its own is never routed to HIP (inside a
+    FeatureExtractor on the HIP route the extractor's entry takes the blocks' operands and this forward does not run)."""
+    out = self.relu(self.bn1(self.conv1(x)))
+    out = self.bn2(self.conv2(out))
+    return self.relu(out + (x if self.downsample is None else self.downsample(x)))
+
+
+class BasicBlock(nn.Module):
+    """Mirror of torchvision's BasicBlock (torchvision is not needed): the same constructor arguments, attributes and state-dict names
+    (`conv1.weight`, `bn1.*`, `conv2.weight`, `bn2.*`, `downsample.*`), so that a resnet18 state dict loads.  Its forward is torch's modules (_block_forward);
+    the fused entry serves it as part of a FeatureExtractor, where stride and downsample are refused."""
+    expansion = 1
+
+    def __init__(self, inplanes, planes, stride=1, downsample=None):
+        super().__init__()
+        self.conv1 = nn.Conv2d(inplanes, planes, kernel_size=3, stride=stride, padding=1, bias=False)
+        self.bn1 = nn.BatchNorm2d(planes)
+        self.relu = nn.ReLU(inplace=True)
+        self.conv2 = nn.Conv2d(planes, planes, kernel_size=3, stride=1, padding=1, bias=False)
+        self.bn2 = nn.BatchNorm2d(planes)
+        self.downsample = downsample
+        self.stride = stride
+
+    forward = _block_forward
+
+
+class FeatureExtractor(nn.Module):
+    """Mirror of upstream's FeatureExtractor: the same constructor (anything with conv1, bn1, relu, maxpool and layer1) and attribute
+    names (`conv1`, `bn1`, `relu`, `maxpool`, `layer`).  The forward is _extractor_forward."""
+
+    def __init__(self, resnet_model):
+        super().__init__()
+        self.conv1, self.bn1, self.relu, self.maxpool = resnet_model.conv1, resnet_model.bn1, resnet_model.relu, resnet_model.maxpool
+        self.layer = resnet_model.layer1
+
+    forward = _extractor_forward
+
+
+class _AdoptedExtractorForward:
+    """The `forward` of an adopted FeatureExtractor: a module-level callable holding the instance (see _AdoptedForward)."""
+
+    def __init__(self, extractor):
+        self.extractor = extractor
+
+    def __call__(self, x):
+        return _extractor_forward(self.extractor, x)
+
+
+def adopt_feature_extractor(fe):
+    """Put an existing upstream FeatureExtractor instance on the forward above: its `forward` is rebound (on the instance); it reads
+    `conv1`, `bn1`, `relu`, `maxpool` and `layer`.  TypeError, naming every wrong fact, unless the extractor is what the entry computes: a
+    7 x 7, stride 2, padding 3, zeros, undilated, ungrouped convolution; a BatchNorm with affine parameters and running statistics; ReLU;
+    a 3 x 3, stride 2, padding 1, undilated max-pool without ceil_mode; at most four blocks of two 3 x 3, stride 1, padding 1 convolutions
+    without bias and two such BatchNorms, without stride or downsample.  Returns the instance; adopting twice changes nothing.  Loading a
+    pickled adopted model needs this package importable."""
+    who = "adopt_feature_extractor"
+    missing = [a for a in ("conv1", "bn1", "relu", "maxpool", "layer") if not hasattr(fe, a)]
+    if missing:
+        raise TypeError(f"{who}: not a FeatureExtractor, it lacks {missing}")
+    wrong = _extractor_facts(fe)
+    if wrong:
+        raise TypeError(f"{who}: the extractor is a 7 x 7, stride 2, padding 3 convolution, a BatchNorm with affine parameters and running "
+                        "statistics, ReLU, a 3 x 3, stride 2, padding 1 max-pool and blocks of 3 x 3, stride 1, padding 1 convolutions without "
+                        f"bias or downsample; this one has {', '.join(wrong)}")
+    if not isinstance(vars(fe).get("forward"), _AdoptedExtractorForward):
+        object.__setattr__(fe, "forward", _AdoptedExtractorForward(fe))
+    return fe
+
+
+def _depth_forward(self, x, R, T, zfar, x_alpha, R_alpha, T_alpha, zfar_alpha, device):
+    """DepthDecoder.forward (ManyDepth.py:474-531), same signature and the same attribute names: x [B,C,H,W], x_alpha [B,A,C,H,W] ->
+    (disp1, disp2, disp3, disp4).  The one difference is the front: where feature_extractor_route says 'hip', the target and the A source
+    images of every batch element go through ops.feature_extractor in ONE call (in eval mode BatchNorm is per image, so no value changes),
+    the map after the first ReLU kept for the target alone; otherwise the extractor's modules are called piece by piece on x and then on
+    the sources, as upstream calls them."""
+    fe = self.feature_extractor
+    B, A = x.shape[0], x_alpha.shape[1]
+    sources = x_alpha.reshape(-1, self.channels, self.height, self.width)
+    layer1, layer1_alpha, conv1 = extractor_front(fe, x, sources)
+    layer1_alpha = layer1_alpha.view(B, A, 64, self.height // 4, self.width // 4)
+    reduced = self.cost_volume_builder(layer1, R, T, zfar, layer1_alpha, R_alpha, T_alpha, zfar_alpha, device=device)
+    layer2 = self.resnet_layer_2(reduced)
+    layer3 = self.resnet_layer_3(layer2)
+    layer4 = self.resnet_layer_4(layer3)
+    iconv5 = self.expansion5(x=layer4, x_add=layer3)
+    iconv4 = self.expansion4(x=iconv5, x_add=layer2)
+    iconv3 = self.expansion3(x=iconv4, x_add=layer1)
+    iconv2 = self.expansion2(x=iconv3, x_add=conv1)
+    iconv1 = self.expansion1(x=iconv2, x_add=x if self.use_input_image_in_skip_connection else None)
+    return self.disp1(iconv1), self.disp2(iconv2), self.disp3(iconv3), self.disp4(iconv4)
+
+
+class _AdoptedDepthForward:
+    """The `forward` of a decoder after adopt_depth_front: a module-level callable holding the instance (see _AdoptedForward)."""
+
+    def __init__(self, decoder):
+        self.decoder = decoder
+
+    def __call__(self, *args, **kwargs):
+        return _depth_forward(self.decoder, *args, **kwargs)
+
+
+_DEPTH_FRONT_ATTRIBUTES = ("feature_extractor", "cost_volume_builder", "resnet_layer_2", "resnet_layer_3", "resnet_layer_4", "disp1", "disp2",
+                           "disp3", "disp4", "height", "width", "channels", "use_input_image_in_skip_connection") + _EXPANSION_NAMES
+
+
+def adopt_depth_front(decoder):
+    """Put the front of an existing upstream DepthDecoder on one extractor call: upstream's forward calls the extractor's parts one by one
+    (ManyDepth.py:486-500), so adopting the extractor alone does not reach it; this adopts decoder.feature_extractor
+    (adopt_feature_extractor, with its refusals) and rebinds the decoder's `forward` (on the instance) to _depth_forward, which is
+    upstream's forward from the cost volume on.  adopt_depth_decoder is independent of it; calling both is the usual combination:
+
+        adopt_depth_front(adopt_depth_decoder(macarons.depth.depth_decoder))
+
+    TypeError if the decoder lacks an attribute that forward reads.  Returns the decoder; adopting twice changes nothing."""
+    missing = [a for a in _DEPTH_FRONT_ATTRIBUTES if not hasattr(decoder, a)]
+    if missing:
+        raise TypeError(f"adopt_depth_front: not a DepthDecoder, it lacks {missing}")
+    adopt_feature_extractor(decoder.feature_extractor)
+    if not isinstance(vars(decoder).get("forward"), _AdoptedDepthForward):
+        object.__setattr__(decoder, "forward", _AdoptedDepthForward(decoder))
     return decoder

@@ -2046,3 +2046,152 @@ def expansion_layer_backward(x, x_add, up_weight, i_weight, u, y, d_y, output_si
                                              c_int(Cmid), c_int(Cadd), c_int(Cout), c_int(h), c_int(w), c_int(H), c_int(W), _p(ws),
                                              c_size(ws.numel()), _stream()), "mcr_expansion_layer_backward")
     return tuple(outs)
+
+
+# ---- depth module: the front of the ResNet encoder (7x7/2 conv + BatchNorm + ReLU + 3x3/2 max-pool; the basic blocks of layer1) ---------
+RESNET_STEM_MAX_CIN = 8
+RESNET_STEM_MAX_COUT = 64
+BASIC_BLOCK_MAX_CHANNELS = 512
+FEATURE_EXTRACTOR_MAX_BLOCKS = 4
+
+
+def resnet_stem_sizes(H, W):
+    """(Hc, Wc, Hp, Wp): the sizes of the stem's convolution (7x7, stride 2, padding 3) and of its max-pool (3x3, stride 2, padding 1)."""
+    Hc, Wc = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+    return Hc, Wc, (Hc - 1) // 2 + 1, (Wc - 1) // 2 + 1
+
+
+def _bn_shapes(name, bn, C):
+    """bn: (weight, bias, running_mean, running_var), each [C]."""
+    if not isinstance(bn, (tuple, list)) or len(bn) != 4:
+        raise ValueError(f"{name} must be (weight, bias, running_mean, running_var)")
+    for part, t in zip(("weight", "bias", "running_mean", "running_var"), bn):
+        if not isinstance(t, torch.Tensor) or tuple(t.shape) != (C,):
+            raise ValueError(f"{name}.{part} must be [{C}], got {tuple(getattr(t, 'shape', ()))}")
+
+
+def _resnet_stem_shapes(x, x_more, weight, bias, bn):
+    """The shapes (ValueError, on any device) -> (N0, N1, Cin, Cout, H, W).  x [N0,Cin,H,W] or None, x_more [N1,Cin,H,W] or None (not
+    both), weight [Cout,Cin,7,7], bias [Cout] or None, bn the four vectors [Cout]."""
+    first = x if x is not None else x_more
+    if first is None:
+        raise ValueError("x and x_more are both None: N0 + N1 must be at least 1")
+    for name, t in (("x", x), ("x_more", x_more)):
+        if t is not None and (not isinstance(t, torch.Tensor) or t.dim() != 4 or tuple(t.shape[1:]) != tuple(first.shape[1:])):
+            raise ValueError(f"{name} must be [N,Cin,H,W] like the other image operand, got {tuple(getattr(t, 'shape', ()))}")
+    N0, N1 = (0 if x is None else int(x.shape[0])), (0 if x_more is None else int(x_more.shape[0]))
+    Cin, H, W = (int(v) for v in first.shape[1:])
+    if N0 + N1 < 1 or H < 1 or W < 1 or not 1 <= Cin <= RESNET_STEM_MAX_CIN:
+        raise ValueError(f"the images are [{N0}+{N1},{Cin},{H},{W}]: N0 + N1, H and W must be at least 1 and Cin between 1 and "
+                         f"{RESNET_STEM_MAX_CIN}")
+    if not isinstance(weight, torch.Tensor) or weight.dim() != 4 or tuple(weight.shape[1:]) != (Cin, 7, 7):
+        raise ValueError(f"weight must be [Cout,Cin,7,7] with Cin = {Cin}, got {tuple(getattr(weight, 'shape', ()))}")
+    Cout = int(weight.shape[0])
+    if not 1 <= Cout <= RESNET_STEM_MAX_COUT:
+        raise ValueError(f"Cout = {Cout} must be between 1 and {RESNET_STEM_MAX_COUT}")
+    if bias is not None and (not isinstance(bias, torch.Tensor) or tuple(bias.shape) != (Cout,)):
+        raise ValueError(f"bias must be [{Cout}] or None, got {tuple(getattr(bias, 'shape', ()))}")
+    _bn_shapes("bn", bn, Cout)
+    Hc, Wc, _, _ = resnet_stem_sizes(H, W)
+    if max((N0 + N1) * Cin * H * W, (N0 + N1) * Cout * Hc * Wc) > 2 ** 31 - 1:
+        raise ValueError(f"the images are [{N0}+{N1},{Cin},{H},{W}], {Cout} output channels: a tensor has 2^31 elements or more")
+    return N0, N1, Cin, Cout, H, W
+
+
+def _basic_block_shapes(x, w1, bn1, w2, bn2, name="block"):
+    """The shapes (ValueError, on any device) -> (B, C, H, W).  x [B,C,H,W], w1 and w2 [C,C,3,3], bn1 and bn2 the four vectors [C]."""
+    if not isinstance(x, torch.Tensor) or x.dim() != 4:
+        raise ValueError(f"x must be [B,C,H,W], got {tuple(getattr(x, 'shape', ()))}")
+    B, C, H, W = (int(v) for v in x.shape)
+    if B < 1 or H < 1 or W < 1 or not 1 <= C <= BASIC_BLOCK_MAX_CHANNELS:
+        raise ValueError(f"x is {tuple(x.shape)}: B, H and W must be at least 1 and C between 1 and {BASIC_BLOCK_MAX_CHANNELS}")
+    for wn, w in (("w1", w1), ("w2", w2)):
+        if not isinstance(w, torch.Tensor) or tuple(w.shape) != (C, C, 3, 3):
+            raise ValueError(f"{name}.{wn} must be [{C},{C},3,3], got {tuple(getattr(w, 'shape', ()))}")
+    _bn_shapes(f"{name}.bn1", bn1, C)
+    _bn_shapes(f"{name}.bn2", bn2, C)
+    if B * C * H * W > 2 ** 31 - 1:
+        raise ValueError(f"x is {tuple(x.shape)}: a tensor has 2^31 elements or more")
+    return B, C, H, W
+
+
+def _req_bn(bn, name):
+    return [_req(t, f"{name}.{part}") for part, t in zip(("weight", "bias", "running_mean", "running_var"), bn)]
+
+
+def resnet_stem(x, x_more, weight, bias, bn, eps, want_conv1=True):
+    """(pooled [N0+N1,Cout,Hp,Wp], conv1 [N0,Cout,Hc,Wc] or None) of max_pool2d(conv1, 3, 2, 1) with conv1 = relu(batch_norm(conv2d(
+    image, weight [Cout,Cin,7,7], bias or None; stride 2, padding 3))), BatchNorm in eval mode (bn = (weight, bias, running_mean,
+    running_var), eps), in one launch (mcr_resnet_stem): the front of upstream's FeatureExtractor.forward (ManyDepth.py:43-47) on the
+    images of x [N0,Cin,H,W] and x_more [N1,Cin,H,W] (either may be None) without a concatenated copy.  conv1 is computed for x's images
+    only, and only with want_conv1.  float32; exact fp32 products; the same bits on every call."""
+    N0, N1, Cin, Cout, H, W = _resnet_stem_shapes(x, x_more, weight, bias, bn)
+    x, x_more, bias = (None if t is None else _req(t, n) for n, t in (("x", x), ("x_more", x_more), ("bias", bias)))
+    weight, bn = _req(weight, "weight"), _req_bn(bn, "bn")
+    dev = weight.device
+    Hc, Wc, Hp, Wp = resnet_stem_sizes(H, W)
+    pooled = torch.empty((N0 + N1, Cout, Hp, Wp), dtype=torch.float32, device=dev)
+    conv1 = torch.empty((N0, Cout, Hc, Wc), dtype=torch.float32, device=dev) if want_conv1 and N0 else None
+    with torch.cuda.device(dev):
+        check(lib().mcr_resnet_stem(*[None if t is None else _p(t) for t in (x, x_more, weight, bias, *bn)], c_f32(eps), _p(pooled),
+                                    None if conv1 is None else _p(conv1), c_i64(N0), c_i64(N1), c_int(Cin), c_int(Cout), c_int(H), c_int(W),
+                                    _stream()), "mcr_resnet_stem")
+    return pooled, conv1
+
+
+def basic_block(x, w1, bn1, eps1, w2, bn2, eps2, return_t=False):
+    """y [B,C,H,W] = relu(batch_norm(conv2d(t, w2)) + x) with t = relu(batch_norm(conv2d(x, w1))), both convolutions 3 x 3, stride 1,
+    padding 1, without bias, both BatchNorms in eval mode (bn = (weight, bias, running_mean, running_var)), in one entry
+    (mcr_basic_block): torchvision's BasicBlock.forward without stride or downsample.  float32; exact fp32 products; the same bits on
+    every call.  return_t: (y, t), t from a freshly allocated workspace instead of the shared arena."""
+    B, C, H, W = _basic_block_shapes(x, w1, bn1, w2, bn2)
+    x, w1, w2, bn1, bn2 = _req(x, "x"), _req(w1, "w1"), _req(w2, "w2"), _req_bn(bn1, "bn1"), _req_bn(bn2, "bn2")
+    dev = x.device
+    y = torch.empty((B, C, H, W), dtype=torch.float32, device=dev)
+    L = lib()
+    sizes = (c_i64(B), c_i64(C), c_i64(H), c_i64(W))
+    if return_t:
+        ws = torch.empty(max(int(L.mcr_basic_block_workspace_bytes(*sizes)), 4 * B * C * H * W), dtype=torch.uint8, device=dev)
+    else:
+        ws = _entry_workspace(dev, L.mcr_basic_block_workspace_bytes, *sizes)
+    with torch.cuda.device(dev):
+        check(L.mcr_basic_block(_p(x), _p(w1), *[_p(t) for t in bn1], c_f32(eps1), _p(w2), *[_p(t) for t in bn2], c_f32(eps2), _p(y),
+                                c_i64(B), c_int(C), c_int(H), c_int(W), _p(ws), c_size(ws.numel()), _stream()), "mcr_basic_block")
+    if return_t:
+        return y, ws[:4 * B * C * H * W].view(torch.float32).view(B, C, H, W)
+    return y
+
+
+def feature_extractor(x, x_more, weight, bias, bn, eps, blocks, want_conv1=True):
+    """(features [N0+N1,Cout,Hp,Wp], conv1 [N0,Cout,Hc,Wc] or None): resnet_stem followed by basic_block for every entry of `blocks`, a
+    sequence of at most four (w1, bn1, eps1, w2, bn2, eps2), in one entry (mcr_feature_extractor, 1 + 2 len(blocks) launches): upstream's
+    FeatureExtractor.forward (ManyDepth.py:43-50) on the images of x and x_more together, with the map after the first ReLU for x."""
+    N0, N1, Cin, Cout, H, W = _resnet_stem_shapes(x, x_more, weight, bias, bn)
+    blocks = list(blocks)
+    if len(blocks) > FEATURE_EXTRACTOR_MAX_BLOCKS:
+        raise ValueError(f"{len(blocks)} blocks, at most {FEATURE_EXTRACTOR_MAX_BLOCKS} are supported")
+    Hc, Wc, Hp, Wp = resnet_stem_sizes(H, W)
+    dev = weight.device
+    pointers, eps_list, keep = [], [], []
+    for k, blk in enumerate(blocks):
+        w1, bn1, eps1, w2, bn2, eps2 = blk
+        _basic_block_shapes(torch.empty((N0 + N1, Cout, Hp, Wp), device="meta"), w1, bn1, w2, bn2, name=f"blocks[{k}]")
+        ts = [_req(w1, "w1"), *_req_bn(bn1, "bn1"), _req(w2, "w2"), *_req_bn(bn2, "bn2")]
+        keep += ts
+        pointers += [t.data_ptr() for t in ts]
+        eps_list += [float(eps1), float(eps2)]
+    x, x_more, bias = (None if t is None else _req(t, n) for n, t in (("x", x), ("x_more", x_more), ("bias", bias)))
+    weight, bn = _req(weight, "weight"), _req_bn(bn, "bn")
+    features = torch.empty((N0 + N1, Cout, Hp, Wp), dtype=torch.float32, device=dev)
+    conv1 = torch.empty((N0, Cout, Hc, Wc), dtype=torch.float32, device=dev) if want_conv1 and N0 else None
+    L = lib()
+    ws = _entry_workspace(dev, L.mcr_feature_extractor_workspace_bytes, c_i64(N0), c_i64(N1), c_i64(Cin), c_i64(Cout), c_i64(H), c_i64(W),
+                          c_i64(len(blocks)))
+    ptr_array = (ctypes.c_void_p * max(len(pointers), 1))(*pointers)
+    eps_array = (ctypes.c_float * max(len(eps_list), 1))(*eps_list)
+    with torch.cuda.device(dev):
+        check(L.mcr_feature_extractor(*[None if t is None else _p(t) for t in (x, x_more, weight, bias, *bn)], c_f32(eps), ptr_array,
+                                      eps_array, c_int(len(blocks)), _p(features), None if conv1 is None else _p(conv1), c_i64(N0),
+                                      c_i64(N1), c_int(Cin), c_int(Cout), c_int(H), c_int(W), _p(ws), c_size(ws.numel()), _stream()),
+              "mcr_feature_extractor")
+    return features, conv1
